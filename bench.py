@@ -12,6 +12,10 @@ collective is the end-of-run reduction of the counters (RCCL).  `python bench.py
 environment starts the N ranks itself (torch.distributed.run, from a parent that never touches the GPU); under a
 launcher (WORLD_SIZE set) the process is one of the ranks and WORLD_SIZE must equal --gpus.
 
+A plain run sets up, warms up, times --steps steps and reports them; --dump-outputs DIR also writes the output of the
+last timed step.  --full adds what takes runs or passes of its own: per-kernel times and the roofline, the
+one-partition-per-call MAC regime, parity of the timed engine against the CPU oracle and the CPU baseline.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -479,6 +483,41 @@ def timed_steps(step, sync, dist, steps, warmup, after_warmup=None, extra=None):
     return mine, time.perf_counter() - t0
 
 
+DUMP_BYTES = 64 * 10**6 - 4096        # --dump-outputs budget, less room for the .npy headers
+DUMP_SEED = 0x5EED
+
+
+def output_sample(out):
+    """What --dump-outputs writes of one step's output `out` (2 S channel rows x n samples, a torch tensor): the whole
+    array when it fits in DUMP_BYTES, else two fixed seeded samples of half the budget each -- every sample of the two
+    channels of some streams, and every channel at some sample positions.  The selection depends on the shape only, so two
+    builds run with the same arguments write comparable arrays."""
+    import torch
+    rows, n = out.shape
+    if rows * n * 8 <= DUMP_BYTES:
+        return {"output": out.cpu().numpy()}
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(rows // 2, DUMP_BYTES // 2 // (2 * n * 8))
+    streams = np.sort(rng.choice(rows // 2, k, replace=False))
+    chans = np.stack([2 * streams, 2 * streams + 1], axis=1).ravel()
+    m = min(n, (DUMP_BYTES - k * 2 * n * 8) // (rows * 8))
+    cols = np.sort(rng.choice(n, m, replace=False))
+    res = {}
+    if k > 0:
+        res["output_streams"] = out[torch.as_tensor(chans, device=out.device)].cpu().numpy()
+    if m > 0:
+        res["output_columns"] = out[:, torch.as_tensor(cols, device=out.device)].cpu().numpy()
+    return res
+
+
+def dump_outputs(path, out):
+    os.makedirs(path, exist_ok=True)
+    arrays = output_sample(out)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def run_stub(args):
     """--stub-step (tests/test_sharding_gloo_cpu.py): the rank layout, the timing harness and the counter reduction of
     the real bench with a sleep in place of the engine call -- no GPU, no library; the line says so and is no measurement."""
@@ -542,8 +581,15 @@ def parse_args(argv=None):
                     help="blocks: calls of whole power-of-two blocks (CPQ_CALLS_WHOLE_BLOCKS); any: CPQ_CALLS_ANY -- --block is then "
                          "the call quantum (480, 441 ...), the reference's Add / Get are reproduced chunk by chunk (plan groups)")
     ap.add_argument("--exact", action="store_true", help="plain linear convolution instead of reference h_eff")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beyond the headline: per-kernel times and the roofline (the library's event "
+                         "profiling), the one-partition-per-call MAC regime, parity of the timed engine against the CPU "
+                         "oracle and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output of the last one to DIR/*.npy (float64; rank 0's streams; "
+                         "whole when it fits in 64 MB, else a fixed seeded sample: see output_sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity check")
     ap.add_argument("--host-buffers", action="store_true", help="diagnostic: host-pointer entry point (PCIe-inclusive rate)")
     ap.add_argument("--pinned", action="store_true", help="with --host-buffers: pin the host buffers (cpq_host_register)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (single-GPU rehearsal of N>1)")
@@ -551,6 +597,8 @@ def parse_args(argv=None):
     ap.add_argument("--pmc-json", default=None, help="PMC summary for roofline.traffic (default: newest profiles/r*_pmc_traffic.json)")
     ap.add_argument("--sq-json", default=None, help="SQ-counter summary for roofline.valu_issue_util (default: newest profiles/r*_sq_counters.json)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.streams <= 0:
         args.streams = STREAMS_CONFIG2 if args.gpus <= 1 else STREAMS_CONFIG5_SHARE
     if args.partition == args.block:
@@ -643,42 +691,47 @@ def main():
         eng.profile_enable(True)        # pre-creates the event pool: no hipEventCreate inside the timed region
         eng.profile_reset()
 
-    # Per-kernel times come from HIP events the library records around every kernel scope on the engine's stream.  Around
-    # long calls they are free (8 scopes per 10 ms); around 512-sample calls every event costs the stream ~10 us of
+    # Per-kernel times (--full) come from HIP events the library records around every kernel scope on the engine's stream.
+    # Around long calls they are free (8 scopes per 10 ms); around 512-sample calls every event costs the stream ~10 us of
     # serialisation -- more than the kernels between them (profiles/r04c_streaming_timeline.txt) -- so for calls below 65536
     # samples the timed region runs WITHOUT them and the same K steps are repeated with them for the per-kernel numbers.
+    # Without --full the timed region never runs them.
     host_side = {}
     separate_profile = n < 65536
     my_elapsed, elapsed = timed_steps(step, torch.cuda.synchronize, dist, args.steps, args.warmup,
-                                      None if separate_profile else start_profile, host_side)
-    profiled_elapsed = None
-    if separate_profile:
-        start_profile()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        profiled_elapsed = time.perf_counter() - t0
-    prof = eng.profile_read()
+                                      start_profile if args.full and not separate_profile else None, host_side)
+    # the output of the last timed step, before anything below overwrites d_out or advances the engine's state
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, torch.from_numpy(host_out) if args.host_buffers else d_out)
 
-    # The same MAC path with ONE partition per call (the reference's own call pattern): every FDL and IR row is
-    # streamed for a single output row, so the kernel is HBM-bound there, whereas at T blocks per call it is past the
-    # fp64 ridge.  Measured after the timed region (not part of `value`) to give the roofline object both regimes.
-    prof1 = None
-    if not (args.eq_only or args.host_buffers or args.schedule == "nuc" or args.call_mode == "any") and rank == 0:
-        P1 = P
-        eng.profile_reset()
-        for _ in range(40):
-            eng.conv_process_device(d_in.data_ptr(), d_out.data_ptr(), P1)
-        torch.cuda.synchronize()
-        prof1 = eng.profile_read()
-    eng.profile_enable(False)
+    profiled_elapsed = prof = prof1 = parity = None
+    if args.full:
+        if separate_profile:
+            start_profile()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            profiled_elapsed = time.perf_counter() - t0
+        prof = eng.profile_read()
 
-    # parity of the timed engine (every rank checks its own shard; squared errors are summed over ranks)
-    parity = None
-    if not (args.no_parity or args.eq_only or args.host_buffers or args.pcm_scale != 1.0) and B == 512:
-        parity = parity_of_timed_engine(amd, eng, d_in, d_out, torch, S, n, L, use_eq, args.saturation, args.eq_preset,
-                                        ids, args.exact, args.shared_ir)
+        # The same MAC path with ONE partition per call (the reference's own call pattern): every FDL and IR row is
+        # streamed for a single output row, so the kernel is HBM-bound there, whereas at T blocks per call it is past the
+        # fp64 ridge.  Measured after the timed region (not part of `value`) to give the roofline object both regimes.
+        if not (args.eq_only or args.host_buffers or args.schedule == "nuc" or args.call_mode == "any") and rank == 0:
+            P1 = P
+            eng.profile_reset()
+            for _ in range(40):
+                eng.conv_process_device(d_in.data_ptr(), d_out.data_ptr(), P1)
+            torch.cuda.synchronize()
+            prof1 = eng.profile_read()
+        eng.profile_enable(False)
+
+        # parity of the timed engine (every rank checks its own shard; squared errors are summed over ranks)
+        if not (args.no_parity or args.eq_only or args.host_buffers or args.pcm_scale != 1.0) and B == 512:
+            parity = parity_of_timed_engine(amd, eng, d_in, d_out, torch, S, n, L, use_eq, args.saturation, args.eq_preset,
+                                            ids, args.exact, args.shared_ir)
 
     samples = float(S) * n * args.steps          # stereo samples this rank processed
     my_rate = samples / my_elapsed / 1e6
@@ -692,117 +745,118 @@ def main():
         parity["sample"] += f"; squared errors summed over {world} ranks"
 
     if rank == 0:
-        n_ch = 2 * S
-        # algorithmic HBM bytes per launch: every row / sample a kernel needs is moved once
-        spec_bytes = P * 16
-        ir_rows = (2 if args.shared_ir else n_ch) * k_parts
         # layers the convolver actually runs: (partition size, partitions of the IR) -> launch_plan()
         if args.schedule == "nuc" or args.call_mode == "any":
             layer_list = [(plan.part_size[l], plan.num_parts_ir[l]) for l in range(plan.num_layers)]
         else:
             layer_list = [(P, k_parts)]
         layers = launch_plan(n, layer_list)
-        ir_mult = 2 if args.shared_ir else n_ch
-        # time-varying plans under reference semantics (a tail partition longer than the IR before it: blocks >= 1024 at the
-        # defaults) run in layered mode on the uniform grid: one forward FFT, then per layer a MAC over that layer's partitions
-        # and an inverse FFT, and the replayed delay-line reader
-        n_tail = plan.num_layers - 1
-        layered = (args.schedule == "uniform" and not args.exact and args.call_mode == "blocks" and
-                   any(plan.part_size[l] > plan.output_delay[l] for l in range(1, plan.num_layers)))
-        mac_layers = launch_plan(n, [(P, (plan.len[l] + P - 1) // P) for l in range(plan.num_layers)]) if layered else layers
-        alg_bytes = algorithmic_bytes_per_step(
-            n_ch, n, ir_mult, layers, mac_layers,
-            layered_tail=(n_tail, [min(n, plan.output_delay[l] + 2 * plan.part_size[l]) for l in range(1, plan.num_layers)]) if layered else None,
-            native_tails=0 if layered else max(0, len(layers) - 1),
-            native_fused=(args.schedule == "nuc" and args.call_mode == "blocks" and B == 512 and not layered))
-        # fp64 operations per step (FMA = 2): the cooperative MAC kernel (>= 48 rows per call) spends 3 real FMAs per complex
-        # MAC (Gauss), the tile kernels 4; SVF: svf_flop_model()
-        mac_flop = lambda nb: 6.0 if nb >= 48 else 8.0
-        n_bands = 20 if args.eq_preset == "bench" else len(load_autoeq_preset()["filters"])
-        svf_model = svf_flop_model(args.saturation)
-        alg_flops = {"k_fdl_mac": sum(lps * mac_flop(nb) * n_ch * nb * kl * pl for pl, kl, nb, lps in mac_layers),
-                     "k_svf_cascade_tp": svf_model["slots"] * n_bands * n_ch * n}
-        per_kernel = {}
-        for name, (cnt, ms) in prof.items():
-            if cnt == 0:
-                continue
-            avg_s = ms / cnt * 1e-3
-            step_s = ms / args.steps * 1e-3
-            per_launch = int(alg_bytes[name] * args.steps / cnt)
-            per_kernel[name] = {"launches": cnt, "avg_launch_ms": round(avg_s * 1e3, 4),
-                                "algorithmic_bytes_per_launch": per_launch,
-                                "achieved_gbs": round(alg_bytes[name] / step_s / 1e9, 1)}
-            if alg_bytes[name] == 0:      # small bookkeeping launches only (no pass over the samples): no bandwidth figure
-                per_kernel[name]["achieved_gbs"] = None
-            if name in alg_flops:
-                per_kernel[name]["fp64_tflops"] = round(alg_flops[name] / step_s / 1e12, 2)
-            if name == "k_svf_cascade_tp":
-                per_kernel[name]["fp64_tflops_arithmetic"] = round(alg_flops[name] * svf_model["arithmetic"] / svf_model["slots"] / step_s / 1e12, 2)
-        tot = {k: v["avg_launch_ms"] * v["launches"] for k, v in per_kernel.items()}
-        dominant = max(tot, key=tot.get)
-        co_dominant = sorted(k for k in tot if tot[k] >= 0.9 * tot[dominant])
-        # the FDL MAC and the SVF cascade can tie within a few percent; when they do, the roofline object describes the
-        # HBM-streaming one (the kernel north_star defines the roofline on), both are listed
-        if "k_fdl_mac" in co_dominant:
-            dominant = "k_fdl_mac"
-        dk = per_kernel[dominant]
-        running = {"streams": S, "ir_len": L, "block": B, "blocks_per_call": T, "partition": P,
-                   "schedule": args.schedule, "eq": use_eq, "kernel_sources": kernel_source_hash()}
-        pmc_path = args.pmc_json or newest_pmc_summary()
-        hbm_regime = None
-        if prof1 and prof1.get("k_fdl_mac", (0, 0.0))[0] > 0:
-            cnt1, ms1 = prof1["k_fdl_mac"]
-            lp1 = launch_plan(P, [(P, (plan.len[l] + P - 1) // P) for l in range(plan.num_layers)] if layered else [(P, k_parts)])
-            # (40 calls of one partition each: bytes of one call / MAC launches per call)
-            b1 = int(algorithmic_bytes_per_step(n_ch, P, ir_mult, lp1, lp1)["k_fdl_mac"] * 40 / cnt1)
-            gbs1 = b1 / (ms1 / cnt1 * 1e-3) / 1e9
-            tr1, src1 = load_pmc_traffic(pmc_path, "k_fdl_mac:tile", running)
-            hbm_regime = {"kernel": "k_fdl_mac", "blocks_per_call": P // B, "algorithmic_bytes_per_launch": b1,
-                          "avg_launch_ms": round(ms1 / cnt1, 4), "achieved": round(gbs1, 1),
-                          "frac": round(gbs1 / HBM_PEAK_GBS, 4), "launches": cnt1, "traffic": tr1}
-        flop_per_byte = alg_flops["k_fdl_mac"] / alg_bytes["k_fdl_mac"] if alg_bytes["k_fdl_mac"] else 0.0
-        ridge = FP64_VECTOR_PEAK_TFLOPS * 1e3 / HBM_PEAK_GBS
-        traffic, traffic_src = load_pmc_traffic(pmc_path, dominant, running)
-        if dominant.startswith("k_svf"):
-            # 16 B of HBM per sample against ~35 fp64 instructions per band-sample: the fp64 vector issue rate bounds it
-            issue_util, issue_src = load_sq_issue_util(args.sq_json or newest_sq_summary(), dominant, running)
-            roof = {"kernel": dominant, "bound": "fp64_vector", "achieved": dk.get("fp64_tflops"),
-                    "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round((dk.get("fp64_tflops") or 0.0) / FP64_VECTOR_PEAK_TFLOPS, 4),
-                    # the same with the arithmetic operations only (no min / max / compare / select slots)
-                    "flops_per_band_sample": svf_model,
-                    "achieved_arithmetic": dk.get("fp64_tflops_arithmetic"),
-                    "frac_arithmetic": round((dk.get("fp64_tflops_arithmetic") or 0.0) / FP64_VECTOR_PEAK_TFLOPS, 4),
-                    # what the SQ counters say about the same kernel: share of the SIMDs' VALU issue slots in use
-                    "valu_issue_util": issue_util, "valu_issue_util_source": issue_src,
-                    "note": "k_svf_cascade_tp is fp64-issue bound, not HBM bound: 20 sequential nonlinear bands per sample, "
-                            f"{svf_model['slots']:.0f} operation slots ({svf_model['arithmetic']:.0f} of them arithmetic) per band-sample in the "
-                            "reference's arithmetic against 16 B of HBM traffic per sample; fp64 "
-                            "MFMA and VALU share one datapath on gfx950 (profiles/r02a_ubench_fp64_valu_mfma_coexec.txt)",
-                    "hbm_kernel": {"kernel": "k_fdl_mac", "achieved": per_kernel["k_fdl_mac"]["achieved_gbs"] if "k_fdl_mac" in per_kernel else None,
-                                   "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                   "frac": round(per_kernel["k_fdl_mac"]["achieved_gbs"] / HBM_PEAK_GBS, 4) if "k_fdl_mac" in per_kernel else None,
-                                   "note": "60 % reads / 40 % writes; MI355X_MICROARCH.md measures 6.0-6.2 TB/s for swept streams "
-                                           "(the attainable part of the 8 TB/s peak that `frac` is quoted against)"}}
-        else:
-            roof = {"kernel": dominant, "bound": "hbm" if flop_per_byte < ridge else "fp64_vector",
-                    "achieved": dk["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(dk["achieved_gbs"] / HBM_PEAK_GBS, 4),
-                    "note": "HBM stream of FDL and IR spectra; `bound` from the kernel's flop/byte against the fp64 ridge"}
-        roof.update({
-            "traffic": traffic, "traffic_source": traffic_src,
-            "frac_of_pmc_traffic": (round(traffic / (dk["avg_launch_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None),
-            "algorithmic_bytes_per_launch": dk["algorithmic_bytes_per_launch"],
-            "avg_launch_ms": dk["avg_launch_ms"], "launches": dk["launches"],
-            "co_dominant_kernels": co_dominant,
-            "fp64_vector": {"achieved_tflops": dk.get("fp64_tflops"), "peak_tflops": FP64_VECTOR_PEAK_TFLOPS},
-            # k_fdl_mac at T partitions per call executes 6 K T flop (3 FMAs per complex MAC) per 16 (2K + T) bytes
-            "mac_flop_per_byte": round(flop_per_byte, 2), "ridge_flop_per_byte": round(ridge, 2),
-            "hbm_regime": hbm_regime,
-        })
-        # a fraction above 1 is an accounting error (more algorithmic bytes or flops charged than the kernel can have moved)
-        fracs = [roof.get("frac"), (roof.get("hbm_kernel") or {}).get("frac"), (hbm_regime or {}).get("frac"), roof.get("frac_arithmetic")]
-        roof["accounting_ok"] = all(f is None or f <= 1.0 for f in fracs)
+        if args.full:
+            n_ch = 2 * S
+            # algorithmic HBM bytes per launch: every row / sample a kernel needs is moved once
+            spec_bytes = P * 16
+            ir_rows = (2 if args.shared_ir else n_ch) * k_parts
+            ir_mult = 2 if args.shared_ir else n_ch
+            # time-varying plans under reference semantics (a tail partition longer than the IR before it: blocks >= 1024 at the
+            # defaults) run in layered mode on the uniform grid: one forward FFT, then per layer a MAC over that layer's partitions
+            # and an inverse FFT, and the replayed delay-line reader
+            n_tail = plan.num_layers - 1
+            layered = (args.schedule == "uniform" and not args.exact and args.call_mode == "blocks" and
+                       any(plan.part_size[l] > plan.output_delay[l] for l in range(1, plan.num_layers)))
+            mac_layers = launch_plan(n, [(P, (plan.len[l] + P - 1) // P) for l in range(plan.num_layers)]) if layered else layers
+            alg_bytes = algorithmic_bytes_per_step(
+                n_ch, n, ir_mult, layers, mac_layers,
+                layered_tail=(n_tail, [min(n, plan.output_delay[l] + 2 * plan.part_size[l]) for l in range(1, plan.num_layers)]) if layered else None,
+                native_tails=0 if layered else max(0, len(layers) - 1),
+                native_fused=(args.schedule == "nuc" and args.call_mode == "blocks" and B == 512 and not layered))
+            # fp64 operations per step (FMA = 2): the cooperative MAC kernel (>= 48 rows per call) spends 3 real FMAs per complex
+            # MAC (Gauss), the tile kernels 4; SVF: svf_flop_model()
+            mac_flop = lambda nb: 6.0 if nb >= 48 else 8.0
+            n_bands = 20 if args.eq_preset == "bench" else len(load_autoeq_preset()["filters"])
+            svf_model = svf_flop_model(args.saturation)
+            alg_flops = {"k_fdl_mac": sum(lps * mac_flop(nb) * n_ch * nb * kl * pl for pl, kl, nb, lps in mac_layers),
+                         "k_svf_cascade_tp": svf_model["slots"] * n_bands * n_ch * n}
+            per_kernel = {}
+            for name, (cnt, ms) in prof.items():
+                if cnt == 0:
+                    continue
+                avg_s = ms / cnt * 1e-3
+                step_s = ms / args.steps * 1e-3
+                per_launch = int(alg_bytes[name] * args.steps / cnt)
+                per_kernel[name] = {"launches": cnt, "avg_launch_ms": round(avg_s * 1e3, 4),
+                                    "algorithmic_bytes_per_launch": per_launch,
+                                    "achieved_gbs": round(alg_bytes[name] / step_s / 1e9, 1)}
+                if alg_bytes[name] == 0:      # small bookkeeping launches only (no pass over the samples): no bandwidth figure
+                    per_kernel[name]["achieved_gbs"] = None
+                if name in alg_flops:
+                    per_kernel[name]["fp64_tflops"] = round(alg_flops[name] / step_s / 1e12, 2)
+                if name == "k_svf_cascade_tp":
+                    per_kernel[name]["fp64_tflops_arithmetic"] = round(alg_flops[name] * svf_model["arithmetic"] / svf_model["slots"] / step_s / 1e12, 2)
+            tot = {k: v["avg_launch_ms"] * v["launches"] for k, v in per_kernel.items()}
+            dominant = max(tot, key=tot.get)
+            co_dominant = sorted(k for k in tot if tot[k] >= 0.9 * tot[dominant])
+            # the FDL MAC and the SVF cascade can tie within a few percent; when they do, the roofline object describes the
+            # HBM-streaming one (the kernel north_star defines the roofline on), both are listed
+            if "k_fdl_mac" in co_dominant:
+                dominant = "k_fdl_mac"
+            dk = per_kernel[dominant]
+            running = {"streams": S, "ir_len": L, "block": B, "blocks_per_call": T, "partition": P,
+                       "schedule": args.schedule, "eq": use_eq, "kernel_sources": kernel_source_hash()}
+            pmc_path = args.pmc_json or newest_pmc_summary()
+            hbm_regime = None
+            if prof1 and prof1.get("k_fdl_mac", (0, 0.0))[0] > 0:
+                cnt1, ms1 = prof1["k_fdl_mac"]
+                lp1 = launch_plan(P, [(P, (plan.len[l] + P - 1) // P) for l in range(plan.num_layers)] if layered else [(P, k_parts)])
+                # (40 calls of one partition each: bytes of one call / MAC launches per call)
+                b1 = int(algorithmic_bytes_per_step(n_ch, P, ir_mult, lp1, lp1)["k_fdl_mac"] * 40 / cnt1)
+                gbs1 = b1 / (ms1 / cnt1 * 1e-3) / 1e9
+                tr1, src1 = load_pmc_traffic(pmc_path, "k_fdl_mac:tile", running)
+                hbm_regime = {"kernel": "k_fdl_mac", "blocks_per_call": P // B, "algorithmic_bytes_per_launch": b1,
+                              "avg_launch_ms": round(ms1 / cnt1, 4), "achieved": round(gbs1, 1),
+                              "frac": round(gbs1 / HBM_PEAK_GBS, 4), "launches": cnt1, "traffic": tr1}
+            flop_per_byte = alg_flops["k_fdl_mac"] / alg_bytes["k_fdl_mac"] if alg_bytes["k_fdl_mac"] else 0.0
+            ridge = FP64_VECTOR_PEAK_TFLOPS * 1e3 / HBM_PEAK_GBS
+            traffic, traffic_src = load_pmc_traffic(pmc_path, dominant, running)
+            if dominant.startswith("k_svf"):
+                # 16 B of HBM per sample against ~35 fp64 instructions per band-sample: the fp64 vector issue rate bounds it
+                issue_util, issue_src = load_sq_issue_util(args.sq_json or newest_sq_summary(), dominant, running)
+                roof = {"kernel": dominant, "bound": "fp64_vector", "achieved": dk.get("fp64_tflops"),
+                        "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round((dk.get("fp64_tflops") or 0.0) / FP64_VECTOR_PEAK_TFLOPS, 4),
+                        # the same with the arithmetic operations only (no min / max / compare / select slots)
+                        "flops_per_band_sample": svf_model,
+                        "achieved_arithmetic": dk.get("fp64_tflops_arithmetic"),
+                        "frac_arithmetic": round((dk.get("fp64_tflops_arithmetic") or 0.0) / FP64_VECTOR_PEAK_TFLOPS, 4),
+                        # what the SQ counters say about the same kernel: share of the SIMDs' VALU issue slots in use
+                        "valu_issue_util": issue_util, "valu_issue_util_source": issue_src,
+                        "note": "k_svf_cascade_tp is fp64-issue bound, not HBM bound: 20 sequential nonlinear bands per sample, "
+                                f"{svf_model['slots']:.0f} operation slots ({svf_model['arithmetic']:.0f} of them arithmetic) per band-sample in the "
+                                "reference's arithmetic against 16 B of HBM traffic per sample; fp64 "
+                                "MFMA and VALU share one datapath on gfx950 (profiles/r02a_ubench_fp64_valu_mfma_coexec.txt)",
+                        "hbm_kernel": {"kernel": "k_fdl_mac", "achieved": per_kernel["k_fdl_mac"]["achieved_gbs"] if "k_fdl_mac" in per_kernel else None,
+                                       "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": round(per_kernel["k_fdl_mac"]["achieved_gbs"] / HBM_PEAK_GBS, 4) if "k_fdl_mac" in per_kernel else None,
+                                       "note": "60 % reads / 40 % writes; MI355X_MICROARCH.md measures 6.0-6.2 TB/s for swept streams "
+                                               "(the attainable part of the 8 TB/s peak that `frac` is quoted against)"}}
+            else:
+                roof = {"kernel": dominant, "bound": "hbm" if flop_per_byte < ridge else "fp64_vector",
+                        "achieved": dk["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(dk["achieved_gbs"] / HBM_PEAK_GBS, 4),
+                        "note": "HBM stream of FDL and IR spectra; `bound` from the kernel's flop/byte against the fp64 ridge"}
+            roof.update({
+                "traffic": traffic, "traffic_source": traffic_src,
+                "frac_of_pmc_traffic": (round(traffic / (dk["avg_launch_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None),
+                "algorithmic_bytes_per_launch": dk["algorithmic_bytes_per_launch"],
+                "avg_launch_ms": dk["avg_launch_ms"], "launches": dk["launches"],
+                "co_dominant_kernels": co_dominant,
+                "fp64_vector": {"achieved_tflops": dk.get("fp64_tflops"), "peak_tflops": FP64_VECTOR_PEAK_TFLOPS},
+                # k_fdl_mac at T partitions per call executes 6 K T flop (3 FMAs per complex MAC) per 16 (2K + T) bytes
+                "mac_flop_per_byte": round(flop_per_byte, 2), "ridge_flop_per_byte": round(ridge, 2),
+                "hbm_regime": hbm_regime,
+            })
+            # a fraction above 1 is an accounting error (more algorithmic bytes or flops charged than the kernel can have moved)
+            fracs = [roof.get("frac"), (roof.get("hbm_kernel") or {}).get("frac"), (hbm_regime or {}).get("frac"), roof.get("frac_arithmetic")]
+            roof["accounting_ok"] = all(f is None or f <= 1.0 for f in fracs)
         config_name = ("configs[1]" if (world == 1 and S == STREAMS_CONFIG2 and L == 131072 and B == 512) else
                        "configs[4] per-GPU share (8192 streams / 8 GPUs)" if (S == STREAMS_CONFIG5_SHARE and L == 131072 and B == 512) else
                        "modified")
@@ -840,26 +894,34 @@ def main():
             },
             "per_rank": {"samples_per_s_mega": [round(r, 1) for r in rates], "min": round(min(rates), 1),
                          "max": round(max(rates), 1)},
-            "parity": ({k: v for k, v in parity.items() if k not in ("err_sq_sum", "count")} if parity else None),
-            "roofline": roof,
-            "kernels": per_kernel,
-            "kernels_ms_per_step": {k: round(v[1] / max(args.steps, 1), 4) for k, v in prof.items()},
-            # streaming diagnostics: kernel scopes the engine enqueued per step (a scope = one kernel family of one stage; the
-            # plan groups launch several kernels per scope) and the host time of one enqueue (includes the host replay of the
-            # reference's Add / Get bookkeeping under CPQ_CALLS_ANY / the native schedule)
-            "kernel_scopes_per_step": round(sum(v[0] for v in prof.values()) / max(args.steps, 1), 2),
-            # calls below 65536 samples: `value` / `ms_per_step` are timed without the library's event profiling, the
-            # per-kernel numbers come from a second pass of the same K steps with it (ms per step of that pass here)
-            "kernel_times_from": ("second pass of the same steps with event profiling on" if separate_profile else "the timed region"),
-            "ms_per_step_profiled_pass": round(profiled_elapsed / args.steps * 1e3, 4) if profiled_elapsed else None,
+        }
+        if args.full:
+            out.update({
+                "parity": ({k: v for k, v in parity.items() if k not in ("err_sq_sum", "count")} if parity else None),
+                "roofline": roof,
+                "kernels": per_kernel,
+                "kernels_ms_per_step": {k: round(v[1] / max(args.steps, 1), 4) for k, v in prof.items()},
+                # streaming diagnostics: kernel scopes the engine enqueued per step (a scope = one kernel family of one stage; the
+                # plan groups launch several kernels per scope) and the host time of one enqueue (includes the host replay of the
+                # reference's Add / Get bookkeeping under CPQ_CALLS_ANY / the native schedule)
+                "kernel_scopes_per_step": round(sum(v[0] for v in prof.values()) / max(args.steps, 1), 2),
+                # calls below 65536 samples: `value` / `ms_per_step` are timed without the library's event profiling, the
+                # per-kernel numbers come from a second pass of the same K steps with it (ms per step of that pass here)
+                "kernel_times_from": ("second pass of the same steps with event profiling on" if separate_profile else "the timed region"),
+                "ms_per_step_profiled_pass": round(profiled_elapsed / args.steps * 1e3, 4) if profiled_elapsed else None,
+            })
+        out.update({
             "host_enqueue_us_per_step": round(host_side.get("enqueue_s", 0.0) / max(args.steps, 1) * 1e6, 1),
             "call_mode": args.call_mode,
             "setup_s": round(setup_s, 2),
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(L, use_eq, args.saturation, args.eq_preset)
-        else:
-            out["cpu_baseline"] = None
+        })
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if args.full:
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(L, use_eq, args.saturation, args.eq_preset)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -10,6 +10,10 @@ and oracle/_ref are only available there).  Fixtures are DATA (inputs + expected
   rbj_biquad_ref.json      the reference's own cookbook designers calcPeakingBiquad / calcLowShelfBiquad / calcHighShelfBiquad
                            (src/tests/EQBoundExcessBenchmark.cpp:188-245, compiled unmodified via oracle/ref_probe_eqbound.cpp)
                            over a grid of frequency x gain x Q x sample rate: the responses calcSVFCoeffs aims at
+  fasttanh_probe_samples.npz  the same FastTanhApprox.h paths at 2200 seeded random arguments (x, scalar, v128)
+  lpf_svf_ref.json         the reference's own calcLPFSVF (src/tests/EQProcessorMaxGainTests.cpp, via oracle/ref_probe_eqmath.cpp)
+                           at the low-pass cases of tests/test_ref_eq_math_cpu.py
+                           (these two let the CPU tests check the oracle where oracle/_ref cannot be built)
   survey_observations.json hand-transcribed observations of the RUNNING reference recorded in SURVEY.md
                            (section 0 findings 2-4, section 8(a) row A6, section 8(c)); provenance: survey session
   nuc_oracle_vectors.npz   outputs of this repo's oracle for fixed seeded inputs (regression pin of the oracle
@@ -65,6 +69,18 @@ def main():
                              "oracle/ref_probe_eqmath.cpp; svf = a1 a2 a3 m0 m1 m2 (this repo's design, hex doubles), "
                              "biquad = b0 b1 b2 a0 a1 a2 (the reference's equivalent biquad, hex doubles); sample rate 48000",
                    "cases": cases}, f, indent=0)
+
+    rng = np.random.default_rng(7)
+    xs = np.concatenate([rng.uniform(-8, 8, 2000), rng.normal(0, 1e-3, 200)])
+    np.savez(os.path.join(HERE, "fasttanh_probe_samples.npz"), x=xs,
+             scalar=np.array([R.ref_fast_tanh_scalar(float(v)) for v in xs]),
+             v128=np.array([R.ref_fast_tanh_v128(float(v)) for v in xs]))
+    lpf = [{"freq": f, "q": q, "svf": [float(v).hex() for v in O.ref_calc_lpf_svf(float(np.float32(f)), float(np.float32(q)), 48000.0)]}
+           for f, q in t.LPF_CASES]
+    with open(os.path.join(HERE, "lpf_svf_ref.json"), "w") as f:
+        json.dump({"source": "reference src/tests/EQProcessorMaxGainTests.cpp calcLPFSVF compiled unmodified via "
+                             "oracle/ref_probe_eqmath.cpp at float32(freq), float32(q), 48000 Hz; "
+                             "svf = a1 a2 a3 m0 m1 m2 (hex doubles)", "cases": lpf}, f, indent=0)
 
     # the reference's cookbook designers over a grid (float-representable parameters: the EQ's parameters are floats)
     rb = []

@@ -89,3 +89,31 @@ def test_bench_bytes_of_the_fused_native_path():
     f1 = b.algorithmic_bytes_per_step(512, 512, 512, lp1, lp1, native_tails=1, native_fused=True)
     p1 = b.algorithmic_bytes_per_step(512, 512, 512, lp1, lp1, native_tails=1)
     assert f1["k_rfft_fwd_ols"] - p1["k_rfft_fwd_ols"] == 512 * 512 * 8       # the block into layer 1's accumulator
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget(tmp_path):
+    """--dump-outputs: an output that fits is written whole; a larger one (the default line: 512 channel rows x 524288
+    samples, 2 GiB) as a sample chosen by the shape alone, under 64 MB in all, whose rows and columns are the output's."""
+    import torch
+    b = _bench()
+    small = torch.arange(8 * 1000, dtype=torch.float64).reshape(8, 1000)
+    info = b.dump_outputs(str(tmp_path / "small"), small)
+    assert info == {"output": [8, 1000]}
+    assert np.array_equal(np.load(tmp_path / "small" / "output.npy"), small.numpy())
+    rows, n = 512, 524288
+    out = torch.arange(rows, dtype=torch.float64)[:, None] * n + torch.arange(n, dtype=torch.float64)[None, :]
+    info = b.dump_outputs(str(tmp_path / "big"), out)
+    files = sorted(os.listdir(tmp_path / "big"))
+    assert files == ["output_columns.npy", "output_streams.npy"]
+    assert sum(os.path.getsize(tmp_path / "big" / f) for f in files) <= 64 * 10**6
+    s = np.load(tmp_path / "big" / "output_streams.npy")
+    c = np.load(tmp_path / "big" / "output_columns.npy")
+    assert s.dtype == c.dtype == np.float64 and info == {"output_streams": list(s.shape), "output_columns": list(c.shape)}
+    assert s.shape[1] == n and s.shape[0] % 2 == 0 and s.shape[0] >= 2 and c.shape[0] == rows and c.shape[1] >= 1000
+    ch = s[:, 0] / n                                            # every value names its (row, column): whole rows, stereo pairs
+    assert np.array_equal(s, ch[:, None] * n + np.arange(n)[None, :])
+    assert np.array_equal(ch[0::2] % 2, np.zeros(len(ch) // 2)) and np.array_equal(ch[1::2], ch[0::2] + 1)
+    cols = c[0]
+    assert np.array_equal(c, np.arange(rows)[:, None] * n + cols[None, :]) and np.all(np.diff(cols) > 0)
+    again = b.output_sample(out)                                # the same selection on every run
+    assert np.array_equal(again["output_streams"], s) and np.array_equal(again["output_columns"], c)

@@ -24,13 +24,36 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = [(0, 120.0, 6.0, 0.7), (0, 80.0, -9.0, 1.2), (1, 1000.0, 6.0, 0.707), (1, 3500.0, -12.0, 4.0), (1, 250.0, 18.0, 0.3),
          (2, 8000.0, 4.5, 0.9), (2, 12000.0, -7.0, 0.6), (3, 1000.0, 0.0, 0.707), (3, 15000.0, 0.0, 2.0), (4, 40.0, 0.0, 0.707),
          (4, 2000.0, 0.0, 1.5), (1, 19000.0, 10.0, 8.0)]
+LPF_CASES = [(1000.0, 0.707), (60.0, 1.0), (15000.0, 2.5), (333.0, 0.5), (4800.0, 12.0)]
+
+
+def _probe_or_none(oracle):
+    R = oracle.ref_probe()
+    return R if R is not None and hasattr(R, "ref_svf_to_display_biquad") else None
 
 
 def _need_probe(oracle):
-    R = oracle.ref_probe()
-    if R is None or not hasattr(R, "ref_svf_to_display_biquad"):
+    R = _probe_or_none(oracle)
+    if R is None:
         pytest.skip("oracle/_ref probe of the reference's EQ math test not available")
     return R
+
+
+def _load(name):
+    with open(os.path.join(HERE, "golden", name)) as f:
+        return json.load(f)
+
+
+def _display_biquad(oracle, btype, freq, gain, q, svf):
+    """(b, a) the reference's svfToDisplayBiquad gives the SVF coefficients `svf`: from the probe where oracle/_ref is built,
+    else from tests/golden/svf_display_biquad_ref.json, whose case must carry exactly these coefficients."""
+    if _probe_or_none(oracle) is not None:
+        return oracle.ref_svf_to_display_biquad(svf)
+    case = next(c for c in _load("svf_display_biquad_ref.json")["cases"]
+                if (c["type"], c["freq"], c["gain_db"], c["q"]) == (btype, freq, gain, q))
+    assert [float(v).hex() for v in svf] == case["svf"]
+    bq = np.array([float.fromhex(v) for v in case["biquad"]])
+    return bq[:3], bq[3:]
 
 
 def test_reference_eq_math_selftest_passes(oracle):
@@ -39,8 +62,10 @@ def test_reference_eq_math_selftest_passes(oracle):
 
 
 def test_lowpass_design_is_the_references_formula(oracle):
-    """calcLPFSVF (reference) == the oracle's orc_svf_design == the product's designSvf for LowPass, bit for bit."""
-    _need_probe(oracle)
+    """calcLPFSVF (reference) == the oracle's orc_svf_design == the product's designSvf for LowPass, bit for bit.  The
+    reference's values come from the probe where oracle/_ref is built (and then must equal tests/golden/lpf_svf_ref.json),
+    else from that fixture."""
+    R = _probe_or_none(oracle)
     import ctypes as C
     lib = None
     try:
@@ -48,8 +73,12 @@ def test_lowpass_design_is_the_references_formula(oracle):
         lib = _capi.load()
     except Exception:                # noqa: BLE001  (no product library in this environment: the oracle half still runs)
         pass
-    for f, q in ((1000.0, 0.707), (60.0, 1.0), (15000.0, 2.5), (333.0, 0.5), (4800.0, 12.0)):
-        ref = oracle.ref_calc_lpf_svf(float(np.float32(f)), float(np.float32(q)), 48000.0)
+    stored = _load("lpf_svf_ref.json")["cases"]
+    assert [(c["freq"], c["q"]) for c in stored] == LPF_CASES
+    for (f, q), case in zip(LPF_CASES, stored):
+        ref = np.array([float.fromhex(v) for v in case["svf"]])
+        if R is not None:
+            assert list(oracle.ref_calc_lpf_svf(float(np.float32(f)), float(np.float32(q)), 48000.0)) == list(ref)
         o = oracle.svf_design(3, f, 0.0, q, 48000.0)
         assert [o.a1, o.a2, o.a3, o.m0, o.m1, o.m2] == list(ref)
         if lib is not None:
@@ -61,10 +90,9 @@ def test_lowpass_design_is_the_references_formula(oracle):
 @pytest.mark.parametrize("btype,freq,gain,q", CASES)
 def test_oracle_band_recurrence_is_the_references_biquad(oracle, btype, freq, gain, q):
     """Oracle recurrence (saturation 0, both arithmetic flavours) == lfilter with the reference's own equivalent biquad."""
-    _need_probe(oracle)
     O = oracle
     c = O.svf_design(btype, freq, gain, q, 48000.0)
-    b, a = O.ref_svf_to_display_biquad([c.a1, c.a2, c.a3, c.m0, c.m1, c.m2])
+    b, a = _display_biquad(O, btype, freq, gain, q, [c.a1, c.a2, c.a3, c.m0, c.m1, c.m2])
     x = O.gen_pcm(16384, stream=3, channel=0)
     ref = lfilter(b / a[0], a / a[0], x)
     for kernel in (O.lib().orc_svf_band_mono, O.lib().orc_svf_band_stereo_lane):

@@ -13,7 +13,7 @@ for r in $(seq $ROUNDS); do
     cp "$v" "$TARGET"
     make -C convopeq_amd/csrc >/dev/null 2>&1 || { echo "build failed: $v"; continue; }
     for extra in "" "${AB_EXTRA[@]}"; do
-    python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-parity $extra 2>/dev/null | python -c "
+    python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-parity $extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$v [$extra]:', d['value'], 'M/s', {k: v for k, v in d['kernels_ms_per_step'].items() if v}, 'step', d['ms_per_step'])"

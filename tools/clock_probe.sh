@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cd /tmp
 run() {  # name, bench args
   n=$1; shift
-  rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $O/$n -o c -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-parity "$@" > $O/$n.log 2>&1
+  rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $O/$n -o c -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-parity "$@" > $O/$n.log 2>&1
   python3 - $O/$n <<'PY'
 import csv, glob, sys, collections, re
 d = sys.argv[1]

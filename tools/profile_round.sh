@@ -9,16 +9,16 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-parity "$@" > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-parity "$@" > $O/stats.log 2>&1
 echo "[profile_round] stats pass done"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o f -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o f -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/fetch.log 2>&1
 echo "[profile_round] FETCH_SIZE pass done"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o w -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o w -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/write.log 2>&1
 echo "[profile_round] WRITE_SIZE pass done"
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA --kernel-trace --output-format csv -d $O/sq -o q -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/sq.log 2>&1 || true
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA --kernel-trace --output-format csv -d $O/sq -o q -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/sq.log 2>&1 || true
 echo "[profile_round] SQ pass done"
 # LDS pipe of every kernel (the P = 4096 FFT kernels are quoted as LDS-bandwidth bound): array cycles, conflict cycles, issue stalls
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/lds -o l -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/lds.log 2>&1 || true
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/lds -o l -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-parity "$@" > $O/lds.log 2>&1 || true
 echo "[profile_round] LDS pass done"
 export CPQ_PROFILES_OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $CPQ_PROFILES_OUT

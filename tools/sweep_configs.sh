@@ -10,7 +10,7 @@
 TAG=${1:-r02}
 OUT=gpurun_out/sweep_$TAG.jsonl
 : > $OUT
-run() { python bench.py --steps 8 --warmup 2 --no-cpu-baseline "$@" >> $OUT 2>/dev/null || echo "FAILED: $*"; echo "done: $*"; }
+run() { python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline "$@" >> $OUT 2>/dev/null || echo "FAILED: $*"; echo "done: $*"; }
 run --saturation 0.0
 run --shared-ir
 run --eq-preset autoeq

@@ -3,7 +3,7 @@
 O=${1:-gpurun_out/sweep_pt}; mkdir -p $O
 for P in 512 1024 2048 4096; do
   for T in 64 128 256 512 1024; do
-    python bench.py --partition $P --blocks-per-call $T --steps 8 --warmup 2 --no-cpu-baseline --no-parity > $O/P${P}_T$T.json 2> $O/P${P}_T$T.err || { echo "P $P T $T failed"; continue; }
+    python bench.py --full --partition $P --blocks-per-call $T --steps 8 --warmup 2 --no-cpu-baseline --no-parity > $O/P${P}_T$T.json 2> $O/P${P}_T$T.err || { echo "P $P T $T failed"; continue; }
     python - <<PY
 import json
 d=json.loads([l for l in open("$O/P${P}_T$T.json") if l.startswith("{")][-1])

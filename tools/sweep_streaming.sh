@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG}_sweep_streaming.jsonl
 : > $OUT
 run() {
   echo "== $*" >&2
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-parity "$@" 2>/dev/null | tail -1 >> $OUT
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-parity "$@" 2>/dev/null | tail -1 >> $OUT
 }
 run --blocks-per-call 1 --steps 200 --warmup 20
 run --blocks-per-call 1 --steps 200 --warmup 20 --schedule nuc
