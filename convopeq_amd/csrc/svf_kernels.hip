@@ -374,15 +374,19 @@ template <int KIND, int N, bool CAP = false, bool UNI = false>
 __device__ __forceinline__ void tp_recur(double (&v)[N], double& ic1, double& ic2, double a1, double a2, double a3,
                                          double m0, double m1, double m2, int capAt = -1, double* c1 = nullptr, double* c2 = nullptr)
 {
+    if (KIND == 2) { ic1 = (fabs(ic1) < 1.0e-20) ? 0.0 : ic1; ic2 = (fabs(ic2) < 1.0e-20) ? 0.0 : ic2; }
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         if (CAP && j > 0) { *c1 = (capAt == j - 1) ? ic1 : *c1; *c2 = (capAt == j - 1) ? ic2 : *c2; }
         const double v0 = v[j];
         if (KIND == 2) {
+            // biquadStep128_FMA with the reference's denormal flush of both new states (src/OutputFilter.cpp:143-165); the start
+            // state is flushed on entry above (a chunk start state from the scan has not been through a flush)
             const double yy = fma(a1, v0, ic1);
             const double n1 = fma(a2, v0, fma(-m0, yy, ic2));
-            ic2 = fma(-m1, yy, a3 * v0);
-            ic1 = n1;
+            const double n2 = fma(-m1, yy, a3 * v0);
+            ic1 = (fabs(n1) < 1.0e-20) ? 0.0 : n1;
+            ic2 = (fabs(n2) < 1.0e-20) ? 0.0 : n2;
             v[j] = yy;
             continue;
         }
@@ -546,7 +550,8 @@ __device__ __forceinline__ void tpv_publish_state(unsigned long long* g, unsigne
 // loads then wait on L2 behind the other waves of the SIMD) and pw is ignored.
 // CHAINED (link != nullptr): the span's start state of band b arrives from the workgroup that has the span before (four
 // lanes of wave 0 poll for it in front of the barrier), the end state is published to the workgroup that has the span behind.
-template <int NTHREADS = kTpChunks, bool CHAINED = false>
+// FLUSH (DF-II-T sections of the OutputFilter): the span's end state gets the reference's denormal flush before it is handed on.
+template <int NTHREADS = kTpChunks, bool CHAINED = false, bool FLUSH = false>
 __device__ __forceinline__ void tp_scan(double ic1, double ic2, double& s0x, double& s0y, const double* Mall, int b,
                                         const TpLanePowers& pw, double* wtot, double* sCur, double* sNext, int tid,
                                         const double* __restrict__ Plate = nullptr, int endTid = -1, const TpvLink* link = nullptr)
@@ -625,9 +630,17 @@ __device__ __forceinline__ void tp_scan(double ic1, double ic2, double& s0x, dou
     if (lane == 0) { s0x = bx; s0y = by; }
     // end of the span: the state behind the last chunk (endTid >= 0: behind chunk endTid -- a span whose tail is padding)
     if (tid == (endTid >= 0 ? endTid : (NTHREADS ? NTHREADS : (int)blockDim.x) - 1)) {
+        if (FLUSH) { sx = (fabs(sx) < 1.0e-20) ? 0.0 : sx; sy = (fabs(sy) < 1.0e-20) ? 0.0 : sy; }
         sNext[2 * b] = sx;
         sNext[2 * b + 1] = sy;
-        if (CHAINED && link->pub && *link->flag == 0) tpv_publish_state(link->pub + b * 4, link->epoch, sx, sy);
+        if (CHAINED && link->pub) {
+            // flag = 1 + the first band whose start state arrived out of range.  Wave 0 may already be in the poll of a later
+            // band and set it there while this thread is still here: band b was computed from good states unless the flag
+            // names b or a band below it, and is published then -- the guarded rerun only publishes the bands from the
+            // flagged one on (k_svf_cascade_tpv), so a band left out here would never reach the next span.
+            const int f = *link->flag;
+            if (f == 0 || f > 1 + b) tpv_publish_state(link->pub + b * 4, link->epoch, sx, sy);
+        }
     }
 }
 
@@ -643,10 +656,7 @@ __device__ void tp_band_guarded(double* buf, int lc, const double* cf, double sa
         for (int i = 0; i < lc && c * lc + i < nSamples; ++i) {
             double y[1] = { buf[c * kTpStride + i] };
             tp_recur<KIND, 1>(y, ic1, ic2, a1, a2, a3, m0, m1, m2);
-            if (KIND == 2) {          // OutputFilter: no output stage, denormal flush of the state (OutputFilter.cpp:154-162)
-                ic1 = (fabs(ic1) < 1.0e-20) ? 0.0 : ic1;
-                ic2 = (fabs(ic2) < 1.0e-20) ? 0.0 : ic2;
-            } else {
+            if (KIND != 2) {          // (OutputFilter: no output stage; tp_recur flushes its states like OutputFilter.cpp:154-162)
                 if (sat > 0.0) tp_nonlinear<KIND == 1, true, 1>(y, sat, oneMinusSat);
                 else           tp_nonlinear<KIND == 1, false, 1>(y, sat, oneMinusSat);
                 ic1 = sanitize(ic1);
@@ -998,7 +1008,7 @@ __device__ __forceinline__ void tpv_band_run(double (&x)[16], double& e0, double
         // the scan is the band's chain of dependent cross-lane steps and LDS round trips, with the workgroup's barrier in it: run
         // ahead of everything else on the SIMD it is over sooner (1 ... 1.5 % on the kernel); the pass behind it runs at the slice's priority
         if (link.slice >= 0) __builtin_amdgcn_s_setprio(3);
-        tp_scan<NT, CHAINED>(e0, e1, s0x, s0y, &sh.M[0][0], b, pw, sh.wtot + par * 2 * (nThreads >> 6), sState, sNext, tidL, &sh.P[b][0][0], PARTIAL ? endTid : -1, &link);
+        tp_scan<NT, CHAINED, CLS == 2>(e0, e1, s0x, s0y, &sh.M[0][0], b, pw, sh.wtot + par * 2 * (nThreads >> 6), sState, sNext, tidL, &sh.P[b][0][0], PARTIAL ? endTid : -1, &link);
         tpv_time_slice(link.slice, clock);
         par ^= 1;
         if (PARTIAL) {

@@ -293,6 +293,18 @@ def eq_params_bench(saturation=0.2):
     return p
 
 
+def eq_params_pass_band(saturation=0.0, channel_mode=0):
+    """One enabled 0 dB peaking band (m0 = 1, m1 = 0) and nothing else: its linear output is its input bit for bit, so an
+    input sample is the value the output stage decides on (tests/test_oracle_cpu.py checks the premise)."""
+    p = eq_params_default()
+    for i in range(20):
+        p.bands[i].enabled = 0
+    b = p.bands[7]
+    b.frequency, b.gain, b.q, b.enabled, b.type, b.channelMode = 1000.0, 0.0, 1.41, 1, 1, channel_mode
+    p.nonlinearSaturation = saturation
+    return p
+
+
 def eq_process_stereo(xl, xr, params, sr=48000.0, block=512, state=None):
     yl = np.array(xl, dtype=np.float64, copy=True)
     yr = np.array(xr, dtype=np.float64, copy=True)

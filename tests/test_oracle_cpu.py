@@ -269,3 +269,17 @@ def test_oracle_passes_the_references_own_nuc_test(oracle, ir_len, block):
         h = oracle.heff(ir, block)
         m = min(len(h), total)
         assert np.abs(y[:m] - h[:m]).max() <= 1e-12
+
+
+def test_pass_band_is_bit_exact(oracle):
+    """The premise of the GPU threshold tests (test_gpu_cascade_edges.py): one enabled 0 dB peaking band passes its input
+    through bit for bit at saturation 0 below the clamp, in the stereo and the Left/Right arithmetic, so the exact boundary
+    values (4.5 and its ulp neighbours, +-100) reach the output stage's decisions unchanged."""
+    O = oracle
+    v = np.array([4.5, -4.5, np.nextafter(4.5, 0.0), np.nextafter(4.5, 9.0), -np.nextafter(4.5, 9.0), 4.6, -4.6, 100.0,
+                  -100.0, np.nextafter(100.0, 0.0), 0.3, -1e-300, 7.25])
+    x = np.tile(v, 50)
+    for mode in (0, 1):
+        yl, yr, _ = O.eq_process_stereo(x, x, O.eq_params_pass_band(0.0, mode))
+        assert np.array_equal(yl, x)
+        assert np.array_equal(yr, x)
