@@ -29,7 +29,7 @@ CPQ_PARTITION_AUTO = -1
 CPQ_ORDER_CONV_THEN_EQ = 0
 CPQ_ORDER_EQ_THEN_CONV = 1
 KERNEL_IDS = {"k_rfft_fwd_ols": 0, "k_fdl_mac": 1, "k_fdl_mac_dcnyq": 2, "k_rfft_inv_ols": 3, "k_svf_cascade": 4,
-              "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7}
+              "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8}
 CPQ_LEVEL_NUC = 0
 CPQ_LEVEL_PROCESSOR = 1
 CPQ_EQ_MODE_AUTO = 0
@@ -37,6 +37,8 @@ CPQ_EQ_MODE_SEQUENTIAL = 1
 CPQ_PHASE_AS_IS = 0
 CPQ_PHASE_MIXED = 1
 CPQ_PHASE_MINIMUM = 2
+CPQ_OS_IIR = 0
+CPQ_OS_LINEAR_PHASE = 1
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -98,6 +100,17 @@ class IrPrepared(C.Structure):
     _fields_ = [("ir", IrBuffer), ("scale", IrScale), ("ir_peak_latency", C.c_int32), ("reserved", C.c_int32)]
 
 
+class OsStageInfo(C.Structure):
+    _fields_ = [("taps", C.c_int32), ("center_tap", C.c_int32), ("center_parity", C.c_int32), ("conv_parity", C.c_int32),
+                ("conv_count", C.c_int32), ("center_delay_input", C.c_int32), ("history_up_keep", C.c_int32),
+                ("history_down_keep", C.c_int32), ("attenuation_db", C.c_double), ("center_coeff", C.c_double)]
+
+
+class OsTelemetry(C.Structure):
+    _fields_ = [("corruption_events", C.c_uint64), ("auto_clears", C.c_uint64), ("consecutive_auto_clears", C.c_int32),
+                ("hard_fallback", C.c_int32), ("corruption_pending", C.c_int32), ("reserved", C.c_int32)]
+
+
 class EngineDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("n_streams", C.c_int32),
                 ("block_size", C.c_int32), ("max_ir_len", C.c_int32), ("max_blocks_per_call", C.c_int32),
@@ -156,6 +169,16 @@ SYMBOLS = {
     "cpq_engine_set_conv_bypass": (C.c_int32, [_E, C.c_int32]),
     "cpq_engine_process_block": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32]),
     "cpq_engine_process_block_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
+    "cpq_os_resolve_factor": (C.c_int32, [C.c_double, C.c_int32]),
+    "cpq_os_design_stage": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(OsStageInfo), c_double_p, C.c_int32]),
+    "cpq_os_latency": (C.c_double, [C.c_int32, C.c_int32]),
+    "cpq_engine_set_oversampling": (C.c_int32, [_E, C.c_int32, C.c_int32]),
+    "cpq_os_up": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32]),
+    "cpq_os_up_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
+    "cpq_os_down": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32]),
+    "cpq_os_down_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
+    "cpq_os_reset": (C.c_int32, [_E]),
+    "cpq_os_read_telemetry": (C.c_int32, [_E, C.c_int32, C.POINTER(OsTelemetry)]),
     "cpq_ir_load_wav": (C.c_int32, [C.c_char_p, C.POINTER(IrBuffer)]),
     "cpq_ir_buffer_free": (None, [C.POINTER(IrBuffer)]),
     "cpq_ir_prepare": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_float, C.c_int32, C.POINTER(IrBuffer), C.c_double, C.POINTER(IrPrepared)]),

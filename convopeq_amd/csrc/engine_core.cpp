@@ -141,6 +141,7 @@ const char* cpq_kernel_name(int32_t id)
         case CPQ_K_SVF_TP: return "k_svf_cascade_tp";
         case CPQ_K_MIX: return "k_convproc_mix";
         case CPQ_K_OUTFILT: return "k_outfilter_cascade";
+        case CPQ_K_OS: return "k_os_halfband";
         default: return "?";
     }
 }
@@ -464,6 +465,9 @@ void cpq_engine_destroy(cpq_engine* e)
         for (int i = 0; i < 4; ++i) { (void)hipEventDestroy(e->evIn[i]); (void)hipEventDestroy(e->evDone[i]); }
     }
     if (e->arena) (void)hipFree(e->arena);
+    freeOversampler(e);
+    for (void* p : { (void*)e->osFlags, (void*)e->osCounts, (void*)e->osNonSilent, (void*)e->osTmp[0], (void*)e->osTmp[1], (void*)e->osWork })
+        if (p) (void)hipFree(p);
     for (double* p : { e->stageIn, e->stageOut, e->mid, e->dryRing, e->latGains, e->layerOut, e->tailRing, e->agcState, e->agcRmsIn, e->agcRmsOut, e->agcGains }) if (p) (void)hipFree(p);
     if (e->agcOn) (void)hipFree(e->agcOn);
     if (e->rampOn) (void)hipFree(e->rampOn);
@@ -514,6 +518,8 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
     if (sampleRate <= 0.0) return fail(e, CPQ_ERR_INVALID_ARG, "sample rate must be positive");
     if (maxBlock <= 0 || maxBlock > e->maxCall)
         return fail(e, CPQ_ERR_INVALID_ARG, "max_block %d exceeds block_size*max_blocks_per_call", maxBlock);
+    if (e->osFactor > 1 && sampleRate > 768000.0)
+        return fail(e, CPQ_ERR_INVALID_ARG, "processing rate %.1f Hz above 768 kHz with oversampling factor %d", sampleRate, e->osFactor);
     const bool rateChanged = sampleRate != e->sampleRate;
     e->sampleRate = sampleRate;
     if (rateChanged) {
@@ -551,6 +557,10 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
         r.remaining = 0;
     }
     for (auto& r : e->gainRamp) { r.current = r.target = r.wanted; r.step = 0.0; r.remaining = 0; }   // setCurrentAndTargetValue (Core.cpp:765)
+    {   // oversampling.prepare -> release(): histories and flags cleared, counters kept
+        const int rc = resetOversampler(e);
+        if (rc != CPQ_OK) return rc;
+    }
     return zeroRuntimeState(e, true, true);
 }
 
@@ -574,8 +584,10 @@ int32_t cpq_engine_set_order(cpq_engine* e, int32_t order)
 }
 
 
+}  // extern "C"
+
 // ------------------------------------------------------------------------ whole path
-static int enqueueBoth(cpq_engine* e, const double* a, double* b, int n)
+int cpqi::enqueueBoth(cpq_engine* e, const double* a, double* b, int n)
 {
     int rc = CPQ_OK;
     auto conv = [e](const double* x, double* y, int t) {
@@ -619,6 +631,8 @@ static int enqueueBoth(cpq_engine* e, const double* a, double* b, int n)
     return rc;
 }
 
+extern "C" {
+
 int32_t cpq_engine_set_gains(cpq_engine* e, int32_t stream, double convInputTrimGain, double outputMakeupGain)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
@@ -657,6 +671,15 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed)
 
 int32_t cpq_engine_process_block_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
+    if (e && e->osFactor > 1) {             // n_samples are base-rate samples: the routing runs on n_samples * factor
+        if (nSamples > e->maxCall / e->osFactor)
+            return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
+                        e->osFactor, e->maxCall);
+        const int rc = checkCall(e, dIn, dOut, nSamples * e->osFactor);
+        if (rc != CPQ_OK) return rc;
+        CPQ_HIP(e, hipSetDevice(e->device));
+        return enqueueOsChain(e, dIn, dOut, nSamples);
+    }
     const int rc = checkCall(e, dIn, dOut, nSamples);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
@@ -665,6 +688,13 @@ int32_t cpq_engine_process_block_device(cpq_engine* e, const double* dIn, double
 
 int32_t cpq_engine_process_block(cpq_engine* e, const double* in, double* out, int32_t nSamples)
 {
+    if (e && e->osFactor > 1) {
+        if (nSamples > e->maxCall / e->osFactor)
+            return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
+                        e->osFactor, e->maxCall);
+        return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return enqueueOsChain(e, a, b, n); },
+                          e->osFactor);
+    }
     return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return enqueueBoth(e, a, b, n); });
 }
 

@@ -280,6 +280,24 @@ struct cpq_engine {
     double* latGains = nullptr;     // [streams][latCap]
     int latCap = 0;
 
+    // half-band oversampler (engine_os.cpp): CustomInputOversampler around the routing
+    struct OsStageDev {
+        int convCount = 0, upKeep = 0, downKeep = 0, centerTap = 0, centerDelay = 0;
+        double centerCoeff = 0.5;
+        double* coef = nullptr;                 // [convCount] device
+        double* up[2] = { nullptr, nullptr };   // [nCh][upKeep] ping-pong
+        double* down[2] = { nullptr, nullptr }; // [nCh][downKeep] ping-pong
+        int upSel = 0, downSel = 0;             // the current history of each direction
+    };
+    int osFactor = 1, osType = CPQ_OS_IIR, osStages = 0;
+    OsStageDev osStage[3];
+    char* osMem = nullptr;                      // coefficients and histories of the stages
+    int* osFlags = nullptr;                     // [streams][4] device (os_kernels.hip)
+    unsigned long long* osCounts = nullptr;     // [streams][2] device
+    int* osNonSilent = nullptr;                 // [3][nCh] device: silence test of each down stage
+    double* osTmp[2] = { nullptr, nullptr };    // [nCh][maxCall / 2] stage-to-stage buffers (allocated on first use)
+    double* osWork = nullptr;                   // [nCh][tMax * P] the routing's block at the internal rate
+
     // profiling
     bool profiling = false;
     ProfileSlot prof[CPQ_K_COUNT];
@@ -349,6 +367,12 @@ int enqueueConv(cpq_engine* e, const double* dIn, double* dOut, int n);
 // engine_proc.cpp
 int uploadProcParams(cpq_engine* e);
 int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n);
+// engine_os.cpp
+void freeOversampler(cpq_engine* e);
+int resetOversampler(cpq_engine* e);            // reset(): histories and flags, not the counters
+int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase);
+// engine_core.cpp: DSPCore's routing of one block (conv / EQ in the configured order, output filter, makeup)
+int enqueueBoth(cpq_engine* e, const double* a, double* b, int n);
 // engine_eq.cpp
 void syncEqBypass(cpq_engine* e);
 int enqueueEq(cpq_engine* e, const double* dIn, double* dOut, int n);
@@ -358,17 +382,19 @@ int enqueueOutFilter(cpq_engine* e, const double* dIn, double* dOut, int n);
 // engine call: the state carries over on the engine's stream) so that the upload of chunk i+1 and the download of chunk
 // i-1 run on two copy streams beside the kernels of chunk i.  With pinned caller buffers (cpq_host_register) the three
 // overlap; pageable buffers take the plain upload / kernels / download sequence.
+// factor > 1 (oversampled routing): the caller's nSamples are base-rate samples, checked and partitioned at nSamples * factor,
+// so every chunk is whole internal partitions; body receives base-rate chunk lengths.
 template <typename F>
-int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& body)
+int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& body, int factor = 1)
 {
-    int rc = checkCall(e, in, out, nSamples);
+    int rc = checkCall(e, in, out, nSamples * factor);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
     rc = ensureCallBuffer(e, &e->stageIn, "upload staging");
     if (rc == CPQ_OK) rc = ensureCallBuffer(e, &e->stageOut, "download staging");
     if (rc != CPQ_OK) return rc;
     constexpr int kChunks = 4;
-    const int T = nSamples / e->P;                                      // partitions in the call (whole ones outside CPQ_CALLS_ANY)
+    const int T = nSamples * factor / e->P;                             // partitions in the call (whole ones outside CPQ_CALLS_ANY)
     auto pinned = [](const void* p) {
         hipPointerAttribute_t a{};
         if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain malloc'd memory
@@ -394,7 +420,7 @@ int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& b
         }
     }
     const int chunkT = T / kChunks;
-    const size_t chunkLen = (size_t)chunkT * e->P;                       // samples per channel and chunk
+    const size_t chunkLen = (size_t)chunkT * e->P / factor;              // samples per channel and chunk
     const size_t hostPitch = (size_t)nSamples * sizeof(double), devPitch = chunkLen * sizeof(double);
     auto download = [&](int i) -> int {
         CPQ_HIP(e, hipStreamWaitEvent(e->copyOut, e->evDone[i], 0));

@@ -1,0 +1,298 @@
+// engine_os.cpp -- the half-band oversampler around the routing (CustomInputOversampler, src/CustomInputOversampler.cpp, as
+// DSPCore::processDouble runs it: processUp, the chain at F x the rate, processDown; DSPCoreDouble.cpp:359-376, :477-531).
+// The stage kernels, guards and per-stream state machine are in os_kernels.hip; the host sizes the buffers, uploads the
+// coefficients and flips the history ping-pong selectors.
+#include "engine_internal.hpp"
+
+namespace cpqi {
+
+void freeOversampler(cpq_engine* e)
+{
+    if (e->osMem) (void)hipFree(e->osMem);
+    e->osMem = nullptr;
+    for (auto& s : e->osStage) s = cpq_engine::OsStageDev{};
+    e->osStages = 0;
+}
+
+int resetOversampler(cpq_engine* e)
+{
+    if (!e->osFlags) return CPQ_OK;
+    CPQ_HIP(e, hipSetDevice(e->device));
+    for (int i = 0; i < e->osStages; ++i) {
+        auto& s = e->osStage[i];
+        for (int b = 0; b < 2; ++b) {
+            CPQ_HIP(e, hipMemsetAsync(s.up[b], 0, sizeof(double) * (size_t)e->nCh * s.upKeep, e->stream));
+            CPQ_HIP(e, hipMemsetAsync(s.down[b], 0, sizeof(double) * (size_t)e->nCh * s.downKeep, e->stream));
+        }
+        s.upSel = s.downSel = 0;
+    }
+    CPQ_HIP(e, hipMemsetAsync(e->osFlags, 0, sizeof(int) * 4 * (size_t)e->desc.n_streams, e->stream));
+    return CPQ_OK;
+}
+
+static int ensureOsTmp(cpq_engine* e)
+{
+    for (double*& p : e->osTmp) {
+        if (p) continue;
+        const size_t bytes = sizeof(double) * (size_t)e->nCh * (size_t)(e->maxCall / 2);
+        if (hipMalloc((void**)&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return fail(e, CPQ_ERR_OOM, "oversampler stage buffer of %zu bytes could not be allocated", bytes);
+        }
+    }
+    return CPQ_OK;
+}
+
+static cpq::OsStageArgs stageArgs(cpq_engine* e, int i)
+{
+    const auto& s = e->osStage[i];
+    cpq::OsStageArgs a{};
+    a.coef = s.coef;
+    a.convCount = s.convCount;
+    a.centerCoeff = s.centerCoeff;
+    a.nCh = e->nCh;
+    a.flags = e->osFlags;
+    a.counts = e->osCounts;
+    return a;
+}
+
+// processUp: in [nCh][inStride] (nBase samples) -> out [nCh][outStride] (nBase * F samples)
+static int enqueueUp(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+{
+    if (e->osStages > 1) { const int rc = ensureOsTmp(e); if (rc != CPQ_OK) return rc; }
+    ProfScope p(e, CPQ_K_OS);
+    const double* src = in;
+    int64_t srcStride = inStride;
+    int n = nBase;
+    for (int i = 0; i < e->osStages; ++i) {
+        auto& s = e->osStage[i];
+        const bool last = i == e->osStages - 1;
+        double* dst = last ? out : e->osTmp[i & 1];
+        const int64_t dstStride = last ? outStride : 2 * (int64_t)n;
+        cpq::OsStageArgs a = stageArgs(e, i);
+        a.in = src; a.inStride = srcStride; a.out = dst; a.outStride = dstStride;
+        a.histOld = s.up[s.upSel]; a.histNew = s.up[s.upSel ^ 1]; a.keep = s.upKeep;
+        a.centerOffset = s.centerDelay;
+        a.n = n;
+        cpq::launch_os_interp(e->stream, a);
+        s.upSel ^= 1;
+        src = dst; srcStride = dstStride; n *= 2;
+    }
+    CPQ_HIP(e, hipGetLastError());
+    return CPQ_OK;
+}
+
+// processDown: in [nCh][inStride] (nBase * F samples) -> out [nCh][outStride] (nBase samples)
+static int enqueueDown(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+{
+    if (e->osStages > 1) { const int rc = ensureOsTmp(e); if (rc != CPQ_OK) return rc; }
+    ProfScope p(e, CPQ_K_OS);
+    cpq::OsHistories hs{};
+    for (int i = 0; i < e->osStages; ++i) {
+        const auto& s = e->osStage[i];
+        hs.up[i] = s.up[s.upSel];
+        hs.down[i] = s.down[s.downSel];
+        hs.upKeep[i] = s.upKeep;
+        hs.downKeep[i] = s.downKeep;
+    }
+    cpq::launch_os_down_state(e->stream, hs, e->osStages, e->desc.n_streams, e->osFlags, e->osCounts, e->osNonSilent);
+    const int top = e->osStages - 1;
+    int n = nBase << top;                                   // outputs of the top stage
+    cpq::launch_os_scan(e->stream, in, inStride, 2 * n, e->nCh, e->osNonSilent + (size_t)top * e->nCh);
+    const double* src = in;
+    int64_t srcStride = inStride;
+    for (int i = top; i >= 0; --i) {
+        auto& s = e->osStage[i];
+        double* dst = i == 0 ? out : e->osTmp[i & 1];
+        const int64_t dstStride = i == 0 ? outStride : (int64_t)n;
+        cpq::OsStageArgs a = stageArgs(e, i);
+        a.in = src; a.inStride = srcStride; a.out = dst; a.outStride = dstStride;
+        a.histOld = s.down[s.downSel]; a.histNew = s.down[s.downSel ^ 1]; a.keep = s.downKeep;
+        a.centerOffset = s.centerTap;
+        a.n = n;
+        cpq::launch_os_decim(e->stream, a, e->osNonSilent + (size_t)i * e->nCh,
+                             i > 0 ? e->osNonSilent + (size_t)(i - 1) * e->nCh : nullptr);
+        s.downSel ^= 1;
+        src = dst; srcStride = dstStride; n /= 2;
+    }
+    CPQ_HIP(e, hipGetLastError());
+    return CPQ_OK;
+}
+
+// whole path with factor > 1: up -> routing on nBase * F samples in the internal work buffer (in place) -> down
+int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase)
+{
+    int rc = ensureCallBuffer(e, &e->osWork, "oversampled block");
+    if (rc != CPQ_OK) return rc;
+    const int n = nBase * e->osFactor;
+    rc = enqueueUp(e, dIn, nBase, e->osWork, n, nBase);
+    if (rc == CPQ_OK) rc = enqueueBoth(e, e->osWork, e->osWork, n);
+    if (rc == CPQ_OK) rc = enqueueDown(e, e->osWork, n, dOut, nBase, nBase);
+    return rc;
+}
+
+}  // namespace cpqi
+
+using namespace cpqi;
+
+// the stand-alone entry points: nBase * F within the engine's call limit, 16-byte aligned buffers
+static int checkOsCall(cpq_engine* e, const void* in, const void* out, int nBase)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    if (e->osFactor == 1) return fail(e, CPQ_ERR_NOT_READY, "oversampling is not set (factor 1)");
+    if (!in || !out) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (nBase <= 0 || nBase > e->maxCall / e->osFactor)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_base=%d outside 1..%d (n_base * factor beyond the call limit %d)", nBase,
+                    e->maxCall / e->osFactor, e->maxCall);
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
+        return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    return CPQ_OK;
+}
+
+template <typename F>
+static int osHost(cpq_engine* e, const double* in, double* out, int nBase, size_t inLen, size_t outLen, F&& body)
+{
+    int rc = checkOsCall(e, in, out, nBase);
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipSetDevice(e->device));
+    rc = ensureCallBuffer(e, &e->stageIn, "upload staging");
+    if (rc == CPQ_OK) rc = ensureCallBuffer(e, &e->stageOut, "download staging");
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, sizeof(double) * (size_t)e->nCh * inLen, hipMemcpyHostToDevice, e->stream));
+    rc = body(e->stageIn, e->stageOut);
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipMemcpyAsync(out, e->stageOut, sizeof(double) * (size_t)e->nCh * outLen, hipMemcpyDeviceToHost, e->stream));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    return CPQ_OK;
+}
+
+extern "C" {
+
+int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    const int nStages = cpq::osStagesFor(factor);
+    if (nStages < 0) return fail(e, CPQ_ERR_INVALID_ARG, "oversampling factor %d is not 1, 2, 4 or 8", factor);
+    if (type != CPQ_OS_IIR && type != CPQ_OS_LINEAR_PHASE) return fail(e, CPQ_ERR_INVALID_ARG, "oversampling type %d", type);
+    if (factor > 1 && e->anyCalls && e->B % factor != 0)
+        return fail(e, CPQ_ERR_INVALID_ARG, "block_size %d is not a multiple of the oversampling factor %d", e->B, factor);
+    if (factor > 1 && e->sampleRate > 768000.0)
+        return fail(e, CPQ_ERR_INVALID_ARG, "processing rate %.1f Hz above 768 kHz (OversamplingPolicy::kMaxInternalRate)", e->sampleRate);
+    CPQ_HIP(e, hipSetDevice(e->device));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    freeOversampler(e);
+    const int S = e->desc.n_streams;
+    if (!e->osFlags) {
+        if (hipMalloc((void**)&e->osFlags, sizeof(int) * 4 * S) != hipSuccess ||
+            hipMalloc((void**)&e->osCounts, sizeof(unsigned long long) * 2 * S) != hipSuccess ||
+            hipMalloc((void**)&e->osNonSilent, sizeof(int) * 3 * e->nCh) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e, CPQ_ERR_OOM, "oversampler state could not be allocated");
+        }
+    }
+    CPQ_HIP(e, hipMemset(e->osCounts, 0, sizeof(unsigned long long) * 2 * S));
+    CPQ_HIP(e, hipMemset(e->osFlags, 0, sizeof(int) * 4 * S));
+    e->osFactor = factor;
+    e->osType = type;
+    if (nStages == 0) return CPQ_OK;
+    cpq::OsStage st[3];
+    size_t bytes = 0;
+    for (int i = 0; i < nStages; ++i) {
+        cpq::osDesignStage(i, type, st[i]);
+        if (!cpq::os_conv_count_supported(st[i].convCount) || st[i].convParity != 0 || st[i].historyUpKeep < st[i].convCount - 1 ||
+            st[i].historyDownKeep < 2 * (st[i].convCount - 1) || st[i].historyDownKeep < st[i].centerTap) {
+            e->osFactor = 1;
+            return fail(e, CPQ_ERR_UNSUPPORTED, "stage %d geometry not supported by the kernels", i);
+        }
+        bytes += (size_t)alignUp(st[i].convCount, 32) + 2 * (size_t)e->nCh * (alignUp(st[i].historyUpKeep, 32) + alignUp(st[i].historyDownKeep, 32));
+    }
+    if (hipMalloc((void**)&e->osMem, bytes * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        e->osMem = nullptr;
+        e->osFactor = 1;
+        return fail(e, CPQ_ERR_OOM, "oversampler histories of %zu bytes could not be allocated", bytes * sizeof(double));
+    }
+    double* p = reinterpret_cast<double*>(e->osMem);
+    for (int i = 0; i < nStages; ++i) {
+        auto& d = e->osStage[i];
+        d.convCount = st[i].convCount;
+        d.upKeep = st[i].historyUpKeep;
+        d.downKeep = st[i].historyDownKeep;
+        d.centerTap = st[i].centerTap;
+        d.centerDelay = st[i].centerDelayInput;
+        d.centerCoeff = st[i].centerCoeff;
+        d.coef = p; p += alignUp(d.convCount, 32);
+        CPQ_HIP(e, hipMemcpy(d.coef, st[i].conv.data(), sizeof(double) * d.convCount, hipMemcpyHostToDevice));
+        for (int b = 0; b < 2; ++b) { d.up[b] = p; p += (size_t)e->nCh * alignUp(d.upKeep, 32); }
+        for (int b = 0; b < 2; ++b) { d.down[b] = p; p += (size_t)e->nCh * alignUp(d.downKeep, 32); }
+    }
+    e->osStages = nStages;
+    const int rc = resetOversampler(e);
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    return CPQ_OK;
+}
+
+int32_t cpq_os_up_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nBase)
+{
+    const int rc = checkOsCall(e, dIn, dOut, nBase);
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipSetDevice(e->device));
+    return enqueueUp(e, dIn, nBase, dOut, (int64_t)nBase * e->osFactor, nBase);
+}
+
+int32_t cpq_os_down_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nBase)
+{
+    const int rc = checkOsCall(e, dIn, dOut, nBase);
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipSetDevice(e->device));
+    return enqueueDown(e, dIn, (int64_t)nBase * e->osFactor, dOut, nBase, nBase);
+}
+
+int32_t cpq_os_up(cpq_engine* e, const double* in, double* out, int32_t nBase)
+{
+    const size_t nOut = e ? (size_t)nBase * e->osFactor : 0;
+    return osHost(e, in, out, nBase, (size_t)nBase, nOut, [&](const double* a, double* b) {
+        return enqueueUp(e, a, nBase, b, (int64_t)nOut, nBase);
+    });
+}
+
+int32_t cpq_os_down(cpq_engine* e, const double* in, double* out, int32_t nBase)
+{
+    const size_t nIn = e ? (size_t)nBase * e->osFactor : 0;
+    return osHost(e, in, out, nBase, nIn, (size_t)nBase, [&](const double* a, double* b) {
+        return enqueueDown(e, a, (int64_t)nIn, b, nBase, nBase);
+    });
+}
+
+int32_t cpq_os_reset(cpq_engine* e)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    const int rc = resetOversampler(e);
+    if (rc != CPQ_OK) return rc;
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    return CPQ_OK;
+}
+
+int32_t cpq_os_read_telemetry(cpq_engine* e, int32_t stream, cpq_os_telemetry* out)
+{
+    if (!e || !out) return CPQ_ERR_INVALID_ARG;
+    if (stream < 0 || stream >= e->desc.n_streams) return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    *out = cpq_os_telemetry{};
+    if (!e->osFlags) return CPQ_OK;
+    CPQ_HIP(e, hipSetDevice(e->device));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    unsigned long long c[2];
+    int f[4];
+    CPQ_HIP(e, hipMemcpy(c, e->osCounts + 2 * stream, sizeof(c), hipMemcpyDeviceToHost));
+    CPQ_HIP(e, hipMemcpy(f, e->osFlags + 4 * stream, sizeof(f), hipMemcpyDeviceToHost));
+    out->corruption_events = c[0];
+    out->auto_clears = c[1];
+    out->corruption_pending = f[0];
+    out->consecutive_auto_clears = f[1];
+    out->hard_fallback = f[2];
+    return CPQ_OK;
+}
+
+}  // extern "C"

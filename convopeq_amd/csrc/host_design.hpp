@@ -34,4 +34,15 @@ bool   buildSvfTpTables(const cpq_svf_coeffs& c, double* out);
 bool   buildBiquadTpTables(const cpq_biquad_coeffs& q, double* out);
 void   designOutputFilter(int convIsLast, int hcMode, int lcMode, int lpMode, double fs, cpq_biquad_coeffs out[3]);
 
+// one half-band stage of the oversampler (os_design.cpp; CustomInputOversampler::prepareStage)
+struct OsStage {
+    int taps = 0, centerTap = 0, centerParity = 0, convParity = 0, convCount = 0;
+    int centerDelayInput = 0, historyUpKeep = 0, historyDownKeep = 0;
+    double attenuationDb = 0.0, centerCoeff = 0.0;
+    std::vector<double> raw;        // [taps]
+    std::vector<double> conv;       // [convCount] raw[convParity + 2 r]
+};
+bool   osDesignStage(int stage, int type, OsStage& out);
+int    osStagesFor(int factor);     // 1/2/4/8 -> 0/1/2/3 stages, else -1
+
 }  // namespace cpq

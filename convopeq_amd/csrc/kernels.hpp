@@ -191,4 +191,40 @@ void launch_direct_head(hipStream_t stream, const double* in, int64_t inStride, 
                         const int* wetOn = nullptr);
 void launch_rows_add(hipStream_t stream, double* out, int64_t outStride, const double* add, int n, int nCh);
 
+// ---- half-band oversampler (os_kernels.hip)
+// per stream: flags[4] = corruption pending, consecutive auto-clears, hard fallback, silenced in this down call;
+// counts[2] = corruption events, auto-clears
+struct OsStageArgs {
+    const double* in; int64_t inStride;          // [nCh] rows
+    double* out; int64_t outStride;
+    const double* histOld; double* histNew;      // [nCh][keep] current / next history (ping-pong)
+    int keep;
+    const double* coef;                          // [convCount] device
+    int convCount;                               // 16 .. 512, a power of two
+    double centerCoeff;
+    int centerOffset;                            // up: centerDelayInput; down: centerTap
+    int n;                                       // input-rate outputs per channel: up = input samples, down = output samples
+    int nCh;
+    int* flags;
+    unsigned long long* counts;
+};
+// the histories a down call's prologue clears / tests: current up and down history of every stage
+struct OsHistories {
+    double* up[3];
+    double* down[3];
+    int upKeep[3];
+    int downKeep[3];
+};
+bool os_conv_count_supported(int convCount);
+// interpolateStage for every channel: out[c][2n], out[c][2n + 1] from in[c][n]
+void launch_os_interp(hipStream_t stream, const OsStageArgs& a);
+// decimateStage for every channel: out[c][n] from in[c][2n]; nonSilent[c] == 0 takes the silence path; a nonzero output
+// sets nonSilentNext[c] (the next, lower stage's input test; may be null)
+void launch_os_decim(hipStream_t stream, const OsStageArgs& a, const int* nonSilent, int* nonSilentNext);
+// processDown's per-stream prologue (auto-clear, hard fallback, clearAllStages) + nonSilent[stage][c] = history test
+void launch_os_down_state(hipStream_t stream, const OsHistories& hs, int nStages, int nStreams, int* flags,
+                          unsigned long long* counts, int* nonSilent);
+// nonSilent[c] |= any |in[c][0..m)| > 1e-20
+void launch_os_scan(hipStream_t stream, const double* in, int64_t stride, int m, int nCh, int* nonSilent);
+
 }  // namespace cpq

@@ -62,6 +62,35 @@ def outfilter_design(conv_is_last, hc_mode, lc_mode, lp_mode, sr):
     return list(out)
 
 
+def os_resolve_factor(base_rate, requested=0):
+    """cpq_os_resolve_factor (OversamplingPolicy::resolve): requested 0 = Auto; 0 returned = rate not supported."""
+    rc = K.load().cpq_os_resolve_factor(float(base_rate), int(requested))
+    if rc < 0:
+        raise CpqError(rc, "cpq_os_resolve_factor")
+    return rc
+
+
+def os_design_stage(stage, os_type=K.CPQ_OS_IIR):
+    """cpq_os_design_stage: (info dict, raw taps float64) of one half-band stage."""
+    info = K.OsStageInfo()
+    n = K.load().cpq_os_design_stage(stage, os_type, C.byref(info), None, 0)
+    if n < 0:
+        raise CpqError(n, "cpq_os_design_stage")
+    taps = np.zeros(n, dtype=np.float64)
+    rc = K.load().cpq_os_design_stage(stage, os_type, None, _dp(taps), n)
+    if rc < 0:
+        raise CpqError(rc, "cpq_os_design_stage")
+    return {f: getattr(info, f) for f, _ in K.OsStageInfo._fields_}, taps
+
+
+def os_latency(factor, os_type=K.CPQ_OS_IIR):
+    """cpq_os_latency: round-trip latency in base-rate samples (not an integer in general)."""
+    v = K.load().cpq_os_latency(int(factor), int(os_type))
+    if v < 0:
+        raise CpqError(int(v), "cpq_os_latency")
+    return v
+
+
 def eq_params_default():
     p = K.EqParams()
     K.load().cpq_eq_params_default(C.byref(p))
@@ -166,6 +195,7 @@ class BatchedEngine:
         self.n_streams = n_streams
         self.n_channels = 2 * n_streams
         self.block_size = block_size
+        self.os_factor = 1
 
     def close(self):
         if getattr(self, "_h", None):
@@ -272,6 +302,41 @@ class BatchedEngine:
         self._ck(self._lib.cpq_conv_get_plan(self._h, C.byref(p)))
         return p
 
+    # ---- oversampling (CustomInputOversampler around the routing)
+    def set_oversampling(self, factor, os_type=K.CPQ_OS_IIR):
+        self._ck(self._lib.cpq_engine_set_oversampling(self._h, int(factor), int(os_type)))
+        self.os_factor = int(factor)
+
+    def os_up(self, x):
+        """processUp: [n_channels, n] -> [n_channels, n * factor]"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.ndim == 2 and x.shape[0] == self.n_channels
+        y = np.empty((self.n_channels, x.shape[1] * self.os_factor), dtype=np.float64)
+        self._ck(self._lib.cpq_os_up(self._h, _dp(x), _dp(y), x.shape[1]))
+        return y
+
+    def os_down(self, x):
+        """processDown: [n_channels, n * factor] -> [n_channels, n]"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.ndim == 2 and x.shape[0] == self.n_channels and x.shape[1] % self.os_factor == 0
+        y = np.empty((self.n_channels, x.shape[1] // self.os_factor), dtype=np.float64)
+        self._ck(self._lib.cpq_os_down(self._h, _dp(x), _dp(y), y.shape[1]))
+        return y
+
+    def os_up_device(self, d_in, d_out, n_base):
+        self._ck(self._lib.cpq_os_up_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_base))
+
+    def os_down_device(self, d_in, d_out, n_base):
+        self._ck(self._lib.cpq_os_down_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_base))
+
+    def os_reset(self):
+        self._ck(self._lib.cpq_os_reset(self._h))
+
+    def os_telemetry(self, stream):
+        t = K.OsTelemetry()
+        self._ck(self._lib.cpq_os_read_telemetry(self._h, stream, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in K.OsTelemetry._fields_ if f != "reserved"}
+
     # ---- host-buffer processing: x is [n_channels, n_samples] float64
     def _host(self, fn, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -312,6 +377,8 @@ class BatchedEngine:
             n = C.c_int64()
             ms = C.c_double()
             self._ck(self._lib.cpq_profile_read(self._h, kid, C.byref(n), C.byref(ms)))
+            if name == "k_os_halfband" and n.value == 0:
+                continue        # listed only for engines that oversample
             out[name] = (n.value, ms.value)
         return out
 

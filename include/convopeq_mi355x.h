@@ -370,6 +370,76 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed);
 int32_t cpq_engine_process_block(cpq_engine* e, const double* in, double* out, int32_t n_samples);
 int32_t cpq_engine_process_block_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_samples);
 
+/* ------------------------------------------------------------- oversampling */
+/* CustomInputOversampler (src/CustomInputOversampler.{h,cpp}) around the processing chain, as DSPCore::processDouble
+ * runs it (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:359-376, :477-531): a cascade of 1..3 Kaiser
+ * half-band FIR stages up, the chain at F x the base rate, the same stages down in reverse order.
+ * Stage 0 works at the base rate.  Presets: IIRLike 511/127/31 taps (140/110/90 dB), LinearPhase 1023/255/63 taps
+ * (160/140/120 dB). */
+typedef enum { CPQ_OS_IIR = 0, CPQ_OS_LINEAR_PHASE = 1 } cpq_os_type;
+
+/* One stage as prepareStage designs it (src/CustomInputOversampler.cpp:287-390). */
+typedef struct {
+    int32_t taps;                    /* raw taps (odd) */
+    int32_t center_tap;              /* (taps - 1) / 2 */
+    int32_t center_parity;           /* center_tap & 1 */
+    int32_t conv_parity;             /* 1 - center_parity */
+    int32_t conv_count;              /* taps of the polyphase FIR branch: raw[conv_parity + 2 r] */
+    int32_t center_delay_input;      /* (center_tap - center_parity) / 2, input-rate samples */
+    int32_t history_up_keep;         /* max(conv_count - 1, center_delay_input) */
+    int32_t history_down_keep;       /* max(center_tap, conv_parity + 2 (conv_count - 1) + 6) */
+    double  attenuation_db;
+    double  center_coeff;            /* 0.5 */
+} cpq_os_stage_info;
+
+/* OversamplingPolicy::resolve (src/audioengine/OversamplingPolicy.h:36-85) for a base (input) rate: requested 0 = Auto
+ * (the largest allowed factor), 1/2/4/8 = capped at the largest allowed factor, anything else = Auto.  Returns the
+ * resolved factor, 0 when the rate is above 768 kHz (not supported), < 0 for a rate that is not positive and finite.
+ * Host only. */
+int32_t cpq_os_resolve_factor(double base_rate, int32_t requested);
+/* prepareStage for stage 0..2 and a cpq_os_type: fills info (may be NULL) and, when taps is not NULL, the raw tap array
+ * (info.taps values; capacity must hold them).  Returns the tap count or < 0.  Host only. */
+int32_t cpq_os_design_stage(int32_t stage, int32_t type, cpq_os_stage_info* info, double* taps, int32_t capacity);
+/* Round trip (up then down) latency in base-rate samples: sum over the stages i of 2 center_tap_i / 2^(i+1)
+ * (290.25 for 8x IIR, 582.25 for 8x LinearPhase; 0 for factor 1).  < 0 for a bad factor or type.  Host only. */
+double  cpq_os_latency(int32_t factor, int32_t type);
+
+/* DSPCore::prepare's oversampling.prepare(...) (DSPCoreLifecycle.cpp:114-138, :182-192): factor 1, 2, 4 or 8 and a
+ * cpq_os_type.  The engine descriptor and cpq_engine_prepare keep describing the PROCESSING domain (conv and EQ run
+ * at the engine's sample rate, as DSPCore prepares them at sampleRate * factor); the base rate is sample_rate / factor.
+ * Resets the oversampler's histories, flags and counters; touches no convolver / EQ state.
+ * CPQ_ERR_INVALID_ARG: bad factor or type, a CPQ_CALLS_ANY engine whose block_size is not a multiple of the factor,
+ * factor > 1 with a processing rate above 768 kHz.
+ * With factor > 1, cpq_engine_process_block[_device] takes n_base samples per channel and runs up -> the routing on
+ * n_base * factor samples -> down; the call limits apply to n_base * factor.  Factor 1 is the plain path. */
+int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type);
+/* processUp for every stream: in [channel][n_base] -> out [channel][n_base * factor].  The guards run on the device: a
+ * bad (non-finite or |v| > 2^53) FIR sum is replaced by 0, a bad centre value zeroes both outputs of its sample and
+ * flags the stream (one corruption event per sample).  A stream in hard fallback outputs silence and does not advance. */
+/* CPQ_ERR_NOT_READY while the factor is 1. */
+int32_t cpq_os_up(cpq_engine* e, const double* in, double* out, int32_t n_base);
+int32_t cpq_os_up_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_base);
+/* processDown for every stream: in [channel][n_base * factor] -> out [channel][n_base].  At the start of the call a
+ * flagged stream is cleared (one auto-clear; all histories of the stream zeroed; the block is silence); after 4
+ * consecutive auto-clears hard fallback latches.  Deviation from the reference: a stream in hard fallback outputs
+ * silence and does not advance its oversampler until cpq_os_reset, cpq_engine_prepare or cpq_engine_set_oversampling
+ * (the reference passes the base-rate block through a chain prepared for factor x the rate). */
+int32_t cpq_os_down(cpq_engine* e, const double* in, double* out, int32_t n_base);
+int32_t cpq_os_down_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_base);
+/* CustomInputOversampler::reset (src/CustomInputOversampler.cpp:452-467): histories, flags, consecutive count and hard
+ * fallback cleared; the event and auto-clear counters stay.  cpq_engine_prepare does the same. */
+int32_t cpq_os_reset(cpq_engine* e);
+/* per-stream counters of one stream; synchronises the engine's stream */
+typedef struct {
+    uint64_t corruption_events;      /* corruptionEventCount */
+    uint64_t auto_clears;            /* corruptionAutoClearCount */
+    int32_t  consecutive_auto_clears;
+    int32_t  hard_fallback;          /* hardFallbackActive */
+    int32_t  corruption_pending;     /* corruptionDetected: the next cpq_os_down silences the stream */
+    int32_t  reserved;
+} cpq_os_telemetry;
+int32_t cpq_os_read_telemetry(cpq_engine* e, int32_t stream, cpq_os_telemetry* out);
+
 /* ---------------------------------------------------------------- IR ingest (host only, no GPU needed) */
 /* Everything between an IR file and cpq_engine_set_impulse(): SURVEY.md N3.  One-off loader-thread work in the
  * reference; plain host code here. */
@@ -444,7 +514,8 @@ typedef enum {
     CPQ_K_SVF_TP   = 5,   /* the time-parallel cascade kernels (k_svf_cascade_tpv / _short; default) */
     CPQ_K_MIX      = 6,   /* k_convproc_mix (processor-level dry/wet stage) */
     CPQ_K_OUTFILT  = 7,   /* output-filter biquad cascade (k_svf_cascade_tp / k_svf_cascade running DF-II-T sections) */
-    CPQ_K_COUNT    = 8
+    CPQ_K_OS       = 8,   /* half-band oversampler stages, up and down (k_os_interp / k_os_decim and their helpers) */
+    CPQ_K_COUNT    = 9
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);
 int32_t     cpq_profile_reset(cpq_engine* e);

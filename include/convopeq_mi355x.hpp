@@ -5,6 +5,7 @@
 //   cpq::BatchedConvolver  ::SetImpulse / Add / Get / Reset / isReady / getLatency
 //        <- convo::MKLNonUniformConvolver (src/MKLNonUniformConvolver.h:197-242), one instance per mono channel
 //           in the reference, here one object for every channel of every stream
+//   cpq::BatchedOversampler ::prepare / processUp / processDown / reset   <- CustomInputOversampler (src/CustomInputOversampler.h)
 //   cpq::BatchedProcessor  ::prepareToPlay / process / setEqParameters / loadImpulse
 //        <- ConvolverProcessor::{prepareToPlay,process} (src/ConvolverProcessor.h:226,259) and
 //           EQProcessor::{prepareToPlay,process(block, params, cache)} (src/eqprocessor/EQProcessor.h:189-205)
@@ -234,6 +235,62 @@ private:
     }
     Engine& e_;
     std::vector<double> scratch_;
+    int status_ = CPQ_OK;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// CustomInputOversampler (src/CustomInputOversampler.h) for every stream of an engine: prepare / processUp / processDown /
+// reset.  The engine keeps describing the processing (oversampled) domain, as DSPCore prepares conv and EQ at
+// sampleRate * factor; processUp takes base-rate blocks, processDown returns them.  Host buffers, staged per call.
+class BatchedOversampler {
+public:
+    enum class Preset { IIRLike = CPQ_OS_IIR, LinearPhase = CPQ_OS_LINEAR_PHASE };
+    explicit BatchedOversampler(Engine& e) : e_(e) {}
+
+    // CustomInputOversampler::prepare(maxInputBlockSize, ratio, preset): ratio 1, 2, 4 or 8
+    bool prepare(int ratio, Preset preset = Preset::IIRLike)
+    {
+        status_ = cpq_engine_set_oversampling(e_.get(), ratio, static_cast<int32_t>(preset));
+        if (status_ == CPQ_OK) ratio_ = ratio;
+        return status_ == CPQ_OK;
+    }
+    int getOversamplingFactor() const noexcept { return ratio_; }
+    // in: numSamples base-rate samples per channel; out: numSamples * factor.  false (out zeroed) on failure
+    bool processUp(const AudioBlockBatch& in, AudioBlockBatch& out) { return run(in, out, true); }
+    // in: numSamples * factor per channel; out: numSamples (= in.numSamples / factor)
+    bool processDown(const AudioBlockBatch& in, AudioBlockBatch& out) { return run(in, out, false); }
+    void reset() { status_ = cpq_os_reset(e_.get()); }
+    bool telemetry(int stream, cpq_os_telemetry& t) { return (status_ = cpq_os_read_telemetry(e_.get(), stream, &t)) == CPQ_OK; }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return e_.lastError(); }
+
+private:
+    bool run(const AudioBlockBatch& in, AudioBlockBatch& out, bool up)
+    {
+        const int nBase = up ? in.numSamples : out.numSamples;
+        const int nIn = in.numSamples, nOut = out.numSamples;
+        if (in.numChannels != e_.channels() || out.numChannels != e_.channels() || nBase <= 0 ||
+            (up ? nOut != nIn * ratio_ : nIn != nOut * ratio_)) {
+            status_ = CPQ_ERR_INVALID_ARG;
+            clear(out);
+            return false;
+        }
+        scratchIn_.resize(static_cast<size_t>(e_.channels()) * nIn);
+        scratchOut_.resize(static_cast<size_t>(e_.channels()) * nOut);
+        for (int c = 0; c < in.numChannels; ++c) std::memcpy(scratchIn_.data() + static_cast<size_t>(c) * nIn, in.channels[c], sizeof(double) * nIn);
+        status_ = up ? cpq_os_up(e_.get(), scratchIn_.data(), scratchOut_.data(), nBase)
+                     : cpq_os_down(e_.get(), scratchIn_.data(), scratchOut_.data(), nBase);
+        if (status_ != CPQ_OK) { clear(out); return false; }
+        for (int c = 0; c < out.numChannels; ++c) std::memcpy(out.channels[c], scratchOut_.data() + static_cast<size_t>(c) * nOut, sizeof(double) * nOut);
+        return true;
+    }
+    static void clear(AudioBlockBatch& b)
+    {
+        for (int c = 0; c < b.numChannels; ++c) std::memset(b.channels[c], 0, sizeof(double) * b.numSamples);
+    }
+    Engine& e_;
+    std::vector<double> scratchIn_, scratchOut_;
+    int ratio_ = 1;
     int status_ = CPQ_OK;
 };
 
