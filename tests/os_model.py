@@ -90,6 +90,8 @@ class Oversampler:
         self.stages = [design_stage(i, os_type) for i in range({1: 0, 2: 1, 4: 2, 8: 3}[factor])]
         self.events = 0
         self.auto_clears = 0
+        self.silent_paths = 0                       # decimator calls that took the silence path (channels x stages)
+        self.silent_discards = 0                    # ... of those, the ones whose input or history held a non-zero value
         self.reset()
 
     def reset(self):
@@ -128,7 +130,9 @@ class Oversampler:
         hist = self.down_hist[i][ch]
         with np.errstate(invalid="ignore"):
             if not np.any(np.abs(x) > DENORM) and not np.any(np.abs(hist) > DENORM):
+                self.silent_discards += int(np.any(x != 0.0) or np.any(hist != 0.0))
                 self.down_hist[i][ch] = np.zeros(keep)
+                self.silent_paths += 1
                 return np.zeros(n)
         ext = np.concatenate([hist, x])
         assert keep % 2 == 0 and st["conv_parity"] == 0
