@@ -221,6 +221,67 @@ int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* 
     return rc;
 }
 
+// The FDL multiply-accumulate kernels in isolation (tests/test_gpu_fdl_mac.py): what engine_conv.cpp / engine_native.cpp launch
+// for one call -- launch_fdl_mac, then launch_fdl_mac_dcnyq when the variant leaves packed bin 0 to it -- on buffers the caller
+// fills in the kernels' own layouts.  Own device buffers, the null stream; no engine.  Every argument set for which a kernel
+// would read or write outside a buffer is refused before anything is allocated (extents: kernels.hpp, launch_fdl_mac).
+int32_t cpq_diag_fdl_mac(int32_t P, int32_t nCh, int32_t K, int32_t T, int32_t tile, int32_t head, int32_t ringSlots,
+                         int32_t nIrSlots, int32_t hRows, int32_t hPrivate, const double* x, const double* h,
+                         const int32_t* irSlot, double* y, int32_t* variantUsed)
+{
+    if (!x || !h || !irSlot || !y || !variantUsed) return CPQ_ERR_INVALID_ARG;
+    if (P < 64 || P > 4096 || (P & (P - 1)) || nCh < 1 || K < 1 || T < 1 || nIrSlots < 1) return CPQ_ERR_INVALID_ARG;
+    if (tile != 0 && tile != 4 && tile != 8 && tile != 16 && tile != 32 && tile != cpq::kMacTileCoop) return CPQ_ERR_INVALID_ARG;
+    // the engines' own sizing rules (engine_core.cpp: ringSlots; engine_native.cpp layerGeometry: hRows, the smaller of the two)
+    const int64_t kPad32 = alignUp(K, cpq::kMacMaxTile);
+    int64_t ringMin = 1;
+    while (ringMin < kPad32 + cpq::kMacMaxTile + T) ringMin <<= 1;
+    if (ringSlots < 1 || (ringSlots & (ringSlots - 1)) || ringSlots < ringMin) return CPQ_ERR_INVALID_ARG;
+    if (hRows < kPad32 + 16) return CPQ_ERR_INVALID_ARG;
+    if (head < 0 || head >= ringSlots) return CPQ_ERR_INVALID_ARG;
+    for (int c = 0; c < nCh; ++c)
+        if (irSlot[c] < 0 || irSlot[c] >= nIrSlots) return CPQ_ERR_INVALID_ARG;
+    const size_t nX = (size_t)nCh * ringSlots * P, nH = (size_t)nIrSlots * hRows * P, nY = (size_t)nCh * T * P;
+    if (nX > ((size_t)1 << 28) || nH > ((size_t)1 << 28) || nY > ((size_t)1 << 28)) return CPQ_ERR_INVALID_ARG;      // 4 GB each: a test tool
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) { (void)hipGetLastError(); return CPQ_ERR_NO_DEVICE; }
+    *variantUsed = cpq::fdl_mac_variant(tile, T);
+
+    // compact (DC, Nyquist) rows: element 0 of every spectrum, which is what the forward FFT and launch_ir_spectra store there
+    const double2* x2 = reinterpret_cast<const double2*>(x);
+    const double2* h2 = reinterpret_cast<const double2*>(h);
+    std::vector<double2> xdn((size_t)nCh * ringSlots), hdn((size_t)nIrSlots * hRows);
+    for (size_t i = 0; i < xdn.size(); ++i) xdn[i] = x2[i * P];
+    for (size_t i = 0; i < hdn.size(); ++i) hdn[i] = h2[i * P];
+
+    double2 *dX = nullptr, *dH = nullptr, *dXdn = nullptr, *dHdn = nullptr, *dY = nullptr;
+    int* dSlot = nullptr;
+    int32_t rc = CPQ_OK;
+    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
+    ok(hipMalloc((void**)&dX, nX * sizeof(double2))) && ok(hipMalloc((void**)&dH, nH * sizeof(double2))) &&
+        ok(hipMalloc((void**)&dXdn, xdn.size() * sizeof(double2))) && ok(hipMalloc((void**)&dHdn, hdn.size() * sizeof(double2))) &&
+        ok(hipMalloc((void**)&dY, nY * sizeof(double2))) && ok(hipMalloc((void**)&dSlot, (size_t)nCh * sizeof(int)));
+    if (rc == CPQ_OK) {
+        ok(hipMemcpy(dX, x, nX * sizeof(double2), hipMemcpyHostToDevice));
+        ok(hipMemcpy(dH, h, nH * sizeof(double2), hipMemcpyHostToDevice));
+        ok(hipMemcpy(dXdn, xdn.data(), xdn.size() * sizeof(double2), hipMemcpyHostToDevice));
+        ok(hipMemcpy(dHdn, hdn.data(), hdn.size() * sizeof(double2), hipMemcpyHostToDevice));
+        ok(hipMemcpy(dSlot, irSlot, (size_t)nCh * sizeof(int), hipMemcpyHostToDevice));
+        ok(hipMemset(dY, 0xFF, nY * sizeof(double2)));          // NaN: an element no kernel stores cannot pass for a result
+    }
+    if (rc == CPQ_OK) {
+        cpq::launch_fdl_mac(nullptr, tile, dX, dH, dSlot, dY, P, nCh, K, ringSlots, head, T, (int64_t)hRows * P, hPrivate != 0);
+        if (cpq::fdl_mac_needs_dcnyq(tile, T))
+            cpq::launch_fdl_mac_dcnyq(nullptr, dXdn, dHdn, dSlot, dY, P, nCh, K, ringSlots, head, T, hRows);
+        ok(hipGetLastError());
+        ok(hipDeviceSynchronize());
+    }
+    if (rc == CPQ_OK) ok(hipMemcpy(y, dY, nY * sizeof(double2), hipMemcpyDeviceToHost));
+    for (void* p : { (void*)dX, (void*)dH, (void*)dXdn, (void*)dHdn, (void*)dY, (void*)dSlot })
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
 // ------------------------------------------------------------------ host-only helpers
 int32_t cpq_nuc_plan_compute(int32_t irLen, int32_t blockSize, int32_t direct, const cpq_filter_spec* spec,
                              cpq_nuc_plan* plan)

@@ -332,6 +332,7 @@ void launch_mac_t(hipStream_t stream, const double2* X, const double2* H, const 
 // of their FMAs on rows that are not there (T = 1, the reference's own call pattern, is HBM-bound at any tile).
 int fdl_mac_variant(int tile, int T)
 {
+    if (tile == kMacTileCoop) return 0;      // the cooperative kernel at any T (cpq_diag_fdl_mac; no engine passes it)
     if (tile) return tile;
     if (T >= 48) return 0;
     if (T >= 12) return 16;

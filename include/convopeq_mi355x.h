@@ -534,6 +534,26 @@ const char* cpq_kernel_name(int32_t kernel_id);
  * Needs a gfx950 device; no engine.  For tests of the FFT kernel families in isolation. */
 int32_t     cpq_diag_partition_fft(int32_t partition, int32_t n_channels, int32_t n_blocks, const double* in,
                                    double* spectra, double* out);
+/* The FDL multiply-accumulate on its own (what replaces the per-partition accumulateSplitComplex loop,
+ * src/MKLNonUniformConvolver.cpp:150-195): exactly the launches an engine makes for one call, on buffers the caller fills.
+ *   y[c][t][b] = sum_{k < k_parts} x[c][(head + t - k) & (ring_slots - 1)][b] * h[ir_slot[c]][k][b]     (complex, b >= 1)
+ *   y[c][t][0] = ( sum_k Re x Re h , sum_k Im x Im h )              (element 0 packs DC and Nyquist, two real products)
+ * x: [n_channels][ring_slots][partition][2], the whole delay-line ring; h: [n_ir_slots][h_rows][partition][2];
+ * ir_slot: [n_channels]; y: [n_channels][n_blocks][partition][2]; all host memory.  The compact DC/Nyquist rows the 16- and
+ * 32-row tiles read are formed from element 0 of x and h.
+ * tile: 0 = automatic (by n_blocks), 4 / 8 / 16 / 32 = that register tile, -1 = the workgroup-cooperative kernel at any
+ * n_blocks (no engine selects it below 48 blocks).  *variant_used = the kernel that ran: 4 / 8 / 16 / 32, or 0 for the
+ * cooperative kernel.  h_private != 0: no two channels share an IR slot (one-tile calls may then stream the IR rows).
+ * Rows k_parts ... h_rows - 1 of a slot, IR slots no channel names and ring slots outside {head + t - k} may hold anything
+ * finite: they may be loaded, never consumed.
+ * CPQ_ERR_INVALID_ARG, before anything is launched, unless: partition is a power of two in 64 ... 4096; n_channels, k_parts,
+ * n_blocks, n_ir_slots >= 1; tile is one of the values above; ring_slots is a power of two >= nextPow2(alignUp(k_parts, 32) +
+ * 32 + n_blocks) (the engines' ring size); h_rows >= alignUp(k_parts, 32) + 16 (the engines' smallest slot); 0 <= head <
+ * ring_slots; 0 <= ir_slot[c] < n_ir_slots; no buffer above 2^28 elements.
+ * Needs a gfx950 device; no engine.  For tests of the MAC kernel variants in isolation. */
+int32_t     cpq_diag_fdl_mac(int32_t partition, int32_t n_channels, int32_t k_parts, int32_t n_blocks, int32_t tile,
+                             int32_t head, int32_t ring_slots, int32_t n_ir_slots, int32_t h_rows, int32_t h_private,
+                             const double* x, const double* h, const int32_t* ir_slot, double* y, int32_t* variant_used);
 /* Chained spans of the EQ / output-filter cascade (engines with fewer channels than the device holds workgroups of the span
  * kernel: the spans of a call are dealt to the workgroups and a band's state is handed from span to span inside the launch).
  * Synchronises the engine's stream; *launches = chained launches so far (0: this engine never chains), *gave_up != 0 when a
