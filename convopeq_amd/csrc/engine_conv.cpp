@@ -160,16 +160,11 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
     const int headTaps = direct ? std::min(irLen, std::min(nextPow2(std::max(e->desc.block_size, 64)), 32)) : 0;
     if (direct && !e->directIr) {
         const size_t callSamples = (size_t)e->tMax * e->P;
-        if (hipMalloc((void**)&e->directIr, sizeof(double) * 32 * e->nCh) != hipSuccess ||
-            hipMalloc((void**)&e->directTaps, sizeof(int) * e->nCh) != hipSuccess ||
-            hipMalloc((void**)&e->directHist[0], sizeof(double) * 32 * e->nCh) != hipSuccess ||
-            hipMalloc((void**)&e->directHist[1], sizeof(double) * 32 * e->nCh) != hipSuccess ||
-            hipMalloc((void**)&e->directOut, sizeof(double) * e->nCh * callSamples) != hipSuccess)
-            return fail(e, CPQ_ERR_OOM, "direct-head buffers could not be allocated");
-        CPQ_HIP(e, hipMemset(e->directIr, 0, sizeof(double) * 32 * e->nCh));
-        CPQ_HIP(e, hipMemset(e->directTaps, 0, sizeof(int) * e->nCh));
-        CPQ_HIP(e, hipMemset(e->directHist[0], 0, sizeof(double) * 32 * e->nCh));
-        CPQ_HIP(e, hipMemset(e->directHist[1], 0, sizeof(double) * 32 * e->nCh));
+        const size_t taps = (size_t)32 * e->nCh;
+        const int rc = allocAll(e, { { e->directIr, taps, true }, { e->directTaps, (size_t)e->nCh, true }, { e->directHist[0], taps, true },
+                                     { e->directHist[1], taps, true }, { e->directOut, e->nCh * callSamples } },
+                                "direct-head buffers could not be allocated");
+        if (rc != CPQ_OK) return rc;
         e->directTapsHost.assign(e->nCh, 0);
     }
     const double* irs[2] = { irL, irR };
@@ -192,27 +187,27 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
             if (anyLoaded && (!e->layered || std::memcmp(&probe, &e->layerPlan, sizeof(probe)) != 0))
                 return fail(e, CPQ_ERR_UNSUPPORTED, "time-varying reference semantics need the same IR length on every stream");
             if (!e->layered) {
-                // lazily allocate the per-layer buffers
+                // the rows of each layer inside a channel's slot; then, lazily, the per-layer buffers; the engine's state last
                 const int nTail = probe.num_layers - 1;
-                int span = 0;
-                for (int l = 1; l < probe.num_layers; ++l) span = std::max(span, probe.output_delay[l] + 2 * probe.part_size[l]);
-                e->tailRingSlots = nextPow2(span + 2 * e->B + e->tMax * e->P);
-                const size_t callSamples = (size_t)e->tMax * e->P;
-                if (hipMalloc((void**)&e->layerOut, sizeof(double) * nTail * e->nCh * callSamples) != hipSuccess ||
-                    hipMalloc((void**)&e->tailRing, sizeof(double) * (size_t)nTail * e->nCh * e->tailRingSlots) != hipSuccess ||
-                    hipMalloc(&e->tailState, 4 * sizeof(long long)) != hipSuccess ||
-                    hipMalloc((void**)&e->tailSched, sizeof(long long) * 2 * ((size_t)e->tMax * e->P / e->B)) != hipSuccess)      // per tail layer and callback
-                    return fail(e, CPQ_ERR_OOM, "layered-mode buffers could not be allocated");
-                CPQ_HIP(e, hipMemset(e->tailRing, 0, sizeof(double) * (size_t)nTail * e->nCh * e->tailRingSlots));
-                CPQ_HIP(e, hipMemset(e->tailState, 0, 4 * sizeof(long long)));
-                e->layerPlan = probe;
-                int row = 0;
+                int row = 0, layerRow[3] = { 0, 0, 0 }, layerK[3] = { 0, 0, 0 };
                 for (int l = 0; l < probe.num_layers; ++l) {
-                    e->layerRow[l] = row;
-                    e->layerK[l] = (probe.len[l] + e->P - 1) / e->P;
-                    row += (int)alignUp(e->layerK[l], cpq::kMacMaxTile) + cpq::kMacMaxTile;
+                    layerRow[l] = row;
+                    layerK[l] = (probe.len[l] + e->P - 1) / e->P;
+                    row += (int)alignUp(layerK[l], cpq::kMacMaxTile) + cpq::kMacMaxTile;
                 }
                 if (row > e->hRows) return fail(e, CPQ_ERR_INVALID_ARG, "layered IR needs %d rows, capacity %d", row, e->hRows);
+                int span = 0;
+                for (int l = 1; l < probe.num_layers; ++l) span = std::max(span, probe.output_delay[l] + 2 * probe.part_size[l]);
+                const int tailRingSlots = nextPow2(span + 2 * e->B + e->tMax * e->P);
+                const size_t callSamples = (size_t)e->tMax * e->P;
+                const int rc = allocAll(e, { { e->layerOut, nTail * e->nCh * callSamples }, { e->tailRing, (size_t)nTail * e->nCh * tailRingSlots, true },
+                                             { e->tailState, 4, true }, { e->tailSched, 2 * ((size_t)e->tMax * e->P / e->B) } },      // per tail layer and callback
+                                        "layered-mode buffers could not be allocated");
+                if (rc != CPQ_OK) return rc;
+                e->tailRingSlots = tailRingSlots;
+                e->layerPlan = probe;
+                std::copy(layerRow, layerRow + 3, e->layerRow);
+                std::copy(layerK, layerK + 3, e->layerK);
                 e->layered = true;
             }
         } else if (e->layered) {
@@ -235,8 +230,8 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
     // src/MKLNonUniformConvolver.cpp:697-714, :880-935): the stream's input history goes -- the direct head's last samples, and on
     // the main path its rows of the frequency-domain delay line and the overlap block; the other streams play on
     for (int s = sFirst; s < sEnd; ++s) {
-        for (double* p : { e->directHist[0], e->directHist[1] })
-            if (p) CPQ_HIP(e, hipMemsetAsync(p + (size_t)2 * s * 32, 0, sizeof(double) * 2 * 32, e->stream));
+        for (const auto& h : e->directHist)
+            if (h) CPQ_HIP(e, hipMemsetAsync(h + (size_t)2 * s * 32, 0, sizeof(double) * 2 * 32, e->stream));
         if (!native && e->X) {
             CPQ_HIP(e, hipMemsetAsync(e->X + (int64_t)2 * s * e->ringSlots * e->P, 0, (size_t)2 * e->ringSlots * e->P * sizeof(double2), e->stream));
             CPQ_HIP(e, hipMemsetAsync(e->XDN + (int64_t)2 * s * e->ringSlots, 0, (size_t)2 * e->ringSlots * sizeof(double2), e->stream));

@@ -58,16 +58,23 @@ int checkCall(cpq_engine* e, const void* in, const void* out, int nSamples)
 
 // Call-sized buffers that only some entry points need are allocated when first used: the staging pair of the host-pointer
 // entry points, the hand-off buffer of the EQ -> convolver order (3 x 2 GB at 256 streams and 524288-sample calls).
-int ensureCallBuffer(cpq_engine* e, double** buf, const char* what)
+int ensureCallBuffer(cpq_engine* e, DeviceBuffer<double>& buf, const char* what)
 {
-    if (*buf) return CPQ_OK;
-    const size_t bytes = (size_t)e->nCh * e->tMax * e->P * sizeof(double);
-    if (hipMalloc((void**)buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        return fail(e, CPQ_ERR_OOM, "%s buffer of %zu bytes could not be allocated", what, bytes);
+    if (buf) return CPQ_OK;
+    const size_t count = (size_t)e->nCh * e->tMax * e->P;
+    return allocAll(e, { { buf, count } }, "%s buffer of %zu bytes could not be allocated", what, count * sizeof(double));
+}
+
+void hostTwiddles(int P, std::vector<double2>& w1, std::vector<double2>& w2)
+{
+    w1.resize((size_t)P);
+    w2.resize((size_t)P);
+    const long double twoPi = 6.283185307179586476925286766559005768L;
+    for (int m = 0; m < P; ++m) {
+        const long double a = -twoPi * m / (long double)P, b = -twoPi * m / (long double)(2 * P);
+        w1[(size_t)m] = make_double2((double)cosl(a), (double)sinl(a));
+        w2[(size_t)m] = make_double2((double)cosl(b), (double)sinl(b));
     }
-    return CPQ_OK;
 }
 
 int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
@@ -81,8 +88,8 @@ int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
         e->head = 0;
         e->histSel = 0;
         { const int rc = resetGroups(e); if (rc != CPQ_OK) return rc; }
-        for (double* p : { e->directHist[0], e->directHist[1] })
-            if (p) CPQ_HIP(e, hipMemsetAsync(p, 0, sizeof(double) * 32 * e->nCh, e->stream));
+        for (const auto& h : e->directHist)
+            if (h) CPQ_HIP(e, hipMemsetAsync(h, 0, sizeof(double) * 32 * e->nCh, e->stream));
         if (e->tailState) CPQ_HIP(e, hipMemsetAsync(e->tailState, 0, 4 * sizeof(long long), e->stream));
         if (e->tailRing) CPQ_HIP(e, hipMemsetAsync(e->tailRing, 0, sizeof(double) * (size_t)(e->layerPlan.num_layers - 1) * e->nCh * e->tailRingSlots, e->stream));
         if (e->dryRing) CPQ_HIP(e, hipMemsetAsync(e->dryRing, 0, (size_t)e->nCh * e->dryRingSize * sizeof(double), e->stream));
@@ -172,24 +179,18 @@ int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* 
     int ringSlots = 1;
     while (ringSlots < T) ringSlots <<= 1;
     const size_t nTime = (size_t)nCh * T * P, nSpec = (size_t)nCh * ringSlots * P;
-    double *dIn = nullptr, *dOut = nullptr, *dHist = nullptr;
-    double2 *dX = nullptr, *dXdn = nullptr, *dTw = nullptr, *dTw2 = nullptr, *dScratch = nullptr, *dY = nullptr;
-    std::vector<double2> w1((size_t)P), w2((size_t)P);
-    const long double twoPi = 6.283185307179586476925286766559005768L;
-    for (int m = 0; m < P; ++m) {
-        const long double a = -twoPi * m / (long double)P, b = -twoPi * m / (long double)(2 * P);
-        w1[(size_t)m] = make_double2((double)cosl(a), (double)sinl(a));
-        w2[(size_t)m] = make_double2((double)cosl(b), (double)sinl(b));
-    }
+    DeviceBuffer<double> dIn, dOut, dHist;
+    DeviceBuffer<double2> dX, dXdn, dTw, dTw2, dScratch, dY;
+    std::vector<double2> w1, w2;
+    hostTwiddles(P, w1, w2);
+    // (dTw, dTw2: the second halves are the reordered tables of the four-step transforms)
+    if (allocAll(nullptr, { { dIn, nTime }, { dOut, nTime }, { dHist, (size_t)2 * nCh * P }, { dX, nSpec }, { dXdn, (size_t)nCh * ringSlots },
+                            { dTw, (size_t)2 * P }, { dTw2, (size_t)2 * P }, { dScratch, P > 4096 ? (size_t)nCh * T * P : 1 },
+                            { dY, (size_t)nCh * T * P } }, "partition FFT diagnostic buffers could not be allocated") != CPQ_OK)
+        return CPQ_ERR_DEVICE;
     int32_t rc = CPQ_OK;
     auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    ok(hipMalloc((void**)&dIn, nTime * sizeof(double))) && ok(hipMalloc((void**)&dOut, nTime * sizeof(double))) &&
-        ok(hipMalloc((void**)&dHist, (size_t)2 * nCh * P * sizeof(double))) && ok(hipMalloc((void**)&dX, nSpec * sizeof(double2))) &&
-        ok(hipMalloc((void**)&dXdn, (size_t)nCh * ringSlots * sizeof(double2))) && ok(hipMalloc((void**)&dTw, (size_t)2 * P * sizeof(double2))) &&
-        ok(hipMalloc((void**)&dTw2, (size_t)2 * P * sizeof(double2))) &&       // (second halves: the reordered tables of the four-step transforms)
-        ok(hipMalloc((void**)&dScratch, (P > 4096 ? (size_t)nCh * T * P : 1) * sizeof(double2))) &&
-        ok(hipMalloc((void**)&dY, (size_t)nCh * T * P * sizeof(double2)));
-    if (rc == CPQ_OK) {
+    {
         ok(hipMemset(dHist, 0, (size_t)2 * nCh * P * sizeof(double)));
         ok(hipMemset(dX, 0, nSpec * sizeof(double2)));
         ok(hipMemcpy(dIn, in, nTime * sizeof(double), hipMemcpyHostToDevice));
@@ -216,8 +217,6 @@ int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* 
         ok(hipMemcpy(spectra, dY, (size_t)nCh * T * P * sizeof(double2), hipMemcpyDeviceToHost));
         ok(hipMemcpy(out, dOut, nTime * sizeof(double), hipMemcpyDeviceToHost));
     }
-    for (void* p : { (void*)dIn, (void*)dOut, (void*)dHist, (void*)dX, (void*)dXdn, (void*)dTw, (void*)dTw2, (void*)dScratch, (void*)dY })
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -254,14 +253,14 @@ int32_t cpq_diag_fdl_mac(int32_t P, int32_t nCh, int32_t K, int32_t T, int32_t t
     for (size_t i = 0; i < xdn.size(); ++i) xdn[i] = x2[i * P];
     for (size_t i = 0; i < hdn.size(); ++i) hdn[i] = h2[i * P];
 
-    double2 *dX = nullptr, *dH = nullptr, *dXdn = nullptr, *dHdn = nullptr, *dY = nullptr;
-    int* dSlot = nullptr;
+    DeviceBuffer<double2> dX, dH, dXdn, dHdn, dY;
+    DeviceBuffer<int> dSlot;
+    if (allocAll(nullptr, { { dX, nX }, { dH, nH }, { dXdn, xdn.size() }, { dHdn, hdn.size() }, { dY, nY }, { dSlot, (size_t)nCh } },
+                 "FDL MAC diagnostic buffers could not be allocated") != CPQ_OK)
+        return CPQ_ERR_DEVICE;
     int32_t rc = CPQ_OK;
     auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    ok(hipMalloc((void**)&dX, nX * sizeof(double2))) && ok(hipMalloc((void**)&dH, nH * sizeof(double2))) &&
-        ok(hipMalloc((void**)&dXdn, xdn.size() * sizeof(double2))) && ok(hipMalloc((void**)&dHdn, hdn.size() * sizeof(double2))) &&
-        ok(hipMalloc((void**)&dY, nY * sizeof(double2))) && ok(hipMalloc((void**)&dSlot, (size_t)nCh * sizeof(int)));
-    if (rc == CPQ_OK) {
+    {
         ok(hipMemcpy(dX, x, nX * sizeof(double2), hipMemcpyHostToDevice));
         ok(hipMemcpy(dH, h, nH * sizeof(double2), hipMemcpyHostToDevice));
         ok(hipMemcpy(dXdn, xdn.data(), xdn.size() * sizeof(double2), hipMemcpyHostToDevice));
@@ -277,8 +276,6 @@ int32_t cpq_diag_fdl_mac(int32_t P, int32_t nCh, int32_t K, int32_t T, int32_t t
         ok(hipDeviceSynchronize());
     }
     if (rc == CPQ_OK) ok(hipMemcpy(y, dY, nY * sizeof(double2), hipMemcpyDeviceToHost));
-    for (void* p : { (void*)dX, (void*)dH, (void*)dXdn, (void*)dHdn, (void*)dY, (void*)dSlot })
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -450,8 +447,7 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
     e->svfChainSpans = chained ? cpq::svf_chain_spans(e->maxCall) : 0;
     int64_t total = 0;
     for (const Item& it : items) total += alignUp(it.bytes, 256);
-    if (hipMalloc((void**)&e->arena, (size_t)total) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!e->arena.alloc((size_t)total)) {
         delete e;
         return fail(nullptr, CPQ_ERR_OOM, "device arena of %lld bytes could not be allocated", (long long)total);
     }
@@ -464,14 +460,8 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
         cpq_engine_destroy(e);
         return fail(nullptr, CPQ_ERR_DEVICE, "hipMemset of the arena failed");
     }
-    // twiddles in extended precision on the host, rounded once (SURVEY.md section 7 "hard parts")
-    std::vector<double2> w512(e->P), w1024(e->P);
-    const long double twoPi = 6.283185307179586476925286766559005768L;
-    for (int m = 0; m < e->P; ++m) {
-        const long double a = -twoPi * m / (long double)e->P, b = -twoPi * m / (long double)(2 * e->P);
-        w512[m] = make_double2((double)cosl(a), (double)sinl(a));
-        w1024[m] = make_double2((double)cosl(b), (double)sinl(b));
-    }
+    std::vector<double2> w512, w1024;
+    hostTwiddles(e->P, w512, w1024);
     if (hipMemcpy(e->tw512, w512.data(), e->P * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(e->tw1024, w1024.data(), e->P * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess) {
         cpq_engine_destroy(e);
@@ -518,40 +508,12 @@ void cpq_engine_destroy(cpq_engine* e)
         for (auto& ev : s.pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
         for (auto& ev : s.freeList) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     }
-    freeGroups(e);
-    freePinnedRing(e);
+    freePinnedRing(e);      // its events
     if (e->copyIn) {
         (void)hipStreamDestroy(e->copyIn);
         (void)hipStreamDestroy(e->copyOut);
         for (int i = 0; i < 4; ++i) { (void)hipEventDestroy(e->evIn[i]); (void)hipEventDestroy(e->evDone[i]); }
     }
-    if (e->arena) (void)hipFree(e->arena);
-    freeOversampler(e);
-    for (void* p : { (void*)e->osFlags, (void*)e->osCounts, (void*)e->osNonSilent, (void*)e->osTmp[0], (void*)e->osTmp[1], (void*)e->osWork })
-        if (p) (void)hipFree(p);
-    for (double* p : { e->stageIn, e->stageOut, e->mid, e->dryRing, e->latGains, e->layerOut, e->tailRing, e->agcState, e->agcRmsIn, e->agcRmsOut, e->agcGains }) if (p) (void)hipFree(p);
-    if (e->agcOn) (void)hipFree(e->agcOn);
-    if (e->rampOn) (void)hipFree(e->rampOn);
-    if (e->rampGains) (void)hipFree(e->rampGains);
-    if (e->tailState) (void)hipFree(e->tailState);
-    if (e->tailSched) (void)hipFree(e->tailSched);
-    if (e->procGains) (void)hipFree(e->procGains);
-    if (e->procDelay) (void)hipFree(e->procDelay);
-    if (e->procWetOn) (void)hipFree(e->procWetOn);
-    for (int* p : { e->latNew, e->latOld, e->latLen }) if (p) (void)hipFree(p);
-    if (e->eqDry) (void)hipFree(e->eqDry);
-    if (e->silentDev) (void)hipFree(e->silentDev);
-    if (e->silentHost) (void)hipHostFree(e->silentHost);
-    if (e->trimDev) (void)hipFree(e->trimDev);
-    if (e->makeupDev) (void)hipFree(e->makeupDev);
-    if (e->blendOn) (void)hipFree(e->blendOn);
-    if (e->blendLen) (void)hipFree(e->blendLen);
-    if (e->blendEnd) (void)hipFree(e->blendEnd);
-    if (e->blendGains) (void)hipFree(e->blendGains);
-    if (e->mixRampLen) (void)hipFree(e->mixRampLen);
-    if (e->mixRampGains) (void)hipFree(e->mixRampGains);
-    for (double* p : { e->directIr, e->directHist[0], e->directHist[1], e->directOut }) if (p) (void)hipFree(p);
-    if (e->directTaps) (void)hipFree(e->directTaps);
     delete e;
 }
 
@@ -661,7 +623,7 @@ int cpqi::enqueueBoth(cpq_engine* e, const double* a, double* b, int n)
     } else if (e->convBypassed) {
         rc = enqueueEq(e, a, b, n);
     } else {
-        rc = ensureCallBuffer(e, &e->mid, "EQ -> convolver hand-off");
+        rc = ensureCallBuffer(e, e->mid, "EQ -> convolver hand-off");
         if (rc == CPQ_OK) rc = enqueueEq(e, a, e->mid, n);
         if (rc == CPQ_OK && e->anyTrim) {       // scaleBlockFallback(block, convolverInputTrimGain) (:440-447)
             ProfScope p(e, CPQ_K_MIX);
@@ -704,9 +666,8 @@ int32_t cpq_engine_set_gains(cpq_engine* e, int32_t stream, double convInputTrim
     CPQ_HIP(e, hipSetDevice(e->device));
     const int S = e->desc.n_streams;
     if (!e->trimDev) {
-        if (hipMalloc((void**)&e->trimDev, sizeof(double) * S) != hipSuccess ||
-            hipMalloc((void**)&e->makeupDev, sizeof(double) * S) != hipSuccess)
-            return fail(e, CPQ_ERR_OOM, "gain buffers could not be allocated");
+        const int rc = allocAll(e, { { e->trimDev, (size_t)S }, { e->makeupDev, (size_t)S } }, "gain buffers could not be allocated");
+        if (rc != CPQ_OK) return rc;
     }
     const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
     const int s1 = (stream == CPQ_ALL_STREAMS) ? S : stream + 1;

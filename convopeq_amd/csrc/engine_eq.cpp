@@ -184,9 +184,8 @@ int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride
         if (anyRamp) {
             const size_t cbMax = (size_t)e->tMax * e->P / e->B;
             if (!e->rampOn) {
-                if (hipMalloc((void**)&e->rampOn, sizeof(int) * S) != hipSuccess ||
-                    hipMalloc((void**)&e->rampGains, sizeof(double) * 2 * S * cbMax) != hipSuccess)
-                    return fail(e, CPQ_ERR_OOM, "gain ramp buffers could not be allocated");
+                const int rcA = allocAll(e, { { e->rampOn, (size_t)S }, { e->rampGains, 2 * S * cbMax } }, "gain ramp buffers could not be allocated");
+                if (rcA != CPQ_OK) return rcA;
             }
             { const int rcUp = stageUpload(e, e->rampOn, rampOnHost.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
             { const int rcUp = stageUpload(e, e->rampGains, rampHost.data(), sizeof(double) * rampHost.size()); if (rcUp != CPQ_OK) return rcUp; }
@@ -297,9 +296,8 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
         if (needSilence) {
             const size_t cbMax = (size_t)e->tMax * e->P / e->B;
             if (!e->silentDev) {
-                if (hipMalloc((void**)&e->silentDev, sizeof(int) * S * cbMax) != hipSuccess ||
-                    hipHostMalloc((void**)&e->silentHost, sizeof(int) * S * cbMax) != hipSuccess)
-                    return fail(e, CPQ_ERR_OOM, "silence flags could not be allocated");
+                const int rcA = allocAll(e, { { e->silentDev, S * cbMax }, { e->silentHost, S * cbMax } }, "silence flags could not be allocated");
+                if (rcA != CPQ_OK) return rcA;
             }
             cpq::launch_block_silence(e->stream, dIn, stride, e->B, cbs, S, e->silentDev);
             CPQ_HIP(e, hipMemcpyAsync(e->silentHost, e->silentDev, sizeof(int) * (size_t)S * cbs, hipMemcpyDeviceToHost, e->stream));
@@ -367,20 +365,11 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
         if (rc != CPQ_OK) break;
         if (anyFade) {
             if (!e->eqDry) {
-                if (hipMalloc((void**)&e->eqDry, sizeof(double) * (size_t)e->nCh * e->tMax * e->P) != hipSuccess ||
-                    hipMalloc((void**)&e->blendOn, sizeof(int) * S) != hipSuccess ||
-                    hipMalloc((void**)&e->blendLen, sizeof(int) * S) != hipSuccess ||
-                    hipMalloc((void**)&e->blendEnd, sizeof(double) * S) != hipSuccess)
-                    return fail(e, CPQ_ERR_OOM, "EQ bypass cross-fade buffers could not be allocated");
+                const int rcA = allocAll(e, { { e->eqDry, (size_t)e->nCh * e->tMax * e->P }, { e->blendOn, (size_t)S }, { e->blendLen, (size_t)S },
+                                              { e->blendEnd, (size_t)S } }, "EQ bypass cross-fade buffers could not be allocated");
+                if (rcA != CPQ_OK) return rcA;
             }
-            if (cap > e->blendCap) {
-                if (e->blendGains) (void)hipFree(e->blendGains);
-                e->blendGains = nullptr;
-                e->blendCap = 0;
-                if (hipMalloc((void**)&e->blendGains, sizeof(double) * (size_t)S * cap) != hipSuccess)
-                    return fail(e, CPQ_ERR_OOM, "EQ bypass cross-fade buffers could not be allocated");
-                e->blendCap = cap;
-            }
+            { const int rcG = grow(e, e->blendGains, e->blendCap, cap, (size_t)S, "EQ bypass cross-fade buffers could not be allocated"); if (rcG != CPQ_OK) return rcG; }
             gainsHost.assign((size_t)S * e->blendCap, 0.0);
             for (int s = 0; s < S; ++s) {
                 if (!onHost[s]) continue;
@@ -499,20 +488,18 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
         if (!e->eqProcessed || p->agc_enabled) { r.current = r.target = r.wanted; r.step = 0.0; r.remaining = 0; }
     }
     for (int s = s0; s < s1; ++s) e->agcOnHost[s] = p->agc_enabled ? 1 : 0;
-    e->anyAgc = false;
-    for (int v : e->agcOnHost) e->anyAgc = e->anyAgc || v;
-    if (e->anyAgc) {
+    e->anyAgc = false;              // the AGC kernels run only once their buffers exist
+    bool anyAgc = false;
+    for (int v : e->agcOnHost) anyAgc = anyAgc || v;
+    if (anyAgc) {
         const int S = e->desc.n_streams;
         const size_t cbMax = (size_t)e->tMax * e->P / e->B;
         if (!e->agcOn) {
-            if (hipMalloc((void**)&e->agcOn, sizeof(int) * S) != hipSuccess ||
-                hipMalloc((void**)&e->agcState, sizeof(double) * 3 * S) != hipSuccess ||
-                hipMalloc((void**)&e->agcRmsIn, sizeof(double) * e->nCh * cbMax) != hipSuccess ||
-                hipMalloc((void**)&e->agcRmsOut, sizeof(double) * e->nCh * cbMax) != hipSuccess ||
-                hipMalloc((void**)&e->agcGains, sizeof(double) * 2 * S * cbMax) != hipSuccess)
-                return fail(e, CPQ_ERR_OOM, "AGC buffers could not be allocated");
-            CPQ_HIP(e, hipMemset(e->agcState, 0, sizeof(double) * 3 * S));
+            const int rc = allocAll(e, { { e->agcOn, (size_t)S }, { e->agcState, (size_t)3 * S, true }, { e->agcRmsIn, e->nCh * cbMax },
+                                         { e->agcRmsOut, e->nCh * cbMax }, { e->agcGains, 2 * S * cbMax } }, "AGC buffers could not be allocated");
+            if (rc != CPQ_OK) return rc;
         }
+        e->anyAgc = true;
         CPQ_HIP(e, hipMemcpy(e->agcOn, e->agcOnHost.data(), sizeof(int) * S, hipMemcpyHostToDevice));
     } else if (e->agcOn) {
         CPQ_HIP(e, hipMemcpy(e->agcOn, e->agcOnHost.data(), sizeof(int) * e->desc.n_streams, hipMemcpyHostToDevice));

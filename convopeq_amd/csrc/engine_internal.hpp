@@ -3,6 +3,8 @@
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
 //   engine_eq.cpp    EQ and output filter: design, device tables, bypass / band-reset state machine
+// Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
+// feature allocated on first use, all of it freed with the engine.
 #pragma once
 
 #include "convopeq_mi355x.h"
@@ -14,11 +16,13 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "device_buffers.hpp"
 #include "host_design.hpp"
 #include "kernels.hpp"
 
@@ -36,18 +40,22 @@ struct ProfileSlot {
 // air-absorption damping) multiply every partition spectrum of a layer at that layer's FFT size, which folds time-aliased
 // energy into the frame (src/MKLNonUniformConvolver.cpp:336-443) -- only reproducible with the same partitioning; and the
 // reference's Add / Get bookkeeping (input fill, distributed tail MAC, delay-line reader) runs per layer.
-struct NativeLayer {
-    int P = 0, K = 0, kPad = 0, hRows = 0, ringSlots = 0, nbMax = 0, accCap = 0, outRing = 0;
+// What a layer carries over when its group is resized or a member is moved to a group of its own: plain host state.
+struct LayerState {
     int head = 0, histSel = 0, accSel = 0, fill = 0;     // FDL ring head, ping-pong selectors, input fill (inputPos)
     int fftAhead = 0;           // blocks of this call already transformed straight from the call's input (groupsAppend), 0 = none
-    double gain = 1.0;          // tail-layer gain applied by the delay-line reader
-    int ppc = 1, outputDelay = 0;       // partsPerCallback (:988-994), outputDelaySamples (:1005-1024)
     // host replay of the reference's integer state: layer 0 -- samples written to / read from the output ring
     // (m_ringAvail = wPos - rPos); tail layers -- delayWriteCursor / delayReadCursor, the distributed MAC's progress
     bool distributing = false;
     int nextPart = 0;
     long long wPos = 0, rPos = 0;
-    char* mem = nullptr;
+};
+
+struct NativeLayer : LayerState {
+    int P = 0, K = 0, kPad = 0, hRows = 0, ringSlots = 0, nbMax = 0, accCap = 0, outRing = 0;
+    double gain = 1.0;          // tail-layer gain applied by the delay-line reader
+    int ppc = 1, outputDelay = 0;       // partsPerCallback (:988-994), outputDelaySamples (:1005-1024)
+    cpqi::DeviceBuffer<char> mem;       // one allocation; the pointers below are carved out of it
     double2 *X = nullptr, *XDN = nullptr, *H = nullptr, *HDN = nullptr, *Y = nullptr, *tw = nullptr, *tw2 = nullptr, *twCol = nullptr, *twSplit = nullptr;
     double *hist[2] = { nullptr, nullptr }, *acc[2] = { nullptr, nullptr }, *ring = nullptr, *gainDev = nullptr;
     double2* scratch = nullptr;   // four-step FFT workspace (P > 4096): [max(nCh * nbMax, K)][P]
@@ -63,9 +71,9 @@ struct PlanGroup {
     bool identityMap = false;                   // chMap[i] == i for every launched channel (layer 0 may then write the output rows itself)
     std::vector<int> streamOfPair;              // pair slot -> stream, -1 = free
     std::vector<NativeLayer> layers;
-    int* chMapDev = nullptr;                    // [capCh] local channel -> row of the call's buffers (-1 = free slot)
-    int* irSlotDev = nullptr;                   // [capCh] local channel -> IR slot
-    long long* tabDev = nullptr;                // the call's chunk tables
+    cpqi::DeviceBuffer<int> chMapDev;                // [capCh] local channel -> row of the call's buffers (-1 = free slot)
+    cpqi::DeviceBuffer<int> irSlotDev;               // [capCh] local channel -> IR slot
+    cpqi::DeviceBuffer<long long> tabDev;            // the call's chunk tables
     int tabCap = 0;
     std::vector<long long> tabHost;
     std::vector<size_t> tabOffs;
@@ -82,7 +90,7 @@ struct PlanGroup {
 // a region is reused only after the copy that read it has run (one event per upload)
 struct PinnedRing {
     struct Pending { size_t begin, end; hipEvent_t ev; };
-    char* host = nullptr;
+    cpqi::PinnedBuffer<char> host;
     size_t cap = 0, head = 0;
     std::vector<Pending> pending;       // in issue order
     std::vector<hipEvent_t> freeEvents;
@@ -110,7 +118,7 @@ struct cpq_engine {
     int maxCall = 0;        // samples per call the engine is sized for (max_blocks_per_call * block_size)
 
     // device arena
-    char* arena = nullptr;
+    cpqi::DeviceBuffer<char> arena;
     int64_t arenaBytes = 0;
     double2* X = nullptr;       // [nCh][ringSlots][e->P]       FDL ring of packed spectra
     double2* XDN = nullptr;     // [nCh][ringSlots]           (DC, Nyquist) of every FDL slot
@@ -118,17 +126,17 @@ struct cpq_engine {
     double2* HDN = nullptr;     // [nCh][hRows]
     double2* Y = nullptr;       // [nCh][tMax][e->P]            accumulated output spectra of the call
     double* hist[2] = { nullptr, nullptr };   // [nCh][e->P]    overlap history, ping-pong
-    double* stageIn = nullptr;  // [nCh][tMax*e->P]             staging for the host-pointer entry points (allocated on first use)
-    double* stageOut = nullptr;
-    double* mid = nullptr;      // [nCh][tMax*e->P]             conv <-> EQ hand-off (not used when in place)
+    cpqi::DeviceBuffer<double> stageIn;  // [nCh][tMax*e->P]             staging for the host-pointer entry points (allocated on first use)
+    cpqi::DeviceBuffer<double> stageOut;
+    cpqi::DeviceBuffer<double> mid;      // [nCh][tMax*e->P]             conv <-> EQ hand-off (not used when in place)
     double* heffDev = nullptr;  // staging for one h_eff upload
     double* gainDev = nullptr;  // [P+1] spectral gains of a FilterSpec
     bool directHead = false;    // last set_impulse enabled the direct head (affects the processor-level dry delay)
     // direct head (allocated on first use): reversed, scaled head taps and tap count per IR slot, input history, output
-    double* directIr = nullptr;         // [nCh slots][32]
-    int* directTaps = nullptr;          // [nCh slots]
-    double* directHist[2] = { nullptr, nullptr };   // [nCh][32] last input samples, ping-pong
-    double* directOut = nullptr;        // [nCh][tMax * P]
+    cpqi::DeviceBuffer<double> directIr;         // [nCh slots][32]
+    cpqi::DeviceBuffer<int> directTaps;          // [nCh slots]
+    cpqi::DeviceBuffer<double> directHist[2];   // [nCh][32] last input samples, ping-pong
+    cpqi::DeviceBuffer<double> directOut;        // [nCh][tMax * P]
     int directSel = 0;
     std::vector<int> directTapsHost;    // per IR slot
     bool anyDirect = false;
@@ -198,47 +206,47 @@ struct cpq_engine {
     std::vector<uint32_t> eqResetPending;
     std::vector<char> agcResetPending;  // requestAgcReset: envelopes and gain back to their initial values at the next processed block
     bool anyEqReset = false;
-    int* silentDev = nullptr;           // [streams][callbacks]
-    int* silentHost = nullptr;          // pinned
+    cpqi::DeviceBuffer<int> silentDev;           // [streams][callbacks]
+    cpqi::PinnedBuffer<int> silentHost;          // pinned
     bool anyEqBypass = false;           // some stream is not in the plain "never bypassed" state
     // DSPCore block routing (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:384-470)
     std::vector<double> trimHost, makeupHost;   // per stream: convolverInputTrimGain (EQ -> conv order), outputMakeupGain
-    double* trimDev = nullptr;
-    double* makeupDev = nullptr;
+    cpqi::DeviceBuffer<double> trimDev;
+    cpqi::DeviceBuffer<double> makeupDev;
     bool anyTrim = false, anyMakeup = false;
     bool convBypassed = false;          // state.convBypassed: the convolver stage is not called
     std::vector<char> ofPass;           // per stream: output filter tables hold pass-through flags (nothing active)
-    double* eqDry = nullptr;            // [nCh][tMax * P] dry copy for the bypass cross-fade (allocated on first use)
-    int* blendOn = nullptr;             // [streams]
-    int* blendLen = nullptr;            // [streams] samples with their own fade gain
-    double* blendEnd = nullptr;         // [streams] gain after those
-    double* blendGains = nullptr;       // [streams][fade steps]
+    cpqi::DeviceBuffer<double> eqDry;            // [nCh][tMax * P] dry copy for the bypass cross-fade (allocated on first use)
+    cpqi::DeviceBuffer<int> blendOn;             // [streams]
+    cpqi::DeviceBuffer<int> blendLen;            // [streams] samples with their own fade gain
+    cpqi::DeviceBuffer<double> blendEnd;         // [streams] gain after those
+    cpqi::DeviceBuffer<double> blendGains;       // [streams][fade steps]
     int blendCap = 0;
-    int* rampOn = nullptr;              // [streams] device
-    double* rampGains = nullptr;        // [streams][callbacks][2] device
+    cpqi::DeviceBuffer<int> rampOn;              // [streams] device
+    cpqi::DeviceBuffer<double> rampGains;        // [streams][callbacks][2] device
 
     // EQ AGC (allocated on first use)
     std::vector<int> agcOnHost;
     bool anyAgc = false;
-    int* agcOn = nullptr;           // [streams]
-    double* agcState = nullptr;     // [streams][3]
-    double* agcRmsIn = nullptr;     // [nCh][callbacks]
-    double* agcRmsOut = nullptr;
-    double* agcGains = nullptr;     // [streams][callbacks][2]
+    cpqi::DeviceBuffer<int> agcOn;           // [streams]
+    cpqi::DeviceBuffer<double> agcState;     // [streams][3]
+    cpqi::DeviceBuffer<double> agcRmsIn;     // [nCh][callbacks]
+    cpqi::DeviceBuffer<double> agcRmsOut;
+    cpqi::DeviceBuffer<double> agcGains;     // [streams][callbacks][2]
 
     // layered (time-varying) reference semantics: per-layer convolutions + replay of the tail delay-line reader
     bool layered = false;
     cpq_nuc_plan layerPlan{};
     int layerRow[3] = { 0, 0, 0 };      // first IR row of each layer inside a channel's slot
     int layerK[3] = { 0, 0, 0 };        // partitions per layer
-    double* layerOut = nullptr;         // [nTail][nCh][tMax*P]
-    double* tailRing = nullptr;         // [nTail][nCh][tailRingSlots]
+    cpqi::DeviceBuffer<double> layerOut;         // [nTail][nCh][tMax*P]
+    cpqi::DeviceBuffer<double> tailRing;         // [nTail][nCh][tailRingSlots]
     int tailRingSlots = 0;
-    void* tailState = nullptr;          // device: callback counter + read cursors
-    long long* tailSched = nullptr;     // device: [nTail][tMax]
+    cpqi::DeviceBuffer<long long> tailState;          // device: callback counter + read cursors
+    cpqi::DeviceBuffer<long long> tailSched;     // device: [nTail][tMax]
 
     // plan groups (engine_native.cpp): streams run on the reference's own layer plan with its Add / Get bookkeeping
-    std::vector<PlanGroup*> groups;
+    std::vector<std::unique_ptr<PlanGroup>> groups;
     std::vector<int> groupOf;           // per stream: index into groups, -1 = main (uniform) path
     bool mainActive = false;            // some loaded stream runs on the main path
     int lastCallSamples = 0;
@@ -249,20 +257,20 @@ struct cpq_engine {
     std::vector<cpq_convproc_params> procParams;   // per stream
     std::vector<char> procBypass, procDryOnly;      // per stream: bypassed / mix <= 0.001 (the convolver is not called)
     std::vector<int> procWetOnHost;                 // per stream: what the device flags hold
-    int* procWetOn = nullptr;                       // [streams] device: 0 = the stream's output is the delayed dry signal
+    cpqi::DeviceBuffer<int> procWetOn;                       // [streams] device: 0 = the stream's output is the delayed dry signal
     bool honourFrozen = false;                      // set around the convolver call of enqueueConvProc: frozen plan groups (and their direct heads) rest
     // mix smoothing (LinearRamp mixSmoother, src/ConvolverProcessor.h:945; Runtime.cpp:340-375, 591-607): per stream
     struct MixRamp { double current = 1.0, target = 1.0, step = 0.0; int remaining = 0, totalSteps = 4800; };
     std::vector<MixRamp> mixRamp;
     bool procProcessed = false;         // a processor-level call has run since create / prepare: parameter changes ramp
-    int* mixRampLen = nullptr;             // [streams] device: leading samples of the call with per-sample gains
-    double* mixRampGains = nullptr;     // [streams][mixRampCap][2] device (allocated when a ramp first runs)
+    cpqi::DeviceBuffer<int> mixRampLen;             // [streams] device: leading samples of the call with per-sample gains
+    cpqi::DeviceBuffer<double> mixRampGains;     // [streams][mixRampCap][2] device (allocated when a ramp first runs)
     int mixRampCap = 0;
-    double* procGains = nullptr;    // [streams][2] device
-    int* procDelay = nullptr;       // [streams] device
+    cpqi::DeviceBuffer<double> procGains;    // [streams][2] device
+    cpqi::DeviceBuffer<int> procDelay;       // [streams] device
     // dry delay line: a ring per channel (the reference's 4 Mi-sample delayBuffer, Runtime.cpp:378-391), sized for the
     // longest delay an IR of max_ir_len can ask for plus one call; every call's input is written before anything reads
-    double* dryRing = nullptr;      // [nCh][dryRingSize] device, allocated on first use
+    cpqi::DeviceBuffer<double> dryRing;      // [nCh][dryRingSize] device, allocated on first use
     int dryRingSize = 0;
     long long dryPos = 0;           // absolute position of the next input sample
     // latency compensation (Runtime.cpp:263-290, 394-540): latencySmoother is only ever snapped, crossfadeGain runs 20 ms
@@ -273,11 +281,11 @@ struct cpq_engine {
         bool primed = false;        // latCurrent holds the prepareToPlay value (Lifecycle.cpp:380-388)
     };
     std::vector<LatencyFade> latFade;
-    int* latNew = nullptr;          // [streams] device: delay of the dry read
-    int* latOld = nullptr;          // [streams] delay faded out
+    cpqi::DeviceBuffer<int> latNew;          // [streams] device: delay of the dry read
+    cpqi::DeviceBuffer<int> latOld;          // [streams] delay faded out
     std::vector<int> latNewHost, latOldHost;    // what the two device arrays hold
-    int* latLen = nullptr;          // [streams] samples of the range that are cross-faded
-    double* latGains = nullptr;     // [streams][latCap]
+    cpqi::DeviceBuffer<int> latLen;          // [streams] samples of the range that are cross-faded
+    cpqi::DeviceBuffer<double> latGains;     // [streams][latCap]
     int latCap = 0;
 
     // half-band oversampler (engine_os.cpp): CustomInputOversampler around the routing
@@ -291,12 +299,12 @@ struct cpq_engine {
     };
     int osFactor = 1, osType = CPQ_OS_IIR, osStages = 0;
     OsStageDev osStage[3];
-    char* osMem = nullptr;                      // coefficients and histories of the stages
-    int* osFlags = nullptr;                     // [streams][4] device (os_kernels.hip)
-    unsigned long long* osCounts = nullptr;     // [streams][2] device
-    int* osNonSilent = nullptr;                 // [3][nCh] device: silence test of each down stage
-    double* osTmp[2] = { nullptr, nullptr };    // [nCh][maxCall / 2] stage-to-stage buffers (allocated on first use)
-    double* osWork = nullptr;                   // [nCh][tMax * P] the routing's block at the internal rate
+    cpqi::DeviceBuffer<char> osMem;                      // coefficients and histories of the stages
+    cpqi::DeviceBuffer<int> osFlags;                     // [streams][4] device (os_kernels.hip)
+    cpqi::DeviceBuffer<unsigned long long> osCounts;     // [streams][2] device
+    cpqi::DeviceBuffer<int> osNonSilent;                 // [3][nCh] device: silence test of each down stage
+    cpqi::DeviceBuffer<double> osTmp[2];    // [nCh][maxCall / 2] stage-to-stage buffers (allocated on first use)
+    cpqi::DeviceBuffer<double> osWork;                   // [nCh][tMax * P] the routing's block at the internal rate
 
     // profiling
     bool profiling = false;
@@ -346,13 +354,14 @@ struct ProfScope {
 
 
 int checkCall(cpq_engine* e, const void* in, const void* out, int nSamples);
-int ensureCallBuffer(cpq_engine* e, double** buf, const char* what);
+int ensureCallBuffer(cpq_engine* e, DeviceBuffer<double>& buf, const char* what);
+// exp(-2 pi i m / P) and exp(-2 pi i m / 2P), m < P: extended precision on the host, rounded once (SURVEY.md section 7 "hard parts")
+void hostTwiddles(int P, std::vector<double2>& w1, std::vector<double2>& w2);
 int zeroRuntimeState(cpq_engine* e, bool conv, bool eq);
 
 // engine_native.cpp
 int stageUpload(cpq_engine* e, void* dst, const void* src, size_t bytes);
 void freePinnedRing(cpq_engine* e);
-void freeGroups(cpq_engine* e);
 int resetGroups(cpq_engine* e);
 int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double* irR, int irLen, double scale, int headTaps,
                      const cpq_filter_spec* spec, const cpq_nuc_plan& pl);
@@ -390,8 +399,8 @@ int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& b
     int rc = checkCall(e, in, out, nSamples * factor);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
-    rc = ensureCallBuffer(e, &e->stageIn, "upload staging");
-    if (rc == CPQ_OK) rc = ensureCallBuffer(e, &e->stageOut, "download staging");
+    rc = ensureCallBuffer(e, e->stageIn, "upload staging");
+    if (rc == CPQ_OK) rc = ensureCallBuffer(e, e->stageOut, "download staging");
     if (rc != CPQ_OK) return rc;
     constexpr int kChunks = 4;
     const int T = nSamples * factor / e->P;                             // partitions in the call (whole ones outside CPQ_CALLS_ANY)

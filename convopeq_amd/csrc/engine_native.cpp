@@ -12,65 +12,70 @@
 // in the reference (src/ConvolverProcessor.h:741-814).
 #include "engine_internal.hpp"
 
+#include <type_traits>
+
 using namespace cpqi;
 
 namespace cpqi {
 
 namespace {
 
-struct BufItem { void** ptr; int64_t rowBytes; bool perSlot; };    // perSlot: [hSlots] rows instead of [capCh]
+struct BufItem { void* ptr; int64_t rowBytes; bool perSlot; };    // perSlot: [hSlots] rows instead of [capCh]
 
-// the device buffers of one layer, as (pointer, bytes per channel row) so that growing a group copies row prefixes
-std::vector<BufItem> layerItems(NativeLayer& t)
+// the row buffers of one layer: f(pointer member, bytes per channel row, perSlot), on a const layer or one being laid out
+template <typename Layer, typename F>
+void forEachRowBuffer(Layer& t, F&& f)
 {
-    return {
-        { (void**)&t.X, (int64_t)t.ringSlots * t.P * (int64_t)sizeof(double2), false },
-        { (void**)&t.XDN, (int64_t)t.ringSlots * (int64_t)sizeof(double2), false },
-        { (void**)&t.H, (int64_t)t.hRows * t.P * (int64_t)sizeof(double2), true },
-        { (void**)&t.HDN, (int64_t)t.hRows * (int64_t)sizeof(double2), true },
-        { (void**)&t.Y, (int64_t)t.nbMax * t.P * (int64_t)sizeof(double2), false },
-        { (void**)&t.hist[0], (int64_t)t.P * (int64_t)sizeof(double), false },
-        { (void**)&t.hist[1], (int64_t)t.P * (int64_t)sizeof(double), false },
-        { (void**)&t.acc[0], (int64_t)t.accCap * (int64_t)sizeof(double), false },
-        { (void**)&t.acc[1], (int64_t)t.accCap * (int64_t)sizeof(double), false },
-        { (void**)&t.ring, (int64_t)t.outRing * (int64_t)sizeof(double), false },
-    };
+    f(t.X, (int64_t)t.ringSlots * t.P * (int64_t)sizeof(double2), false);
+    f(t.XDN, (int64_t)t.ringSlots * (int64_t)sizeof(double2), false);
+    f(t.H, (int64_t)t.hRows * t.P * (int64_t)sizeof(double2), true);
+    f(t.HDN, (int64_t)t.hRows * (int64_t)sizeof(double2), true);
+    f(t.Y, (int64_t)t.nbMax * t.P * (int64_t)sizeof(double2), false);
+    f(t.hist[0], (int64_t)t.P * (int64_t)sizeof(double), false);
+    f(t.hist[1], (int64_t)t.P * (int64_t)sizeof(double), false);
+    f(t.acc[0], (int64_t)t.accCap * (int64_t)sizeof(double), false);
+    f(t.acc[1], (int64_t)t.accCap * (int64_t)sizeof(double), false);
+    f(t.ring, (int64_t)t.outRing * (int64_t)sizeof(double), false);
 }
 
-int allocLayer(cpq_engine* e, PlanGroup& g, NativeLayer& t, int capCh, int hSlots)
+// the same as (pointer, bytes per channel row) so that growing a group copies row prefixes
+std::vector<BufItem> layerItems(const NativeLayer& t)
 {
-    auto items = layerItems(t);
+    std::vector<BufItem> items;
+    forEachRowBuffer(t, [&](auto* p, int64_t rowBytes, bool perSlot) { items.push_back(BufItem{ p, rowBytes, perSlot }); });
+    return items;
+}
+
+// lays the layer out in one allocation that it owns: on failure the layer is dropped with whatever it holds
+int allocLayer(cpq_engine* e, NativeLayer& t, int capCh, int hSlots)
+{
     int64_t total = 0;
-    for (const BufItem& it : items) total += alignUp(it.rowBytes * (it.perSlot ? hSlots : capCh), 256);
+    forEachRowBuffer(t, [&](auto*, int64_t rowBytes, bool perSlot) { total += alignUp(rowBytes * (perSlot ? hSlots : capCh), 256); });
     const int64_t twBytes = alignUp(t.P * (int64_t)sizeof(double2), 256);
     const int64_t gainBytes = alignUp((t.P + 1) * (int64_t)sizeof(double), 256);
     const int64_t scratchBytes = t.P > 4096 ? alignUp(std::max<int64_t>((int64_t)capCh * t.nbMax, t.K) * t.P * (int64_t)sizeof(double2), 256) : 256;
     const bool big = t.P > 4096;          // four-step transforms: + the two reordered tables (kernels.hpp: FftTables)
     total += (big ? 4 : 2) * twBytes + gainBytes + scratchBytes;
-    char* mem = nullptr;
-    if (hipMalloc((void**)&mem, (size_t)total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e, CPQ_ERR_OOM, "plan group layer (partition %d, %d channels): %lld bytes could not be allocated", t.P, capCh,
-                    (long long)total);
+    {
+        const int rc = allocAll(e, { { t.mem, (size_t)total } }, "plan group layer (partition %d, %d channels): %lld bytes could not be allocated",
+                                t.P, capCh, (long long)total);
+        if (rc != CPQ_OK) return rc;
     }
+    char* const mem = t.mem;
     CPQ_HIP(e, hipMemsetAsync(mem, 0, (size_t)total, e->stream));
     int64_t off = 0;
-    for (const BufItem& it : items) { *it.ptr = mem + off; off += alignUp(it.rowBytes * (it.perSlot ? hSlots : capCh), 256); }
+    forEachRowBuffer(t, [&](auto*& p, int64_t rowBytes, bool perSlot) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(mem + off);
+        off += alignUp(rowBytes * (perSlot ? hSlots : capCh), 256);
+    });
     t.tw = (double2*)(mem + off); off += twBytes;
     t.tw2 = (double2*)(mem + off); off += twBytes;
     t.twCol = t.twSplit = nullptr;
     if (big) { t.twCol = (double2*)(mem + off); off += twBytes; t.twSplit = (double2*)(mem + off); off += twBytes; }
     t.gainDev = (double*)(mem + off); off += gainBytes;
     t.scratch = (double2*)(mem + off);
-    t.mem = mem;
-    // twiddles in extended precision, rounded once
-    std::vector<double2> w(t.P), w2(t.P);
-    const long double twoPi = 6.283185307179586476925286766559005768L;
-    for (int m = 0; m < t.P; ++m) {
-        const long double a = -twoPi * m / (long double)t.P, b = -twoPi * m / (long double)(2 * t.P);
-        w[m] = make_double2((double)cosl(a), (double)sinl(a));
-        w2[m] = make_double2((double)cosl(b), (double)sinl(b));
-    }
+    std::vector<double2> w, w2;
+    hostTwiddles(t.P, w, w2);
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     CPQ_HIP(e, hipMemcpy(t.tw, w.data(), t.P * sizeof(double2), hipMemcpyHostToDevice));
     CPQ_HIP(e, hipMemcpy(t.tw2, w2.data(), t.P * sizeof(double2), hipMemcpyHostToDevice));
@@ -80,7 +85,6 @@ int allocLayer(cpq_engine* e, PlanGroup& g, NativeLayer& t, int capCh, int hSlot
         CPQ_HIP(e, hipMemcpy(t.twCol, wc.data(), t.P * sizeof(double2), hipMemcpyHostToDevice));
         CPQ_HIP(e, hipMemcpy(t.twSplit, ws.data(), t.P * sizeof(double2), hipMemcpyHostToDevice));
     }
-    (void)g;
     return CPQ_OK;
 }
 
@@ -100,17 +104,6 @@ void layerGeometry(const cpq_engine* e, const cpq_nuc_plan& pl, int l, NativeLay
     // layer 0: the output ring holds what Get() has not read yet (< P0 + one chunk) plus one call of new blocks;
     // tail layers: the reader is at most outputDelay behind the writer, blocks are stored when their partition fills
     t.outRing = (l == 0) ? nextPow2(2 * t.P + nMax + t.P) : nextPow2(pl.output_delay[l] + 3 * t.P + nMax + e->B);
-}
-
-void freeGroupBuffers(PlanGroup& g)
-{
-    for (NativeLayer& t : g.layers) if (t.mem) (void)hipFree(t.mem);
-    g.layers.clear();
-    if (g.chMapDev) (void)hipFree(g.chMapDev);
-    if (g.irSlotDev) (void)hipFree(g.irSlotDev);
-    if (g.tabDev) (void)hipFree(g.tabDev);
-    g.chMapDev = g.irSlotDev = nullptr;
-    g.tabDev = nullptr;
 }
 
 void resetGroupHost(PlanGroup& g)
@@ -144,11 +137,11 @@ int uploadGroupMaps(cpq_engine* e, PlanGroup& g)
     return CPQ_OK;
 }
 
-int tabEntries(const cpq_engine* e, const PlanGroup& g)
+int tabEntries(const cpq_engine* e, const std::vector<NativeLayer>& layers)
 {
     const int chunks = (e->maxCall + e->B - 1) / e->B + 1;
     int n = 2 * chunks;                                             // layer 0: pos, cnt per chunk
-    for (size_t l = 1; l < g.layers.size(); ++l) n += chunks + g.layers[l].nbMax + 1;     // sched per chunk, put position per block
+    for (size_t l = 1; l < layers.size(); ++l) n += chunks + layers[l].nbMax + 1;     // sched per chunk, put position per block
     return n;
 }
 
@@ -160,53 +153,43 @@ int sizeGroup(cpq_engine* e, PlanGroup& g, int capPairs)
     const int hSlots = g.shared ? 2 : newCapCh;
     const std::vector<NativeLayer>& old = g.layers;
     const int oldCapCh = g.capCh, oldHSlots = g.shared ? 2 : oldCapCh;
-    std::vector<NativeLayer> fresh;
-    int* chMapNew = nullptr;
-    int* irSlotNew = nullptr;
-    long long* tabNew = nullptr;
+    std::vector<NativeLayer> fresh;           // owners: whatever has been built is freed on every way out but the swap
+    DeviceBuffer<int> chMapNew, irSlotNew;
+    DeviceBuffer<long long> tabNew;
+    fresh.reserve((size_t)g.plan.num_layers);
     auto undo = [&](int rc) {
-        (void)hipStreamSynchronize(e->stream);      // row copies into the fresh buffers may still be in flight
-        for (NativeLayer& t : fresh) if (t.mem) (void)hipFree(t.mem);
-        if (chMapNew) (void)hipFree(chMapNew);
-        if (irSlotNew) (void)hipFree(irSlotNew);
-        if (tabNew) (void)hipFree(tabNew);
+        (void)hipStreamSynchronize(e->stream);      // row copies into the fresh buffers may still be in flight before they are freed
         (void)hipGetLastError();
         return rc;
     };
     for (int l = 0; l < g.plan.num_layers; ++l) {
-        NativeLayer t;
-        if (!old.empty()) { t = old[(size_t)l]; t.mem = nullptr; }
+        fresh.emplace_back();
+        NativeLayer& t = fresh.back();
+        if (!old.empty()) static_cast<LayerState&>(t) = old[(size_t)l];
         layerGeometry(e, g.plan, l, t);
-        const int rc = allocLayer(e, g, t, newCapCh, hSlots);
+        const int rc = allocLayer(e, t, newCapCh, hSlots);
         if (rc != CPQ_OK) return undo(rc);
-        fresh.push_back(t);
         if (!old.empty()) {
-            const NativeLayer& o = old[(size_t)l];
-            NativeLayer oc = o;
-            auto src = layerItems(oc), dst = layerItems(fresh.back());
+            auto src = layerItems(old[(size_t)l]), dst = layerItems(t);
             for (size_t i = 0; i < src.size(); ++i) {
                 const int64_t rows = src[i].perSlot ? oldHSlots : oldCapCh;
-                if (hipMemcpyAsync(*dst[i].ptr, *src[i].ptr, (size_t)(rows * src[i].rowBytes), hipMemcpyDeviceToDevice, e->stream) != hipSuccess)
+                if (hipMemcpyAsync(dst[i].ptr, src[i].ptr, (size_t)(rows * src[i].rowBytes), hipMemcpyDeviceToDevice, e->stream) != hipSuccess)
                     return undo(fail(e, CPQ_ERR_DEVICE, "plan group rows could not be copied"));
             }
         }
     }
     if (hipStreamSynchronize(e->stream) != hipSuccess) return undo(fail(e, CPQ_ERR_DEVICE, "plan group resize: stream error"));
-    PlanGroup probe = g;                      // table size of the new geometry
-    probe.layers = fresh;
-    const int tabCap = tabEntries(e, probe);
-    if (hipMalloc((void**)&chMapNew, sizeof(int) * newCapCh) != hipSuccess || hipMalloc((void**)&irSlotNew, sizeof(int) * newCapCh) != hipSuccess ||
-        hipMalloc((void**)&tabNew, sizeof(long long) * (size_t)tabCap) != hipSuccess)
-        return undo(fail(e, CPQ_ERR_OOM, "plan group tables could not be allocated"));
-    // success: swap
-    for (NativeLayer& o : g.layers) if (o.mem) (void)hipFree(o.mem);
-    if (g.chMapDev) (void)hipFree(g.chMapDev);
-    if (g.irSlotDev) (void)hipFree(g.irSlotDev);
-    if (g.tabDev) (void)hipFree(g.tabDev);
-    g.layers = fresh;
-    g.chMapDev = chMapNew;
-    g.irSlotDev = irSlotNew;
-    g.tabDev = tabNew;
+    const int tabCap = tabEntries(e, fresh);  // table size of the new geometry
+    {
+        const int rc = allocAll(e, { { chMapNew, (size_t)newCapCh }, { irSlotNew, (size_t)newCapCh }, { tabNew, (size_t)tabCap } },
+                                "plan group tables could not be allocated");
+        if (rc != CPQ_OK) return undo(rc);
+    }
+    // success: swap (the move assignments free what the group held, in the order layers, channel map, IR slots, tables)
+    g.layers = std::move(fresh);
+    g.chMapDev = std::move(chMapNew);
+    g.irSlotDev = std::move(irSlotNew);
+    g.tabDev = std::move(tabNew);
     g.capCh = newCapCh;
     g.streamOfPair.resize((size_t)capPairs, -1);
     g.tabCap = tabCap;
@@ -220,7 +203,7 @@ int zeroPairState(cpq_engine* e, PlanGroup& g, int pair)
         auto items = layerItems(t);
         for (const BufItem& it : items) {
             if (it.perSlot) continue;
-            CPQ_HIP(e, hipMemsetAsync((char*)*it.ptr + (int64_t)2 * pair * it.rowBytes, 0, (size_t)(2 * it.rowBytes), e->stream));
+            CPQ_HIP(e, hipMemsetAsync((char*)it.ptr + (int64_t)2 * pair * it.rowBytes, 0, (size_t)(2 * it.rowBytes), e->stream));
         }
     }
     return CPQ_OK;
@@ -239,11 +222,8 @@ int stageUpload(cpq_engine* e, void* dst, const void* src, size_t bytes)
     PinnedRing& r = e->pinned;
     if (!r.host) {
         r.cap = (size_t)8 << 20;
-        if (hipHostMalloc((void**)&r.host, r.cap) != hipSuccess) {
-            (void)hipGetLastError();
-            r.host = nullptr;
-            return fail(e, CPQ_ERR_OOM, "pinned staging ring could not be allocated");
-        }
+        const int rc = allocAll(e, { { r.host, r.cap } }, "pinned staging ring could not be allocated");
+        if (rc != CPQ_OK) return rc;
     }
     const size_t need = (bytes + 255) & ~(size_t)255;
     if (need > r.cap / 4) {
@@ -290,25 +270,17 @@ void freePinnedRing(cpq_engine* e)
     for (auto& ev : r.freeEvents) (void)hipEventDestroy(ev);
     r.pending.clear();
     r.freeEvents.clear();
-    (void)hipHostFree(r.host);
-    r.host = nullptr;
-}
-
-void freeGroups(cpq_engine* e)
-{
-    for (PlanGroup* g : e->groups) { freeGroupBuffers(*g); delete g; }
-    e->groups.clear();
-    std::fill(e->groupOf.begin(), e->groupOf.end(), -1);
+    r.host.reset();
 }
 
 int resetGroups(cpq_engine* e)
 {
-    for (PlanGroup* gp : e->groups) {
+    for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
         for (NativeLayer& t : g.layers) {
             auto items = layerItems(t);
             for (const BufItem& it : items)
-                if (!it.perSlot) CPQ_HIP(e, hipMemsetAsync(*it.ptr, 0, (size_t)(it.rowBytes * g.capCh), e->stream));
+                if (!it.perSlot) CPQ_HIP(e, hipMemsetAsync(it.ptr, 0, (size_t)(it.rowBytes * g.capCh), e->stream));
         }
         resetGroupHost(g);
         g.frozen = false;       // resting is processor-level state: the next processor-level call re-establishes it (enqueueConvProc)
@@ -332,9 +304,7 @@ int leaveNativeGroup(cpq_engine* e, int stream)
     for (int s : g.streamOfPair) empty = empty && s < 0;
     if (empty) {
         CPQ_HIP(e, hipStreamSynchronize(e->stream));
-        freeGroupBuffers(g);
-        delete e->groups[(size_t)gi];
-        e->groups.erase(e->groups.begin() + gi);
+        e->groups.erase(e->groups.begin() + gi);        // frees the group's buffers
         for (int& go : e->groupOf) if (go > gi) --go;
         return CPQ_OK;
     }
@@ -356,7 +326,7 @@ static int isolateStream(cpq_engine* e, int stream)
         if (g.streamOfPair[p] == stream) pair = (int)p;
     }
     if (members <= 1 || pair < 0) return CPQ_OK;
-    PlanGroup* n = new (std::nothrow) PlanGroup();
+    std::unique_ptr<PlanGroup> n(new (std::nothrow) PlanGroup());
     if (!n) return fail(e, CPQ_ERR_OOM, "host allocation failed");
     n->plan = g.plan;
     n->hasSpec = g.hasSpec;
@@ -366,33 +336,32 @@ static int isolateStream(cpq_engine* e, int stream)
     n->lastGot = g.lastGot;
     n->lastCall = g.lastCall;
     int rc = sizeGroup(e, *n, 1);
-    if (rc != CPQ_OK) { freeGroupBuffers(*n); delete n; return rc; }
+    if (rc != CPQ_OK) return rc;
     for (size_t l = 0; l < g.layers.size(); ++l) {
-        NativeLayer& src = g.layers[l];
+        const NativeLayer& src = g.layers[l];
         NativeLayer& dst = n->layers[l];
         auto si = layerItems(src), di = layerItems(dst);
         for (size_t i = 0; i < si.size(); ++i) {
             const int64_t rows = 2, from = si[i].perSlot ? (g.shared ? 0 : 2 * pair) : 2 * pair;
-            if (hipMemcpyAsync(*di[i].ptr, (char*)*si[i].ptr + from * si[i].rowBytes, (size_t)(rows * si[i].rowBytes),
+            if (hipMemcpyAsync(di[i].ptr, (char*)si[i].ptr + from * si[i].rowBytes, (size_t)(rows * si[i].rowBytes),
                                hipMemcpyDeviceToDevice, e->stream) != hipSuccess) {
-                (void)hipStreamSynchronize(e->stream);
-                freeGroupBuffers(*n);
-                delete n;
+                (void)hipStreamSynchronize(e->stream);          // before the new group's buffers go
                 return fail(e, CPQ_ERR_DEVICE, "plan group rows could not be copied");
             }
         }
-        dst.head = src.head; dst.histSel = src.histSel; dst.accSel = src.accSel; dst.fill = src.fill;
-        dst.distributing = src.distributing; dst.nextPart = src.nextPart; dst.wPos = src.wPos; dst.rPos = src.rPos;
+        static_cast<LayerState&>(dst) = src;
+        dst.fftAhead = 0;               // (belongs to a call in flight)
     }
     n->streamOfPair[0] = stream;
     // the stream is the new group's from here on, whatever happens below: the engine stays consistent
     g.streamOfPair[(size_t)pair] = -1;
-    e->groups.push_back(n);
+    PlanGroup& isolated = *n;
+    e->groups.push_back(std::move(n));
     e->groupOf[(size_t)stream] = (int)e->groups.size() - 1;
     rc = zeroPairState(e, g, pair);
     if (rc != CPQ_OK) return rc;
     rc = uploadGroupMaps(e, g);
-    if (rc == CPQ_OK) rc = uploadGroupMaps(e, *n);
+    if (rc == CPQ_OK) rc = uploadGroupMaps(e, isolated);
     return rc;
 }
 
@@ -413,7 +382,7 @@ int setStreamFrozen(cpq_engine* e, int stream, bool frozen)
 
 void clearFrozen(cpq_engine* e)
 {
-    for (PlanGroup* g : e->groups) g->frozen = false;
+    for (const auto& g : e->groups) g->frozen = false;
 }
 
 // SetImpulse of one stream (or of all streams with one shared stereo IR) on the reference's own layer plan
@@ -440,15 +409,16 @@ int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double*
             if (!c.shared && !c.frozen && c.samplesSinceReset == 0 && sameSpec && std::memcmp(&c.plan, &pl, sizeof(pl)) == 0) { g = &c; gi = (int)i; }     // (a resting group holds one isolated stream: nobody joins it)
         }
     if (!g) {
-        g = new (std::nothrow) PlanGroup();
-        if (!g) return fail(e, CPQ_ERR_OOM, "host allocation failed");
+        std::unique_ptr<PlanGroup> made(new (std::nothrow) PlanGroup());
+        if (!made) return fail(e, CPQ_ERR_OOM, "host allocation failed");
+        g = made.get();
         g->plan = pl;
         g->hasSpec = spec != nullptr;
         if (spec) g->spec = *spec;
         g->shared = shared;
         const int rc = sizeGroup(e, *g, shared ? S : 1);       // one pair, doubled as members join: 256 one-member groups (256 IR lengths) cost what they use
-        if (rc != CPQ_OK) { freeGroupBuffers(*g); delete g; return rc; }
-        e->groups.push_back(g);
+        if (rc != CPQ_OK) return rc;
+        e->groups.push_back(std::move(made));
         gi = (int)e->groups.size() - 1;
     }
     // pair slots
@@ -574,7 +544,7 @@ static bool layer0WasEmpty(const PlanGroup& g, long long w0, long long r0)
 
 int groupsAppend(cpq_engine* e, const double* dIn, int n)
 {
-    for (PlanGroup* gp : e->groups) {
+    for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
         if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
         // every layer accumulates the same input (Add(), :1431-1446): one pass over it.  A layer whose accumulator is
@@ -706,7 +676,7 @@ static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, co
 // layer 0 of every group: blocks, then the chunk-wise ring read into the members' output rows (which it overwrites)
 int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
 {
-    for (PlanGroup* gp : e->groups) {
+    for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
         if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
         const long long w0 = g.callW0, r0 = g.callR0;        // (replayed in groupsAppend)
@@ -755,7 +725,7 @@ int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
 // tail layers of every group: blocks into the delay lines, then the chunk-wise read-add with the layer gain (:1620-1633)
 int groupsRunTails(cpq_engine* e, double* dOut, int n)
 {
-    for (PlanGroup* gp : e->groups) {
+    for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
         if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
         if (g.tailsDone) { g.tailsDone = false; continue; }     // (ran ahead of layer 0, whose transform added their blocks: groupsRunLayer0)

@@ -8,8 +8,7 @@ namespace cpqi {
 
 void freeOversampler(cpq_engine* e)
 {
-    if (e->osMem) (void)hipFree(e->osMem);
-    e->osMem = nullptr;
+    e->osMem.reset();
     for (auto& s : e->osStage) s = cpq_engine::OsStageDev{};
     e->osStages = 0;
 }
@@ -32,14 +31,11 @@ int resetOversampler(cpq_engine* e)
 
 static int ensureOsTmp(cpq_engine* e)
 {
-    for (double*& p : e->osTmp) {
-        if (p) continue;
-        const size_t bytes = sizeof(double) * (size_t)e->nCh * (size_t)(e->maxCall / 2);
-        if (hipMalloc((void**)&p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail(e, CPQ_ERR_OOM, "oversampler stage buffer of %zu bytes could not be allocated", bytes);
-        }
+    for (auto& b : e->osTmp) {
+        if (b) continue;
+        const size_t count = (size_t)e->nCh * (size_t)(e->maxCall / 2);
+        const int rc = allocAll(e, { { b, count } }, "oversampler stage buffer of %zu bytes could not be allocated", count * sizeof(double));
+        if (rc != CPQ_OK) return rc;
     }
     return CPQ_OK;
 }
@@ -123,7 +119,7 @@ static int enqueueDown(cpq_engine* e, const double* in, int64_t inStride, double
 // whole path with factor > 1: up -> routing on nBase * F samples in the internal work buffer (in place) -> down
 int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase)
 {
-    int rc = ensureCallBuffer(e, &e->osWork, "oversampled block");
+    int rc = ensureCallBuffer(e, e->osWork, "oversampled block");
     if (rc != CPQ_OK) return rc;
     const int n = nBase * e->osFactor;
     rc = enqueueUp(e, dIn, nBase, e->osWork, n, nBase);
@@ -156,8 +152,8 @@ static int osHost(cpq_engine* e, const double* in, double* out, int nBase, size_
     int rc = checkOsCall(e, in, out, nBase);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
-    rc = ensureCallBuffer(e, &e->stageIn, "upload staging");
-    if (rc == CPQ_OK) rc = ensureCallBuffer(e, &e->stageOut, "download staging");
+    rc = ensureCallBuffer(e, e->stageIn, "upload staging");
+    if (rc == CPQ_OK) rc = ensureCallBuffer(e, e->stageOut, "download staging");
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, sizeof(double) * (size_t)e->nCh * inLen, hipMemcpyHostToDevice, e->stream));
     rc = body(e->stageIn, e->stageOut);
@@ -184,12 +180,9 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
     freeOversampler(e);
     const int S = e->desc.n_streams;
     if (!e->osFlags) {
-        if (hipMalloc((void**)&e->osFlags, sizeof(int) * 4 * S) != hipSuccess ||
-            hipMalloc((void**)&e->osCounts, sizeof(unsigned long long) * 2 * S) != hipSuccess ||
-            hipMalloc((void**)&e->osNonSilent, sizeof(int) * 3 * e->nCh) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(e, CPQ_ERR_OOM, "oversampler state could not be allocated");
-        }
+        const int rc = allocAll(e, { { e->osFlags, (size_t)4 * S }, { e->osCounts, (size_t)2 * S }, { e->osNonSilent, (size_t)3 * e->nCh } },
+                                "oversampler state could not be allocated");
+        if (rc != CPQ_OK) return rc;
     }
     CPQ_HIP(e, hipMemset(e->osCounts, 0, sizeof(unsigned long long) * 2 * S));
     CPQ_HIP(e, hipMemset(e->osFlags, 0, sizeof(int) * 4 * S));
@@ -207,13 +200,11 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
         }
         bytes += (size_t)alignUp(st[i].convCount, 32) + 2 * (size_t)e->nCh * (alignUp(st[i].historyUpKeep, 32) + alignUp(st[i].historyDownKeep, 32));
     }
-    if (hipMalloc((void**)&e->osMem, bytes * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        e->osMem = nullptr;
+    if (!e->osMem.alloc(bytes * sizeof(double))) {
         e->osFactor = 1;
         return fail(e, CPQ_ERR_OOM, "oversampler histories of %zu bytes could not be allocated", bytes * sizeof(double));
     }
-    double* p = reinterpret_cast<double*>(e->osMem);
+    double* p = reinterpret_cast<double*>(e->osMem.get());
     for (int i = 0; i < nStages; ++i) {
         auto& d = e->osStage[i];
         d.convCount = st[i].convCount;

@@ -42,30 +42,27 @@ int uploadProcParams(cpq_engine* e)
     CPQ_HIP(e, hipSetDevice(e->device));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     if (!e->procGains) {
-        CPQ_HIP(e, hipMalloc((void**)&e->procGains, sizeof(double) * 2 * S));
-        CPQ_HIP(e, hipMalloc((void**)&e->procDelay, sizeof(int) * S));
+        const int rc = allocAll(e, { { e->procGains, (size_t)2 * S }, { e->procDelay, (size_t)S } }, "processor-level gain buffers could not be allocated");
+        if (rc != CPQ_OK) return rc;
     }
     // delay ring: the longest delay in sight (any IR that fits the engine: irPeakLatency < irLen) plus one call; a larger
     // request later grows it, keeping what it holds
     const int64_t need = (int64_t)std::max(maxDelay, e->P0 + e->desc.max_ir_len) + (int64_t)e->tMax * e->P + 1;
     if (need > e->dryRingSize) {
         const int size = nextPow2((int)std::min<int64_t>(need, (int64_t)1 << 30));
-        double* ring = nullptr;
-        if (hipMalloc((void**)&ring, sizeof(double) * (size_t)e->nCh * size) != hipSuccess)
-            return fail(e, CPQ_ERR_OOM, "dry delay line of %d samples per channel could not be allocated", size);
-        CPQ_HIP(e, hipMemset(ring, 0, sizeof(double) * (size_t)e->nCh * size));
+        DeviceBuffer<double> ring;
+        const int rc = allocAll(e, { { ring, (size_t)e->nCh * size, true } }, "dry delay line of %d samples per channel could not be allocated", size);
+        if (rc != CPQ_OK) return rc;
         if (e->dryRing) {
             cpq::launch_ring_regrow(e->stream, e->dryRing, e->dryRingSize, ring, size, e->dryPos, e->nCh);
             CPQ_HIP(e, hipStreamSynchronize(e->stream));
-            (void)hipFree(e->dryRing);
         }
-        e->dryRing = ring;
+        e->dryRing = std::move(ring);       // frees the old ring
         e->dryRingSize = size;
     }
     if (!e->latNew) {
-        if (hipMalloc((void**)&e->latNew, sizeof(int) * S) != hipSuccess || hipMalloc((void**)&e->latOld, sizeof(int) * S) != hipSuccess ||
-            hipMalloc((void**)&e->latLen, sizeof(int) * S) != hipSuccess)
-            return fail(e, CPQ_ERR_OOM, "latency buffers could not be allocated");
+        const int rc = allocAll(e, { { e->latNew, (size_t)S }, { e->latOld, (size_t)S }, { e->latLen, (size_t)S } }, "latency buffers could not be allocated");
+        if (rc != CPQ_OK) return rc;
     }
     CPQ_HIP(e, hipMemcpy(e->procGains, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice));
     CPQ_HIP(e, hipMemcpy(e->procDelay, d.data(), sizeof(int) * d.size(), hipMemcpyHostToDevice));
@@ -140,16 +137,11 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
         }
     }
     if (anyRamp) {
-        if (!e->mixRampLen && hipMalloc((void**)&e->mixRampLen, sizeof(int) * S) != hipSuccess)
-            return fail(e, CPQ_ERR_OOM, "mix-ramp buffers could not be allocated");
-        if (rampStride > e->mixRampCap) {
-            if (e->mixRampGains) (void)hipFree(e->mixRampGains);
-            e->mixRampGains = nullptr;
-            e->mixRampCap = 0;
-            if (hipMalloc((void**)&e->mixRampGains, sizeof(double) * 2 * (size_t)S * rampStride) != hipSuccess)
-                return fail(e, CPQ_ERR_OOM, "mix-ramp buffers could not be allocated");
-            e->mixRampCap = rampStride;
+        if (!e->mixRampLen) {
+            const int rc = allocAll(e, { { e->mixRampLen, (size_t)S } }, "mix-ramp buffers could not be allocated");
+            if (rc != CPQ_OK) return rc;
         }
+        { const int rc = grow(e, e->mixRampGains, e->mixRampCap, rampStride, (size_t)2 * S, "mix-ramp buffers could not be allocated"); if (rc != CPQ_OK) return rc; }
         { const int rcUp = stageUpload(e, e->mixRampLen, mixRampLenHost.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
         { const int rcUp = stageUpload(e, e->mixRampGains, rampHost.data(), sizeof(double) * rampHost.size()); if (rcUp != CPQ_OK) return rcUp; }
     }
@@ -176,8 +168,10 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
         std::vector<int> wetOn((size_t)S);
         for (int s = 0; s < S; ++s) wetOn[s] = rest[s] ? 0 : 1;
         if (wetOn != e->procWetOnHost) {
-            if (!e->procWetOn && hipMalloc((void**)&e->procWetOn, sizeof(int) * S) != hipSuccess)
-                return fail(e, CPQ_ERR_OOM, "processor-level flags could not be allocated");
+            if (!e->procWetOn) {
+                const int rcA = allocAll(e, { { e->procWetOn, (size_t)S } }, "processor-level flags could not be allocated");
+                if (rcA != CPQ_OK) return rcA;
+            }
             const int rc = stageUpload(e, e->procWetOn, wetOn.data(), sizeof(int) * S);
             if (rc != CPQ_OK) return rc;
             e->procWetOnHost = wetOn;
@@ -285,13 +279,9 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     }
     bool anyFadeValues = false;            // a fade of ONE value (a one-sample call) needs the buffer as well
     for (int r = 0; r < R; ++r) anyFadeValues = anyFadeValues || !xg[r].empty();
-    if (anyFadeValues && e->latCap < xTotal + e->B) {
-        if (e->latGains) (void)hipFree(e->latGains);
-        e->latGains = nullptr;
-        e->latCap = 0;
-        if (hipMalloc((void**)&e->latGains, sizeof(double) * (size_t)S * (xTotal + e->B)) != hipSuccess)
-            return fail(e, CPQ_ERR_OOM, "latency cross-fade buffer could not be allocated");
-        e->latCap = xTotal + e->B;
+    if (anyFadeValues) {
+        const int rc = grow(e, e->latGains, e->latCap, xTotal + e->B, (size_t)S, "latency cross-fade buffer could not be allocated");
+        if (rc != CPQ_OK) return rc;
     }
     for (int r = 0; r < R; ++r) {
         const int off = ranges[r].c0 * e->B, len = std::min(ranges[r].c1 * e->B, n) - off;

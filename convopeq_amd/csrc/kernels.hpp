@@ -151,8 +151,6 @@ void launch_rows_copy(hipStream_t stream, const double* src, int64_t srcStride, 
                       int64_t dstStride, int64_t dstOff, int n, int nCh);
 void launch_ring_put(hipStream_t stream, const double* z, int64_t zStride, int n, double* ring, int ringSize,
                      long long pos, int nCh);
-void launch_ring_add(hipStream_t stream, double* out, int64_t outStride, int n, int B, const double* ring, int ringSize,
-                     const long long* sched, double gain, int nCh);
 // Layered mode with the reader's additions inside the layer-0 inverse transform: the schedule first (launch_tail_schedule),
 // then launch_rfft_inv_ols_tail writes out = layer-0 convolution + what the reader adds (from layerOut / the rings), then
 // launch_tail_append stores what later calls may still read into the rings.
@@ -167,8 +165,6 @@ void launch_tail_schedule(hipStream_t stream, void* state, long long* sched, int
 
 // Plan groups (engine_native.cpp): chMap[local channel] = row of the call's buffers (-1 = unused slot); q = chunk length
 // (one Add / Get pair of the reference per chunk); pos / cnt / sched: per chunk, replayed on the host.
-void launch_rows_gather(hipStream_t stream, const double* src, int64_t srcStride, const int* chMap, double* dst,
-                        int64_t dstStride, int64_t dstOff, int n, int nCh);
 // up to three layers' accumulators in one pass over the input; both tail layers' read-add in one pass over the output
 // tabDst / tab / nTab: a small table (<= kGatherTabMax entries) that rides along as kernel arguments and is stored to tabDst by
 // the launch -- the call's chunk schedule of a plan group without a host -> device copy of its own
@@ -179,8 +175,6 @@ void launch_rows_gather_multi(hipStream_t stream, const double* src, int64_t src
 void launch_ring_add_chunks2(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
                              const double* ringA, int ringSizeA, const long long* schedA, double gainA,
                              const double* ringB, int ringSizeB, const long long* schedB, double gainB, int nCh);
-void launch_ring_put_blocks(hipStream_t stream, const double* z, int64_t zStride, int P, int nb, double* ring, int ringSize,
-                            const long long* pos, int nCh);
 // launch_ring_get_chunks and launch_ring_add_chunks[2] in one pass over the output (ringB may be null)
 void launch_ring_get_add_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
                                 const double* ring0, int ringSize0, const long long* pos, const long long* cnt,

@@ -247,56 +247,10 @@ __global__ __launch_bounds__(256) void k_ring_put(const double* __restrict__ z, 
         r[(pos + i) & mask] = s[i];
 }
 
-// delayLineReadAdd (NUC.cpp:1653-1688) for the callbacks of one call: callback cb reads B samples at delay-line position
-// sched[cb] (k_tail_schedule replays the reader; -1 = "writer not far enough ahead", nothing is added):
-// out[c][cb B + j] += ring[c][(sched[cb] + j) & mask] * gain
-__global__ __launch_bounds__(256) void k_ring_add(double* out, int64_t outStride, int n, int B, const double* __restrict__ ring,
-                                                  int mask, const long long* __restrict__ sched, double gain)
-{
-    double* o = out + (int64_t)blockIdx.y * outStride;
-    const double* r = ring + (int64_t)blockIdx.y * (mask + 1);
-    const bool unity = fabs(gain - 1.0) < 1.0e-12;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int cb = i / B, j = i - cb * B;
-        const long long s0 = sched[cb];
-        if (s0 < 0) continue;
-        const double v = r[(s0 + j) & mask];
-        o[i] = unity ? (o[i] + v) : (o[i] + v * gain);
-    }
-}
-
 
 // ---- plan groups (engine_native.cpp): a group's channels are rows chMap[local] of the call's buffers (-1 = unused slot);
 // every Add / Get pair of the reference is one CHUNK of the call (q samples, the last one possibly shorter), whose read
 // positions the host replays (ringRead :1376-1402, delayLineReadAdd :1653-1688) and uploads per call.
-// acc[local][dstOff + i] = in[chMap[local]][i]: input accumulation of one layer (inputAccBuf, NUC.cpp:1431-1446)
-__global__ __launch_bounds__(256) void k_rows_gather(const double* __restrict__ src, int64_t srcStride,
-                                                     const int* __restrict__ chMap, double* __restrict__ dst,
-                                                     int64_t dstStride, int64_t dstOff, int n)
-{
-    const int g = chMap[blockIdx.y];
-    if (g < 0) return;
-    const double* s = src + (int64_t)g * srcStride;
-    double* d = dst + (int64_t)blockIdx.y * dstStride + dstOff;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) d[i] = s[i];
-}
-
-// ring[c][(pos[j] + i) & mask] = z[c][j P + i]: the blocks a layer finished in this call go to its output ring / delay
-// line at the position each one has in the reference (ringWrite :1341-1371, delayLineWrite :1639-1648)
-__global__ __launch_bounds__(256) void k_ring_put_blocks(const double* __restrict__ z, int64_t zStride, int P, int nb,
-                                                         double* __restrict__ ring, int mask,
-                                                         const long long* __restrict__ pos)
-{
-    const double* s = z + (int64_t)blockIdx.y * zStride;
-    double* r = ring + (int64_t)blockIdx.y * (mask + 1);
-    const int n = nb * P;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int j = i / P;
-        const long long p = pos[j];
-        if (p >= 0) r[(p + (i - j * P)) & mask] = s[i];
-    }
-}
-
 // Get() of layer 0 per chunk: cnt[cb] samples from ring position pos[cb], zero-filled to the chunk's end (:1376-1402)
 // the call's input into the accumulators of up to three layers of a plan group at once (Add(): every layer accumulates the
 // same input, src/MKLNonUniformConvolver.cpp:1431-1446): the input row is read once
@@ -603,20 +557,6 @@ void launch_ring_put(hipStream_t stream, const double* z, int64_t zStride, int n
     hipLaunchKernelGGL(k_ring_put, rowsGrid(n, nCh), dim3(256), 0, stream, z, zStride, n, ring, ringSize - 1, pos);
 }
 
-void launch_ring_add(hipStream_t stream, double* out, int64_t outStride, int n, int B, const double* ring, int ringSize,
-                     const long long* sched, double gain, int nCh)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_ring_add, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, n, B, ring, ringSize - 1, sched, gain);
-}
-
-void launch_rows_gather(hipStream_t stream, const double* src, int64_t srcStride, const int* chMap, double* dst,
-                        int64_t dstStride, int64_t dstOff, int n, int nCh)
-{
-    if (n <= 0 || nCh <= 0) return;
-    hipLaunchKernelGGL(k_rows_gather, rowsGrid(n, nCh), dim3(256), 0, stream, src, srcStride, chMap, dst, dstStride, dstOff, n);
-}
-
 void launch_rows_gather_multi(hipStream_t stream, const double* src, int64_t srcStride, const int* chMap, int nLayers,
                               double* const* dst, const int64_t* dstStride, const int64_t* dstOff, int n, int nCh,
                               long long* tabDst, const long long* tab, int nTab)
@@ -647,13 +587,6 @@ void launch_ring_get_add_chunks(hipStream_t stream, double* out, int64_t outStri
     if (n <= 0 || nCh <= 0) return;
     hipLaunchKernelGGL(k_ring_get_add_chunks, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, ring0, ringSize0 - 1, pos, cnt,
                        ringA, ringSizeA - 1, schedA, gainA, ringB, ringSizeB - 1, schedB, gainB);
-}
-
-void launch_ring_put_blocks(hipStream_t stream, const double* z, int64_t zStride, int P, int nb, double* ring, int ringSize,
-                            const long long* pos, int nCh)
-{
-    if (nb <= 0 || nCh <= 0) return;
-    hipLaunchKernelGGL(k_ring_put_blocks, rowsGrid(nb * P, nCh), dim3(256), 0, stream, z, zStride, P, nb, ring, ringSize - 1, pos);
 }
 
 void launch_ring_get_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
