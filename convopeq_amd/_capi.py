@@ -29,7 +29,7 @@ CPQ_PARTITION_AUTO = -1
 CPQ_ORDER_CONV_THEN_EQ = 0
 CPQ_ORDER_EQ_THEN_CONV = 1
 KERNEL_IDS = {"k_rfft_fwd_ols": 0, "k_fdl_mac": 1, "k_fdl_mac_dcnyq": 2, "k_rfft_inv_ols": 3, "k_svf_cascade": 4,
-              "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8}
+              "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8, "k_meter": 9}
 CPQ_LEVEL_NUC = 0
 CPQ_LEVEL_PROCESSOR = 1
 CPQ_EQ_MODE_AUTO = 0
@@ -39,6 +39,9 @@ CPQ_PHASE_MIXED = 1
 CPQ_PHASE_MINIMUM = 2
 CPQ_OS_IIR = 0
 CPQ_OS_LINEAR_PHASE = 1
+CPQ_METER_LOUDNESS = 1
+CPQ_METER_TRUE_PEAK = 2
+METER_RING = 4096
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -111,6 +114,11 @@ class OsTelemetry(C.Structure):
                 ("hard_fallback", C.c_int32), ("corruption_pending", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MeterBlock(C.Structure):
+    _fields_ = [("mean_square", C.c_double), ("peak_linear", C.c_double), ("true_peak", C.c_double),
+                ("true_peak_hold", C.c_double), ("block_index", C.c_uint64)]
+
+
 class EngineDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("n_streams", C.c_int32),
                 ("block_size", C.c_int32), ("max_ir_len", C.c_int32), ("max_blocks_per_call", C.c_int32),
@@ -179,6 +187,13 @@ SYMBOLS = {
     "cpq_os_down_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
     "cpq_os_reset": (C.c_int32, [_E]),
     "cpq_os_read_telemetry": (C.c_int32, [_E, C.c_int32, C.POINTER(OsTelemetry)]),
+    "cpq_meter_kweighting": (C.c_int32, [C.c_double, c_double_p, c_double_p]),
+    "cpq_meter_tp_design_stage": (C.c_int32, [C.c_int32, C.POINTER(OsStageInfo), c_double_p, C.c_int32]),
+    "cpq_engine_set_metering": (C.c_int32, [_E, C.c_int32]),
+    "cpq_meter_reset": (C.c_int32, [_E]),
+    "cpq_meter_process": (C.c_int32, [_E, c_double_p, C.c_int32]),
+    "cpq_meter_process_device": (C.c_int32, [_E, C.c_void_p, C.c_int32]),
+    "cpq_meter_read_blocks": (C.c_int32, [_E, C.POINTER(MeterBlock), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "cpq_ir_load_wav": (C.c_int32, [C.c_char_p, C.POINTER(IrBuffer)]),
     "cpq_ir_buffer_free": (None, [C.POINTER(IrBuffer)]),
     "cpq_ir_prepare": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_float, C.c_int32, C.POINTER(IrBuffer), C.c_double, C.POINTER(IrPrepared)]),

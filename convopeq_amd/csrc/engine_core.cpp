@@ -149,6 +149,7 @@ const char* cpq_kernel_name(int32_t id)
         case CPQ_K_MIX: return "k_convproc_mix";
         case CPQ_K_OUTFILT: return "k_outfilter_cascade";
         case CPQ_K_OS: return "k_os_halfband";
+        case CPQ_K_METER: return "k_meter";
         default: return "?";
     }
 }
@@ -584,6 +585,10 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
         const int rc = resetOversampler(e);
         if (rc != CPQ_OK) return rc;
     }
+    {   // truePeakDetector.prepare / loudnessMeter.prepare: coefficients for the new base rate, everything cleared
+        const int rc = refreshMeters(e);
+        if (rc != CPQ_OK) return rc;
+    }
     return zeroRuntimeState(e, true, true);
 }
 
@@ -691,33 +696,35 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed)
     return CPQ_OK;
 }
 
+// the meters read the base-rate rows the call delivers, after everything that writes them (DSPCoreDouble.cpp:695-701)
+static int meteredChain(cpq_engine* e, const double* a, double* b, int n)
+{
+    int rc = e->osFactor > 1 ? enqueueOsChain(e, a, b, n) : enqueueBoth(e, a, b, n);
+    if (rc == CPQ_OK && e->meterFlags) rc = enqueueMeters(e, b, n, n);
+    return rc;
+}
+
 int32_t cpq_engine_process_block_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
-    if (e && e->osFactor > 1) {             // n_samples are base-rate samples: the routing runs on n_samples * factor
-        if (nSamples > e->maxCall / e->osFactor)
-            return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
-                        e->osFactor, e->maxCall);
-        const int rc = checkCall(e, dIn, dOut, nSamples * e->osFactor);
-        if (rc != CPQ_OK) return rc;
-        CPQ_HIP(e, hipSetDevice(e->device));
-        return enqueueOsChain(e, dIn, dOut, nSamples);
-    }
-    const int rc = checkCall(e, dIn, dOut, nSamples);
+    const int factor = e ? e->osFactor : 1;
+    if (factor > 1 && nSamples > e->maxCall / factor)   // n_samples are base-rate samples: the routing runs on n_samples * factor
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
+                    factor, e->maxCall);
+    int rc = checkCall(e, dIn, dOut, nSamples * factor);
+    if (rc == CPQ_OK) rc = checkMeterCall(e, nSamples);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
-    return enqueueBoth(e, dIn, dOut, nSamples);
+    return meteredChain(e, dIn, dOut, nSamples);
 }
 
 int32_t cpq_engine_process_block(cpq_engine* e, const double* in, double* out, int32_t nSamples)
 {
-    if (e && e->osFactor > 1) {
-        if (nSamples > e->maxCall / e->osFactor)
-            return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
-                        e->osFactor, e->maxCall);
-        return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return enqueueOsChain(e, a, b, n); },
-                          e->osFactor);
-    }
-    return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return enqueueBoth(e, a, b, n); });
+    const int factor = e ? e->osFactor : 1;
+    if (factor > 1 && nSamples > e->maxCall / factor)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
+                    factor, e->maxCall);
+    if (e && nSamples > 0) { const int rc = checkMeterCall(e, nSamples); if (rc != CPQ_OK) return rc; }
+    return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return meteredChain(e, a, b, n); }, factor);
 }
 
 // -------------------------------------------------------------------------- profiling

@@ -306,6 +306,19 @@ struct cpq_engine {
     cpqi::DeviceBuffer<double> osTmp[2];    // [nCh][maxCall / 2] stage-to-stage buffers (allocated on first use)
     cpqi::DeviceBuffer<double> osWork;                   // [nCh][tMax * P] the routing's block at the internal rate
 
+    // meters (engine_meter.cpp): LoudnessMeter and TruePeakDetector on the base-rate output rows, one record per callback
+    int meterFlags = 0;                                 // CPQ_METER_*; 0 = off
+    cpqi::DeviceBuffer<double> meterTab;                // K-weighting section tables, then the two stages' FIR branches
+    cpqi::DeviceBuffer<double> meterState;              // [nCh][8] x1 x2 | pre y1 y2 | rlb y1 y2
+    cpqi::DeviceBuffer<double> meterHist[2];            // [nCh][32] last scrubbed inputs (true peak), ping-pong
+    cpqi::DeviceBuffer<double> meterHold;               // [streams] peakHold
+    cpqi::DeviceBuffer<double> meterChSum, meterChPeak; // [nCh][meterCbCap] of the call in flight
+    cpqi::DeviceBuffer<unsigned long long> meterTp;     // [streams][meterCbCap]
+    cpqi::DeviceBuffer<cpq_meter_block> meterRing;      // [streams][kMeterRing]
+    int meterHistSel = 0, meterCbCap = 0;
+    // every stream sees the same callbacks: one pair of ring counters, one block counter (LockFreeRingBuffer, blockCounter)
+    unsigned long long meterWrite = 0, meterRead = 0, meterIndex = 0, meterDropped = 0;
+
     // profiling
     bool profiling = false;
     ProfileSlot prof[CPQ_K_COUNT];
@@ -380,6 +393,11 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n);
 void freeOversampler(cpq_engine* e);
 int resetOversampler(cpq_engine* e);            // reset(): histories and flags, not the counters
 int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase);
+// engine_meter.cpp
+constexpr int kMeterRing = 4096;                // LockFreeRingBuffer<BlockPower, 4096>
+int refreshMeters(cpq_engine* e);               // redesign for the present base rate and reset; nothing while metering is off
+int checkMeterCall(cpq_engine* e, int nBase);   // the refusals, before anything is enqueued
+int enqueueMeters(cpq_engine* e, const double* rows, int64_t stride, int nBase);
 // engine_core.cpp: DSPCore's routing of one block (conv / EQ in the configured order, output filter, makeup)
 int enqueueBoth(cpq_engine* e, const double* a, double* b, int n);
 // engine_eq.cpp

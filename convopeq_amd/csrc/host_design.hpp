@@ -43,6 +43,17 @@ struct OsStage {
     std::vector<double> conv;       // [convCount] raw[convParity + 2 r]
 };
 bool   osDesignStage(int stage, int type, OsStage& out);
+void   osDesignHalfband(int taps, double attenuationDb, OsStage& out);     // the design behind it, for any tap count
+// meters (meter_design.cpp): LoudnessMeter::updateCoefficients, TruePeakDetector's two stages, and the tables of the
+// time-parallel K-weighting kernel
+void   meterKWeighting(double fs, double pre[5], double rlb[5]);
+bool   meterTpDesignStage(int stage, OsStage& out);
+constexpr int kMeterChunk = 8;          // samples a lane of the K-weighting kernel holds
+constexpr int kMeterScanSteps = 7;      // powers M^(chunk * 2^k): k < 6 the scan inside a wave, k = 6 one whole wave (64 lanes)
+// per section: {b0, b1, b2, a1, a2, c = 1 + a1 + a2, -, -}, then M^(chunk * 2^k) for k < 7, then M^(chunk * lane) for lane < 64
+// (row-major 2x2, M = [[1 - c, a2], [-c, a2]] acting on (y[n-1], y[n-1] - y[n-2])), computed in long double
+constexpr int kMeterSectionDoubles = 8 + 4 * kMeterScanSteps + 4 * 64;
+void   meterSectionTables(const double coef[5], double* out);
 int    osStagesFor(int factor);     // 1/2/4/8 -> 0/1/2/3 stages, else -1
 
 }  // namespace cpq

@@ -236,4 +236,26 @@ void launch_os_down_state(hipStream_t stream, const OsHistories& hs, int nStages
 // nonSilent[c] |= any |in[c][0..m)| > 1e-20
 void launch_os_scan(hipStream_t stream, const double* in, int64_t stride, int m, int nCh, int* nonSilent);
 
+// ---- meters (meter_kernels.hip): LoudnessMeter and TruePeakDetector on a call's base-rate rows, one record per callback
+// K-weighting of every channel: chSum / chPeak [nCh][cbCap] = sum of squares and peak of callback k (cb samples, the last one of
+// a ragged call shorter); tab = two sections of kMeterSectionDoubles; state [nCh][8] carried across calls
+void launch_meter_kweight(hipStream_t stream, const double* in, int64_t stride, int n, int cb, int nCh, const double* tab,
+                          double* state, double* chSum, double* chPeak, int cbCap);
+// tp[stream][k] (bit pattern of a double >= 0, zeroed by the caller) = max |4x interpolated sample| of callback k over both
+// channels; n is a multiple of cb, cb >= 8; hist [nCh][32] = the last scrubbed inputs, ping-pong; coef0 [32], coef1 [16]
+void launch_meter_true_peak(hipStream_t stream, const double* in, int64_t stride, int n, int cb, int nCh, const double* histOld,
+                            double* histNew, const double* coef0, const double* coef1, unsigned long long* tp, int cbCap);
+struct MeterFinishArgs {
+    int flags;                                   // CPQ_METER_*
+    int n, cb, nCb;                              // samples and callbacks of the call
+    int nStore;                                  // the first nStore callbacks find room in the ring
+    int cbCap, ringSize;
+    unsigned long long write0, index0;           // ring write counter and blockCounter before the call
+    const double* chSum; const double* chPeak;
+    const unsigned long long* tp;
+    double* hold;                                // [streams] peakHold
+    cpq_meter_block* ring;                       // [streams][ringSize]
+};
+void launch_meter_finish(hipStream_t stream, const MeterFinishArgs& a, int nStreams);
+
 }  // namespace cpq

@@ -29,14 +29,20 @@ double besselI0(double x)
 
 }  // namespace
 
-// prepareStage (:287-390) in the reference's operation order
 bool osDesignStage(int stage, int type, OsStage& out)
 {
     if (stage < 0 || stage > 2 || (type != CPQ_OS_IIR && type != CPQ_OS_LINEAR_PHASE)) return false;
+    osDesignHalfband(kOsTaps[type][stage], kOsAtten[type][stage], out);
+    return true;
+}
+
+// prepareStage (:287-390) in the reference's operation order; TruePeakDetector::prepareStage (src/TruePeakDetector.cpp) is
+// the same text with its own tap counts and attenuation
+void osDesignHalfband(int taps, double atten, OsStage& out)
+{
     const double pi = 3.141592653589793238;       // juce::MathConstants<double>::pi
-    const double atten = kOsAtten[type][stage];
     OsStage s{};
-    s.taps = std::max(3, kOsTaps[type][stage] | 1);
+    s.taps = std::max(3, taps | 1);
     s.centerTap = (s.taps - 1) / 2;
     s.centerParity = s.centerTap & 1;
     s.convParity = 1 - s.centerParity;
@@ -83,7 +89,6 @@ bool osDesignStage(int stage, int type, OsStage& out)
     s.historyUpKeep = std::max(s.convCount - 1, s.centerDelayInput);
     s.historyDownKeep = std::max(s.centerTap, s.convParity + ((s.convCount - 1) << 1) + 6);
     out = std::move(s);
-    return true;
 }
 
 int osStagesFor(int factor) { return factor == 8 ? 3 : factor == 4 ? 2 : factor == 2 ? 1 : factor == 1 ? 0 : -1; }

@@ -91,6 +91,28 @@ def os_latency(factor, os_type=K.CPQ_OS_IIR):
     return v
 
 
+def meter_kweighting(rate):
+    """cpq_meter_kweighting: (pre, rlb) float64[5] each, {b0, b1, b2, a1, a2} of the two K-weighting biquads at `rate`."""
+    pre, rlb = np.empty(5), np.empty(5)
+    rc = K.load().cpq_meter_kweighting(float(rate), _dp(pre), _dp(rlb))
+    if rc != 0:
+        raise CpqError(rc, "cpq_meter_kweighting")
+    return pre, rlb
+
+
+def meter_tp_design_stage(stage):
+    """cpq_meter_tp_design_stage: (info dict, raw taps float64) of one true-peak interpolator stage."""
+    info = K.OsStageInfo()
+    n = K.load().cpq_meter_tp_design_stage(stage, C.byref(info), None, 0)
+    if n < 0:
+        raise CpqError(n, "cpq_meter_tp_design_stage")
+    taps = np.empty(n)
+    rc = K.load().cpq_meter_tp_design_stage(stage, None, _dp(taps), n)
+    if rc < 0:
+        raise CpqError(rc, "cpq_meter_tp_design_stage")
+    return {f: getattr(info, f) for f, _ in K.OsStageInfo._fields_}, taps
+
+
 def eq_params_default():
     p = K.EqParams()
     K.load().cpq_eq_params_default(C.byref(p))
@@ -337,6 +359,32 @@ class BatchedEngine:
         self._ck(self._lib.cpq_os_read_telemetry(self._h, stream, C.byref(t)))
         return {f: getattr(t, f) for f, _ in K.OsTelemetry._fields_ if f != "reserved"}
 
+    # ---- metering (LoudnessMeter / TruePeakDetector on the base-rate output rows)
+    def set_metering(self, flags):
+        self._ck(self._lib.cpq_engine_set_metering(self._h, int(flags)))
+
+    def meter_reset(self):
+        self._ck(self._lib.cpq_meter_reset(self._h))
+
+    def meter_process(self, x):
+        """Meter rows [n_channels, n] as the engine's output would be, without running the chain."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.ndim == 2 and x.shape[0] == self.n_channels
+        self._ck(self._lib.cpq_meter_process(self._h, _dp(x), x.shape[1]))
+
+    def meter_process_device(self, d_in, n_samples):
+        self._ck(self._lib.cpq_meter_process_device(self._h, C.c_void_p(d_in), n_samples))
+
+    def meter_read_blocks(self, max_blocks=K.METER_RING):
+        """Pops up to max_blocks records per stream: (structured array [n_streams, n], records dropped since the last read)."""
+        buf = (K.MeterBlock * (self.n_streams * max_blocks))()
+        n = C.c_int32()
+        dropped = C.c_int64()
+        self._ck(self._lib.cpq_meter_read_blocks(self._h, buf, max_blocks, C.byref(n), C.byref(dropped)))
+        dt = np.dtype([(f, np.uint64 if f == "block_index" else np.float64) for f, _ in K.MeterBlock._fields_])
+        rec = np.frombuffer(buf, dtype=dt).reshape(self.n_streams, max_blocks)[:, :n.value].copy()
+        return rec, dropped.value
+
     # ---- host-buffer processing: x is [n_channels, n_samples] float64
     def _host(self, fn, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -377,8 +425,8 @@ class BatchedEngine:
             n = C.c_int64()
             ms = C.c_double()
             self._ck(self._lib.cpq_profile_read(self._h, kid, C.byref(n), C.byref(ms)))
-            if name == "k_os_halfband" and n.value == 0:
-                continue        # listed only for engines that oversample
+            if name in ("k_os_halfband", "k_meter") and n.value == 0:
+                continue        # listed only for engines that oversample / meter
             out[name] = (n.value, ms.value)
         return out
 

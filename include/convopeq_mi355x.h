@@ -502,6 +502,48 @@ double  cpq_ir_estimate_max_frequency_response_gain(const double* const* ir, int
 /* LoaderThread::estimatePeakLatencySamples (LoaderThread.cpp:149-209) */
 int32_t cpq_ir_estimate_peak_latency(const double* const* ir, int32_t n_channels, int32_t n_samples);
 
+/* ---------------------------------------------------------------- metering */
+/* The two meters DSPCore runs on the final block of every callback (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:
+ * 695-701): LoudnessMeter::processBlock (src/LoudnessMeter.{h,cpp}; ITU-R BS.1770 K-weighting, mean square and peak per
+ * callback) and TruePeakDetector::processBlock (src/TruePeakDetector.{h,cpp}; 4x oversampled peak from two half-band FIR
+ * stages, decaying hold).  They read the base-rate output rows of cpq_engine_process_block[_device] (with oversampling: after
+ * the down stages), one callback = block_size / factor samples at a time, and never alter them.  A sample that is not finite
+ * or has |v| >= 1e300 is read as 0 (the scrub at :665-693 runs before the meters).  Off by default. */
+#define CPQ_METER_LOUDNESS  1
+#define CPQ_METER_TRUE_PEAK 2
+
+/* one callback of one stream; the fields of a meter that is off are 0 */
+typedef struct {
+    double   mean_square;            /* (sum L^2 + sum R^2) / n of the K-weighted callback (BlockPower::meanSquare) */
+    double   peak_linear;            /* max |K-weighted sample| over both channels (BlockPower::peakLinear) */
+    double   true_peak;              /* max |4x oversampled sample| over both channels of this callback */
+    double   true_peak_hold;         /* peakHold after this callback: tp > hold ? tp : hold * 0.999 */
+    uint64_t block_index;            /* blockCounter++: counts on for records dropped on a full ring */
+} cpq_meter_block;
+
+/* LoudnessMeter::updateCoefficients(fs) in the reference's operation order: pre[5] = the +4 dB high shelf at 1500 Hz
+ * (Q = 1/sqrt 2), rlb[5] = the 38 Hz high-pass (Q = 0.5), both {b0, b1, b2, a1, a2} / a0 of Direct Form I.  Host only. */
+int32_t cpq_meter_kweighting(double rate, double pre[5], double rlb[5]);
+/* TruePeakDetector::prepareStage for stage 0 (63 taps) or 1 (31 taps), 100 dB: as cpq_os_design_stage.  Host only. */
+int32_t cpq_meter_tp_design_stage(int32_t stage, cpq_os_stage_info* info, double* taps, int32_t capacity);
+/* flags: 0 = off, or CPQ_METER_LOUDNESS | CPQ_METER_TRUE_PEAK.  Any change resets the meters.  The filters are designed for
+ * the base rate sample_rate / factor; cpq_engine_prepare and cpq_engine_set_oversampling redesign them and reset the meters.
+ * While true peak is on a call must be whole callbacks (else CPQ_ERR_UNSUPPORTED, before any state moves: the reference's
+ * result then depends on stale memory) and a callback must hold at least 8 samples; loudness alone accepts the ragged calls
+ * of CPQ_CALLS_ANY, the short last chunk being one callback of its own length. */
+int32_t cpq_engine_set_metering(cpq_engine* e, int32_t flags);
+/* LoudnessMeter::reset + TruePeakDetector::reset: filter states, histories, hold, block counter and the ring */
+int32_t cpq_meter_reset(cpq_engine* e);
+/* Meters caller rows [channel][n_samples] exactly as the engine's output would be, without running the chain.
+ * CPQ_ERR_NOT_READY while metering is off. */
+int32_t cpq_meter_process(cpq_engine* e, const double* in, int32_t n_samples);
+int32_t cpq_meter_process_device(cpq_engine* e, const double* d_in, int32_t n_samples);
+/* Synchronises the engine's stream and pops the oldest min(max_blocks, stored) records of every stream at once:
+ * out[stream * max_blocks + i].  Every stream holds a ring of 4096 records; a record that finds it full is dropped (its
+ * block_index is still consumed).  *n_blocks = records popped per stream, *n_dropped = records dropped per stream since the
+ * last read (either may be NULL).  CPQ_ERR_NOT_READY while metering is off. */
+int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t max_blocks, int32_t* n_blocks, int64_t* n_dropped);
+
 /* ---------------------------------------------------------------- profiling */
 /* Per-kernel HIP-event timing on the engine's stream (counterpart of the reference's CONV_TIME /
  * EQ_TIME diagnostics, src/convolver/ConvolverProcessor.Runtime.cpp:679-721). */
@@ -515,7 +557,8 @@ typedef enum {
     CPQ_K_MIX      = 6,   /* k_convproc_mix (processor-level dry/wet stage) */
     CPQ_K_OUTFILT  = 7,   /* output-filter biquad cascade (k_svf_cascade_tp / k_svf_cascade running DF-II-T sections) */
     CPQ_K_OS       = 8,   /* half-band oversampler stages, up and down (k_os_interp / k_os_decim and their helpers) */
-    CPQ_K_COUNT    = 9
+    CPQ_K_METER    = 9,   /* loudness and true-peak meters (k_meter_kweight / k_meter_true_peak / k_meter_finish) */
+    CPQ_K_COUNT    = 10
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);
 int32_t     cpq_profile_reset(cpq_engine* e);

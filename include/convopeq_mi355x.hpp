@@ -5,6 +5,7 @@
 //   cpq::BatchedConvolver  ::SetImpulse / Add / Get / Reset / isReady / getLatency
 //        <- convo::MKLNonUniformConvolver (src/MKLNonUniformConvolver.h:197-242), one instance per mono channel
 //           in the reference, here one object for every channel of every stream
+//   cpq::BatchedMeters      ::prepare / processBlock / readBlocks / reset          <- LoudnessMeter + TruePeakDetector (src/LoudnessMeter.h, src/TruePeakDetector.h)
 //   cpq::BatchedOversampler ::prepare / processUp / processDown / reset   <- CustomInputOversampler (src/CustomInputOversampler.h)
 //   cpq::BatchedProcessor  ::prepareToPlay / process / setEqParameters / loadImpulse
 //        <- ConvolverProcessor::{prepareToPlay,process} (src/ConvolverProcessor.h:226,259) and
@@ -291,6 +292,43 @@ private:
     Engine& e_;
     std::vector<double> scratchIn_, scratchOut_;
     int ratio_ = 1;
+    int status_ = CPQ_OK;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// LoudnessMeter + TruePeakDetector (src/LoudnessMeter.h, src/TruePeakDetector.h) for every stream of an engine.  Once
+// prepared, cpq_engine_process_block meters its own output; processBlock meters caller blocks without running the chain.
+class BatchedMeters {
+public:
+    explicit BatchedMeters(Engine& e) : e_(e) {}
+    // loudness and / or truePeak; both false switches metering off
+    bool prepare(bool loudness = true, bool truePeak = true)
+    {
+        status_ = cpq_engine_set_metering(e_.get(), (loudness ? CPQ_METER_LOUDNESS : 0) | (truePeak ? CPQ_METER_TRUE_PEAK : 0));
+        return status_ == CPQ_OK;
+    }
+    bool processBlock(const AudioBlockBatch& in)
+    {
+        if (in.numChannels != e_.channels() || in.numSamples <= 0) { status_ = CPQ_ERR_INVALID_ARG; return false; }
+        scratch_.resize(static_cast<size_t>(e_.channels()) * in.numSamples);
+        for (int c = 0; c < in.numChannels; ++c)
+            std::memcpy(scratch_.data() + static_cast<size_t>(c) * in.numSamples, in.channels[c], sizeof(double) * in.numSamples);
+        return (status_ = cpq_meter_process(e_.get(), scratch_.data(), in.numSamples)) == CPQ_OK;
+    }
+    // pops up to maxBlocks records per stream into out[stream * maxBlocks + i]; returns the count per stream, -1 on failure
+    int readBlocks(cpq_meter_block* out, int maxBlocks, int64_t* dropped = nullptr)
+    {
+        int32_t n = 0;
+        status_ = cpq_meter_read_blocks(e_.get(), out, maxBlocks, &n, dropped);
+        return status_ == CPQ_OK ? n : -1;
+    }
+    void reset() { status_ = cpq_meter_reset(e_.get()); }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return e_.lastError(); }
+
+private:
+    Engine& e_;
+    std::vector<double> scratch_;
     int status_ = CPQ_OK;
 };
 
