@@ -131,8 +131,8 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
     if (!irL || !irR || irLen <= 0) return fail(e, CPQ_ERR_INVALID_ARG, "null impulse or non-positive length");
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    int sFirst = 0, sEnd = 0;
+    CPQ_TRY(streamRange(e, stream, sFirst, sEnd));
     if (irLen > e->desc.max_ir_len) return fail(e, CPQ_ERR_INVALID_ARG, "ir_len %d > max_ir_len %d", irLen, e->desc.max_ir_len);
     // Which path runs this IR?  A plan group (engine_native.cpp: every layer at the reference's own partition size, the
     // Add / Get bookkeeping replayed per chunk) takes it when the engine accepts any call quantum (CPQ_CALLS_ANY), when it
@@ -225,7 +225,6 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
         e->directTapsHost[slot] = headTaps;
         return CPQ_OK;
     };
-    const int sFirst = (stream == CPQ_ALL_STREAMS) ? 0 : stream, sEnd = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
     // SetImpulse leaves a convolver that has seen no input (every buffer is allocated anew and zeroed,
     // src/MKLNonUniformConvolver.cpp:697-714, :880-935): the stream's input history goes -- the direct head's last samples, and on
     // the main path its rows of the frequency-domain delay line and the overlap block; the other streams play on

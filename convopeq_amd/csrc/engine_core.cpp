@@ -77,6 +77,15 @@ void hostTwiddles(int P, std::vector<double2>& w1, std::vector<double2>& w2)
     }
 }
 
+int streamRange(cpq_engine* e, int stream, int& s0, int& s1)
+{
+    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
+        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
+    s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
+    return CPQ_OK;
+}
+
 int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
 {
     CPQ_HIP(e, hipSetDevice(e->device));
@@ -94,7 +103,7 @@ int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
         if (e->tailRing) CPQ_HIP(e, hipMemsetAsync(e->tailRing, 0, sizeof(double) * (size_t)(e->layerPlan.num_layers - 1) * e->nCh * e->tailRingSlots, e->stream));
         if (e->dryRing) CPQ_HIP(e, hipMemsetAsync(e->dryRing, 0, (size_t)e->nCh * e->dryRingSize * sizeof(double), e->stream));
         e->dryPos = 0;
-        for (auto& f : e->latFade) f = cpq_engine::LatencyFade{};
+        for (auto& f : e->latFade) f = LatencyFade{};
     }
     if (eq) {
         CPQ_HIP(e, hipMemsetAsync(e->svfState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
@@ -477,10 +486,10 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
     e->eqMidSide.assign(d->n_streams, 0);
     e->eqParamsHost.assign(d->n_streams, cpq_eq_params{});
     e->eqParamsSet.assign(d->n_streams, 0);
-    e->eqBypass.assign(d->n_streams, cpq_engine::EqBypass{});
+    e->eqBypass.assign(d->n_streams, EqBypass{});
     e->eqResetPending.assign(d->n_streams, 0u);
     e->agcResetPending.assign(d->n_streams, 0);
-    e->latFade.assign(d->n_streams, cpq_engine::LatencyFade{});
+    e->latFade.assign(d->n_streams, LatencyFade{});
     e->trimHost.assign(d->n_streams, 1.0);
     e->makeupHost.assign(d->n_streams, 1.0);
     e->ofPass.assign(d->n_streams, 0);
@@ -489,9 +498,9 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
     e->procParams.assign(d->n_streams, cpq_convproc_params{ 1.0f, 0, 0, 0.0f });
     e->procBypass.assign(d->n_streams, 0);
     e->procDryOnly.assign(d->n_streams, 0);
-    e->mixRamp.assign(d->n_streams, cpq_engine::MixRamp{});
+    e->mixRamp.assign(d->n_streams, MixRamp{});
     e->agcOnHost.assign(d->n_streams, 0);
-    e->gainRamp.assign(d->n_streams, cpq_engine::GainRamp{});
+    e->gainRamp.assign(d->n_streams, GainRamp{});
     if (hipMemcpy(e->irSlot, e->irSlotHost.data(), sizeof(int) * e->nCh, hipMemcpyHostToDevice) != hipSuccess) {
         cpq_engine_destroy(e);
         return fail(nullptr, CPQ_ERR_DEVICE, "irSlot upload failed");
@@ -574,13 +583,8 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
     e->eqProcessed = false;
     e->procProcessed = false;
     syncEqBypass(e);
-    for (size_t s = 0; s < e->mixRamp.size(); ++s) {      // mixSmoother.setCurrentAndTargetValue(mix) (Lifecycle.cpp:370-371)
-        auto& r = e->mixRamp[s];
-        r.current = r.target = (double)e->procParams[s].mix;
-        r.step = 0.0;
-        r.remaining = 0;
-    }
-    for (auto& r : e->gainRamp) { r.current = r.target = r.wanted; r.step = 0.0; r.remaining = 0; }   // setCurrentAndTargetValue (Core.cpp:765)
+    for (size_t s = 0; s < e->mixRamp.size(); ++s) e->mixRamp[s].ramp.setCurrentAndTargetValue((double)e->procParams[s].mix);   // Lifecycle.cpp:370-371
+    for (auto& r : e->gainRamp) r.snap();       // setCurrentAndTargetValue (Core.cpp:765)
     {   // oversampling.prepare -> release(): histories and flags cleared, counters kept
         const int rc = resetOversampler(e);
         if (rc != CPQ_OK) return rc;
@@ -646,7 +650,7 @@ int cpqi::enqueueBoth(cpq_engine* e, const double* a, double* b, int n)
             if (pass == e->ofPass[s] || !e->ofModesSet[s]) continue;
             int flags[2 * kBands] = {};
             if (!pass) for (int ch = 0; ch < 2; ++ch) for (int k = 0; k < 3; ++k) flags[ch * kBands + k] = 1 | 4;
-            { const int rcUp = stageUpload(e, e->ofFlags + (size_t)2 * s * kBands, flags, sizeof(flags)); if (rcUp != CPQ_OK) return rcUp; }
+            CPQ_TRY(stageUpload(e, e->ofFlags + (size_t)2 * s * kBands, flags, sizeof(flags)));
             e->ofPass[s] = pass;
         }
         if (anyActive) rc = enqueueOutFilter(e, b, b, n);
@@ -664,8 +668,8 @@ extern "C" {
 int32_t cpq_engine_set_gains(cpq_engine* e, int32_t stream, double convInputTrimGain, double outputMakeupGain)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     if (!std::isfinite(convInputTrimGain) || !std::isfinite(outputMakeupGain))
         return fail(e, CPQ_ERR_INVALID_ARG, "gains must be finite");
     CPQ_HIP(e, hipSetDevice(e->device));
@@ -674,8 +678,6 @@ int32_t cpq_engine_set_gains(cpq_engine* e, int32_t stream, double convInputTrim
         const int rc = allocAll(e, { { e->trimDev, (size_t)S }, { e->makeupDev, (size_t)S } }, "gain buffers could not be allocated");
         if (rc != CPQ_OK) return rc;
     }
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? S : stream + 1;
     for (int s = s0; s < s1; ++s) {
         // the trim is applied only when it differs from 1 by more than 1e-12 (:440)
         e->trimHost[s] = std::fabs(convInputTrimGain - 1.0) > 1e-12 ? convInputTrimGain : 1.0;

@@ -36,11 +36,8 @@ void syncEqBypass(cpq_engine* e)
     std::fill(e->agcResetPending.begin(), e->agcResetPending.end(), 0);
     e->anyEqReset = false;
     for (auto& b : e->eqBypass) {
-        b.effective = b.requested;
-        b.current = b.target = b.requested ? 0.0 : 1.0;
-        b.step = 0.0;
-        b.remaining = 0;
-        e->anyEqBypass = e->anyEqBypass || b.requested || b.mode != 0;
+        b.sync();
+        e->anyEqBypass = e->anyEqBypass || b.active();
     }
 }
 
@@ -100,8 +97,8 @@ int setEqStreamMode(cpq_engine* e, int s, int mode)
     if (mode == 2) {
         int zeros[2 * kBands] = {};
         const double sg[4] = { 0.0, 1.0, 0.0, 1.0 };
-        { const int rcUp = stageUpload(e, e->svfFlags + c0 * kBands, zeros, sizeof(zeros)); if (rcUp != CPQ_OK) return rcUp; }
-        { const int rcUp = stageUpload(e, e->svfSatGain + c0 * 2, sg, sizeof(sg)); if (rcUp != CPQ_OK) return rcUp; }
+        CPQ_TRY(stageUpload(e, e->svfFlags + c0 * kBands, zeros, sizeof(zeros)));
+        CPQ_TRY(stageUpload(e, e->svfSatGain + c0 * 2, sg, sizeof(sg)));
         e->eqTpSafe[s] = 1;
         e->eqMidSide[s] = 0;
         e->gainRamp[s].devUnity = true;
@@ -110,17 +107,17 @@ int setEqStreamMode(cpq_engine* e, int s, int mode)
         EqDesign d;
         designEqStream(e, e->eqParamsHost[s], mode == 1, d);
         double sg[4] = { d.satGain[0], d.satGain[1], d.satGain[0], d.satGain[1] };
-        { const int rcUp = stageUpload(e, e->svfCoef + c0 * kBands * 6, d.coef, sizeof(d.coef)); if (rcUp != CPQ_OK) return rcUp; }
-        { const int rcUp = stageUpload(e, e->svfFlags + c0 * kBands, d.flags, sizeof(d.flags)); if (rcUp != CPQ_OK) return rcUp; }
-        { const int rcUp = stageUpload(e, e->svfSatGain + c0 * 2, sg, sizeof(sg)); if (rcUp != CPQ_OK) return rcUp; }
-        { const int rcUp = stageUpload(e, e->svfTp + (size_t)s * d.tp.size(), d.tp.data(), d.tp.size() * sizeof(double)); if (rcUp != CPQ_OK) return rcUp; }
+        CPQ_TRY(stageUpload(e, e->svfCoef + c0 * kBands * 6, d.coef, sizeof(d.coef)));
+        CPQ_TRY(stageUpload(e, e->svfFlags + c0 * kBands, d.flags, sizeof(d.flags)));
+        CPQ_TRY(stageUpload(e, e->svfSatGain + c0 * 2, sg, sizeof(sg)));
+        CPQ_TRY(stageUpload(e, e->svfTp + (size_t)s * d.tp.size(), d.tp.data(), d.tp.size() * sizeof(double)));
         e->eqTpSafe[s] = d.tpSafe ? 1 : 0;
         e->eqMidSide[s] = d.midSide ? 1 : 0;
         e->gainRamp[s].devUnity = false;          // the constant gain (or 1.0 with AGC) is on the device again
     }
     if (e->agcOn) {
         const int on = (mode != 2 && e->agcOnHost[s]) ? 1 : 0;
-        { const int rcUp = stageUpload(e, e->agcOn + s, &on, sizeof(int)); if (rcUp != CPQ_OK) return rcUp; }
+        CPQ_TRY(stageUpload(e, e->agcOn + s, &on, sizeof(int)));
     }
     bp.mode = mode;
     return CPQ_OK;
@@ -141,32 +138,18 @@ int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride
     bool anyRamp = false;
     {
         const int S = e->desc.n_streams;
-        const int total = std::max(1, (int)(e->sampleRate * 0.05 + 0.5));
+        const int total = LinearRamp::stepsFor(e->sampleRate, 0.05);
         for (int s = 0; s < S; ++s) {
             auto& r = e->gainRamp[s];
-            if (e->agcOnHost[s] || (pass && pass[s])) continue;
-            const bool moving = r.remaining > 0 || std::fabs(r.target - r.wanted) > 1e-6 || r.current != r.wanted;
-            if (!moving) continue;
+            if (e->agcOnHost[s] || (pass && pass[s]) || !r.moving()) continue;
             if (raggedTail)
                 return fail(e, CPQ_ERR_UNSUPPORTED, "a total-gain ramp is running: the call must be whole callbacks of %d samples until it ends", e->B);
             if (!anyRamp) { rampOnHost.assign(S, 0); rampHost.assign((size_t)S * cbs * 2, 0.0); anyRamp = true; }
             rampOnHost[s] = 1;
             for (int t = 0; t < cbs; ++t) {
-                if (std::fabs(r.target - r.wanted) > 1e-6) {           // setTargetValue
-                    if (r.wanted != r.target) {
-                        r.target = r.wanted;
-                        const int steps = r.remaining > 0 ? r.remaining : total;
-                        r.step = (r.target - r.current) / (double)steps;
-                        r.remaining = steps;
-                    }
-                }
-                const double start = r.current;
-                if (r.remaining > 0) {                                  // skip(numSamples)
-                    if (e->B >= r.remaining) { r.current = r.target; r.remaining = 0; }
-                    else { r.current += r.step * (double)e->B; r.remaining -= e->B; }
-                }
-                rampHost[((size_t)s * cbs + t) * 2] = start;
-                rampHost[((size_t)s * cbs + t) * 2 + 1] = (r.current - start) / (double)e->B;
+                const GainRamp::Segment g = r.callback(e->B, total);
+                rampHost[((size_t)s * cbs + t) * 2] = g.start;
+                rampHost[((size_t)s * cbs + t) * 2 + 1] = g.increment;
             }
         }
         // streams whose gain is applied by the ramp kernel need unity gain in the cascade kernel, and back again
@@ -177,18 +160,16 @@ int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride
             if (needUnity != r.devUnity) {
                 const double g = needUnity ? 1.0 : r.wanted;
                 for (int ch = 0; ch < 2; ++ch)
-                    { const int rcUp = stageUpload(e, e->svfSatGain + (size_t)(2 * s + ch) * 2 + 1, &g, sizeof(double)); if (rcUp != CPQ_OK) return rcUp; }
+                    CPQ_TRY(stageUpload(e, e->svfSatGain + (size_t)(2 * s + ch) * 2 + 1, &g, sizeof(double)));
                 r.devUnity = needUnity;
             }
         }
         if (anyRamp) {
             const size_t cbMax = (size_t)e->tMax * e->P / e->B;
-            if (!e->rampOn) {
-                const int rcA = allocAll(e, { { e->rampOn, (size_t)S }, { e->rampGains, 2 * S * cbMax } }, "gain ramp buffers could not be allocated");
-                if (rcA != CPQ_OK) return rcA;
-            }
-            { const int rcUp = stageUpload(e, e->rampOn, rampOnHost.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
-            { const int rcUp = stageUpload(e, e->rampGains, rampHost.data(), sizeof(double) * rampHost.size()); if (rcUp != CPQ_OK) return rcUp; }
+            if (!e->rampOn)
+                CPQ_TRY(allocAll(e, { { e->rampOn, (size_t)S }, { e->rampGains, 2 * S * cbMax } }, "gain ramp buffers could not be allocated"));
+            CPQ_TRY(stageUpload(e, e->rampOn, rampOnHost.data(), sizeof(int) * S));
+            CPQ_TRY(stageUpload(e, e->rampGains, rampHost.data(), sizeof(double) * rampHost.size()));
         }
     }
     e->eqProcessed = true;
@@ -248,39 +229,19 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
     if (n % e->B != 0)
         return fail(e, CPQ_ERR_UNSUPPORTED, "an EQ bypass transition or band reset is pending: the call must be whole callbacks of %d samples", e->B);
     const int cbs = n / e->B;
-    const int total = std::max(1, (int)(e->sampleRate * 0.005 + 0.5));       // BYPASS_FADE_TIME_SEC (EQProcessor.h:564)
-    enum : char { kNormal = 0, kFade = 1, kPass = 2 };
+    const int total = LinearRamp::stepsFor(e->sampleRate, 0.005);            // BYPASS_FADE_TIME_SEC (EQProcessor.h:564)
+    using enum EqBypass::Class;         // kNormal, kFade, kPass
     std::vector<char> cls((size_t)S * cbs, kNormal);
     std::vector<uint32_t> reset((size_t)S * cbs, 0u);           // bands cleared at the start of the callback
     std::vector<char> released((size_t)S * cbs, 0);             // the bypass is released here: every band is to be cleared
     std::vector<std::vector<double>> gains(S);          // fade values of a stream's kFade callbacks, in order
     bool stillActive = false;
-    for (int s = 0; s < S; ++s) {
-        auto& b = e->eqBypass[s];
+    for (int s = 0; s < S; ++s)
         for (int t = 0; t < cbs; ++t) {
-            const double want = b.requested ? 0.0 : 1.0;
-            if (std::fabs(b.target - want) > 1.0e-12) {
-                if (!b.requested && b.effective) { released[(size_t)s * cbs + t] = 1; b.effective = false; }
-                if (want != b.target) {                                       // LinearRamp::setTargetValue
-                    b.target = want;
-                    const int steps = b.remaining > 0 ? b.remaining : total;
-                    b.step = (b.target - b.current) / (double)steps;
-                    b.remaining = steps;
-                }
-            }
-            const bool transition = b.remaining > 0;
-            if (b.requested && !b.effective && !transition) b.effective = true;
-            if (b.requested && b.effective && !transition) { cls[(size_t)s * cbs + t] = kPass; continue; }
-            if (!transition) continue;
-            cls[(size_t)s * cbs + t] = kFade;
-            for (int i = 0; i < e->B && b.remaining > 0; ++i) {              // getNextValue while the ramp runs
-                b.current += b.step;
-                if (--b.remaining <= 0) b.current = b.target;
-                gains[s].push_back(b.current);
-            }
-            if (b.remaining <= 0) b.effective = b.requested;
+            const EqBypass::Step st = e->eqBypass[s].callback(e->B, total, gains[s]);
+            cls[(size_t)s * cbs + t] = st.cls;
+            released[(size_t)s * cbs + t] = st.released ? 1 : 0;
         }
-    }
     // pending band resets: at the first callback that is fading (canSafelyResetState, :565-568) or whose input block is
     // silent; a fully bypassed callback returns before it gets there.  Silence is only known on the device: one small
     // kernel, one read-back and ONE stream synchronisation per call while a reset waits on a stream that is playing.
@@ -295,10 +256,8 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
         }
         if (needSilence) {
             const size_t cbMax = (size_t)e->tMax * e->P / e->B;
-            if (!e->silentDev) {
-                const int rcA = allocAll(e, { { e->silentDev, S * cbMax }, { e->silentHost, S * cbMax } }, "silence flags could not be allocated");
-                if (rcA != CPQ_OK) return rcA;
-            }
+            if (!e->silentDev)
+                CPQ_TRY(allocAll(e, { { e->silentDev, S * cbMax }, { e->silentHost, S * cbMax } }, "silence flags could not be allocated"));
             cpq::launch_block_silence(e->stream, dIn, stride, e->B, cbs, S, e->silentDev);
             CPQ_HIP(e, hipMemcpyAsync(e->silentHost, e->silentDev, sizeof(int) * (size_t)S * cbs, hipMemcpyDeviceToHost, e->stream));
             CPQ_HIP(e, hipStreamSynchronize(e->stream));
@@ -358,28 +317,26 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
                 anyFade = true;
                 lenHost[s] = (int)std::min<size_t>(gains[s].size() - used[s], (size_t)nSeg);
                 // past the end of the ramp getNextValue keeps returning its final value
-                endHost[s] = gains[s].empty() ? e->eqBypass[s].current : gains[s][std::min(gains[s].size(), used[s] + (size_t)nSeg) - 1];
+                endHost[s] = gains[s].empty() ? e->eqBypass[s].fade.current : gains[s][std::min(gains[s].size(), used[s] + (size_t)nSeg) - 1];
                 cap = std::max(cap, lenHost[s]);
             }
         }
         if (rc != CPQ_OK) break;
         if (anyFade) {
-            if (!e->eqDry) {
-                const int rcA = allocAll(e, { { e->eqDry, (size_t)e->nCh * e->tMax * e->P }, { e->blendOn, (size_t)S }, { e->blendLen, (size_t)S },
-                                              { e->blendEnd, (size_t)S } }, "EQ bypass cross-fade buffers could not be allocated");
-                if (rcA != CPQ_OK) return rcA;
-            }
-            { const int rcG = grow(e, e->blendGains, e->blendCap, cap, (size_t)S, "EQ bypass cross-fade buffers could not be allocated"); if (rcG != CPQ_OK) return rcG; }
+            if (!e->eqDry)
+                CPQ_TRY(allocAll(e, { { e->eqDry, (size_t)e->nCh * e->tMax * e->P }, { e->blendOn, (size_t)S }, { e->blendLen, (size_t)S },
+                                              { e->blendEnd, (size_t)S } }, "EQ bypass cross-fade buffers could not be allocated"));
+            CPQ_TRY(grow(e, e->blendGains, e->blendCap, cap, (size_t)S, "EQ bypass cross-fade buffers could not be allocated"));
             gainsHost.assign((size_t)S * e->blendCap, 0.0);
             for (int s = 0; s < S; ++s) {
                 if (!onHost[s]) continue;
                 std::memcpy(&gainsHost[(size_t)s * e->blendCap], gains[s].data() + used[s], sizeof(double) * (size_t)lenHost[s]);
                 used[s] += (size_t)lenHost[s];
             }
-            { const int rcUp = stageUpload(e, e->blendOn, onHost.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
-            { const int rcUp = stageUpload(e, e->blendLen, lenHost.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
-            { const int rcUp = stageUpload(e, e->blendEnd, endHost.data(), sizeof(double) * S); if (rcUp != CPQ_OK) return rcUp; }
-            { const int rcUp = stageUpload(e, e->blendGains, gainsHost.data(), sizeof(double) * gainsHost.size()); if (rcUp != CPQ_OK) return rcUp; }
+            CPQ_TRY(stageUpload(e, e->blendOn, onHost.data(), sizeof(int) * S));
+            CPQ_TRY(stageUpload(e, e->blendLen, lenHost.data(), sizeof(int) * S));
+            CPQ_TRY(stageUpload(e, e->blendEnd, endHost.data(), sizeof(double) * S));
+            CPQ_TRY(stageUpload(e, e->blendGains, gainsHost.data(), sizeof(double) * gainsHost.size()));
             ProfScope p(e, CPQ_K_MIX);
             cpq::launch_rows_copy(e->stream, dIn, stride, off, e->eqDry, (int64_t)nSeg, 0, nSeg, e->nCh);
         }
@@ -394,7 +351,7 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
     }
     // after the pieces ran: a stream whose tables were left on the basic path's band nodes (its fade ended inside this call)
     // still needs the next call to come through here, which puts the parameter tables back
-    for (const auto& b : e->eqBypass) stillActive = stillActive || b.requested || b.effective || b.remaining > 0 || b.mode != 0;
+    for (const auto& b : e->eqBypass) stillActive = stillActive || b.active();
     e->anyEqBypass = stillActive;
     return rc;
 }
@@ -408,10 +365,7 @@ int enqueueEq(cpq_engine* e, const double* dIn, double* dOut, int n)
 {
     const int r = n % e->B;
     bool perCallback = e->anyAgc || e->anyEqBypass || e->anyEqReset;
-    for (size_t s = 0; s < e->gainRamp.size() && !perCallback; ++s) {
-        const auto& g = e->gainRamp[s];
-        perCallback = !e->agcOnHost[s] && (g.remaining > 0 || std::fabs(g.target - g.wanted) > 1e-6 || g.current != g.wanted);
-    }
+    for (size_t s = 0; s < e->gainRamp.size() && !perCallback; ++s) perCallback = !e->agcOnHost[s] && e->gainRamp[s].moving();
     if (r == 0 || !perCallback) return enqueueEqRange(e, dIn, dOut, (int64_t)n, n);
     int rc = CPQ_OK;
     if (n - r > 0) rc = enqueueEqRange(e, dIn, dOut, (int64_t)n, n - r);
@@ -441,8 +395,8 @@ extern "C" {
 int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
 {
     if (!e || !p) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     if (p->filter_structure != 0 && p->filter_structure != 1) return fail(e, CPQ_ERR_INVALID_ARG, "filter_structure must be 0 (serial) or 1 (parallel)");
     for (int b = 0; b < kBands; ++b)
         if (p->bands[b].enabled && (p->bands[b].channel_mode < 0 || p->bands[b].channel_mode > 4))
@@ -458,8 +412,6 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
     const double satGain[2] = { d.satGain[0], d.satGain[1] };
 
     CPQ_HIP(e, hipSetDevice(e->device));
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
     std::vector<double> hc((size_t)(s1 - s0) * 2 * kBands * 6), hs((size_t)(s1 - s0) * 2 * 2);
     std::vector<int> hf((size_t)(s1 - s0) * 2 * kBands);
     std::vector<double> ht((size_t)(s1 - s0) * tp.size());
@@ -485,7 +437,7 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
         auto& r = e->gainRamp[s];
         r.wanted = cpq::totalGainLinear(p->total_gain_db);
         r.devUnity = false;               // the upload above put the constant gain (or 1.0 with AGC) on the device
-        if (!e->eqProcessed || p->agc_enabled) { r.current = r.target = r.wanted; r.step = 0.0; r.remaining = 0; }
+        if (!e->eqProcessed || p->agc_enabled) r.snap();
     }
     for (int s = s0; s < s1; ++s) e->agcOnHost[s] = p->agc_enabled ? 1 : 0;
     e->anyAgc = false;              // the AGC kernels run only once their buffers exist
@@ -510,32 +462,23 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
 int32_t cpq_eq_set_bypass(cpq_engine* e, int32_t stream, int32_t bypassed)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     for (int s = s0; s < s1; ++s) {
         auto& b = e->eqBypass[s];
         b.requested = bypassed != 0;
-        if (!e->eqProcessed) {            // before the first callback the fade is synchronised, not run (Core.cpp:288, 802)
-            b.effective = b.requested;
-            b.current = b.target = b.requested ? 0.0 : 1.0;
-            b.step = 0.0;
-            b.remaining = 0;
-        }
+        if (!e->eqProcessed) b.sync();    // before the first callback the fade is synchronised, not run (Core.cpp:288, 802)
     }
     e->anyEqBypass = false;
-    for (const auto& b : e->eqBypass) e->anyEqBypass = e->anyEqBypass || b.requested || b.effective || b.remaining > 0 || b.mode != 0;
+    for (const auto& b : e->eqBypass) e->anyEqBypass = e->anyEqBypass || b.active();
     return CPQ_OK;
 }
 
 int32_t cpq_eq_request_band_reset(cpq_engine* e, int32_t stream, uint32_t bandMask)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     // requestBandReset(-1) asks for every band (mask 0xFFFFFFFF); single bands keep only the 20 real bits
     const uint32_t m = bandMask == 0xFFFFFFFFu ? bandMask : (bandMask & ((1u << kBands) - 1u));
     for (int s = s0; s < s1; ++s) {
@@ -548,10 +491,8 @@ int32_t cpq_eq_request_band_reset(cpq_engine* e, int32_t stream, uint32_t bandMa
 int32_t cpq_eq_request_agc_reset(cpq_engine* e, int32_t stream)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     for (int s = s0; s < s1; ++s) e->agcResetPending[s] = 1;
     return CPQ_OK;
 }
@@ -596,8 +537,8 @@ int32_t cpq_outfilter_set_params(cpq_engine* e, int32_t stream, int32_t convIsLa
                                  int32_t lpMode)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     cpq_biquad_coeffs q[3];
     const int rc = cpq_outfilter_design(convIsLast, hcMode, lcMode, lpMode, e->sampleRate, q);
     if (rc != CPQ_OK) return fail(e, rc, "bad output filter mode");
@@ -612,8 +553,6 @@ int32_t cpq_outfilter_set_params(cpq_engine* e, int32_t stream, int32_t convIsLa
     }
     CPQ_HIP(e, hipSetDevice(e->device));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
     const double sg[2] = { 0.0, 1.0 };
     for (int s = s0; s < s1; ++s) { e->ofModesHost[s] = cpq_engine::OfModes{ convIsLast, hcMode, lcMode, lpMode }; e->ofModesSet[s] = 1; }
     for (int s = s0; s < s1; ++s) {

@@ -3,6 +3,8 @@
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
 //   engine_eq.cpp    EQ and output filter: design, device tables, bypass / band-reset state machine
+// The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
+// host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
 // feature allocated on first use, all of it freed with the engine.
 #pragma once
@@ -24,6 +26,7 @@
 
 #include "device_buffers.hpp"
 #include "host_design.hpp"
+#include "host_replay.hpp"
 #include "kernels.hpp"
 
 using cpq::kBands;
@@ -189,18 +192,11 @@ struct cpq_engine {
     double sampleRate = 48000.0;
 
     // total-gain LinearRamp per stream (src/DspNumericPolicy.h:319-421; 50 ms, EQProcessor.h SMOOTHING_TIME_SEC)
-    struct GainRamp { double current = 1.0, target = 1.0, step = 0.0; int remaining = 0; double wanted = 1.0; bool devUnity = false; };
-    std::vector<GainRamp> gainRamp;     // per stream
+    std::vector<cpqi::GainRamp> gainRamp;     // per stream
     bool eqProcessed = false;           // a process call has consumed EQ parameters since prepare
     // EQ bypass per stream (EQProcessor::setBypassFromRT + the fade of the basic process(block),
     // src/eqprocessor/EQProcessor.Processing.cpp:499-526, 977-1015): LinearRamp bypassFadeGain over 5 ms
-    struct EqBypass {
-        bool requested = false, effective = false;
-        double current = 1.0, target = 1.0, step = 0.0;
-        int remaining = 0;
-        int mode = 0;                   // what the device tables of the stream hold now: 0 parameters as set,
-    };                                  // 1 band nodes of the basic path, 2 pass-through
-    std::vector<EqBypass> eqBypass;
+    std::vector<cpqi::EqBypass> eqBypass;
     // requestBandReset (EQProcessor.h; Processing.cpp:595-624): bands whose state is cleared at the first callback where
     // that is safe -- the block is silent, or a bypass fade is running
     std::vector<uint32_t> eqResetPending;
@@ -260,8 +256,7 @@ struct cpq_engine {
     cpqi::DeviceBuffer<int> procWetOn;                       // [streams] device: 0 = the stream's output is the delayed dry signal
     bool honourFrozen = false;                      // set around the convolver call of enqueueConvProc: frozen plan groups (and their direct heads) rest
     // mix smoothing (LinearRamp mixSmoother, src/ConvolverProcessor.h:945; Runtime.cpp:340-375, 591-607): per stream
-    struct MixRamp { double current = 1.0, target = 1.0, step = 0.0; int remaining = 0, totalSteps = 4800; };
-    std::vector<MixRamp> mixRamp;
+    std::vector<cpqi::MixRamp> mixRamp;
     bool procProcessed = false;         // a processor-level call has run since create / prepare: parameter changes ramp
     cpqi::DeviceBuffer<int> mixRampLen;             // [streams] device: leading samples of the call with per-sample gains
     cpqi::DeviceBuffer<double> mixRampGains;     // [streams][mixRampCap][2] device (allocated when a ramp first runs)
@@ -274,13 +269,7 @@ struct cpq_engine {
     int dryRingSize = 0;
     long long dryPos = 0;           // absolute position of the next input sample
     // latency compensation (Runtime.cpp:263-290, 394-540): latencySmoother is only ever snapped, crossfadeGain runs 20 ms
-    struct LatencyFade {
-        double latCurrent = 0.0, latTarget = 0.0, oldDelay = 0.0;
-        double current = 1.0, target = 1.0, step = 0.0;
-        int remaining = 0;
-        bool primed = false;        // latCurrent holds the prepareToPlay value (Lifecycle.cpp:380-388)
-    };
-    std::vector<LatencyFade> latFade;
+    std::vector<cpqi::LatencyFade> latFade;
     cpqi::DeviceBuffer<int> latNew;          // [streams] device: delay of the dry read
     cpqi::DeviceBuffer<int> latOld;          // [streams] delay faded out
     std::vector<int> latNewHost, latOldHost;    // what the two device arrays hold
@@ -335,6 +324,15 @@ int fail(cpq_engine* e, int code, const char* fmt, ...);
             return fail((e), CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__));      \
     } while (0)
 
+// a step that reports a status: anything but CPQ_OK ends the calling function with it
+#define CPQ_TRY(expr)                                                                                \
+    do {                                                                                             \
+        const int rc__ = (expr);                                                                     \
+        if (rc__ != CPQ_OK) return rc__;                                                             \
+    } while (0)
+
+// the stream argument of an entry point, one stream or CPQ_ALL_STREAMS, as the range [s0, s1); refuses any other value
+int streamRange(cpq_engine* e, int stream, int& s0, int& s1);
 
 int nextPow2(int v);
 int64_t alignUp(int64_t v, int64_t a);

@@ -74,20 +74,14 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     if (!e->procGains) { const int rc = uploadProcParams(e); if (rc != CPQ_OK) return rc; }
     {
         // feasibility first, before the ramp replay below consumes samples: resting ONE convolver needs that stream in a plan
-        // group.  Which convolvers rest in THIS call is predicted from the ramps exactly as the replay below will decide it (a
+        // group.  Which convolvers rest in THIS call is what the replay below will decide, asked of a copy of each ramp (a
         // dry-only stream keeps convolving while its mix ramp runs: streams set dry-only together can still differ for a call or
         // two when their ramps have different lengths left) -- nothing is mutated here.
         const int Sn = e->desc.n_streams;
         bool allWant = true, anyWant = false;
         std::vector<char> want((size_t)Sn, 0);
         for (int s = 0; s < Sn; ++s) {
-            bool willRamp = false;
-            if (!e->procBypass[s]) {
-                const auto& r = e->mixRamp[s];
-                const double tgt = (double)e->procParams[s].mix;
-                const bool retarget = std::fabs(r.target - tgt) > 1.0e-5 && tgt != r.target;
-                willRamp = (retarget ? (r.remaining > 0 ? r.remaining : r.totalSteps) : r.remaining) > 0;
-            }
+            const bool willRamp = !e->procBypass[s] && e->mixRamp[s].wouldSmooth((double)e->procParams[s].mix, n, e->B);
             want[(size_t)s] = e->procBypass[s] || (e->procDryOnly[s] && !willRamp);
             allWant = allWant && want[(size_t)s];
             anyWant = anyWant || want[(size_t)s];
@@ -110,29 +104,19 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     {
         for (int s = 0; s < S; ++s) {
             if (e->procBypass[s]) continue;             // the bypass path does not touch the smoother (:123-186)
-            auto& r = e->mixRamp[s];
-            const double tgt = (double)e->procParams[s].mix;
-            if (std::fabs(r.target - tgt) > 1.0e-5 && tgt != r.target) {                 // setTargetValue
-                r.target = tgt;
-                const int steps = r.remaining > 0 ? r.remaining : r.totalSteps;
-                r.step = (r.target - r.current) / (double)steps;
-                r.remaining = steps;
-            }
-            if (r.remaining <= 0) continue;
+            const int len = e->mixRamp[s].beginCall((double)e->procParams[s].mix, n, e->B);
+            if (len <= 0) continue;
             if (!anyRamp) { mixRampLenHost.assign(S, 0); anyRamp = true; }
-            mixRampLenHost[s] = (int)std::min<int64_t>(n, ((int64_t)r.remaining + e->B - 1) / e->B * e->B);
-            rampStride = std::max(rampStride, mixRampLenHost[s]);
+            mixRampLenHost[s] = len;
+            rampStride = std::max(rampStride, len);
         }
         if (anyRamp) rampHost.assign((size_t)S * rampStride * 2, 0.0);
         for (int s = 0; s < S && anyRamp; ++s) {
             auto& r = e->mixRamp[s];
             for (int i = 0; i < mixRampLenHost[s]; ++i) {
-                if (r.remaining > 0) {                                                  // getNextValue
-                    r.current += r.step;
-                    if (--r.remaining <= 0) r.current = r.target;
-                }
-                rampHost[((size_t)s * rampStride + i) * 2] = equalPowerSin(r.current) * 1.0;
-                rampHost[((size_t)s * rampStride + i) * 2 + 1] = equalPowerSin(1.0 - r.current);
+                const double mix = r.next();
+                rampHost[((size_t)s * rampStride + i) * 2] = equalPowerSin(mix) * 1.0;
+                rampHost[((size_t)s * rampStride + i) * 2 + 1] = equalPowerSin(1.0 - mix);
             }
         }
     }
@@ -142,8 +126,8 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
             if (rc != CPQ_OK) return rc;
         }
         { const int rc = grow(e, e->mixRampGains, e->mixRampCap, rampStride, (size_t)2 * S, "mix-ramp buffers could not be allocated"); if (rc != CPQ_OK) return rc; }
-        { const int rcUp = stageUpload(e, e->mixRampLen, mixRampLenHost.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
-        { const int rcUp = stageUpload(e, e->mixRampGains, rampHost.data(), sizeof(double) * rampHost.size()); if (rcUp != CPQ_OK) return rcUp; }
+        CPQ_TRY(stageUpload(e, e->mixRampLen, mixRampLenHost.data(), sizeof(int) * S));
+        CPQ_TRY(stageUpload(e, e->mixRampGains, rampHost.data(), sizeof(double) * rampHost.size()));
     }
     const bool firstCall = !e->procProcessed;
     e->procProcessed = true;
@@ -168,10 +152,8 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
         std::vector<int> wetOn((size_t)S);
         for (int s = 0; s < S; ++s) wetOn[s] = rest[s] ? 0 : 1;
         if (wetOn != e->procWetOnHost) {
-            if (!e->procWetOn) {
-                const int rcA = allocAll(e, { { e->procWetOn, (size_t)S } }, "processor-level flags could not be allocated");
-                if (rcA != CPQ_OK) return rcA;
-            }
+            if (!e->procWetOn)
+                CPQ_TRY(allocAll(e, { { e->procWetOn, (size_t)S } }, "processor-level flags could not be allocated"));
             const int rc = stageUpload(e, e->procWetOn, wetOn.data(), sizeof(int) * S);
             if (rc != CPQ_OK) return rc;
             e->procWetOnHost = wetOn;
@@ -196,34 +178,22 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     // (:141-145).  Ranges of the call between the callbacks where some stream starts a fade go to one launch each.
     const int cbs = (n + e->B - 1) / e->B;                  // callbacks (chunks of the call quantum; the last one may be shorter)
     auto lenOf = [&](int t) { return std::min(e->B, n - t * e->B); };
-    const int xTotal = std::max(1, (int)(e->sampleRate * 0.02 + 0.5));
+    const int xTotal = LinearRamp::stepsFor(e->sampleRate, 0.02);
     struct Range { int c0, c1; };
     std::vector<Range> ranges;
     std::vector<int> dNew, dOld, xLen;
     std::vector<std::vector<double>> xg;          // per range: [S][len]
     {
         std::vector<char> starts((size_t)cbs, 0);
-        // pass 1: where do fades start (needs the per-stream replay, so replay on copies)
-        {
-            for (int s = 0; s < S; ++s) {
-                if (e->procBypass[s]) continue;
-                auto f = e->latFade[s];
-                const double total = (double)procDelayOf(e, s);
-                if (!f.primed || firstCall) {             // prepareToPlay: latency + irLatency, fade gain at 1 (Lifecycle.cpp:377-388)
-                    f.latCurrent = f.latTarget = f.oldDelay = (double)std::min(e->P0 + std::min(std::max(0, (int)e->procParams[s].ir_peak_latency), 2097152), 2097152 + 524288);
-                    f.current = f.target = 1.0; f.remaining = 0; f.primed = true;
-                }
-                for (int t = 0; t < cbs; ++t) {
-                    if (std::fabs(f.latTarget - total) >= 2.0 && f.remaining <= 0) {
-                        f.oldDelay = f.latCurrent; f.current = 0.0; f.target = 1.0; f.step = 1.0 / (double)xTotal; f.remaining = xTotal;
-                        f.latTarget = total;
-                        if (t > 0) starts[t] = 1;
-                    }
-                    if (f.remaining > 0) {
-                        f.remaining = std::max(0, f.remaining - lenOf(t));
-                        if (f.remaining <= 0) { f.latCurrent = f.latTarget; f.oldDelay = f.latCurrent; }
-                    }
-                }
+        // pass 1: where do fades start -- the replay of pass 2, on a copy of each stream's state
+        for (int s = 0; s < S; ++s) {
+            if (e->procBypass[s]) continue;
+            LatencyFade f = e->latFade[s];
+            const double total = (double)procDelayOf(e, s);
+            if (!f.primed || firstCall) f.prime(e->P0, (int)e->procParams[s].ir_peak_latency);
+            for (int t = 0; t < cbs; ++t) {
+                if (f.beginCallback(total, xTotal) && t > 0) starts[t] = 1;
+                f.advance(lenOf(t), nullptr);
             }
         }
         int c0 = 0;
@@ -240,35 +210,16 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
             for (int r = 0; r < R; ++r) dNew[(size_t)r * S + s] = dOld[(size_t)r * S + s] = totalI;
             continue;
         }
-        if (!f.primed || firstCall) {
-            f.latCurrent = f.latTarget = f.oldDelay = (double)std::min(e->P0 + std::min(std::max(0, (int)e->procParams[s].ir_peak_latency), 2097152), 2097152 + 524288);
-            f.current = f.target = 1.0; f.step = 0.0; f.remaining = 0; f.primed = true;
-        }
+        if (!f.primed || firstCall) f.prime(e->P0, (int)e->procParams[s].ir_peak_latency);
         for (int r = 0; r < R; ++r) {
             std::vector<double> vals;
-            bool fading = false;
             for (int t = ranges[r].c0; t < ranges[r].c1; ++t) {
-                if (std::fabs(f.latTarget - (double)totalI) >= 2.0 && f.remaining <= 0) {
-                    f.oldDelay = f.latCurrent;
-                    f.current = 0.0; f.target = 1.0;                     // applyImmediateValueRT(0), setTargetValue(1)
-                    f.step = (f.target - f.current) / (double)xTotal;
-                    f.remaining = xTotal;
-                    f.latTarget = (double)totalI;
-                }
+                f.beginCallback((double)totalI, xTotal);
                 if (t == ranges[r].c0) {
-                    fading = f.remaining > 0;
-                    dNew[(size_t)r * S + s] = fading ? (int)f.latTarget : (int)(f.latCurrent + 0.5);
+                    dNew[(size_t)r * S + s] = f.newDelay();
                     dOld[(size_t)r * S + s] = (int)f.oldDelay;
                 }
-                if (f.remaining > 0) {
-                    for (int i = 0; i < lenOf(t); ++i) {                 // getNextValue until the ramp has ended
-                        f.current += f.step;
-                        if (--f.remaining <= 0) f.current = f.target;
-                        vals.push_back(f.current);
-                        if (f.remaining <= 0) break;
-                    }
-                    if (f.remaining <= 0) { f.latCurrent = f.latTarget; f.oldDelay = f.latCurrent; }
-                }
+                f.advance(lenOf(t), &vals);
             }
             xLen[(size_t)r * S + s] = (int)vals.size();
             if (!vals.empty()) {
@@ -289,16 +240,16 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
         const std::vector<int> rn(dNew.begin() + (size_t)r * S, dNew.begin() + (size_t)(r + 1) * S);
         const std::vector<int> ro(dOld.begin() + (size_t)r * S, dOld.begin() + (size_t)(r + 1) * S);
         if (rn != e->latNewHost) {
-            { const int rcUp = stageUpload(e, e->latNew, rn.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
+            CPQ_TRY(stageUpload(e, e->latNew, rn.data(), sizeof(int) * S));
             e->latNewHost = rn;
         }
         if (ro != e->latOldHost) {
-            { const int rcUp = stageUpload(e, e->latOld, ro.data(), sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
+            CPQ_TRY(stageUpload(e, e->latOld, ro.data(), sizeof(int) * S));
             e->latOldHost = ro;
         }
         if (fade) {
-            { const int rcUp = stageUpload(e, e->latLen, &xLen[(size_t)r * S], sizeof(int) * S); if (rcUp != CPQ_OK) return rcUp; }
-            { const int rcUp = stageUpload(e, e->latGains, xg[r].data(), sizeof(double) * xg[r].size()); if (rcUp != CPQ_OK) return rcUp; }
+            CPQ_TRY(stageUpload(e, e->latLen, &xLen[(size_t)r * S], sizeof(int) * S));
+            CPQ_TRY(stageUpload(e, e->latGains, xg[r].data(), sizeof(double) * xg[r].size()));
         }
         ProfScope p(e, CPQ_K_MIX);
         cpq::launch_convproc_mix(e->stream, dOut + off, dOut + off, (int64_t)n, e->nCh, len, e->procGains, e->dryRing,
@@ -317,8 +268,8 @@ extern "C" {
 int32_t cpq_convproc_set_params(cpq_engine* e, int32_t stream, const cpq_convproc_params* p)
 {
     if (!e || !p) return CPQ_ERR_INVALID_ARG;
-    if (stream != CPQ_ALL_STREAMS && (stream < 0 || stream >= e->desc.n_streams))
-        return fail(e, CPQ_ERR_INVALID_ARG, "stream %d out of range", stream);
+    int s0 = 0, s1 = 0;
+    CPQ_TRY(streamRange(e, stream, s0, s1));
     if (!(p->mix >= 0.0f && p->mix <= 1.0f)) return fail(e, CPQ_ERR_INVALID_ARG, "mix must be in [0, 1]");
     if (p->ir_peak_latency < 0) return fail(e, CPQ_ERR_INVALID_ARG, "ir_peak_latency must be >= 0");
     const bool dryOnly = !((double)p->mix > 0.001);        // needsConvolution, :374
@@ -326,19 +277,16 @@ int32_t cpq_convproc_set_params(cpq_engine* e, int32_t stream, const cpq_convpro
         return fail(e, CPQ_ERR_UNSUPPORTED, "a per-stream bypass / dry-only rests ONE convolver: the stream must run on the reference's own "
                     "layer plan (CPQ_CALLS_ANY, CPQ_SCHED_REFERENCE_NUC or a FilterSpec plan with tail layers); on the uniform path set it "
                     "for CPQ_ALL_STREAMS");
-    const int s0 = (stream == CPQ_ALL_STREAMS) ? 0 : stream;
-    const int s1 = (stream == CPQ_ALL_STREAMS) ? e->desc.n_streams : stream + 1;
     if (p->smoothing_time_sec != 0.0f && !(p->smoothing_time_sec >= 0.01f && p->smoothing_time_sec <= 0.5f))
         return fail(e, CPQ_ERR_INVALID_ARG, "smoothing_time_sec must be 0 (default 0.1 s) or in [0.01, 0.5]");
     for (int s = s0; s < s1; ++s) {
         e->procParams[s] = *p;
-        auto& r = e->mixRamp[s];
+        LinearRamp& r = e->mixRamp[s].ramp;
         const double t = p->smoothing_time_sec != 0.0f ? (double)p->smoothing_time_sec : 0.1;     // SMOOTHING_TIME_DEFAULT_SEC
-        const int steps = (int)(e->sampleRate * t + 0.5);
-        r.totalSteps = steps > 0 ? steps : 1;
+        r.totalSteps = LinearRamp::stepsFor(e->sampleRate, t);
         // before the first processor-level call (the reference's prepareToPlay: setCurrentAndTargetValue, Lifecycle.cpp:370)
         // the mix applies at once; afterwards it is the ramp's new target
-        if (!e->procProcessed) { r.current = r.target = (double)p->mix; r.step = 0.0; r.remaining = 0; }
+        if (!e->procProcessed) r.setCurrentAndTargetValue((double)p->mix);
     }
     for (int s = s0; s < s1; ++s) { e->procBypass[s] = p->bypassed != 0; e->procDryOnly[s] = dryOnly; }
     return uploadProcParams(e);

@@ -1,0 +1,366 @@
+// Host-only driver for convopeq_amd/csrc/host_replay.hpp (tests/test_host_replay_cpu.py): the ramps and fades the engine replays
+// per callback, with no HIP and no engine.  Every check is exact (== on doubles): the properties hold bit for bit by construction.
+//   1. LinearRamp semantics
+//   2. call-split invariance: N callbacks as one call, as every split into two calls and as N calls give the same outputs and
+//      leave the same state (the reference only ever sees callbacks, so it has this by construction)
+//   3. what is predicted on a copy (which convolver rests, where latency fades start) is what the replay then does, and the
+//      original is untouched by the prediction
+// The per-call drivers below are the loops of enqueueEqCore / enqueueEqRange / enqueueConvProc without their uploads.
+#include "host_replay.hpp"
+
+#include <cstdio>
+
+using namespace cpqi;
+
+static int g_failed = 0, g_checks = 0;
+#define CHECK(cond)                                                                   \
+    do {                                                                              \
+        ++g_checks;                                                                   \
+        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
+    } while (0)
+
+struct Rng {        // seeded, the same everywhere
+    uint64_t s;
+    uint32_t next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33); }
+    int below(int n) { return (int)(next() % (uint32_t)n); }
+    double unit() { return (double)next() / 2147483648.0; }
+};
+
+static bool same(const LinearRamp& a, const LinearRamp& b)
+{
+    return a.current == b.current && a.target == b.target && a.step == b.step && a.remaining == b.remaining && a.totalSteps == b.totalSteps;
+}
+static bool same(const GainRamp& a, const GainRamp& b) { return same(a.ramp, b.ramp) && a.wanted == b.wanted && a.devUnity == b.devUnity; }
+static bool same(const EqBypass& a, const EqBypass& b)
+{
+    return same(a.fade, b.fade) && a.requested == b.requested && a.effective == b.effective && a.mode == b.mode;
+}
+static bool same(const MixRamp& a, const MixRamp& b) { return same(a.ramp, b.ramp); }
+static bool same(const LatencyFade& a, const LatencyFade& b)
+{
+    return same(a.fade, b.fade) && a.latCurrent == b.latCurrent && a.latTarget == b.latTarget && a.oldDelay == b.oldDelay && a.primed == b.primed;
+}
+
+// ---------------------------------------------------------------------------------------------------- per-call drivers
+struct Shape { int B; double rate; };
+
+struct GainOut { double start, increment; bool operator==(const GainOut&) const = default; };
+// enqueueEqCore: a stream that is not moving at the start of the call draws nothing (the cascade kernel applies `wanted`)
+static void gainCall(GainRamp& r, const Shape& sh, int cbs, std::vector<GainOut>& out)
+{
+    const int total = LinearRamp::stepsFor(sh.rate, 0.05);
+    if (!r.moving()) { out.insert(out.end(), (size_t)cbs, GainOut{ r.wanted, 0.0 }); return; }
+    for (int t = 0; t < cbs; ++t) {
+        const GainRamp::Segment g = r.callback(sh.B, total);
+        out.push_back({ g.start, g.increment });
+    }
+}
+
+struct BypassOut {
+    std::vector<char> cls, released;
+    std::vector<double> vals;
+    bool operator==(const BypassOut&) const = default;
+};
+static void bypassCall(EqBypass& b, const Shape& sh, int cbs, BypassOut& out)
+{
+    const int total = LinearRamp::stepsFor(sh.rate, 0.005);
+    for (int t = 0; t < cbs; ++t) {
+        const EqBypass::Step st = b.callback(sh.B, total, out.vals);
+        out.cls.push_back(st.cls);
+        out.released.push_back(st.released ? 1 : 0);
+    }
+}
+
+// enqueueConvProc, mix: per-sample values over the smoothed prefix, the value the ramp rests at behind it
+struct MixState { MixRamp r; double mix; };
+static bool same(const MixState& a, const MixState& b) { return same(a.r, b.r) && a.mix == b.mix; }
+static void mixCall(MixState& m, const Shape& sh, int n, std::vector<double>& out)
+{
+    const MixRamp before = m.r;
+    const bool predicted = m.r.wouldSmooth(m.mix, n, sh.B);
+    CHECK(same(before, m.r));                                   // the prediction moved nothing
+    const int len = m.r.beginCall(m.mix, n, sh.B);
+    CHECK(predicted == (len > 0));                              // ... and is what the replay decides
+    CHECK(len <= n && (len == n || len % sh.B == 0));
+    for (int i = 0; i < len; ++i) out.push_back(m.r.next());
+    if (len < n) CHECK(!m.r.ramp.isSmoothing());                // the prefix covers the whole ramp or the whole call
+    for (int i = len; i < n; ++i) out.push_back(m.r.ramp.current);
+}
+
+// enqueueConvProc, latency: pass 1 on a copy finds the callbacks where a fade starts, pass 2 replays range by range
+struct LatState { LatencyFade f; bool processed; int total, irPeak; };
+static bool same(const LatState& a, const LatState& b) { return same(a.f, b.f) && a.processed == b.processed && a.total == b.total; }
+struct LatSample { int dNew, dOld; double g; bool operator==(const LatSample&) const = default; };
+constexpr int kP0 = 64;
+static void latCall(LatState& st, const Shape& sh, int n, std::vector<LatSample>& out)
+{
+    const int B = sh.B, cbs = (n + B - 1) / B, xTotal = LinearRamp::stepsFor(sh.rate, 0.02);
+    auto lenOf = [&](int t) { return std::min(B, n - t * B); };
+    const bool firstCall = !st.processed;
+    st.processed = true;
+    std::vector<char> starts((size_t)cbs, 0);
+    {
+        const LatencyFade before = st.f;
+        LatencyFade f = st.f;
+        if (!f.primed || firstCall) f.prime(kP0, st.irPeak);
+        for (int t = 0; t < cbs; ++t) {
+            if (f.beginCallback((double)st.total, xTotal) && t > 0) starts[(size_t)t] = 1;
+            f.advance(lenOf(t), nullptr);
+        }
+        CHECK(same(before, st.f));
+    }
+    LatencyFade& f = st.f;
+    if (!f.primed || firstCall) f.prime(kP0, st.irPeak);
+    for (int c0 = 0, t1 = 1; t1 <= cbs; ++t1) {
+        if (t1 != cbs && !starts[(size_t)t1]) continue;
+        std::vector<double> vals;
+        int dNew = 0, dOld = 0, len = 0;
+        for (int t = c0; t < t1; ++t) {
+            const bool started = f.beginCallback((double)st.total, xTotal);
+            CHECK(t == 0 || started == (starts[(size_t)t] != 0));        // pass 1 found exactly the starts of pass 2
+            CHECK(!started || t == c0);
+            if (t == c0) { dNew = f.newDelay(); dOld = (int)f.oldDelay; }
+            f.advance(lenOf(t), &vals);
+            len += lenOf(t);
+        }
+        CHECK((int)vals.size() <= len && (int)vals.size() <= xTotal);
+        for (int i = 0; i < len; ++i)
+            out.push_back(i < (int)vals.size() ? LatSample{ dNew, dOld, vals[(size_t)i] } : LatSample{ dNew, -1, 1.0 });
+        c0 = t1;
+    }
+}
+
+// One stretch of callbacks (lens: B, ..., B and possibly a shorter last one) from state s0: as one call, as every split into two
+// calls, as one call per callback.  Returns the state behind it.
+template <class State, class Out, class Call>
+static State splitInvariant(const State& s0, const std::vector<int>& lens, bool bySamples, Call call, Out& whole)
+{
+    const int N = (int)lens.size();
+    auto size = [&](int a, int b) { int n = 0; for (int t = a; t < b; ++t) n += bySamples ? lens[(size_t)t] : 1; return n; };
+    State end = s0;
+    call(end, size(0, N), whole);
+    for (int k = 1; k < N; ++k) {
+        State s = s0;
+        Out o;
+        call(s, size(0, k), o);
+        call(s, size(k, N), o);
+        CHECK(o == whole);
+        CHECK(same(s, end));
+    }
+    State s = s0;
+    Out o;
+    for (int t = 0; t < N; ++t) call(s, size(t, t + 1), o);
+    CHECK(o == whole);
+    CHECK(same(s, end));
+    return end;
+}
+
+static void rampSemantics()
+{
+    for (double rate : { 44100.0, 48000.0, 384000.0 })
+        for (double t : { 0.005, 0.02, 0.05, 0.1 }) {
+            const int n = LinearRamp::stepsFor(rate, t);
+            CHECK(n >= 1 && n == (int)(rate * t + 0.5));
+        }
+    CHECK(LinearRamp::stepsFor(44100.0, 0.005) == 221 && LinearRamp::stepsFor(44100.0, 0.02) == 882 && LinearRamp::stepsFor(44100.0, 0.05) == 2205);
+    CHECK(LinearRamp::stepsFor(48000.0, 0.005) == 240 && LinearRamp::stepsFor(48000.0, 0.1) == 4800 && LinearRamp::stepsFor(384000.0, 0.05) == 19200);
+    CHECK(LinearRamp::stepsFor(48000.0, 0.0) == 1 && LinearRamp::stepsFor(1.0, 0.005) == 1 && LinearRamp::stepsFor(48000.0, -1.0) == 1);
+
+    LinearRamp r;
+    CHECK(r.current == 1.0 && r.target == 1.0 && !r.isSmoothing());
+    r.totalSteps = 10;
+    r.setTargetValue(1.0);                                      // the target it has: nothing happens
+    CHECK(!r.isSmoothing() && r.step == 0.0 && r.getNextValue() == 1.0);
+    r.setTargetValue(0.3);
+    CHECK(r.isSmoothing() && r.remaining == 10 && r.step == (0.3 - 1.0) / 10.0);
+    { const LinearRamp was = r; r.setTargetValue(0.3); CHECK(same(was, r)); }
+    double c = 1.0;
+    for (int i = 0; i < 4; ++i) { c += r.step; CHECK(r.getNextValue() == c); }
+    r.setTargetValue(0.9);                                      // in mid-ramp: the 6 steps left, not 10
+    CHECK(r.remaining == 6 && r.step == (0.9 - c) / 6.0);
+    for (int i = 0; i < 5; ++i) { c += r.step; CHECK(r.getNextValue() == c); }
+    CHECK(r.remaining == 1 && r.current != 0.9);                // accumulated rounding: not there yet ...
+    CHECK(r.getNextValue() == 0.9 && !r.isSmoothing());         // ... the last step lands on the target itself
+    CHECK(r.getNextValue() == 0.9 && r.current == 0.9);         // at rest it keeps returning it
+
+    r.setCurrentAndTargetValue(0.1);
+    r.totalSteps = 7;
+    r.setTargetValue(0.7);
+    {   // skip(n), n < remaining: one multiply-add -- and that is NOT n additions (0.1 -> 0.7 in 7 steps tells them apart)
+        LinearRamp a = r, b = r;
+        a.skip(5);
+        CHECK(a.current == 0.1 + a.step * 5.0 && a.remaining == 2 && a.isSmoothing());
+        for (int i = 0; i < 5; ++i) b.getNextValue();
+        CHECK(b.remaining == 2 && b.current != a.current);
+        a.skip(0); a.skip(-3);
+        CHECK(a.current == 0.1 + a.step * 5.0 && a.remaining == 2);
+        a.skip(2);                                              // n == remaining: snaps
+        CHECK(a.current == 0.7 && !a.isSmoothing());
+        LinearRamp d = r;
+        d.skip(1000);
+        CHECK(d.current == 0.7 && d.remaining == 0);
+        d.skip(3);
+        CHECK(d.current == 0.7);
+    }
+    r.setCurrentAndTargetValue(0.25);
+    CHECK(r.current == 0.25 && r.target == 0.25 && r.step == 0.0 && r.remaining == 0 && r.totalSteps == 7);
+}
+
+static std::vector<int> callbacks(Rng& rng, int B, bool ragged)
+{
+    std::vector<int> lens((size_t)(1 + rng.below(6)), B);
+    if (ragged && rng.below(2)) lens.push_back(1 + rng.below(B - 1));
+    return lens;
+}
+
+static void splitScripts()
+{
+    const Shape shapes[3] = { { 64, 48000.0 }, { 441, 44100.0 }, { 512, 48000.0 } };
+    const double gainsOf[6] = { 1.0, 0.5, 2.0, 0.5 + 1.0e-7, 0.25, 1.0 + 5.0e-7 };
+    const int peaks[5] = { 0, 150, 151, 900, 3000 };
+    for (const Shape& sh : shapes)
+        for (uint64_t seed = 1; seed <= 6; ++seed) {
+            Rng rng{ seed * 7919u + (uint64_t)sh.B };
+            GainRamp gain;
+            EqBypass byp;
+            MixState mix{ MixRamp{}, 1.0 };
+            mix.r.ramp.totalSteps = LinearRamp::stepsFor(sh.rate, seed % 2 ? 0.1 : 0.01);
+            LatState lat{ LatencyFade{}, false, kP0, 0 };
+            bool sawFade = false, sawPass = false, sawRelease = false, sawLatFade = false, sawMixRamp = false, sawGainRamp = false;
+            for (int seg = 0; seg < 60; ++seg) {
+                // parameters change between calls only
+                if (rng.below(3) == 0) gain.wanted = rng.below(4) ? gainsOf[rng.below(6)] : 0.1 + rng.unit();
+                if (rng.below(4) == 0) byp.requested = !byp.requested;
+                if (rng.below(3) == 0) mix.mix = rng.below(3) ? (double)(float)rng.unit() : (rng.below(2) ? 0.0 : mix.mix + 5.0e-6);
+                if (rng.below(3) == 0) { lat.irPeak = peaks[rng.below(5)]; lat.total = kP0 + lat.irPeak; }
+                const std::vector<int> whole = callbacks(rng, sh.B, false), ragged = callbacks(rng, sh.B, true);
+
+                std::vector<GainOut> go;
+                gain = splitInvariant(gain, whole, false, [&](GainRamp& r, int cbs, std::vector<GainOut>& o) { gainCall(r, sh, cbs, o); }, go);
+                for (const auto& g : go) sawGainRamp = sawGainRamp || g.increment != 0.0;
+                BypassOut bo;
+                byp = splitInvariant(byp, whole, false, [&](EqBypass& b, int cbs, BypassOut& o) { bypassCall(b, sh, cbs, o); }, bo);
+                sawFade = sawFade || !bo.vals.empty();
+                for (size_t t = 0; t < bo.cls.size(); ++t) { sawPass = sawPass || bo.cls[t] == EqBypass::kPass; sawRelease = sawRelease || bo.released[t]; }
+                CHECK(byp.active() == (byp.requested || byp.effective || byp.fade.isSmoothing()));
+                std::vector<double> mo;
+                mix = splitInvariant(mix, ragged, true, [&](MixState& m, int n, std::vector<double>& o) { mixCall(m, sh, n, o); }, mo);
+                for (double v : mo) sawMixRamp = sawMixRamp || v != mo.back();
+                std::vector<LatSample> lo;
+                lat = splitInvariant(lat, ragged, true, [&](LatState& l, int n, std::vector<LatSample>& o) { latCall(l, sh, n, o); }, lo);
+                for (const auto& v : lo) sawLatFade = sawLatFade || v.dOld >= 0;
+            }
+            CHECK(sawFade && sawPass && sawRelease && sawLatFade && sawMixRamp && sawGainRamp);   // the scripts reach every machine
+        }
+}
+
+// test_latency_cross_fade_starting_in_a_one_sample_call: quantum 96, the latency moves just before a call of ONE sample
+static void oneSampleFadeStart()
+{
+    const Shape sh{ 96, 48000.0 };
+    LatState st{ LatencyFade{}, false, kP0 + 700, 700 };
+    std::vector<LatSample> o;
+    latCall(st, sh, 96 * 2, o);
+    CHECK(o.size() == 192 && o[0] == (LatSample{ kP0 + 700, -1, 1.0 }) && !st.f.fading());
+    st.irPeak = 150; st.total = kP0 + 150;
+    o.clear();
+    latCall(st, sh, 1, o);
+    CHECK(o.size() == 1 && o[0] == (LatSample{ kP0 + 150, kP0 + 700, 1.0 / 960.0 }) && st.f.fade.remaining == 959);
+    // ... and the same stretch in any cut: 1 + 288 + 2 samples as three calls or as callbacks of the quantum
+    LatState a{ LatencyFade{}, false, kP0 + 700, 700 }, b = a;
+    std::vector<LatSample> oa, ob;
+    latCall(a, sh, 192, oa); latCall(b, sh, 192, ob);
+    a.irPeak = b.irPeak = 150; a.total = b.total = kP0 + 150;
+    for (int n : { 1, 288, 2 }) latCall(a, sh, n, oa);
+    for (int n : { 96, 96, 96, 3 }) latCall(b, sh, n, ob);
+    CHECK(oa == ob && same(a, b));
+}
+
+// test_processor_level_dry_only_with_unequal_ramps_fails_before_any_state_moves: B = 512, calls of 4 callbacks; stream 0 is in
+// mid-ramp when both streams are set dry-only, so its ramp ends a call before stream 1's: in that call stream 0 would rest and
+// stream 1 not, which has to be known -- twice, the call is refused and made again -- before either ramp moves
+static void unequalRamps()
+{
+    const Shape sh{ 512, 48000.0 };
+    const int n = 4 * 512;
+    MixState m[2] = { { MixRamp{}, 1.0 }, { MixRamp{}, 1.0 } };
+    for (auto& s : m) s.r.ramp.totalSteps = LinearRamp::stepsFor(sh.rate, 0.1);
+    std::vector<double> o;
+    for (auto& s : m) mixCall(s, sh, n, o);
+    m[0].mix = (double)0.5f;
+    for (auto& s : m) mixCall(s, sh, n, o);
+    CHECK(m[0].r.ramp.remaining == 2752 && !m[1].r.ramp.isSmoothing());
+    m[0].mix = m[1].mix = 0.0;
+    for (auto& s : m) mixCall(s, sh, n, o);
+    CHECK(m[0].r.ramp.remaining == 704 && m[1].r.ramp.remaining == 2752);
+    for (auto& s : m) mixCall(s, sh, n, o);
+    CHECK(!m[0].r.ramp.isSmoothing() && m[1].r.ramp.remaining == 704);
+    const MixState was[2] = { m[0], m[1] };
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        CHECK(!m[0].r.wouldSmooth(m[0].mix, n, sh.B) && m[1].r.wouldSmooth(m[1].mix, n, sh.B));    // dry-only: 0 rests, 1 does not
+        CHECK(same(was[0], m[0]) && same(was[1], m[1]));
+    }
+    CHECK(m[0].r.beginCall(m[0].mix, n, sh.B) == 0 && m[1].r.beginCall(m[1].mix, n, sh.B) == 1024);
+}
+
+static void policies()
+{
+    GainRamp g;
+    CHECK(!g.moving());
+    g.wanted = 1.0 + 5.0e-7;                                    // below the retarget threshold: no ramp, yet not at rest either
+    CHECK(g.moving());
+    const GainRamp::Segment s = g.callback(64, 2400);
+    CHECK(s.start == 1.0 && s.increment == 0.0 && !g.ramp.isSmoothing() && g.moving());
+    g.snap();
+    CHECK(!g.moving() && g.ramp.current == g.wanted && g.ramp.target == g.wanted);
+
+    EqBypass b;
+    CHECK(!b.active());
+    b.requested = true;
+    CHECK(b.active());
+    b.sync();
+    CHECK(b.effective && b.fade.current == 0.0 && b.fade.target == 0.0 && !b.fade.isSmoothing() && b.active());
+    std::vector<double> vals;
+    EqBypass::Step st = b.callback(64, 240, vals);
+    CHECK(st.cls == EqBypass::kPass && !st.released && vals.empty());
+    b.requested = false;
+    st = b.callback(64, 240, vals);
+    CHECK(st.cls == EqBypass::kFade && st.released && vals.size() == 64 && !b.effective && b.active());
+    b.mode = 1;
+    for (int t = 0; t < 3; ++t) st = b.callback(64, 240, vals);
+    CHECK(st.cls == EqBypass::kFade && !st.released && vals.size() == 240 && vals.back() == 1.0 && b.active());     // mode != 0 alone
+    st = b.callback(64, 240, vals);
+    CHECK(st.cls == EqBypass::kNormal && vals.size() == 240);
+    b.mode = 0;
+    CHECK(!b.active());
+
+    LatencyFade f;
+    f.prime(64, -5);
+    CHECK(f.latCurrent == 64.0 && f.primed && f.fade.current == 1.0);
+    f.prime(64, 1 << 30);
+    CHECK(f.latCurrent == 64.0 + 2097152.0);
+    f.prime(1 << 22, 1 << 30);
+    CHECK(f.latCurrent == 2097152.0 + 524288.0 && f.latTarget == f.latCurrent && f.oldDelay == f.latCurrent);
+    f.prime(64, 100);
+    CHECK(!f.beginCallback(165.0, 960) && f.newDelay() == 164);          // a move of less than 2 samples starts nothing
+    CHECK(f.beginCallback(166.0, 960) && f.fade.current == 0.0 && f.fade.remaining == 960 && f.oldDelay == 164.0 && f.newDelay() == 166);
+    CHECK(!f.beginCallback(300.0, 960));                                 // not while one is running
+    f.advance(959, nullptr);
+    CHECK(f.fading() && f.latCurrent == 164.0);
+    std::vector<double> one;
+    f.advance(64, &one);
+    CHECK(one.size() == 1 && one[0] == 1.0 && !f.fading() && f.latCurrent == 166.0 && f.oldDelay == 166.0);
+    f.advance(64, &one);
+    CHECK(one.size() == 1);
+}
+
+int main()
+{
+    rampSemantics();
+    policies();
+    oneSampleFadeStart();
+    unequalRamps();
+    splitScripts();
+    std::printf("%d checks, %d failed checks\n", g_checks, g_failed);
+    return g_failed ? 1 : 0;
+}
