@@ -29,7 +29,8 @@ CPQ_PARTITION_AUTO = -1
 CPQ_ORDER_CONV_THEN_EQ = 0
 CPQ_ORDER_EQ_THEN_CONV = 1
 KERNEL_IDS = {"k_rfft_fwd_ols": 0, "k_fdl_mac": 1, "k_fdl_mac_dcnyq": 2, "k_rfft_inv_ols": 3, "k_svf_cascade": 4,
-              "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8, "k_meter": 9}
+              "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8, "k_meter": 9,
+              "k_pcm": 10}
 CPQ_LEVEL_NUC = 0
 CPQ_LEVEL_PROCESSOR = 1
 CPQ_EQ_MODE_AUTO = 0
@@ -42,6 +43,14 @@ CPQ_OS_LINEAR_PHASE = 1
 CPQ_METER_LOUDNESS = 1
 CPQ_METER_TRUE_PEAK = 2
 METER_RING = 4096
+CPQ_PCM_F64 = 0
+CPQ_PCM_F32 = 1
+CPQ_PCM_S16 = 2
+CPQ_PCM_S24 = 3
+CPQ_PCM_S32 = 4
+CPQ_PCM_PLANAR = 0
+CPQ_PCM_INTERLEAVED = 1
+CPQ_PCM_SANITIZE = 1
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -130,6 +139,7 @@ class EngineDesc(C.Structure):
 _E = C.c_void_p
 SYMBOLS = {
     "cpq_abi_version": (C.c_int32, []),
+    "cpq_abi_revision": (C.c_int32, []),
     "cpq_status_string": (C.c_char_p, [C.c_int32]),
     "cpq_last_error": (C.c_char_p, [_E]),
     "cpq_nuc_plan_compute": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(FilterSpec), C.POINTER(NucPlan)]),
@@ -194,6 +204,13 @@ SYMBOLS = {
     "cpq_meter_process": (C.c_int32, [_E, c_double_p, C.c_int32]),
     "cpq_meter_process_device": (C.c_int32, [_E, C.c_void_p, C.c_int32]),
     "cpq_meter_read_blocks": (C.c_int32, [_E, C.POINTER(MeterBlock), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "cpq_pcm_bytes_per_sample": (C.c_int32, [C.c_int32]),
+    "cpq_pcm_unpack": (C.c_int32, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32]),
+    "cpq_pcm_unpack_device": (C.c_int32, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32]),
+    "cpq_pcm_pack": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "cpq_pcm_pack_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "cpq_engine_process_block_pcm": (C.c_int32, [_E, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_int32]),
+    "cpq_engine_process_block_pcm_device": (C.c_int32, [_E, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_int32]),
     "cpq_ir_load_wav": (C.c_int32, [C.c_char_p, C.POINTER(IrBuffer)]),
     "cpq_ir_buffer_free": (None, [C.POINTER(IrBuffer)]),
     "cpq_ir_prepare": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_float, C.c_int32, C.POINTER(IrBuffer), C.c_double, C.POINTER(IrPrepared)]),

@@ -122,6 +122,7 @@ using namespace cpqi;
 extern "C" {
 
 int32_t cpq_abi_version(void) { return CPQ_ABI_VERSION; }
+int32_t cpq_abi_revision(void) { return CPQ_ABI_REVISION; }
 
 const char* cpq_status_string(int32_t s)
 {
@@ -159,6 +160,7 @@ const char* cpq_kernel_name(int32_t id)
         case CPQ_K_OUTFILT: return "k_outfilter_cascade";
         case CPQ_K_OS: return "k_os_halfband";
         case CPQ_K_METER: return "k_meter";
+        case CPQ_K_PCM: return "k_pcm";
         default: return "?";
     }
 }
@@ -698,22 +700,32 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed)
     return CPQ_OK;
 }
 
+}  // extern "C"
+
 // the meters read the base-rate rows the call delivers, after everything that writes them (DSPCoreDouble.cpp:695-701)
-static int meteredChain(cpq_engine* e, const double* a, double* b, int n)
+int cpqi::meteredChain(cpq_engine* e, const double* a, double* b, int n)
 {
     int rc = e->osFactor > 1 ? enqueueOsChain(e, a, b, n) : enqueueBoth(e, a, b, n);
     if (rc == CPQ_OK && e->meterFlags) rc = enqueueMeters(e, b, n, n);
     return rc;
 }
 
-int32_t cpq_engine_process_block_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
+int cpqi::checkBlockCall(cpq_engine* e, const void* in, const void* out, int nSamples)
 {
     const int factor = e ? e->osFactor : 1;
     if (factor > 1 && nSamples > e->maxCall / factor)   // n_samples are base-rate samples: the routing runs on n_samples * factor
         return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
                     factor, e->maxCall);
-    int rc = checkCall(e, dIn, dOut, nSamples * factor);
+    int rc = checkCall(e, in, out, nSamples * factor);
     if (rc == CPQ_OK) rc = checkMeterCall(e, nSamples);
+    return rc;
+}
+
+extern "C" {
+
+int32_t cpq_engine_process_block_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
+{
+    const int rc = checkBlockCall(e, dIn, dOut, nSamples);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
     return meteredChain(e, dIn, dOut, nSamples);

@@ -3,6 +3,7 @@
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
 //   engine_eq.cpp    EQ and output filter: design, device tables, bypass / band-reset state machine
+//   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
@@ -308,6 +309,10 @@ struct cpq_engine {
     // every stream sees the same callbacks: one pair of ring counters, one block counter (LockFreeRingBuffer, blockCounter)
     unsigned long long meterWrite = 0, meterRead = 0, meterIndex = 0, meterDropped = 0;
 
+    // packed PCM entry points (engine_pcm.cpp): the call's packed input and output on the device, one group
+    cpqi::DeviceBuffer<char> pcmIn, pcmOut;
+    size_t pcmInCap = 0, pcmOutCap = 0;
+
     // profiling
     bool profiling = false;
     ProfileSlot prof[CPQ_K_COUNT];
@@ -398,6 +403,9 @@ int checkMeterCall(cpq_engine* e, int nBase);   // the refusals, before anything
 int enqueueMeters(cpq_engine* e, const double* rows, int64_t stride, int nBase);
 // engine_core.cpp: DSPCore's routing of one block (conv / EQ in the configured order, output filter, makeup)
 int enqueueBoth(cpq_engine* e, const double* a, double* b, int n);
+// the whole-chain call behind cpq_engine_process_block: oversampling around the routing, then the meters; and its refusals
+int meteredChain(cpq_engine* e, const double* a, double* b, int n);
+int checkBlockCall(cpq_engine* e, const void* in, const void* out, int nSamples);
 // engine_eq.cpp
 void syncEqBypass(cpq_engine* e);
 int enqueueEq(cpq_engine* e, const double* dIn, double* dOut, int n);
@@ -409,10 +417,15 @@ int enqueueOutFilter(cpq_engine* e, const double* dIn, double* dOut, int n);
 // overlap; pageable buffers take the plain upload / kernels / download sequence.
 // factor > 1 (oversampled routing): the caller's nSamples are base-rate samples, checked and partitioned at nSamples * factor,
 // so every chunk is whole internal partitions; body receives base-rate chunk lengths.
-template <typename F>
-int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& body, int factor = 1)
+// What crosses the bus is the Io's business -- fp64 rows (RowsHostIo, viaStaging) or packed PCM (engine_pcm.cpp) -- the cut of
+// the call, the streams and the events are this one loop's: body always sees chunk i at stageIn / stageOut + i * nCh * chunkLen.
+//   hostIn() / hostOut()                         the caller's two buffers (checked, asked for pinnedness)
+//   uploadAll(n) / downloadAll(n)                the whole call, on the engine's stream
+//   uploadChunk(i, len, n) / downloadChunk(..)   time chunk i of len samples per channel, on e->copyIn / e->copyOut
+template <typename Io, typename F>
+int stagedCall(cpq_engine* e, Io& io, int nSamples, F&& body, int factor = 1)
 {
-    int rc = checkCall(e, in, out, nSamples * factor);
+    int rc = checkCall(e, io.hostIn(), io.hostOut(), nSamples * factor);
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipSetDevice(e->device));
     rc = ensureCallBuffer(e, e->stageIn, "upload staging");
@@ -427,12 +440,11 @@ int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& b
     };
     // pageable buffers: the runtime stages every copy and blocks the host, so chunking only adds strided copies
     // (measured 1157 vs 1230 M samples/s); one upload, one download
-    if (e->anyCalls || T < 32 || T % kChunks != 0 || !pinned(in) || !pinned(out)) {
-        const size_t bytes = (size_t)e->nCh * nSamples * sizeof(double);
-        CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, bytes, hipMemcpyHostToDevice, e->stream));
+    if (e->anyCalls || T < 32 || T % kChunks != 0 || !pinned(io.hostIn()) || !pinned(io.hostOut())) {
+        CPQ_TRY(io.uploadAll(e, nSamples));
         rc = body(e->stageIn, e->stageOut, nSamples);
         if (rc != CPQ_OK) return rc;
-        CPQ_HIP(e, hipMemcpyAsync(out, e->stageOut, bytes, hipMemcpyDeviceToHost, e->stream));
+        CPQ_TRY(io.downloadAll(e, nSamples));
         CPQ_HIP(e, hipStreamSynchronize(e->stream));
         return CPQ_OK;
     }
@@ -446,18 +458,14 @@ int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& b
     }
     const int chunkT = T / kChunks;
     const size_t chunkLen = (size_t)chunkT * e->P / factor;              // samples per channel and chunk
-    const size_t hostPitch = (size_t)nSamples * sizeof(double), devPitch = chunkLen * sizeof(double);
     auto download = [&](int i) -> int {
         CPQ_HIP(e, hipStreamWaitEvent(e->copyOut, e->evDone[i], 0));
-        CPQ_HIP(e, hipMemcpy2DAsync(out + i * chunkLen, hostPitch, e->stageOut + (size_t)i * e->nCh * chunkLen, devPitch, devPitch,
-                                    (size_t)e->nCh, hipMemcpyDeviceToHost, e->copyOut));
-        return CPQ_OK;
+        return io.downloadChunk(e, i, chunkLen, nSamples);
     };
     for (int i = 0; i < kChunks; ++i) {
         double* dIn = e->stageIn + (size_t)i * e->nCh * chunkLen;
         double* dOut = e->stageOut + (size_t)i * e->nCh * chunkLen;
-        CPQ_HIP(e, hipMemcpy2DAsync(dIn, devPitch, in + i * chunkLen, hostPitch, devPitch, (size_t)e->nCh, hipMemcpyHostToDevice,
-                                    e->copyIn));
+        CPQ_TRY(io.uploadChunk(e, i, chunkLen, nSamples));
         CPQ_HIP(e, hipEventRecord(e->evIn[i], e->copyIn));
         CPQ_HIP(e, hipStreamWaitEvent(e->stream, e->evIn[i], 0));
         rc = body(dIn, dOut, (int)chunkLen);
@@ -472,5 +480,43 @@ int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& b
     return CPQ_OK;
 }
 
+// fp64 rows [nCh][nSamples] on both sides: the copies land in, and leave from, the staging rows themselves
+struct RowsHostIo {
+    const double* in;
+    double* out;
+    const void* hostIn() const { return in; }
+    const void* hostOut() const { return out; }
+    int uploadAll(cpq_engine* e, int n) const
+    {
+        CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, (size_t)e->nCh * n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        return CPQ_OK;
+    }
+    int downloadAll(cpq_engine* e, int n) const
+    {
+        CPQ_HIP(e, hipMemcpyAsync(out, e->stageOut, (size_t)e->nCh * n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        return CPQ_OK;
+    }
+    int uploadChunk(cpq_engine* e, int i, size_t chunkLen, int n) const
+    {
+        const size_t hostPitch = (size_t)n * sizeof(double), devPitch = chunkLen * sizeof(double);
+        CPQ_HIP(e, hipMemcpy2DAsync(e->stageIn + (size_t)i * e->nCh * chunkLen, devPitch, in + i * chunkLen, hostPitch, devPitch,
+                                    (size_t)e->nCh, hipMemcpyHostToDevice, e->copyIn));
+        return CPQ_OK;
+    }
+    int downloadChunk(cpq_engine* e, int i, size_t chunkLen, int n) const
+    {
+        const size_t hostPitch = (size_t)n * sizeof(double), devPitch = chunkLen * sizeof(double);
+        CPQ_HIP(e, hipMemcpy2DAsync(out + i * chunkLen, hostPitch, e->stageOut + (size_t)i * e->nCh * chunkLen, devPitch, devPitch,
+                                    (size_t)e->nCh, hipMemcpyDeviceToHost, e->copyOut));
+        return CPQ_OK;
+    }
+};
+
+template <typename F>
+int viaStaging(cpq_engine* e, const double* in, double* out, int nSamples, F&& body, int factor = 1)
+{
+    RowsHostIo io{ in, out };
+    return stagedCall(e, io, nSamples, body, factor);
+}
 
 }  // namespace cpqi

@@ -258,4 +258,11 @@ struct MeterFinishArgs {
 };
 void launch_meter_finish(hipStream_t stream, const MeterFinishArgs& a, int nStreams);
 
+// ---- packed PCM converters (pcm_kernels.hip): cpq_pcm_format x cpq_pcm_layout <-> fp64 rows [2 nStreams][n]
+constexpr int kPcmTile = 4096;     // samples of the packed side per workgroup: 4096 of a planar row, 2048 stereo frames
+// pcm aligned to its element (S24: any byte), rows to 8 bytes; sanitizeCb > 0: CPQ_PCM_SANITIZE with callbacks of that many
+// samples (the last one of a row shorter when n is no multiple).  false: no kernel for that format.
+bool launch_pcm_unpack(hipStream_t stream, const void* pcm, int format, int layout, double* rows, int n, int nStreams, int sanitizeCb);
+bool launch_pcm_pack(hipStream_t stream, const double* rows, void* pcm, int format, int layout, int n, int nStreams);
+
 }  // namespace cpq

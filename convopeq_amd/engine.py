@@ -113,6 +113,20 @@ def meter_tp_design_stage(stage):
     return {f: getattr(info, f) for f, _ in K.OsStageInfo._fields_}, taps
 
 
+def pcm_bytes_per_sample(fmt):
+    """cpq_pcm_bytes_per_sample: bytes of one packed sample, -1 for an unknown format."""
+    return K.load().cpq_pcm_bytes_per_sample(int(fmt))
+
+
+def pcm_buffer(fmt, layout, n_streams, n):
+    """An empty host buffer of the packed side of a call: uint8 [n_streams * 2 * n * 3] for S24, else [2 S][n] (planar) or
+    [S][n][2] (interleaved) of the format's own dtype."""
+    if fmt == K.CPQ_PCM_S24:
+        return np.empty(n_streams * 2 * n * 3, dtype=np.uint8)
+    dt = {K.CPQ_PCM_F64: np.float64, K.CPQ_PCM_F32: np.float32, K.CPQ_PCM_S16: np.int16, K.CPQ_PCM_S32: np.int32}[fmt]
+    return np.empty((n_streams, n, 2) if layout == K.CPQ_PCM_INTERLEAVED else (2 * n_streams, n), dtype=dt)
+
+
 def eq_params_default():
     p = K.EqParams()
     K.load().cpq_eq_params_default(C.byref(p))
@@ -402,6 +416,43 @@ class BatchedEngine:
     def process(self, x):
         return self._host(self._lib.cpq_engine_process_block, x)
 
+    # ---- packed PCM in and out: buffers are contiguous numpy arrays of the packed side (pcm_buffer), n samples per channel
+    def _pcm_ptr(self, a, fmt, n):
+        assert a.flags["C_CONTIGUOUS"] and a.nbytes == self.n_channels * n * K.load().cpq_pcm_bytes_per_sample(fmt), "packed buffer size"
+        return C.c_void_p(a.ctypes.data)
+
+    def pcm_unpack(self, pcm, fmt, n, layout=K.CPQ_PCM_PLANAR, flags=0):
+        """cpq_pcm_unpack: packed buffer -> rows [n_channels, n] float64"""
+        rows = np.empty((self.n_channels, n), dtype=np.float64)
+        self._ck(self._lib.cpq_pcm_unpack(self._h, self._pcm_ptr(pcm, fmt, n), fmt, layout, flags, C.c_void_p(rows.ctypes.data), n))
+        return rows
+
+    def pcm_pack(self, rows, fmt, layout=K.CPQ_PCM_PLANAR):
+        """cpq_pcm_pack: rows [n_channels, n] float64 -> packed buffer"""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        assert rows.ndim == 2 and rows.shape[0] == self.n_channels
+        out = pcm_buffer(fmt, layout, self.n_streams, rows.shape[1])
+        self._ck(self._lib.cpq_pcm_pack(self._h, C.c_void_p(rows.ctypes.data), C.c_void_p(out.ctypes.data), fmt, layout, rows.shape[1]))
+        return out
+
+    def pcm_unpack_device(self, d_pcm, fmt, d_rows, n, layout=K.CPQ_PCM_PLANAR, flags=0):
+        self._ck(self._lib.cpq_pcm_unpack_device(self._h, C.c_void_p(d_pcm), fmt, layout, flags, C.c_void_p(d_rows), n))
+
+    def pcm_pack_device(self, d_rows, d_pcm, fmt, n, layout=K.CPQ_PCM_PLANAR):
+        self._ck(self._lib.cpq_pcm_pack_device(self._h, C.c_void_p(d_rows), C.c_void_p(d_pcm), fmt, layout, n))
+
+    def process_pcm(self, x, in_format, out_format, n, layout=K.CPQ_PCM_PLANAR, flags=0, out=None):
+        """cpq_engine_process_block_pcm: the whole chain on a packed buffer; returns the packed result (`out`, or a new buffer)."""
+        if out is None:
+            out = pcm_buffer(out_format, layout, self.n_streams, n)
+        self._ck(self._lib.cpq_engine_process_block_pcm(self._h, self._pcm_ptr(x, in_format, n), in_format,
+                                                        self._pcm_ptr(out, out_format, n), out_format, layout, flags, n))
+        return out
+
+    def process_pcm_device(self, d_in, in_format, d_out, out_format, n, layout=K.CPQ_PCM_PLANAR, flags=0):
+        self._ck(self._lib.cpq_engine_process_block_pcm_device(self._h, C.c_void_p(d_in), in_format, C.c_void_p(d_out), out_format,
+                                                               layout, flags, n))
+
     # ---- device-pointer processing (no sync): raw HBM addresses
     def conv_process_device(self, d_in, d_out, n_samples):
         self._ck(self._lib.cpq_conv_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_samples))
@@ -425,8 +476,8 @@ class BatchedEngine:
             n = C.c_int64()
             ms = C.c_double()
             self._ck(self._lib.cpq_profile_read(self._h, kid, C.byref(n), C.byref(ms)))
-            if name in ("k_os_halfband", "k_meter") and n.value == 0:
-                continue        # listed only for engines that oversample / meter
+            if name in ("k_os_halfband", "k_meter", "k_pcm") and n.value == 0:
+                continue        # listed only for engines that oversample / meter / take packed PCM
             out[name] = (n.value, ms.value)
         return out
 

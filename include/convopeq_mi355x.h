@@ -29,6 +29,8 @@ extern "C" {
 #endif
 
 #define CPQ_ABI_VERSION 2
+/* additions that leave every earlier entry point as it was count here: 1 = the packed PCM entry points */
+#define CPQ_ABI_REVISION 1
 
 typedef enum {
     CPQ_OK               =  0,
@@ -178,6 +180,7 @@ typedef struct cpq_engine cpq_engine;
 
 /* ------------------------------------------------------------------ library */
 int32_t     cpq_abi_version(void);
+int32_t     cpq_abi_revision(void);
 const char* cpq_status_string(int32_t status);
 /* last error text of this handle (or of the last failed create when e == NULL) */
 const char* cpq_last_error(const cpq_engine* e);
@@ -544,6 +547,51 @@ int32_t cpq_meter_process_device(cpq_engine* e, const double* d_in, int32_t n_sa
  * last read (either may be NULL).  CPQ_ERR_NOT_READY while metering is off. */
 int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t max_blocks, int32_t* n_blocks, int64_t* n_dropped);
 
+/* ------------------------------------------------------- packed PCM in and out */
+/* The whole-chain call with a converter at each end: float32 or integer PCM, planar or interleaved, instead of fp64 rows.
+ * What the reference does around its chain in float (DSPCore::processInput -> convertFloatToDoubleHighQuality,
+ * src/InputBitDepthTransform.h:102-121; processOutput's final static_cast<float>,
+ * src/audioengine/AudioEngine.Processing.DSPCoreIO.cpp:532-537) and what a file reader does before it.  All conversions are exact
+ * statements, there is no tolerance:
+ *   in,  F32          (double)x
+ *   in,  S16/S24/S32  the JUCE reader's convention, as cpq_ir_load_wav decodes: left-justified to 32 bits, converted to float
+ *                     (round to nearest), times 1.0f / (float)0x7fffffff (= 2^-31) in float arithmetic, widened to double.
+ *                     S16 and S24 are therefore exact; S32 is rounded to 24 significant bits, as the reference's reader does.
+ *   in,  F64          a copy (planar) or a de-interleave
+ *   CPQ_PCM_SANITIZE  input_transform::applyHighQuality64BitTransform(gain = 1) on the widened input, per callback of
+ *                     block_size / oversampling factor base-rate samples (the ragged last chunk of a CPQ_CALLS_ANY call is a
+ *                     callback of its own length): NaN and |v| < 1e-20 become +0.0, the rest is clamped to [-1, 1]; an infinity
+ *                     clamps to +-1 in the 4-wide body of a callback and becomes 0 in its scalar tail, the last len % 4 samples.
+ *                     Without the flag the widened value goes in untouched, as the fp64 entry point takes it.
+ *   out, F32          static_cast<float>: round to nearest even, overflow to +-inf, NaN stays NaN
+ *   out, S24/S32      rint(x * 2^(b-1)), ties to even, saturated to [-2^(b-1), 2^(b-1) - 1], NaN -> 0; S24 as three
+ *                     little-endian bytes
+ *   out, F64          a copy or an interleave
+ *   out, S16          CPQ_ERR_UNSUPPORTED: a 16-bit result wants the dither stage, which this engine does not have
+ * Packed buffers are aligned to their element (S24: any byte), fp64 rows to 8 bytes; the buffers of
+ * cpq_engine_process_block_pcm[_device] to 16 bytes like those of cpq_engine_process_block.  No byte outside
+ * [base, base + bytes) of a buffer is read or written. */
+typedef enum { CPQ_PCM_F64 = 0, CPQ_PCM_F32 = 1, CPQ_PCM_S16 = 2, CPQ_PCM_S24 = 3 /* packed, 3 bytes, LE */, CPQ_PCM_S32 = 4 } cpq_pcm_format;
+typedef enum { CPQ_PCM_PLANAR = 0      /* [2 S][n], the existing row order */,
+               CPQ_PCM_INTERLEAVED = 1 /* [S][n][2]: stereo frames per stream, as in a file */ } cpq_pcm_layout;
+#define CPQ_PCM_SANITIZE 1u   /* flags bit */
+
+int32_t cpq_pcm_bytes_per_sample(int32_t format);                 /* host only; -1 for an unknown format */
+/* The converters alone on caller buffers (host pointers; _device: device pointers, enqueued on the engine's stream, no
+ * synchronisation): pcm -> rows [2 S][n] and rows -> pcm.  n is 1 .. block_size * max_blocks_per_call. */
+int32_t cpq_pcm_unpack(cpq_engine* e, const void* pcm, int32_t format, int32_t layout, uint32_t flags, double* rows, int32_t n);
+int32_t cpq_pcm_unpack_device(cpq_engine* e, const void* d_pcm, int32_t format, int32_t layout, uint32_t flags, double* d_rows, int32_t n);
+int32_t cpq_pcm_pack(cpq_engine* e, const double* rows, void* pcm, int32_t format, int32_t layout, int32_t n);
+int32_t cpq_pcm_pack_device(cpq_engine* e, const double* d_rows, void* d_pcm, int32_t format, int32_t layout, int32_t n);
+/* cpq_engine_process_block with the converters around it: the same routing, oversampling and metering (the meters read the
+ * fp64 rows the chain delivered, before packing), the same n_samples rules (base-rate samples on both sides with
+ * oversampling).  in and out may be the same buffer only when in_format == out_format; any other overlap of the two byte
+ * ranges is CPQ_ERR_INVALID_ARG.  Every refusal happens before any state moves or anything is enqueued. */
+int32_t cpq_engine_process_block_pcm(cpq_engine* e, const void* in, int32_t in_format, void* out, int32_t out_format,
+                                     int32_t layout, uint32_t flags, int32_t n_samples);
+int32_t cpq_engine_process_block_pcm_device(cpq_engine* e, const void* d_in, int32_t in_format, void* d_out, int32_t out_format,
+                                            int32_t layout, uint32_t flags, int32_t n_samples);
+
 /* ---------------------------------------------------------------- profiling */
 /* Per-kernel HIP-event timing on the engine's stream (counterpart of the reference's CONV_TIME /
  * EQ_TIME diagnostics, src/convolver/ConvolverProcessor.Runtime.cpp:679-721). */
@@ -558,7 +606,8 @@ typedef enum {
     CPQ_K_OUTFILT  = 7,   /* output-filter biquad cascade (k_svf_cascade_tp / k_svf_cascade running DF-II-T sections) */
     CPQ_K_OS       = 8,   /* half-band oversampler stages, up and down (k_os_interp / k_os_decim and their helpers) */
     CPQ_K_METER    = 9,   /* loudness and true-peak meters (k_meter_kweight / k_meter_true_peak / k_meter_finish) */
-    CPQ_K_COUNT    = 10
+    CPQ_K_PCM      = 10,  /* packed PCM converters (k_pcm_unpack / k_pcm_pack) */
+    CPQ_K_COUNT    = 11
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);
 int32_t     cpq_profile_reset(cpq_engine* e);

@@ -226,6 +226,17 @@ public:
         return true;
     }
 
+    // float in, float out, as DSPCore::processInput / processOutput hand the chain its blocks: planar rows
+    // [channel][numSamples] of float32 on both sides (16-byte aligned; the same buffer, or two that do not overlap), widened
+    // and narrowed on the device.  A refused or failed call zeroes `out` and returns false.
+    bool process(const float* in, float* out, int numSamples)
+    {
+        status_ = cpq_engine_process_block_pcm(e_.get(), in, CPQ_PCM_F32, out, CPQ_PCM_F32, CPQ_PCM_PLANAR, 0u, numSamples);
+        if (status_ == CPQ_OK) return true;
+        if (out && numSamples > 0) std::memset(out, 0, sizeof(float) * static_cast<size_t>(e_.channels()) * numSamples);
+        return false;
+    }
+
     int lastStatus() const noexcept { return status_; }
     const char* lastError() const noexcept { return e_.lastError(); }
 
