@@ -161,6 +161,7 @@ const char* cpq_kernel_name(int32_t id)
         case CPQ_K_OS: return "k_os_halfband";
         case CPQ_K_METER: return "k_meter";
         case CPQ_K_PCM: return "k_pcm";
+        case CPQ_K_OUT: return "k_out";
         default: return "?";
     }
 }
@@ -595,6 +596,7 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
         const int rc = refreshMeters(e);
         if (rc != CPQ_OK) return rc;
     }
+    CPQ_TRY(refreshOutStage(e));        // dcBlockers().output*.init / peakLimiter.prepare + reset at the new base rate
     return zeroRuntimeState(e, true, true);
 }
 
@@ -702,11 +704,14 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed)
 
 }  // extern "C"
 
-// the meters read the base-rate rows the call delivers, after everything that writes them (DSPCoreDouble.cpp:695-701)
+// the meters read the base-rate rows the call delivers, after everything that writes them (DSPCoreDouble.cpp:695-701); with
+// the output stage on that is where the reference's meters sit: after the scrub (:665-693), before the limiter (:703-710)
 int cpqi::meteredChain(cpq_engine* e, const double* a, double* b, int n)
 {
     int rc = e->osFactor > 1 ? enqueueOsChain(e, a, b, n) : enqueueBoth(e, a, b, n);
+    if (rc == CPQ_OK) rc = enqueueOutPre(e, b, n, b, n, n);           // each half returns at once when its flags are off
     if (rc == CPQ_OK && e->meterFlags) rc = enqueueMeters(e, b, n, n);
+    if (rc == CPQ_OK) rc = enqueueOutPost(e, b, n, b, n, n);
     return rc;
 }
 

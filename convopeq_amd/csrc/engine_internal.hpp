@@ -4,6 +4,7 @@
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
 //   engine_eq.cpp    EQ and output filter: design, device tables, bypass / band-reset state machine
 //   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
+//   engine_out.cpp   output stage: DC blocker, headroom, limiter and clamp on the delivered rows
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
@@ -309,6 +310,13 @@ struct cpq_engine {
     // every stream sees the same callbacks: one pair of ring counters, one block counter (LockFreeRingBuffer, blockCounter)
     unsigned long long meterWrite = 0, meterRead = 0, meterIndex = 0, meterDropped = 0;
 
+    // output stage (engine_out.cpp): DC blocker, headroom + scrub, limiter, clamp on the base-rate output rows; one group
+    int outFlags = 0;                                   // CPQ_OUT_*; 0 = off
+    cpqi::DeviceBuffer<double> outTab;                  // the two DC sections' tables (kOutSectionDoubles each)
+    cpqi::DeviceBuffer<double> outDc;                   // [nCh][2] one-pole states
+    cpqi::DeviceBuffer<double> outEnv;                  // [streams] limiter envelopes
+    double outRelease = 0.0;                            // SimplePeakLimiter::releaseCoeff at the base rate
+
     // packed PCM entry points (engine_pcm.cpp): the call's packed input and output on the device, one group
     cpqi::DeviceBuffer<char> pcmIn, pcmOut;
     size_t pcmInCap = 0, pcmOutCap = 0;
@@ -401,9 +409,16 @@ constexpr int kMeterRing = 4096;                // LockFreeRingBuffer<BlockPower
 int refreshMeters(cpq_engine* e);               // redesign for the present base rate and reset; nothing while metering is off
 int checkMeterCall(cpq_engine* e, int nBase);   // the refusals, before anything is enqueued
 int enqueueMeters(cpq_engine* e, const double* rows, int64_t stride, int nBase);
+// engine_out.cpp
+int refreshOutStage(cpq_engine* e);             // redesign for the present base rate and reset; nothing while the stage is off
+// the steps before the meters (DC blocker, headroom + scrub) and after them (limiter, clamp); in == out allowed.  A half whose
+// flags are off launches nothing and leaves out untouched
+int enqueueOutPre(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
+int enqueueOutPost(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
 // engine_core.cpp: DSPCore's routing of one block (conv / EQ in the configured order, output filter, makeup)
 int enqueueBoth(cpq_engine* e, const double* a, double* b, int n);
-// the whole-chain call behind cpq_engine_process_block: oversampling around the routing, then the meters; and its refusals
+// the whole-chain call behind cpq_engine_process_block: oversampling around the routing, then the output stage with the meters
+// between its two halves; and its refusals
 int meteredChain(cpq_engine* e, const double* a, double* b, int n);
 int checkBlockCall(cpq_engine* e, const void* in, const void* out, int nSamples);
 // engine_eq.cpp

@@ -55,5 +55,26 @@ constexpr int kMeterScanSteps = 7;      // powers M^(chunk * 2^k): k < 6 the sca
 constexpr int kMeterSectionDoubles = 8 + 4 * kMeterScanSteps + 4 * 64;
 void   meterSectionTables(const double coef[5], double* out);
 int    osStagesFor(int factor);     // 1/2/4/8 -> 0/1/2/3 stages, else -1
+// output stage (out_design.cpp): the base-rate steps of DSPCore::processOutputDouble with dither off
+constexpr double kOutHeadroom = 0.8912509381337456;             // kOutputHeadroom, -1 dBFS
+constexpr double kOutLimiterThreshold = 0.8413951287507587;     // kPLThreshold
+constexpr double kOutLimiterKnee = 0.108748;                    // kPLKnee
+void   outDesign(double fs, double alpha[2], double* releaseCoeff);     // UltraHighRateDCBlocker::init(fs, 3), SimplePeakLimiter::prepare(fs, 100)
+constexpr int kOutChunk = 8;            // samples a lane of the DC kernel holds
+constexpr int kOutScanSteps = 7;        // powers a^(chunk * 2^k): k < 6 the scan inside a wave, k = 6 one whole wave
+// per one-pole section: {alpha, a^(chunk * 2^k) for k < 7, a^(chunk * lane) for lane < 64}, a = 1 - alpha, in long double
+constexpr int kOutSectionDoubles = 1 + kOutScanSteps + 64;
+void   outSectionTable(double alpha, double* out);
+double outDesiredGain(double l, double r);      // SimplePeakLimiter's desiredGain of one stereo sample
+double outClamp(double v);
+// one stream of the stage, sequential, in the reference's operation order; a call of process() is one callback
+struct OutStageHost {
+    double alpha[2] = { 1.0e-6, 1.0e-6 }, releaseCoeff = 0.0;
+    double dc[2][2] = { { 0.0, 0.0 }, { 0.0, 0.0 } };       // [channel][section]
+    double envelope = 1.0;
+    void prepare(double fs);
+    void reset();
+    void process(double* l, double* r, int n, int flags);   // flags: CPQ_OUT_*
+};
 
 }  // namespace cpq

@@ -258,6 +258,15 @@ struct MeterFinishArgs {
 };
 void launch_meter_finish(hipStream_t stream, const MeterFinishArgs& a, int nStreams);
 
+// ---- output stage (out_kernels.hip): DSPCore::processOutputDouble's base-rate steps on rows [nCh][n]; in and out may be the same
+// DC blocker (tab = two sections of kOutSectionDoubles, dcState [nCh][2] carried across calls, cb = callback length: the state
+// guards sit at the callback ends) and / or the headroom multiply with the scrub; nothing is launched when both are off
+void launch_out_pre(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int cb, int nCh,
+                    bool dcBlock, bool headroom, const double* tab, double* dcState);
+// SimplePeakLimiter (env [nStreams] carried across calls) and / or the clamp; nothing is launched when both are off
+void launch_out_post(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nStreams,
+                     bool limiter, bool clamp, double release, double* env);
+
 // ---- packed PCM converters (pcm_kernels.hip): cpq_pcm_format x cpq_pcm_layout <-> fp64 rows [2 nStreams][n]
 constexpr int kPcmTile = 4096;     // samples of the packed side per workgroup: 4096 of a planar row, 2048 stereo frames
 // pcm aligned to its element (S24: any byte), rows to 8 bytes; sanitizeCb > 0: CPQ_PCM_SANITIZE with callbacks of that many

@@ -113,6 +113,15 @@ def meter_tp_design_stage(stage):
     return {f: getattr(info, f) for f, _ in K.OsStageInfo._fields_}, taps
 
 
+def out_design(rate):
+    """cpq_out_design: (alpha float64[2] of the output DC blocker's sections, the limiter's release coefficient) at `rate`."""
+    alpha, rel = np.empty(2), C.c_double()
+    rc = K.load().cpq_out_design(float(rate), _dp(alpha), C.byref(rel))
+    if rc != 0:
+        raise CpqError(rc, "cpq_out_design")
+    return alpha, rel.value
+
+
 def pcm_bytes_per_sample(fmt):
     """cpq_pcm_bytes_per_sample: bytes of one packed sample, -1 for an unknown format."""
     return K.load().cpq_pcm_bytes_per_sample(int(fmt))
@@ -399,6 +408,25 @@ class BatchedEngine:
         rec = np.frombuffer(buf, dtype=dt).reshape(self.n_streams, max_blocks)[:, :n.value].copy()
         return rec, dropped.value
 
+    # ---- output stage (DC blocker, headroom + scrub, limiter, clamp on the base-rate rows)
+    def set_output_stage(self, flags):
+        self._ck(self._lib.cpq_engine_set_output_stage(self._h, int(flags)))
+
+    def out_reset(self):
+        self._ck(self._lib.cpq_out_reset(self._h))
+
+    def out_process(self, x):
+        """The stage alone on rows [n_channels, n], as the engine's output would pass it."""
+        return self._host(self._lib.cpq_out_process, x)
+
+    def out_process_device(self, d_in, d_out, n_samples):
+        self._ck(self._lib.cpq_out_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_samples))
+
+    def out_read_envelope(self, stream):
+        v = C.c_double()
+        self._ck(self._lib.cpq_out_read_envelope(self._h, int(stream), C.byref(v)))
+        return v.value
+
     # ---- host-buffer processing: x is [n_channels, n_samples] float64
     def _host(self, fn, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -476,8 +504,8 @@ class BatchedEngine:
             n = C.c_int64()
             ms = C.c_double()
             self._ck(self._lib.cpq_profile_read(self._h, kid, C.byref(n), C.byref(ms)))
-            if name in ("k_os_halfband", "k_meter", "k_pcm") and n.value == 0:
-                continue        # listed only for engines that oversample / meter / take packed PCM
+            if name in ("k_os_halfband", "k_meter", "k_pcm", "k_out") and n.value == 0:
+                continue        # listed only for engines that oversample / meter / take packed PCM / run the output stage
             out[name] = (n.value, ms.value)
         return out
 

@@ -31,6 +31,10 @@ extern "C" {
 #define CPQ_ABI_VERSION 2
 /* additions that leave every earlier entry point as it was count here: 1 = the packed PCM entry points */
 #define CPQ_ABI_REVISION 1
+/* later additions announce themselves at compile time: defined when the output stage entry points
+ * (cpq_engine_set_output_stage, cpq_out_*) exist.  cpq_abi_revision() does not count them, so at run time a caller that may
+ * meet an older library finds out by looking the symbol up (dlsym) */
+#define CPQ_HAS_OUTPUT_STAGE 1
 
 typedef enum {
     CPQ_OK               =  0,
@@ -547,6 +551,47 @@ int32_t cpq_meter_process_device(cpq_engine* e, const double* d_in, int32_t n_sa
  * last read (either may be NULL).  CPQ_ERR_NOT_READY while metering is off. */
 int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t max_blocks, int32_t* n_blocks, int64_t* n_dropped);
 
+/* ---------------------------------------------------------------- output stage */
+/* The base-rate steps DSPCore::processOutputDouble runs on the chain's result when dither is off
+ * (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:577-744), in its order:
+ *   CPQ_OUT_DC_BLOCK   the 3 Hz output UltraHighRateDCBlocker (src/UltraHighRateDCBlocker.h): two one-pole sections at 2.7 and
+ *                      3.3 Hz, s += alpha (x - s), x -= s; at the end of every callback a state that is not finite or not below
+ *                      1e15 becomes 0
+ *   CPQ_OUT_HEADROOM   x *= 0.8912509381337456 (kOutputHeadroom, -1 dBFS), then the scrub: not finite or |x| >= 1e300 becomes 0,
+ *                      written into the delivered rows
+ *   CPQ_OUT_LIMITER    SimplePeakLimiter (src/audioengine/SimplePeakLimiter.h): threshold 0.8413951287507587, knee 0.108748,
+ *                      release 100 ms, one envelope per stream carried across callbacks and calls
+ *   CPQ_OUT_CLAMP      min(max(x, -0.8912509381337456), 0.8912509381337456) as the reference's 4-wide body computes it (a NaN,
+ *                      which only a stage without CPQ_OUT_HEADROOM can meet, becomes the lower limit)
+ * The stage runs on the base-rate rows at the end of cpq_engine_process_block[_device] and of the PCM calls: after the
+ * oversampler's down stages, before the pack, one callback = block_size / factor samples (the ragged last chunk of a
+ * CPQ_CALLS_ANY call is a callback of its own length).  With the stage on the meters read where the reference's do: after the
+ * scrub, before the limiter.  Not built: dither and the noise shapers, the soft clipper, the fade-in, the fixed latency delay. */
+#define CPQ_OUT_DC_BLOCK 1
+#define CPQ_OUT_HEADROOM 2
+#define CPQ_OUT_LIMITER  4
+#define CPQ_OUT_CLAMP    8
+#define CPQ_OUT_ALL      15
+
+/* UltraHighRateDCBlocker::init(rate, 3.0) -> alpha[2] and SimplePeakLimiter::prepare(rate, 100.0) -> *release_coeff, with the
+ * reference's fallbacks for a rate that is not positive and finite (alpha 1e-6, release 0).  Host only. */
+int32_t cpq_out_design(double rate, double alpha[2], double* release_coeff);
+/* flags: 0 = off (the default: the rows leave the engine as they always did), or CPQ_OUT_* bits; any other bit is
+ * CPQ_ERR_INVALID_ARG.  Applies to every stream.  The coefficients are designed for the base rate sample_rate / factor;
+ * cpq_engine_prepare, cpq_engine_set_oversampling and any change of the flags redesign them, clear the DC states and set the
+ * envelopes to 1.0. */
+int32_t cpq_engine_set_output_stage(cpq_engine* e, int32_t flags);
+/* DC states to 0, envelopes to 1.0.  CPQ_ERR_NOT_READY while the stage is off (so for the four calls below). */
+int32_t cpq_out_reset(cpq_engine* e);
+/* The stage alone on caller rows [channel][n_samples], exactly as the engine's output would pass it (the meters are not run):
+ * n_samples is 1 .. block_size * max_blocks_per_call / factor, whole callbacks unless the engine takes CPQ_CALLS_ANY.  in and
+ * out may be the same buffer.  _device: device pointers, enqueued on the engine's stream, no synchronisation.  Every refusal
+ * happens before any state moves. */
+int32_t cpq_out_process(cpq_engine* e, const double* in, double* out, int32_t n_samples);
+int32_t cpq_out_process_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_samples);
+/* synchronises the engine's stream; *envelope = the limiter's envelope of one stream */
+int32_t cpq_out_read_envelope(cpq_engine* e, int32_t stream, double* envelope);
+
 /* ------------------------------------------------------- packed PCM in and out */
 /* The whole-chain call with a converter at each end: float32 or integer PCM, planar or interleaved, instead of fp64 rows.
  * What the reference does around its chain in float (DSPCore::processInput -> convertFloatToDoubleHighQuality,
@@ -607,7 +652,8 @@ typedef enum {
     CPQ_K_OS       = 8,   /* half-band oversampler stages, up and down (k_os_interp / k_os_decim and their helpers) */
     CPQ_K_METER    = 9,   /* loudness and true-peak meters (k_meter_kweight / k_meter_true_peak / k_meter_finish) */
     CPQ_K_PCM      = 10,  /* packed PCM converters (k_pcm_unpack / k_pcm_pack) */
-    CPQ_K_COUNT    = 11
+    CPQ_K_OUT      = 11,  /* output stage (k_out_pre / k_out_headroom / k_out_post) */
+    CPQ_K_COUNT    = 12
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);
 int32_t     cpq_profile_reset(cpq_engine* e);

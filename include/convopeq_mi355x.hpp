@@ -6,6 +6,7 @@
 //        <- convo::MKLNonUniformConvolver (src/MKLNonUniformConvolver.h:197-242), one instance per mono channel
 //           in the reference, here one object for every channel of every stream
 //   cpq::BatchedMeters      ::prepare / processBlock / readBlocks / reset          <- LoudnessMeter + TruePeakDetector (src/LoudnessMeter.h, src/TruePeakDetector.h)
+//   cpq::BatchedOutputStage ::prepare / process / envelope / reset                 <- DSPCore::processOutputDouble, dither off
 //   cpq::BatchedOversampler ::prepare / processUp / processDown / reset   <- CustomInputOversampler (src/CustomInputOversampler.h)
 //   cpq::BatchedProcessor  ::prepareToPlay / process / setEqParameters / loadImpulse
 //        <- ConvolverProcessor::{prepareToPlay,process} (src/ConvolverProcessor.h:226,259) and
@@ -334,6 +335,44 @@ public:
         return status_ == CPQ_OK ? n : -1;
     }
     void reset() { status_ = cpq_meter_reset(e_.get()); }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return e_.lastError(); }
+
+private:
+    Engine& e_;
+    std::vector<double> scratch_;
+    int status_ = CPQ_OK;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// DSPCore's output stage (processOutputDouble with dither off: DC blocker, headroom + scrub, SimplePeakLimiter, clamp) for
+// every stream of an engine.  Once prepared, cpq_engine_process_block passes its own output through it; process runs it on
+// caller blocks, in place, without the chain.
+class BatchedOutputStage {
+public:
+    explicit BatchedOutputStage(Engine& e) : e_(e) {}
+    // flags: CPQ_OUT_* bits; 0 switches the stage off
+    bool prepare(int flags = CPQ_OUT_ALL) { return (status_ = cpq_engine_set_output_stage(e_.get(), flags)) == CPQ_OK; }
+    bool process(AudioBlockBatch& io)
+    {
+        if (io.numChannels != e_.channels() || io.numSamples <= 0) { status_ = CPQ_ERR_INVALID_ARG; return false; }
+        scratch_.resize(static_cast<size_t>(e_.channels()) * io.numSamples);
+        for (int c = 0; c < io.numChannels; ++c)
+            std::memcpy(scratch_.data() + static_cast<size_t>(c) * io.numSamples, io.channels[c], sizeof(double) * io.numSamples);
+        status_ = cpq_out_process(e_.get(), scratch_.data(), scratch_.data(), io.numSamples);
+        if (status_ != CPQ_OK) return false;
+        for (int c = 0; c < io.numChannels; ++c)
+            std::memcpy(io.channels[c], scratch_.data() + static_cast<size_t>(c) * io.numSamples, sizeof(double) * io.numSamples);
+        return true;
+    }
+    // SimplePeakLimiter::getCurrentEnvelope of one stream; 1.0 when it cannot be read
+    double envelope(int stream)
+    {
+        double v = 1.0;
+        status_ = cpq_out_read_envelope(e_.get(), stream, &v);
+        return v;
+    }
+    void reset() { status_ = cpq_out_reset(e_.get()); }
     int lastStatus() const noexcept { return status_; }
     const char* lastError() const noexcept { return e_.lastError(); }
 
