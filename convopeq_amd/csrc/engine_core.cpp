@@ -186,6 +186,15 @@ int32_t cpq_diag_eq_chain_status(cpq_engine* e, uint32_t* launches, uint32_t* ga
 
 int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* in, double* spectra, double* out)
 {
+    return cpq_diag_partition_fft_split(P, nCh, T, 0, in, spectra, out);
+}
+
+// split > 0 at P = 4096: that many workgroups walk the frames of a channel (at most one per frame), so that a small test decides
+// how many consecutive frames one workgroup transforms; otherwise the launchers' own choice
+int32_t cpq_diag_partition_fft_split(int32_t P, int32_t nCh, int32_t T, int32_t split, const double* in, double* spectra, double* out)
+{
+    if (P != 4096 || split < 0) split = 0;
+    if (split > T) return CPQ_ERR_INVALID_ARG;
     if (P < 64 || P > 131072 || (P & (P - 1)) || nCh <= 0 || T <= 0 || !in || !spectra || !out) return CPQ_ERR_INVALID_ARG;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) { (void)hipGetLastError(); return CPQ_ERR_NO_DEVICE; }
@@ -218,11 +227,11 @@ int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* 
     }
     if (rc == CPQ_OK) {
         const cpq::FftTables tw{ dTw, dTw2, P > 4096 ? dTw + P : nullptr, P > 4096 ? dTw2 + P : nullptr };
-        cpq::launch_rfft_fwd_ols(nullptr, dIn, (int64_t)T * P, dHist, dHist + (size_t)nCh * P, dX, dXdn, tw, P, nCh, T, 0, ringSlots, dScratch);
+        cpq::launch_rfft_fwd_ols(nullptr, dIn, (int64_t)T * P, dHist, dHist + (size_t)nCh * P, dX, dXdn, tw, P, nCh, T, 0, ringSlots, dScratch, split);
         // the ring holds block t of channel c at [c][t] of ringSlots slots: [c][t] of T slots for the inverse and the caller
         for (int c = 0; c < nCh && rc == CPQ_OK; ++c)
             ok(hipMemcpyAsync(dY + (size_t)c * T * P, dX + (size_t)c * ringSlots * P, (size_t)T * P * sizeof(double2), hipMemcpyDeviceToDevice, nullptr));
-        cpq::launch_rfft_inv_ols(nullptr, dY, dOut, (int64_t)T * P, tw, P, nCh, T, dScratch);
+        cpq::launch_rfft_inv_ols(nullptr, dY, dOut, (int64_t)T * P, tw, P, nCh, T, dScratch, split);
         ok(hipGetLastError());
         ok(hipDeviceSynchronize());
     }

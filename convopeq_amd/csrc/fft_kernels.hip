@@ -664,6 +664,8 @@ __global__ __launch_bounds__(512) void k_rfft_inv_ols_wg(const double2* __restri
 // Twiddles never come from global memory inside the loop: W4096^(j k1) factors over the octal digits of j into entries of
 // three 8 x 8 tables in LDS (3 KB, filled once per workgroup from the engine's extended-precision table; the first two
 // are also the tables of the wave-level transform), the split twiddle is one per-thread constant times W16^r.
+// Loading frame t + 1 while frame t computes (16 more registers forward, 32 inverse) was built and measured: no gain in
+// either kernel, the CU's second workgroup already covers the loads (RESULTS.md, tools/variants/fft_p4_prefetch.patch).
 constexpr int kP4 = 4096;
 constexpr int kP4Row = kLdsPerWave;     // 576: row stride of the exchange buffer = one wave's scratch slice
 
@@ -1173,7 +1175,7 @@ static int genericThreads(int P) { return P / 2 < 64 ? 64 : (P / 2 > 256 ? 256 :
 
 void launch_rfft_fwd_ols(hipStream_t stream, const double* in, int64_t chStride, const double* histOld,
                          double* histNew, double2* X, double2* XDN, FftTables tw, int P, int nCh, int T, int head,
-                         int ringSlots, double2* scratch)
+                         int ringSlots, double2* scratch, int forceSplit)
 {
     if (P > 4096) {         // four-step: column pass into scratch [nCh * T][P], then row pass + split into the FDL ring
         const int M1 = P >> 9;
@@ -1187,7 +1189,7 @@ void launch_rfft_fwd_ols(hipStream_t stream, const double* in, int64_t chStride,
         hipLaunchKernelGGL(k_rfft_fwd_ols<false>, dim3(nCh * T), dim3(64), 0, stream, in, chStride, histOld, histNew, X, XDN,
                            tw, T, head, ringSlots - 1, FwdSide{});
     else if (P == kP4) {
-        const int split = p4Split(nCh, T);
+        const int split = forceSplit > 0 ? forceSplit : p4Split(nCh, T);
         allowLargeLds(k_rfft_fwd_ols_p4, wgLdsBytes(P));
         hipLaunchKernelGGL(k_rfft_fwd_ols_p4, dim3(nCh * split), dim3(512), wgLdsBytes(P), stream, in, chStride, histOld,
                            histNew, X, XDN, tw, T, split, head, ringSlots - 1);
@@ -1254,7 +1256,7 @@ void launch_spectrum_gain(hipStream_t stream, double2* H, double2* HDN, const do
 namespace {
 template <int MODE>
 void launch_inv(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw, int P, int nCh, int T,
-                double2* scratch, OutSpec ro)
+                double2* scratch, OutSpec ro, int forceSplit = 0)
 {
     if (P > 4096) {         // scratch [nCh * T][P]
         const int M1 = P >> 9;
@@ -1266,7 +1268,7 @@ void launch_inv(hipStream_t stream, const double2* Y, double* out, int64_t chStr
     if (P == kP)
         hipLaunchKernelGGL(k_rfft_inv_ols<MODE>, dim3(nCh * T), dim3(64), 0, stream, Y, out, chStride, tw, T, ro);
     else if (P == kP4) {
-        const int split = p4Split(nCh, T);
+        const int split = forceSplit > 0 ? forceSplit : p4Split(nCh, T);
         allowLargeLds(k_rfft_inv_ols_p4<MODE>, wgLdsBytes(P));
         hipLaunchKernelGGL(k_rfft_inv_ols_p4<MODE>, dim3(nCh * split), dim3(512), wgLdsBytes(P), stream, Y, out, chStride, tw, T,
                            split, ro);
@@ -1281,9 +1283,9 @@ void launch_inv(hipStream_t stream, const double2* Y, double* out, int64_t chStr
 }  // namespace
 
 void launch_rfft_inv_ols(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw, int P,
-                         int nCh, int T, double2* scratch)
+                         int nCh, int T, double2* scratch, int forceSplit)
 {
-    launch_inv<0>(stream, Y, out, chStride, tw, P, nCh, T, scratch, OutSpec{});
+    launch_inv<0>(stream, Y, out, chStride, tw, P, nCh, T, scratch, OutSpec{}, forceSplit);
 }
 
 void launch_rfft_inv_ols_add(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw, int nCh, int T,

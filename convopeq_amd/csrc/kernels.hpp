@@ -28,9 +28,10 @@ void fill_big_twiddles(const double2* tw512, const double2* tw1024, int P, doubl
 
 // Overlap-save framing + 1024-point real FFT of T blocks per channel into the frequency-domain delay
 // line (FDL) ring; also saves the last block as the next call's overlap history.
+// forceSplit > 0 (P = 4096 only, the diagnostic entry): that many workgroups walk a channel's frames instead of the launcher's choice
 void launch_rfft_fwd_ols(hipStream_t stream, const double* in, int64_t chStride, const double* histOld,
                          double* histNew, double2* X, double2* XDN, FftTables tw, int P, int nCh, int T,
-                         int head, int ringSlots, double2* scratch = nullptr);
+                         int head, int ringSlots, double2* scratch = nullptr, int forceSplit = 0);
 
 // P = 512 only (rfft_fwd_can_carry_side): the same launch also copies every block into up to two other accumulators
 // (dst[a] + channel * dstStride[a] + dstOff[a], offsets even) and stores a table of <= kGatherTabMax entries to tabDst -- a plan
@@ -86,8 +87,9 @@ void launch_fdl_mac_dcnyq(hipStream_t stream, const double2* XDN, const double2*
 // inverse 1024-point real FFT of Y, scaled 1/N, second half (P samples) to out.
 // P > 4096 (8192 ... 131072): four-step transforms through `scratch` ([transforms][P] double2); the spectra are
 // then stored permuted (element k1 * 512 + k2 = bin k1 + (P / 512) k2), consistently in all three launchers.
+// forceSplit: as in launch_rfft_fwd_ols.
 void launch_rfft_inv_ols(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw,
-                         int P, int nCh, int T, double2* scratch = nullptr);
+                         int P, int nCh, int T, double2* scratch = nullptr, int forceSplit = 0);
 // The same transform with its result stored straight into per-channel rings: block t of channel c at ring[c][(p_t + i) &
 // (ringSize - 1)], p_t = pos[t] (device table; negative: the block is dropped) or pos0 + t P when pos is null -- the
 // output-ring / delay-line write of a plan-group layer without the pass over the blocks in between.

@@ -672,6 +672,12 @@ const char* cpq_kernel_name(int32_t kernel_id);
  * Needs a gfx950 device; no engine.  For tests of the FFT kernel families in isolation. */
 int32_t     cpq_diag_partition_fft(int32_t partition, int32_t n_channels, int32_t n_blocks, const double* in,
                                    double* spectra, double* out);
+/* The same with the work split of the partition = 4096 kernels chosen by the caller: `split` workgroups (1 ... n_blocks) walk
+ * the blocks of a channel, each a contiguous range of ceil(n_blocks / split) blocks (the last ranges may be shorter or empty),
+ * so that a small test decides how many consecutive frames one workgroup transforms.  split <= 0 or partition != 4096: the
+ * engine's own choice, i.e. cpq_diag_partition_fft.  The results do not depend on split. */
+int32_t     cpq_diag_partition_fft_split(int32_t partition, int32_t n_channels, int32_t n_blocks, int32_t split,
+                                         const double* in, double* spectra, double* out);
 /* The FDL multiply-accumulate on its own (what replaces the per-partition accumulateSplitComplex loop,
  * src/MKLNonUniformConvolver.cpp:150-195): exactly the launches an engine makes for one call, on buffers the caller fills.
  *   y[c][t][b] = sum_{k < k_parts} x[c][(head + t - k) & (ring_slots - 1)][b] * h[ir_slot[c]][k][b]     (complex, b >= 1)
