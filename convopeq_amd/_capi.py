@@ -236,6 +236,13 @@ SYMBOLS = {
     "cpq_diag_partition_fft": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "cpq_diag_partition_fft_split": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "cpq_diag_fdl_mac": (C.c_int32, [C.c_int32] * 10 + [c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, C.POINTER(C.c_int32)]),
+    "cpq_diag_fft_forward": (C.c_int32, [C.c_int32] * 6 + [c_double_p, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         C.POINTER(C.c_int64), c_double_p]),
+    "cpq_diag_fft_inverse_store": (C.c_int32, [C.c_int32] * 4 + [c_double_p, c_double_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, c_double_p,
+                                               C.c_int32, C.POINTER(C.c_int64), c_double_p, c_double_p, C.c_int32, C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_double, C.c_double, c_double_p]),
+    "cpq_diag_ir_spectra": (C.c_int32, [C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "cpq_diag_eq_chain_status": (C.c_int32, [_E, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "cpq_kernel_name": (C.c_char_p, [C.c_int32]),
 }

@@ -698,6 +698,63 @@ int32_t     cpq_diag_partition_fft_split(int32_t partition, int32_t n_channels, 
 int32_t     cpq_diag_fdl_mac(int32_t partition, int32_t n_channels, int32_t k_parts, int32_t n_blocks, int32_t tile,
                              int32_t head, int32_t ring_slots, int32_t n_ir_slots, int32_t h_rows, int32_t h_private,
                              const double* x, const double* h, const int32_t* ir_slot, double* y, int32_t* variant_used);
+/* The launch variants of the partition transforms on their own (tests/test_gpu_fft_variants.py): the launches an engine makes
+ * around cpq_diag_partition_fft's plain rows -- a moving ring head and a carried history, the side copies of the 512-sample
+ * forward transform, the three store modes of the inverse transform, the IR spectra and their spectral gain.  All pointers are
+ * host memory; spectra are in the storage order described at cpq_diag_partition_fft.  Every buffer a kernel may write is
+ * filled with 0xFF bytes (NaN; -1 in the table) before the launch, unless the caller supplies its contents, and is returned
+ * whole, so that what a launch leaves alone can be told from what it stores.  Each entry returns CPQ_ERR_INVALID_ARG, before
+ * anything is allocated or launched (and before a device is looked for), for every argument set with which a kernel would read
+ * or write outside a buffer or a launcher's precondition would not hold.  "partition" below: a power of two in 64 ... 131072;
+ * no buffer may exceed 2^28 elements.  Need a gfx950 device; no engine.
+ *
+ * Forward (launch_rfft_fwd_ols; side != 0: launch_rfft_fwd_ols_side).  in: [n_channels][n_blocks * partition + tail_len] (the
+ * device rows are padded to an even length), hist_old: [n_channels][partition], the block in front of block 0.  Block t of
+ * channel c is transformed as the frame [block t - 1 | block t] into slot (head + t) & (ring_slots - 1) of
+ * ring: [n_channels][ring_slots][partition][2]; xdn: [n_channels][ring_slots][2] receives element 0 of every slot written;
+ * hist_new: [n_channels][partition] the last block.
+ *   side != 0 also: n_side <= 2 destinations side_out0 / side_out1: [n_channels][side_stride[a]], block t of channel c copied
+ *   to [c][side_off[a] + t * partition ...); tab_out: [64] receives tab[0 .. n_tab); tail_out: [n_channels][tail_stride] receives
+ *   the tail_len samples behind the blocks of every input row.
+ * Refused unless: n_channels, n_blocks >= 1; ring_slots a power of two >= n_blocks; 0 <= head < ring_slots; side == 0:
+ * tail_len == 0; side != 0: partition == 512, 0 <= n_side <= 2, side_stride[a] and side_off[a] even (the launcher's
+ * rfft_fwd_can_carry_side), 0 <= side_off[a], side_off[a] + n_blocks * partition <= side_stride[a], 0 <= n_tab <= 64,
+ * 0 <= tail_len <= tail_stride, tail_stride >= 1, every pointer that is used non-null. */
+int32_t     cpq_diag_fft_forward(int32_t partition, int32_t n_channels, int32_t n_blocks, int32_t head, int32_t ring_slots,
+                                 int32_t tail_len, const double* in, const double* hist_old, int32_t side, int32_t n_side,
+                                 const int64_t* side_stride, const int64_t* side_off, const int64_t* tab, int32_t n_tab,
+                                 int32_t tail_stride, double* ring, double* xdn, double* hist_new, double* side_out0,
+                                 double* side_out1, int64_t* tab_out, double* tail_out);
+/* Inverse transform of spectra: [n_channels][n_blocks][partition][2] (second half of every frame, scaled 1 / (2 * partition)),
+ * stored by
+ *   mode 1 (launch_rfft_inv_ols_ring): sample i of block t to ring_a[c][(p_t + i) & (ring_a_size - 1)], p_t = pos_a[t] (a
+ *     negative entry drops the block) or pos0 + t * partition when pos_a is null.  ring_a: [n_channels][ring_a_size], in and out.
+ *   mode 2 (launch_rfft_inv_ols_tail): to out: [n_channels][n_blocks * partition] plus what the delay-line reader of n_tail tail
+ *     layers adds there: for sample n of the call, callback n / callback_size, layer l (gain g1, then g2): s = sched[l][callback];
+ *     s >= 0 adds x (gain within 1e-12 of 1) or x * gain, x = layer_out[l][c][s + n % callback_size - g0] when that index is
+ *     >= 0, else tail_ring[l][c][(s + n % callback_size) & (tail_ring_size - 1)]; g0 = tail_state[3].  layer_out: [n_tail]
+ *     [n_channels][n_blocks * partition], tail_ring: [n_tail][n_channels][tail_ring_size], sched: [n_tail][n_blocks * partition
+ *     / callback_size], tail_state: [4].
+ *   mode 3 (launch_rfft_inv_ols_add, partition 512): to out plus, for block t, ring_a[c][(pos_a[t] + i) & mask] (gain g1) and then
+ *     ring_b[c][(pos_b[t] + i) & mask] (gain g2; ring_b may be null); negative positions add nothing.  The rings come back as
+ *     they are after the launch.
+ * Refused unless: n_channels, n_blocks >= 1; mode 1: ring_a_size a power of two >= partition and >= 2, positions <= 2^62,
+ * 0 <= pos0 when pos_a is null, the blocks that are written at least a partition apart on the ring (no element stored twice);
+ * mode 2: partition <= 4096, n_tail 1 or 2, callback_size a power of two dividing n_blocks * partition, tail_ring_size a power
+ * of two >= 2, 0 <= g0 <= 2^62, every entry s >= 0 of sched with s + callback_size <= g0 + n_blocks * partition; mode 3:
+ * partition == 512, ring sizes powers of two >= partition, positions <= 2^62, pos_a non-null, pos_b non-null with ring_b. */
+int32_t     cpq_diag_fft_inverse_store(int32_t mode, int32_t partition, int32_t n_channels, int32_t n_blocks, const double* spectra,
+                                       double* ring_a, int32_t ring_a_size, const int64_t* pos_a, int64_t pos0, double* ring_b,
+                                       int32_t ring_b_size, const int64_t* pos_b, const double* layer_out, const double* tail_ring,
+                                       int32_t tail_ring_size, const int64_t* tail_state, const int64_t* sched,
+                                       int32_t callback_size, int32_t n_tail, double g1, double g2, double* out);
+/* launch_ir_spectra on heff[0 .. heff_len): h: [n_parts][partition][2] the spectra of the frames [heff[k * partition ..
+ * (k + 1) * partition) | zeros] (zeros from heff_len on), hdn: [n_parts][2] their elements 0.  The device copy of heff holds
+ * n_parts * partition elements, NaN from heff_len on.  gain: null, or [partition + 1] factors per bin: launch_spectrum_gain is
+ * then applied and h_gain / hdn_gain receive both buffers again.
+ * Refused unless: n_parts >= 1, 1 <= heff_len <= n_parts * partition, h_gain and hdn_gain non-null with gain. */
+int32_t     cpq_diag_ir_spectra(int32_t partition, int32_t n_parts, const double* heff, int32_t heff_len, const double* gain,
+                                double* h, double* hdn, double* h_gain, double* hdn_gain);
 /* Chained spans of the EQ / output-filter cascade (engines with fewer channels than the device holds workgroups of the span
  * kernel: the spans of a call are dealt to the workgroups and a band's state is handed from span to span inside the launch).
  * Synchronises the engine's stream; *launches = chained launches so far (0: this engine never chains), *gave_up != 0 when a

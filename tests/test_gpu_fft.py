@@ -14,10 +14,10 @@ itself), and the round trip.  One case per kernel family:
 Tolerance: 4e-15 of the largest spectral magnitude on the forward transform and of the largest sample against numpy's
 inverse, 2e-15 on the round trip
 (log2(N) = 7 ... 16 butterfly levels of fp64 rounding; measured values are printed)."""
-import ctypes as C
-
 import numpy as np
 import pytest
+
+from fft_layout import bins as _bins, dp
 
 pytestmark = pytest.mark.gpu
 
@@ -29,15 +29,6 @@ def amd():
         pytest.fail("no GPU visible: the -m gpu tests need a gfx950 device")
     import convopeq_amd
     return convopeq_amd
-
-
-def _bins(P):
-    """storage element -> bin of the packed spectrum (element 0 = (DC, Nyquist))"""
-    e = np.arange(P)
-    if P <= 2048:
-        return e
-    m1 = P // 512
-    return (e // 512) + m1 * (e % 512)
 
 
 @pytest.mark.parametrize("P", [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 131072])
@@ -52,7 +43,6 @@ def test_partition_fft_forward_inverse_round_trip(amd, P):
     x[2, 0, 17] = 1.0                                       # an impulse
     spec = np.empty((n_ch, T, P, 2))
     out = np.empty((n_ch, T, P))
-    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
     assert lib.cpq_diag_partition_fft(P, n_ch, T, dp(np.ascontiguousarray(x)), dp(spec), dp(out)) == 0
     bins = _bins(P)
     assert sorted(bins.tolist()) == list(range(P))          # the documented storage order is a permutation

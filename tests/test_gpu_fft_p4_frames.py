@@ -20,10 +20,11 @@ One case through an engine: 3 streams, P = 4096, two consecutive calls of 3 and 
 time-varying plan (1024-sample callbacks, 131072 taps), i.e. the layered path whose last inverse transform stores through
 the delay-line reader (MODE 2), whose tail layers store plain rows (MODE 0) and whose forward transform carries histNew from
 the first call into the second; against the oracle at 1e-13 RMS like tests/test_gpu_parity.py."""
-import ctypes as C
-
 import numpy as np
 import pytest
+
+import fft_layout
+from fft_layout import dp
 
 pytestmark = pytest.mark.gpu
 
@@ -42,8 +43,7 @@ def lib():
 
 def _bins():
     """storage element -> bin of the packed spectrum (element 0 = (DC, Nyquist)), as tests/test_gpu_fft.py"""
-    e = np.arange(P)
-    return (e // 512) + (P // 512) * (e % 512)
+    return fft_layout.bins(P)
 
 
 def _input(n_ch, T):
@@ -59,7 +59,6 @@ def _run(lib, x, split):
     n_ch, T, _ = x.shape
     spec = np.empty((n_ch, T, P, 2))
     out = np.empty((n_ch, T, P))
-    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
     assert lib.cpq_diag_partition_fft_split(P, n_ch, T, split, dp(x), dp(spec), dp(out)) == 0
     return spec, out
 
@@ -98,7 +97,6 @@ def test_split_argument(lib):
     """split <= 0 is the engine's own choice (the result of cpq_diag_partition_fft); more workgroups than frames are refused;
     other partitions ignore the argument"""
     x = _input(3, 5)
-    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
     spec0, out0 = np.empty((3, 5, P, 2)), np.empty((3, 5, P))
     assert lib.cpq_diag_partition_fft(P, 3, 5, dp(x), dp(spec0), dp(out0)) == 0
     for split in (0, -3, 5):

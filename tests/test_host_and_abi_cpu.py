@@ -150,6 +150,22 @@ def test_invalid_arguments_are_rejected_without_gpu(amd):
     assert lib.cpq_kernel_name(1) == b"k_fdl_mac"
 
 
+def test_fft_launch_diagnostics_refuse_before_looking_for_a_device(amd):
+    """cpq_diag_fft_forward / _inverse_store / _ir_spectra: every refusal rule of the header once (the table the device test
+    walks, tests/fft_variant_calls.py) is CPQ_ERR_INVALID_ARG here too -- the arguments are checked before hipGetDeviceCount,
+    so an argument set that would take a kernel outside a buffer never gets as far as a device; the valid sets get past the
+    checks and, without a GPU, end at CPQ_ERR_NO_DEVICE"""
+    import torch
+    import fft_variant_calls as V
+    from convopeq_amd import _capi
+    lib = _capi.load()
+    res = V.walk_refusals(lib)
+    assert len(res) >= 55 and {k for k, _, _ in res} == {"forward", "inverse", "ir"}
+    assert [r for r in res if r[2] != _capi.CPQ_ERR_INVALID_ARG] == []
+    if not torch.cuda.is_available():
+        assert {rc for _, rc in V.valid_calls(lib)} == {V.NO_DEVICE}
+
+
 def test_outfilter_design_matches_oracle_and_rbj(amd, oracle):
     """N2: OutputFilter::prepare coefficient design through the C ABI == oracle restatement; sanity vs scipy."""
     from scipy.signal import freqz
