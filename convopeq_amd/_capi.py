@@ -142,6 +142,8 @@ class EngineDesc(C.Structure):
 
 # every symbol include/convopeq_mi355x.h declares: (restype, argtypes)
 _E = C.c_void_p
+_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
 SYMBOLS = {
     "cpq_abi_version": (C.c_int32, []),
     "cpq_abi_revision": (C.c_int32, []),
@@ -243,6 +245,21 @@ SYMBOLS = {
                                                C.c_int32, C.POINTER(C.c_int64), c_double_p, c_double_p, C.c_int32, C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_double, C.c_double, c_double_p]),
     "cpq_diag_ir_spectra": (C.c_int32, [C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "cpq_diag_direct_head": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, c_double_p, c_double_p, _i32p, _i32p, c_double_p, _i32p,
+                                         c_double_p, c_double_p, c_double_p, C.c_int64]),
+    "cpq_diag_agc": (C.c_int32, [C.c_int32] * 4 + [C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, _i32p, c_double_p, C.c_double,
+                                                   C.c_double, C.c_double, c_double_p, _i32p]),
+    "cpq_diag_ring_chunks": (C.c_int32, [C.c_int32] * 5 + [C.c_int64, c_double_p, _i32p, c_double_p, C.c_int32, _i64p, _i64p, c_double_p,
+                                                           C.c_int32, _i64p, C.c_double, c_double_p, C.c_int32, _i64p, C.c_double,
+                                                           C.c_int32, _i64p, _i64p, c_double_p, c_double_p, c_double_p, _i64p, C.c_int32,
+                                                           _i64p]),
+    "cpq_diag_convproc_mix": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p,
+                                          C.c_int32, C.c_int64, _i32p, _i32p, _i32p, c_double_p, C.c_int32, C.c_int32, _i32p, c_double_p,
+                                          C.c_int32, C.c_int32, _i32p, c_double_p, C.c_int32, C.c_int64, c_double_p, C.c_int64, C.c_int32]),
+    "cpq_diag_tail_reader": (C.c_int32, [C.c_int32, _i32p] + [C.c_int32] * 8 + [_i64p, _i64p, _i64p, C.c_int32, C.c_int32, c_double_p,
+                                                                               c_double_p, C.c_int32]),
+    "cpq_diag_rows": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int64, C.c_int64, c_double_p, C.c_int64, C.c_int64,
+                                  c_double_p, _i32p, _i32p, c_double_p, c_double_p, C.c_int32]),
     "cpq_diag_eq_chain_status": (C.c_int32, [_E, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "cpq_kernel_name": (C.c_char_p, [C.c_int32]),
 }

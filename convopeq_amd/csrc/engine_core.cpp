@@ -108,7 +108,7 @@ int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
     if (eq) {
         CPQ_HIP(e, hipMemsetAsync(e->svfState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
         CPQ_HIP(e, hipMemsetAsync(e->ofState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
-        if (e->agcState) CPQ_HIP(e, hipMemsetAsync(e->agcState, 0, (size_t)e->desc.n_streams * 3 * sizeof(double), e->stream));
+        if (e->agcState) { const int rc = agcStateReset(e, 0, e->desc.n_streams); if (rc != CPQ_OK) return rc; }
     }
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;

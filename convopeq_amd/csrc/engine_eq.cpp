@@ -5,6 +5,16 @@ using namespace cpqi;
 
 namespace cpqi {
 
+// The gain is kept as it is (rtAgcCurrentGainShadow), not as gain - 1: (gain - 1) + 1 is not the gain again below 0.5, and a
+// gain carried across a call boundary would then differ from the reference's in its last bit.  1.0 = 0x3FF00000'00000000.
+int agcStateReset(cpq_engine* e, int s0, int n)
+{
+    CPQ_HIP(e, hipMemsetAsync(e->agcState + (size_t)s0 * 3, 0, (size_t)n * 3 * sizeof(double), e->stream));
+    for (int s = s0; s < s0 + n; ++s)
+        CPQ_HIP(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<char*>(e->agcState + (size_t)s * 3 + 2) + 4), 0x3FF00000, 1, e->stream));
+    return CPQ_OK;
+}
+
 // one cascade launch: the time-parallel kernels over every even number of samples, the lane-skewed one over a last odd sample (or everything)
 int enqueueCascade(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int n, bool tp, int idTp, int idSeq,
                    const double* coef, const int* flags, const double* satGain, double* state, const double* tables,
@@ -216,7 +226,7 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
     if (!e->eqSet) return fail(e, CPQ_ERR_NOT_READY, "cpq_eq_set_params has not been called");
     const int S = e->desc.n_streams;
     auto agcReset = [e](int s) -> int {        // rtAgcCurrentGainShadow = 1, envelopes = 0 (Processing.cpp:586-593, 1070-1077)
-        if (e->agcState) CPQ_HIP(e, hipMemsetAsync(e->agcState + (size_t)s * 3, 0, sizeof(double) * 3, e->stream));
+        if (e->agcState) { const int rc = agcStateReset(e, s, 1); if (rc != CPQ_OK) return rc; }
         e->agcResetPending[s] = 0;
         return CPQ_OK;
     };
@@ -450,6 +460,9 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
             const int rc = allocAll(e, { { e->agcOn, (size_t)S }, { e->agcState, (size_t)3 * S, true }, { e->agcRmsIn, e->nCh * cbMax },
                                          { e->agcRmsOut, e->nCh * cbMax }, { e->agcGains, 2 * S * cbMax } }, "AGC buffers could not be allocated");
             if (rc != CPQ_OK) return rc;
+            const int rs = agcStateReset(e, 0, S);
+            if (rs != CPQ_OK) return rs;
+            CPQ_HIP(e, hipStreamSynchronize(e->stream));
         }
         e->anyAgc = true;
         CPQ_HIP(e, hipMemcpy(e->agcOn, e->agcOnHost.data(), sizeof(int) * S, hipMemcpyHostToDevice));

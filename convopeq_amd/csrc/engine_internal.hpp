@@ -347,6 +347,9 @@ int fail(cpq_engine* e, int code, const char* fmt, ...);
 // the stream argument of an entry point, one stream or CPQ_ALL_STREAMS, as the range [s0, s1); refuses any other value
 int streamRange(cpq_engine* e, int stream, int& s0, int& s1);
 
+// AGC state [envIn, envOut, gain] of streams s0 .. s0 + n - 1 back to 0, 0, 1 on the engine's stream (agcState must exist)
+int agcStateReset(cpq_engine* e, int s0, int n);
+
 int nextPow2(int v);
 int64_t alignUp(int64_t v, int64_t a);
 cpq::FftTables tables(const cpq_engine* e);

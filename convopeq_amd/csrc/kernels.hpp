@@ -138,7 +138,7 @@ void launch_ring_regrow(hipStream_t stream, const double* oldRing, int oldSize, 
 
 // EQ AGC (EQProcessor::processAGC): per-callback-block RMS in the reference's accumulation order, then envelopes /
 // gain per block (one thread per stream) and the linear gain ramp with the reference's incremental-add pattern.
-// rms: [nCh][T]; state: [S][3] = envIn, envOut, gain-1; gains: [S][T][2] = start gain, per-sample increment.
+// rms: [nCh][T]; state: [S][3] = envIn, envOut, gain; gains: [S][T][2] = start gain, per-sample increment.
 void launch_agc_block_rms(hipStream_t stream, const double* x, int64_t chStride, int nCh, int B, int T, double* rms);
 void launch_agc_apply(hipStream_t stream, double* data, int64_t chStride, int S, int B, int T, const double* rmsIn,
                       const double* rmsOut, double* state, const int* agcOn, double* gains, double bAtt, double bRel,

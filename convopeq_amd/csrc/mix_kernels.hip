@@ -167,7 +167,7 @@ __global__ __launch_bounds__(64) void k_agc_gains(const double* __restrict__ rms
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S || !agcOn[s]) return;
-    double envIn = state[3 * s], envOut = state[3 * s + 1], cur = state[3 * s + 2] + 1.0;
+    double envIn = state[3 * s], envOut = state[3 * s + 1], cur = state[3 * s + 2];
     for (int t = 0; t < T; ++t) {
         double inR = fmax(rmsIn[(2 * s) * T + t], rmsIn[(2 * s + 1) * T + t]);        // max over channels, starting from 0
         double outR = fmax(rmsOut[(2 * s) * T + t], rmsOut[(2 * s + 1) * T + t]);
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(64) void k_agc_gains(const double* __restrict__ rms
         gains[((int64_t)s * T + t) * 2 + 1] = (next - cur) / (double)B;
         cur = next;
     }
-    state[3 * s] = envIn; state[3 * s + 1] = envOut; state[3 * s + 2] = cur - 1.0;
+    state[3 * s] = envIn; state[3 * s + 1] = envOut; state[3 * s + 2] = cur;
 }
 
 // applyGainRamp_AVX2 (:279-337): gain of sample i = 16 m + 4 q + j is lane j's start value advanced m times by

@@ -755,6 +755,87 @@ int32_t     cpq_diag_fft_inverse_store(int32_t mode, int32_t partition, int32_t 
  * Refused unless: n_parts >= 1, 1 <= heff_len <= n_parts * partition, h_gain and hdn_gain non-null with gain. */
 int32_t     cpq_diag_ir_spectra(int32_t partition, int32_t n_parts, const double* heff, int32_t heff_len, const double* gain,
                                 double* h, double* hdn, double* h_gain, double* hdn_gain);
+/* The launchers of mix_kernels.hip on their own (tests/test_gpu_mix_kernels.py): direct head, AGC, plan-group ring chunks,
+ * processor-level mix with its delay ring, the delay-line reader's schedule, and the row helpers.  Conventions of the FFT
+ * launch diagnostics above: all pointers are host memory; one stream, synchronised before the entry returns; every device row
+ * is allocated at exactly the size stated here; every buffer a kernel may write is filled with 0xFF bytes (NaN; -1 for integers)
+ * before the launch unless the caller supplies its contents ("in and out"), and is returned whole.  Each entry returns
+ * CPQ_ERR_INVALID_ARG, before anything is allocated and before a device is looked for, unless the rules of its "Refused unless"
+ * hold (and every pointer that is used is non-null); no buffer may exceed 2^28 elements.  Need a gfx950 device; no engine.
+ *
+ * cpq_diag_direct_head: launch_direct_head, then with out != null launch_rows_add of dout into out.
+ *   in: [n_ch][in_stride] (n samples used per row), ir_rev: [n_slots][32] reversed taps, taps: [n_slots], ir_slot: [n_ch],
+ *   hist_old: [n_ch][32], wet_on: [n_ch / 2] or null; dout: [n_ch][n] and hist_new: [n_ch][32] out; out: [n_ch][out_stride] in
+ *   and out, or null.
+ *   Refused unless: n_ch, n_slots >= 1; 1 <= n <= in_stride; 0 <= taps[s] <= 32; 0 <= ir_slot[c] < n_slots; n_ch even with
+ *   wet_on; out_stride >= n with out. */
+int32_t     cpq_diag_direct_head(int32_t n_ch, int32_t n, int64_t in_stride, int32_t n_slots, const double* in,
+                                 const double* ir_rev, const int32_t* taps, const int32_t* ir_slot, const double* hist_old,
+                                 const int32_t* wet_on, double* dout, double* hist_new, double* out, int64_t out_stride);
+/* cpq_diag_agc on data: [n_ch][ch_stride] (in and out; callback t of a row is [t * B, (t + 1) * B)), S = n_ch / 2 streams:
+ *   op 0 launch_agc_block_rms: rms: [n_ch][T] out.
+ *   op 1 launch_agc_apply (gains, then ramp): rms_in, rms_out: [n_ch][T]; state: [S][3] = envIn, envOut, gain, in and out; on: [S]; gains: [S][T][2]
+ *        out; b_att, b_rel, b_sm the per-callback coefficients.
+ *   op 2 launch_gain_ramp: gains: [S][T][2] in; on: [S].
+ *   op 3 launch_block_silence: silent: [S][T] out.
+ *   Refused unless: op in 0 .. 3; n_ch, B, T >= 1; ch_stride >= B * T; ops 1 .. 3: n_ch even (S >= 1). */
+int32_t     cpq_diag_agc(int32_t op, int32_t n_ch, int32_t B, int32_t T, int64_t ch_stride, double* data, const double* rms_in,
+                         const double* rms_out, double* state, const int32_t* on, double* gains, double b_att, double b_rel,
+                         double b_sm, double* rms, int32_t* silent);
+/* cpq_diag_ring_chunks: the plan-group kernels on out: [rows][out_stride] (in and out), ch_map: [n_ch] (row of out per local
+ * channel, -1 = unused slot), n samples in chunks of q (ceil(n / q) chunks, the last one possibly shorter):
+ *   op 0 launch_rows_gather_multi: out is the source; n_dst destinations dst0 .. dst2: [n_ch][dst_stride[l]] (out), the n samples
+ *        at dst_off[l] of every row; tab[0 .. n_tab) stored to tab_out: [64] (out).
+ *   op 1 launch_ring_get_chunks: ring0: [n_ch][size0], pos, cnt: [chunks].
+ *   op 2 launch_ring_add_chunks: ring_a: [n_ch][size_a], sched_a: [chunks] (negative: nothing added), gain_a.
+ *   op 3 launch_ring_add_chunks2: ring_a and ring_b with their schedules and gains.
+ *   op 4 launch_ring_get_add_chunks: ring0, pos, cnt, ring_a, sched_a, gain_a; ring_b may be null.
+ *   Refused unless: op in 0 .. 4; rows, n_ch, n, q >= 1; out_stride >= n; every ch_map entry -1 or < rows and no row named
+ *   twice; ring sizes powers of two >= 2; 0 <= cnt <= q; 0 <= pos <= 2^62; schedule entries <= 2^62; op 0: 1 <= n_dst <= 3,
+ *   0 <= dst_off[l], dst_off[l] + n <= dst_stride[l], 0 <= n_tab <= 64 (the launcher would drop a longer table silently). */
+int32_t     cpq_diag_ring_chunks(int32_t op, int32_t rows, int32_t n_ch, int32_t n, int32_t q, int64_t out_stride, double* out,
+                                 const int32_t* ch_map, const double* ring0, int32_t size0, const int64_t* pos, const int64_t* cnt,
+                                 const double* ring_a, int32_t size_a, const int64_t* sched_a, double gain_a, const double* ring_b,
+                                 int32_t size_b, const int64_t* sched_b, double gain_b, int32_t n_dst, const int64_t* dst_stride,
+                                 const int64_t* dst_off, double* dst0, double* dst1, double* dst2, const int64_t* tab,
+                                 int32_t n_tab, int64_t* tab_out);
+/* cpq_diag_convproc_mix: with old_ring != null launch_ring_regrow of old_ring: [n_ch][old_size] up to position regrow_end into a
+ * zeroed ring (the contents of `ring` are then not read); with ring_in != null launch_ring_put of n_put samples of ring_in:
+ * [n_ch][ring_in_stride] at pos0; then launch_convproc_mix over one range of n samples (n = 0: nothing is launched for it).
+ *   wet, out: [n_ch][ch_stride]; in_place != 0: one device buffer, filled from wet and returned in out.  gains: [S][2] (wet, dry);
+ *   ring: [n_ch][ring_size] in and out; d_new, d_old: [S]; x_len: [S] or null, x_gains: [S][x_cap]; ramp_len: [S] or null,
+ *   ramp_gains: [S][ramp_cap][2]; wet_on: [S] or null.  S = n_ch / 2.
+ *   Refused unless: n_ch even >= 2; 0 <= n <= ch_stride, ch_stride >= 1; ring_size a power of two >= 2; 0 <= pos0 <= 2^62;
+ *   0 <= d_new[s], d_old[s] < ring_size; with x_len: x_cap >= 1 and 0 <= x_len[s] <= min(n, x_cap); with ramp_len: ramp_cap >= 1,
+ *   ramp_off >= 0 and ramp_len[s] - ramp_off <= ramp_cap - ramp_off; with old_ring: old_size a power of two >= 2, ring_size >=
+ *   old_size, 0 <= regrow_end <= 2^62; with ring_in: 1 <= n_put <= min(ring_in_stride, ring_size). */
+int32_t     cpq_diag_convproc_mix(int32_t n_ch, int32_t n, int64_t ch_stride, const double* wet, double* out, int32_t in_place,
+                                  const double* gains, double* ring, int32_t ring_size, int64_t pos0, const int32_t* d_new,
+                                  const int32_t* d_old, const int32_t* x_len, const double* x_gains, int32_t x_cap,
+                                  int32_t wet_valid, const int32_t* ramp_len, const double* ramp_gains, int32_t ramp_cap,
+                                  int32_t ramp_off, const int32_t* wet_on, const double* old_ring, int32_t old_size,
+                                  int64_t regrow_end, const double* ring_in, int64_t ring_in_stride, int32_t n_put);
+/* cpq_diag_tail_reader: launch_tail_schedule for n_calls consecutive calls of T[i] callbacks of B samples, starting from
+ * state_in: [4] = callbacks so far, read cursor of tail layer 1, of layer 2, first sample of the last call.  Layer l has
+ * partition pl, outputDelaySamples ol and d callbacks between partition fill and delay-line write.  sched_out: the calls'
+ * schedules one behind the other, call i as [n_tail][T[i]]; states_out: [n_calls][4] the state after every call.  With
+ * layer_out != null launch_tail_append follows the last schedule: layer_out: [n_tail][n_ch][n_samples], ring: [n_tail][n_ch]
+ * [ring_size] in and out.
+ *   Refused unless: 1 <= n_calls <= 4096; T[i] >= 1, their sum <= 2^20; B >= 1; n_tail 1 or 2; per layer in use pl >= B,
+ *   pl % B == 0, ol >= 0, d >= 0; 0 <= state_in[k] <= 2^62; with layer_out: n_ch, n_samples >= 1, ring_size a power of two >= 2. */
+int32_t     cpq_diag_tail_reader(int32_t n_calls, const int32_t* T, int32_t B, int32_t n_tail, int32_t pl1, int32_t ol1, int32_t d1,
+                                 int32_t pl2, int32_t ol2, int32_t d2, const int64_t* state_in, int64_t* sched_out,
+                                 int64_t* states_out, int32_t n_ch, int32_t n_samples, const double* layer_out, double* ring,
+                                 int32_t ring_size);
+/* cpq_diag_rows on dst: [n_ch][dst_stride] (in and out):
+ *   op 0 launch_rows_copy: dst[c][dst_off + i] = src[c][src_off + i], i < n; src: [n_ch][src_stride].
+ *   op 1 launch_rows_scale: the first n samples of every row times gain[c / 2]; gain: [n_ch / 2].
+ *   op 2 launch_bypass_blend: dst = out, src = dry; on, len, g_end: [n_ch / 2]; gains: [n_ch / 2][cap].
+ *   Refused unless: op in 0 .. 2; n_ch, n >= 1; 0 <= offset and offset + n <= stride on both sides in use; ops 1, 2: n_ch even
+ *   and both offsets 0; op 2: cap >= 1 and 0 <= len[s] <= cap. */
+int32_t     cpq_diag_rows(int32_t op, int32_t n_ch, int32_t n, const double* src, int64_t src_stride, int64_t src_off, double* dst,
+                          int64_t dst_stride, int64_t dst_off, const double* gain, const int32_t* on, const int32_t* len,
+                          const double* g_end, const double* gains, int32_t cap);
 /* Chained spans of the EQ / output-filter cascade (engines with fewer channels than the device holds workgroups of the span
  * kernel: the spans of a call are dealt to the workgroups and a band's state is handed from span to span inside the launch).
  * Synchronises the engine's stream; *launches = chained launches so far (0: this engine never chains), *gave_up != 0 when a

@@ -166,6 +166,21 @@ def test_fft_launch_diagnostics_refuse_before_looking_for_a_device(amd):
         assert {rc for _, rc in V.valid_calls(lib)} == {V.NO_DEVICE}
 
 
+def test_mix_kernel_diagnostics_refuse_before_looking_for_a_device(amd):
+    """cpq_diag_direct_head / _agc / _ring_chunks / _convproc_mix / _tail_reader / _rows: every refusal rule of the header once
+    (tests/mix_kernel_calls.py, the table the device test imports) is CPQ_ERR_INVALID_ARG without a device; the valid sets get
+    past the checks and, without a GPU, end at CPQ_ERR_NO_DEVICE"""
+    import torch
+    import mix_kernel_calls as K
+    from convopeq_amd import _capi
+    lib = _capi.load()
+    res = K.walk_refusals(lib)
+    assert len(res) >= 100 and {k for k, _, _ in res} == set(K.CALLERS)
+    assert [r for r in res if r[2] != _capi.CPQ_ERR_INVALID_ARG] == []
+    if not torch.cuda.is_available():
+        assert {rc for _, rc, _, _ in K.valid_calls(lib)} == {K.NO_DEVICE}
+
+
 def test_outfilter_design_matches_oracle_and_rbj(amd, oracle):
     """N2: OutputFilter::prepare coefficient design through the C ABI == oracle restatement; sanity vs scipy."""
     from scipy.signal import freqz
