@@ -166,416 +166,6 @@ const char* cpq_kernel_name(int32_t id)
     }
 }
 
-// ------------------------------------------------------------------ diagnostics
-// The partition FFT kernels in isolation (tests/test_gpu_fft.py): forward of every overlap-save frame from a silent history,
-// inverse of the same spectra.  Own device buffers and twiddles, the null stream; no engine.
-int32_t cpq_diag_eq_chain_status(cpq_engine* e, uint32_t* launches, uint32_t* gaveUp)
-{
-    if (!e || !launches || !gaveUp) return CPQ_ERR_INVALID_ARG;
-    *launches = 0;
-    *gaveUp = 0;
-    if (!e->svfChain || e->svfChainSpans <= 0) return CPQ_OK;
-    (void)hipSetDevice(e->device);
-    uint32_t hdr[4] = { 0, 0, 0, 0 };          // generation, finished workgroups, ticket, error (svf_kernels.hip: TpvChainHeader)
-    CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    CPQ_HIP(e, hipMemcpy(hdr, e->svfChain, sizeof(hdr), hipMemcpyDeviceToHost));
-    *launches = hdr[0];
-    *gaveUp = hdr[3];
-    return CPQ_OK;
-}
-
-int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* in, double* spectra, double* out)
-{
-    return cpq_diag_partition_fft_split(P, nCh, T, 0, in, spectra, out);
-}
-
-// split > 0 at P = 4096: that many workgroups walk the frames of a channel (at most one per frame), so that a small test decides
-// how many consecutive frames one workgroup transforms; otherwise the launchers' own choice
-int32_t cpq_diag_partition_fft_split(int32_t P, int32_t nCh, int32_t T, int32_t split, const double* in, double* spectra, double* out)
-{
-    if (P != 4096 || split < 0) split = 0;
-    if (split > T) return CPQ_ERR_INVALID_ARG;
-    if (P < 64 || P > 131072 || (P & (P - 1)) || nCh <= 0 || T <= 0 || !in || !spectra || !out) return CPQ_ERR_INVALID_ARG;
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) { (void)hipGetLastError(); return CPQ_ERR_NO_DEVICE; }
-    int ringSlots = 1;
-    while (ringSlots < T) ringSlots <<= 1;
-    const size_t nTime = (size_t)nCh * T * P, nSpec = (size_t)nCh * ringSlots * P;
-    DeviceBuffer<double> dIn, dOut, dHist;
-    DeviceBuffer<double2> dX, dXdn, dTw, dTw2, dScratch, dY;
-    std::vector<double2> w1, w2;
-    hostTwiddles(P, w1, w2);
-    // (dTw, dTw2: the second halves are the reordered tables of the four-step transforms)
-    if (allocAll(nullptr, { { dIn, nTime }, { dOut, nTime }, { dHist, (size_t)2 * nCh * P }, { dX, nSpec }, { dXdn, (size_t)nCh * ringSlots },
-                            { dTw, (size_t)2 * P }, { dTw2, (size_t)2 * P }, { dScratch, P > 4096 ? (size_t)nCh * T * P : 1 },
-                            { dY, (size_t)nCh * T * P } }, "partition FFT diagnostic buffers could not be allocated") != CPQ_OK)
-        return CPQ_ERR_DEVICE;
-    int32_t rc = CPQ_OK;
-    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    {
-        ok(hipMemset(dHist, 0, (size_t)2 * nCh * P * sizeof(double)));
-        ok(hipMemset(dX, 0, nSpec * sizeof(double2)));
-        ok(hipMemcpy(dIn, in, nTime * sizeof(double), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dTw, w1.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dTw2, w2.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice));
-        if (P > 4096) {
-            std::vector<double2> wc((size_t)P), ws((size_t)P);
-            cpq::fill_big_twiddles(w1.data(), w2.data(), P, wc.data(), ws.data());
-            ok(hipMemcpy(dTw + P, wc.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice));
-            ok(hipMemcpy(dTw2 + P, ws.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice));
-        }
-    }
-    if (rc == CPQ_OK) {
-        const cpq::FftTables tw{ dTw, dTw2, P > 4096 ? dTw + P : nullptr, P > 4096 ? dTw2 + P : nullptr };
-        cpq::launch_rfft_fwd_ols(nullptr, dIn, (int64_t)T * P, dHist, dHist + (size_t)nCh * P, dX, dXdn, tw, P, nCh, T, 0, ringSlots, dScratch, split);
-        // the ring holds block t of channel c at [c][t] of ringSlots slots: [c][t] of T slots for the inverse and the caller
-        for (int c = 0; c < nCh && rc == CPQ_OK; ++c)
-            ok(hipMemcpyAsync(dY + (size_t)c * T * P, dX + (size_t)c * ringSlots * P, (size_t)T * P * sizeof(double2), hipMemcpyDeviceToDevice, nullptr));
-        cpq::launch_rfft_inv_ols(nullptr, dY, dOut, (int64_t)T * P, tw, P, nCh, T, dScratch, split);
-        ok(hipGetLastError());
-        ok(hipDeviceSynchronize());
-    }
-    if (rc == CPQ_OK) {
-        ok(hipMemcpy(spectra, dY, (size_t)nCh * T * P * sizeof(double2), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(out, dOut, nTime * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return rc;
-}
-
-// The FDL multiply-accumulate kernels in isolation (tests/test_gpu_fdl_mac.py): what engine_conv.cpp / engine_native.cpp launch
-// for one call -- launch_fdl_mac, then launch_fdl_mac_dcnyq when the variant leaves packed bin 0 to it -- on buffers the caller
-// fills in the kernels' own layouts.  Own device buffers, the null stream; no engine.  Every argument set for which a kernel
-// would read or write outside a buffer is refused before anything is allocated (extents: kernels.hpp, launch_fdl_mac).
-int32_t cpq_diag_fdl_mac(int32_t P, int32_t nCh, int32_t K, int32_t T, int32_t tile, int32_t head, int32_t ringSlots,
-                         int32_t nIrSlots, int32_t hRows, int32_t hPrivate, const double* x, const double* h,
-                         const int32_t* irSlot, double* y, int32_t* variantUsed)
-{
-    if (!x || !h || !irSlot || !y || !variantUsed) return CPQ_ERR_INVALID_ARG;
-    if (P < 64 || P > 4096 || (P & (P - 1)) || nCh < 1 || K < 1 || T < 1 || nIrSlots < 1) return CPQ_ERR_INVALID_ARG;
-    if (tile != 0 && tile != 4 && tile != 8 && tile != 16 && tile != 32 && tile != cpq::kMacTileCoop) return CPQ_ERR_INVALID_ARG;
-    // the engines' own sizing rules (engine_core.cpp: ringSlots; engine_native.cpp layerGeometry: hRows, the smaller of the two)
-    const int64_t kPad32 = alignUp(K, cpq::kMacMaxTile);
-    int64_t ringMin = 1;
-    while (ringMin < kPad32 + cpq::kMacMaxTile + T) ringMin <<= 1;
-    if (ringSlots < 1 || (ringSlots & (ringSlots - 1)) || ringSlots < ringMin) return CPQ_ERR_INVALID_ARG;
-    if (hRows < kPad32 + 16) return CPQ_ERR_INVALID_ARG;
-    if (head < 0 || head >= ringSlots) return CPQ_ERR_INVALID_ARG;
-    for (int c = 0; c < nCh; ++c)
-        if (irSlot[c] < 0 || irSlot[c] >= nIrSlots) return CPQ_ERR_INVALID_ARG;
-    const size_t nX = (size_t)nCh * ringSlots * P, nH = (size_t)nIrSlots * hRows * P, nY = (size_t)nCh * T * P;
-    if (nX > ((size_t)1 << 28) || nH > ((size_t)1 << 28) || nY > ((size_t)1 << 28)) return CPQ_ERR_INVALID_ARG;      // 4 GB each: a test tool
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) { (void)hipGetLastError(); return CPQ_ERR_NO_DEVICE; }
-    *variantUsed = cpq::fdl_mac_variant(tile, T);
-
-    // compact (DC, Nyquist) rows: element 0 of every spectrum, which is what the forward FFT and launch_ir_spectra store there
-    const double2* x2 = reinterpret_cast<const double2*>(x);
-    const double2* h2 = reinterpret_cast<const double2*>(h);
-    std::vector<double2> xdn((size_t)nCh * ringSlots), hdn((size_t)nIrSlots * hRows);
-    for (size_t i = 0; i < xdn.size(); ++i) xdn[i] = x2[i * P];
-    for (size_t i = 0; i < hdn.size(); ++i) hdn[i] = h2[i * P];
-
-    DeviceBuffer<double2> dX, dH, dXdn, dHdn, dY;
-    DeviceBuffer<int> dSlot;
-    if (allocAll(nullptr, { { dX, nX }, { dH, nH }, { dXdn, xdn.size() }, { dHdn, hdn.size() }, { dY, nY }, { dSlot, (size_t)nCh } },
-                 "FDL MAC diagnostic buffers could not be allocated") != CPQ_OK)
-        return CPQ_ERR_DEVICE;
-    int32_t rc = CPQ_OK;
-    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    {
-        ok(hipMemcpy(dX, x, nX * sizeof(double2), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dH, h, nH * sizeof(double2), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dXdn, xdn.data(), xdn.size() * sizeof(double2), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dHdn, hdn.data(), hdn.size() * sizeof(double2), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dSlot, irSlot, (size_t)nCh * sizeof(int), hipMemcpyHostToDevice));
-        ok(hipMemset(dY, 0xFF, nY * sizeof(double2)));          // NaN: an element no kernel stores cannot pass for a result
-    }
-    if (rc == CPQ_OK) {
-        cpq::launch_fdl_mac(nullptr, tile, dX, dH, dSlot, dY, P, nCh, K, ringSlots, head, T, (int64_t)hRows * P, hPrivate != 0);
-        if (cpq::fdl_mac_needs_dcnyq(tile, T))
-            cpq::launch_fdl_mac_dcnyq(nullptr, dXdn, dHdn, dSlot, dY, P, nCh, K, ringSlots, head, T, hRows);
-        ok(hipGetLastError());
-        ok(hipDeviceSynchronize());
-    }
-    if (rc == CPQ_OK) ok(hipMemcpy(y, dY, nY * sizeof(double2), hipMemcpyDeviceToHost));
-    return rc;
-}
-
-}  // extern "C"
-
-namespace {
-
-// what the three FFT launch diagnostics below share: the twiddle tables of one partition size on the device
-// (second halves: the reordered tables of the four-step transforms, as in cpq_diag_partition_fft)
-struct DiagTwiddles {
-    DeviceBuffer<double2> tw, tw2;
-    int P = 0;
-    bool upload(int partition)
-    {
-        P = partition;
-        std::vector<double2> w1, w2;
-        hostTwiddles(P, w1, w2);
-        if (allocAll(nullptr, { { tw, (size_t)2 * P }, { tw2, (size_t)2 * P } }, "FFT diagnostic twiddles could not be allocated") != CPQ_OK) return false;
-        bool good = hipMemcpy(tw, w1.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(tw2, w2.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice) == hipSuccess;
-        if (good && P > 4096) {
-            std::vector<double2> wc((size_t)P), ws((size_t)P);
-            cpq::fill_big_twiddles(w1.data(), w2.data(), P, wc.data(), ws.data());
-            good = hipMemcpy(tw + P, wc.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice) == hipSuccess &&
-                   hipMemcpy(tw2 + P, ws.data(), (size_t)P * sizeof(double2), hipMemcpyHostToDevice) == hipSuccess;
-        }
-        if (!good) (void)hipGetLastError();
-        return good;
-    }
-    cpq::FftTables tables() const { return cpq::FftTables{ tw, tw2, P > 4096 ? tw + P : nullptr, P > 4096 ? tw2 + P : nullptr }; }
-};
-
-constexpr size_t kDiagMaxElems = (size_t)1 << 28;      // per buffer (4 GB of double2): test tools
-constexpr long long kDiagMaxPos = 1LL << 62;           // ring positions and schedule entries: position + block stays inside 64 bits
-
-bool diagPow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
-bool diagPartition(int P) { return P >= 64 && P <= 131072 && diagPow2(P); }
-bool diagHaveDevice()
-{
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) { (void)hipGetLastError(); return false; }
-    return true;
-}
-
-}  // namespace
-
-extern "C" {
-
-// The forward transform launches in isolation (tests/test_gpu_fft_variants.py): launch_rfft_fwd_ols, or with side != 0
-// launch_rfft_fwd_ols_side, as engine_conv.cpp / engine_native.cpp make them -- a moving head, a carried history, a ring that
-// wraps.  Every destination is filled with 0xFF bytes (NaN) first and comes back whole.  Own device buffers, the null stream;
-// no engine.  Every argument set for which a kernel would read or write outside a buffer is refused before anything is allocated.
-int32_t cpq_diag_fft_forward(int32_t P, int32_t nCh, int32_t T, int32_t head, int32_t ringSlots, int32_t tailLen, const double* in,
-                             const double* histOld, int32_t side, int32_t nSide, const int64_t* sideStride, const int64_t* sideOff,
-                             const int64_t* tab, int32_t nTab, int32_t tailStride, double* ring, double* xdn, double* histNew,
-                             double* sideOut0, double* sideOut1, int64_t* tabOut, double* tailOut)
-{
-    if (!in || !histOld || !ring || !xdn || !histNew) return CPQ_ERR_INVALID_ARG;
-    if (!diagPartition(P) || nCh < 1 || T < 1 || tailLen < 0) return CPQ_ERR_INVALID_ARG;
-    if (!diagPow2(ringSlots) || ringSlots < T || head < 0 || head >= ringSlots) return CPQ_ERR_INVALID_ARG;
-    const size_t rowLen = (size_t)T * P + (size_t)tailLen;
-    const size_t inStride = rowLen + (rowLen & 1);          // even: every channel's row starts on 16 bytes (the kernels load double2)
-    const size_t nRing = (size_t)nCh * ringSlots * P;
-    if (nRing > kDiagMaxElems || (size_t)nCh * inStride > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-    size_t nSideElems[2] = { 0, 0 };
-    double* sideOut[2] = { sideOut0, sideOut1 };
-    if (side) {
-        // the launcher's own precondition first (P = 512, at most two even-placed destinations, a table of <= 64 entries)
-        if (nSide < 0 || nSide > 2 || (nSide > 0 && (!sideStride || !sideOff))) return CPQ_ERR_INVALID_ARG;
-        if (!cpq::rfft_fwd_can_carry_side(P, nSide, sideStride, sideOff, nTab)) return CPQ_ERR_INVALID_ARG;
-        if (nTab > 0 && (!tab || !tabOut)) return CPQ_ERR_INVALID_ARG;
-        if (!tailOut || tailStride < 1 || tailLen > tailStride || (size_t)nCh * tailStride > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-        for (int a = 0; a < nSide; ++a) {          // destination a: [nCh][stride] doubles, the T blocks at off inside every row
-            if (!sideOut[a] || sideStride[a] < 1 || sideOff[a] < 0 || sideOff[a] + (int64_t)T * P > sideStride[a]) return CPQ_ERR_INVALID_ARG;
-            if ((uint64_t)sideStride[a] > kDiagMaxElems / (size_t)nCh) return CPQ_ERR_INVALID_ARG;
-            nSideElems[a] = (size_t)nCh * (size_t)sideStride[a];
-        }
-    } else if (tailLen != 0) return CPQ_ERR_INVALID_ARG;      // only the side launch moves a tail
-    if (!diagHaveDevice()) return CPQ_ERR_NO_DEVICE;
-
-    DiagTwiddles tw;
-    DeviceBuffer<double> dIn, dHistOld, dHistNew, dSide[2], dTail;
-    DeviceBuffer<double2> dX, dXdn, dScratch;
-    DeviceBuffer<long long> dTab;
-    if (!tw.upload(P)) return CPQ_ERR_DEVICE;
-    if (allocAll(nullptr, { { dIn, (size_t)nCh * inStride }, { dHistOld, (size_t)nCh * P }, { dHistNew, (size_t)nCh * P }, { dX, nRing },
-                            { dXdn, (size_t)nCh * ringSlots }, { dScratch, P > 4096 ? (size_t)nCh * T * P : 1 },
-                            { dSide[0], std::max<size_t>(nSideElems[0], 1) }, { dSide[1], std::max<size_t>(nSideElems[1], 1) },
-                            { dTail, side ? (size_t)nCh * tailStride : 1 }, { dTab, (size_t)cpq::kGatherTabMax } },
-                 "forward FFT diagnostic buffers could not be allocated") != CPQ_OK)
-        return CPQ_ERR_DEVICE;
-    int32_t rc = CPQ_OK;
-    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    {
-        ok(hipMemset(dIn, 0xFF, (size_t)nCh * inStride * sizeof(double)));      // (the pad element of an odd row stays NaN)
-        for (int c = 0; c < nCh; ++c)
-            ok(hipMemcpy(dIn + (size_t)c * inStride, in + (size_t)c * rowLen, rowLen * sizeof(double), hipMemcpyHostToDevice));
-        ok(hipMemcpy(dHistOld, histOld, (size_t)nCh * P * sizeof(double), hipMemcpyHostToDevice));
-        ok(hipMemset(dHistNew, 0xFF, (size_t)nCh * P * sizeof(double)));
-        ok(hipMemset(dX, 0xFF, nRing * sizeof(double2)));
-        ok(hipMemset(dXdn, 0xFF, (size_t)nCh * ringSlots * sizeof(double2)));
-        for (int a = 0; a < 2; ++a) ok(hipMemset(dSide[a], 0xFF, dSide[a].count() * sizeof(double)));
-        ok(hipMemset(dTail, 0xFF, dTail.count() * sizeof(double)));
-        ok(hipMemset(dTab, 0xFF, dTab.count() * sizeof(long long)));
-    }
-    if (rc == CPQ_OK) {
-        if (side) {
-            double* dst[2] = { dSide[0], dSide[1] };
-            static_assert(sizeof(long long) == sizeof(int64_t), "the table travels as long long");
-            cpq::launch_rfft_fwd_ols_side(nullptr, dIn, (int64_t)inStride, dHistOld, dHistNew, dX, dXdn, tw.tables(), nCh, T, head, ringSlots,
-                                          nSide, dst, sideStride, sideOff, nTab > 0 ? dTab.get() : nullptr,
-                                          reinterpret_cast<const long long*>(tab), nTab, dTail, tailStride, tailLen);
-        } else
-            cpq::launch_rfft_fwd_ols(nullptr, dIn, (int64_t)inStride, dHistOld, dHistNew, dX, dXdn, tw.tables(), P, nCh, T, head, ringSlots, dScratch);
-        ok(hipGetLastError());
-        ok(hipDeviceSynchronize());
-    }
-    if (rc == CPQ_OK) {
-        ok(hipMemcpy(ring, dX, nRing * sizeof(double2), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(xdn, dXdn, (size_t)nCh * ringSlots * sizeof(double2), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(histNew, dHistNew, (size_t)nCh * P * sizeof(double), hipMemcpyDeviceToHost));
-        if (side) {
-            for (int a = 0; a < nSide; ++a) ok(hipMemcpy(sideOut[a], dSide[a], nSideElems[a] * sizeof(double), hipMemcpyDeviceToHost));
-            if (tabOut) ok(hipMemcpy(tabOut, dTab, (size_t)cpq::kGatherTabMax * sizeof(long long), hipMemcpyDeviceToHost));
-            ok(hipMemcpy(tailOut, dTail, (size_t)nCh * tailStride * sizeof(double), hipMemcpyDeviceToHost));
-        }
-    }
-    return rc;
-}
-
-// The inverse transform's store modes in isolation: launch_rfft_inv_ols_ring (mode 1), launch_rfft_inv_ols_tail (mode 2) and
-// launch_rfft_inv_ols_add (mode 3) on spectra, rings, position tables and schedules the caller fills.  Same rules as above.
-int32_t cpq_diag_fft_inverse_store(int32_t mode, int32_t P, int32_t nCh, int32_t T, const double* spectra, double* ringA,
-                                   int32_t ringSizeA, const int64_t* posA, int64_t pos0, double* ringB, int32_t ringSizeB,
-                                   const int64_t* posB, const double* layerOut, const double* tailRing, int32_t tailRingSize,
-                                   const int64_t* tailState, const int64_t* sched, int32_t B, int32_t nTail, double g1, double g2,
-                                   double* out)
-{
-    if (mode < 1 || mode > 3 || !spectra) return CPQ_ERR_INVALID_ARG;
-    if (!diagPartition(P) || nCh < 1 || T < 1) return CPQ_ERR_INVALID_ARG;
-    const size_t nTime = (size_t)nCh * T * P;
-    if (nTime > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-    int nCb = 0;
-    if (mode == 1) {
-        // a ring of at least one block and of two elements, so that i and i + 1 are distinct; blocks that are written lie at
-        // least P apart on the ring (two workgroups never store to one element: every engine's positions advance by P)
-        if (!ringA || !diagPow2(ringSizeA) || ringSizeA < P || ringSizeA < 2 || (size_t)nCh * ringSizeA > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-        if (!posA && (pos0 < 0 || pos0 > kDiagMaxPos)) return CPQ_ERR_INVALID_ARG;
-        for (int t = 0; t < T; ++t) {
-            const long long pt = posA ? posA[t] : pos0 + (long long)t * P;
-            if (pt > kDiagMaxPos) return CPQ_ERR_INVALID_ARG;
-            if (pt < 0) continue;
-            for (int u = 0; u < t; ++u) {
-                const long long pu = posA ? posA[u] : pos0 + (long long)u * P;
-                if (pu < 0) continue;
-                const long long d = (pt - pu) & (ringSizeA - 1);
-                if (d < P || ringSizeA - d < P) return CPQ_ERR_INVALID_ARG;
-            }
-        }
-    } else if (mode == 2) {
-        if (P > 4096 || !out || !layerOut || !tailRing || !tailState || !sched) return CPQ_ERR_INVALID_ARG;
-        if (nTail < 1 || nTail > 2 || !diagPow2(B) || ((int64_t)T * P) % B != 0) return CPQ_ERR_INVALID_ARG;
-        if (!diagPow2(tailRingSize) || tailRingSize < 2 || (size_t)nTail * nCh * tailRingSize > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-        if ((size_t)nTail * nTime > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-        const long long g0 = tailState[3], nSamples = (long long)T * P;
-        if (g0 < 0 || g0 > kDiagMaxPos) return CPQ_ERR_INVALID_ARG;
-        nCb = (int)(nSamples / B);
-        // an entry's B samples end inside the call (samples at or behind g0 come from layerOut[.. nSamples); older ones from the ring)
-        for (long long i = 0; i < (long long)nTail * nCb; ++i)
-            if (sched[i] >= 0 && sched[i] + B > g0 + nSamples) return CPQ_ERR_INVALID_ARG;
-    } else {
-        if (P != cpq::kP || !out || !ringA || !posA) return CPQ_ERR_INVALID_ARG;
-        if (!diagPow2(ringSizeA) || ringSizeA < P || ringSizeA < 2 || (size_t)nCh * ringSizeA > kDiagMaxElems) return CPQ_ERR_INVALID_ARG;
-        if (ringB && (!posB || !diagPow2(ringSizeB) || ringSizeB < P || ringSizeB < 2 || (size_t)nCh * ringSizeB > kDiagMaxElems)) return CPQ_ERR_INVALID_ARG;
-        for (int t = 0; t < T; ++t)
-            if (posA[t] > kDiagMaxPos || (ringB && posB[t] > kDiagMaxPos)) return CPQ_ERR_INVALID_ARG;
-    }
-    if (!diagHaveDevice()) return CPQ_ERR_NO_DEVICE;
-
-    const size_t nRingA = mode != 2 ? (size_t)nCh * ringSizeA : 1, nRingB = (mode == 3 && ringB) ? (size_t)nCh * ringSizeB : 1;
-    const size_t nLayer = mode == 2 ? (size_t)nTail * nTime : 1, nTailRing = mode == 2 ? (size_t)nTail * nCh * tailRingSize : 1;
-    const size_t nSched = mode == 2 ? (size_t)nTail * nCb : (size_t)T;
-    DiagTwiddles tw;
-    DeviceBuffer<double2> dY, dScratch;
-    DeviceBuffer<double> dOut, dRingA, dRingB, dLayer, dTailRing;
-    DeviceBuffer<long long> dPosA, dPosB, dState;
-    if (!tw.upload(P)) return CPQ_ERR_DEVICE;
-    if (allocAll(nullptr, { { dY, nTime }, { dScratch, P > 4096 ? nTime : 1 }, { dOut, nTime }, { dRingA, nRingA }, { dRingB, nRingB },
-                            { dLayer, nLayer }, { dTailRing, nTailRing }, { dPosA, nSched }, { dPosB, (size_t)T }, { dState, 4 } },
-                 "inverse FFT diagnostic buffers could not be allocated") != CPQ_OK)
-        return CPQ_ERR_DEVICE;
-    int32_t rc = CPQ_OK;
-    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    {
-        ok(hipMemcpy(dY, spectra, nTime * sizeof(double2), hipMemcpyHostToDevice));
-        ok(hipMemset(dOut, 0xFF, nTime * sizeof(double)));
-        if (mode != 2) ok(hipMemcpy(dRingA, ringA, nRingA * sizeof(double), hipMemcpyHostToDevice));      // initial contents: the caller's
-        if (mode == 3 && ringB) {
-            ok(hipMemcpy(dRingB, ringB, nRingB * sizeof(double), hipMemcpyHostToDevice));
-            ok(hipMemcpy(dPosB, posB, (size_t)T * sizeof(long long), hipMemcpyHostToDevice));
-        }
-        if (mode != 2 && posA) ok(hipMemcpy(dPosA, posA, (size_t)T * sizeof(long long), hipMemcpyHostToDevice));
-        if (mode == 2) {
-            ok(hipMemcpy(dLayer, layerOut, nLayer * sizeof(double), hipMemcpyHostToDevice));
-            ok(hipMemcpy(dTailRing, tailRing, nTailRing * sizeof(double), hipMemcpyHostToDevice));
-            ok(hipMemcpy(dPosA, sched, nSched * sizeof(long long), hipMemcpyHostToDevice));
-            ok(hipMemcpy(dState, tailState, 4 * sizeof(long long), hipMemcpyHostToDevice));
-        }
-    }
-    if (rc == CPQ_OK) {
-        const int64_t stride = (int64_t)T * P;
-        if (mode == 1)
-            cpq::launch_rfft_inv_ols_ring(nullptr, dY, dRingA, ringSizeA, posA ? dPosA.get() : nullptr, pos0, tw.tables(), P, nCh, T, dScratch);
-        else if (mode == 2)
-            cpq::launch_rfft_inv_ols_tail(nullptr, dY, dOut, stride, tw.tables(), P, nCh, T, dScratch, dLayer, dTailRing, tailRingSize, dState,
-                                          dPosA, nCb, B, nTail, g1, g2);
-        else
-            cpq::launch_rfft_inv_ols_add(nullptr, dY, dOut, stride, tw.tables(), nCh, T, dRingA, ringSizeA, dPosA, g1,
-                                         ringB ? dRingB.get() : nullptr, ringB ? ringSizeB : 2, ringB ? dPosB.get() : nullptr, g2);
-        ok(hipGetLastError());
-        ok(hipDeviceSynchronize());
-    }
-    if (rc == CPQ_OK) {
-        if (mode != 1) ok(hipMemcpy(out, dOut, nTime * sizeof(double), hipMemcpyDeviceToHost));
-        if (mode != 2) ok(hipMemcpy(ringA, dRingA, nRingA * sizeof(double), hipMemcpyDeviceToHost));
-        if (mode == 3 && ringB) ok(hipMemcpy(ringB, dRingB, nRingB * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return rc;
-}
-
-// launch_ir_spectra and, with a gain, launch_spectrum_gain behind it, on one h_eff.  The device copy of h_eff holds
-// nParts * P elements, NaN from heffLen on: a load past the end cannot pass for a zero.
-int32_t cpq_diag_ir_spectra(int32_t P, int32_t nParts, const double* heff, int32_t heffLen, const double* gain, double* H, double* HDN,
-                            double* Hg, double* HDNg)
-{
-    if (!heff || !H || !HDN || (gain && (!Hg || !HDNg))) return CPQ_ERR_INVALID_ARG;
-    if (!diagPartition(P) || nParts < 1) return CPQ_ERR_INVALID_ARG;
-    const size_t n = (size_t)nParts * P;
-    if (n > kDiagMaxElems || heffLen < 1 || (size_t)heffLen > n) return CPQ_ERR_INVALID_ARG;
-    if (!diagHaveDevice()) return CPQ_ERR_NO_DEVICE;
-
-    DiagTwiddles tw;
-    DeviceBuffer<double> dHeff, dGain;
-    DeviceBuffer<double2> dH, dHdn, dScratch;
-    if (!tw.upload(P)) return CPQ_ERR_DEVICE;
-    if (allocAll(nullptr, { { dHeff, n }, { dGain, (size_t)P + 1 }, { dH, n }, { dHdn, (size_t)nParts }, { dScratch, P > 4096 ? n : 1 } },
-                 "IR spectra diagnostic buffers could not be allocated") != CPQ_OK)
-        return CPQ_ERR_DEVICE;
-    int32_t rc = CPQ_OK;
-    auto ok = [&](hipError_t err) { if (err != hipSuccess && rc == CPQ_OK) { (void)hipGetLastError(); rc = CPQ_ERR_DEVICE; } return err == hipSuccess; };
-    {
-        ok(hipMemset(dHeff, 0xFF, n * sizeof(double)));
-        ok(hipMemcpy(dHeff, heff, (size_t)heffLen * sizeof(double), hipMemcpyHostToDevice));
-        ok(hipMemset(dH, 0xFF, n * sizeof(double2)));
-        ok(hipMemset(dHdn, 0xFF, (size_t)nParts * sizeof(double2)));
-        if (gain) ok(hipMemcpy(dGain, gain, ((size_t)P + 1) * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (rc == CPQ_OK) {
-        cpq::launch_ir_spectra(nullptr, dHeff, heffLen, dH, dHdn, tw.tables(), P, nParts, dScratch);
-        ok(hipGetLastError());
-        ok(hipDeviceSynchronize());
-    }
-    if (rc == CPQ_OK) {
-        ok(hipMemcpy(H, dH, n * sizeof(double2), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(HDN, dHdn, (size_t)nParts * sizeof(double2), hipMemcpyDeviceToHost));
-    }
-    if (rc == CPQ_OK && gain) {
-        cpq::launch_spectrum_gain(nullptr, dH, dHdn, dGain, P, nParts);
-        ok(hipGetLastError());
-        ok(hipDeviceSynchronize());
-        if (rc == CPQ_OK) {
-            ok(hipMemcpy(Hg, dH, n * sizeof(double2), hipMemcpyDeviceToHost));
-            ok(hipMemcpy(HDNg, dHdn, (size_t)nParts * sizeof(double2), hipMemcpyDeviceToHost));
-        }
-    }
-    return rc;
-}
-
 // ------------------------------------------------------------------ host-only helpers
 int32_t cpq_nuc_plan_compute(int32_t irLen, int32_t blockSize, int32_t direct, const cpq_filter_spec* spec,
                              cpq_nuc_plan* plan)

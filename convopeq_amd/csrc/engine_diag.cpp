@@ -1,18 +1,25 @@
-// engine_diag.cpp -- the launchers of mix_kernels.hip in isolation (tests/test_gpu_mix_kernels.py): cpq_diag_direct_head, _agc,
-// _ring_chunks, _convproc_mix, _tail_reader and _rows of include/convopeq_mi355x.h.  Same conventions as the FFT and MAC
-// diagnostics of engine_core.cpp: host pointers, own device buffers of exactly the documented sizes, the null stream, no engine;
-// what a kernel may write is filled with 0xFF bytes unless the caller supplies its contents, and comes back whole; every
-// argument set with which a kernel would leave a buffer is refused before anything is allocated or a device is looked for.
+// engine_diag.cpp -- every cpq_diag_* entry of include/convopeq_mi355x.h: launchers on their own, for the tests of single kernels.
+//   partition FFT, FDL MAC           cpq_diag_partition_fft(_split), _fdl_mac      tests/test_gpu_fft.py, _fft_p4_frames.py, _fdl_mac.py
+//   FFT launch variants, IR spectra  cpq_diag_fft_forward, _fft_inverse_store, _ir_spectra                tests/test_gpu_fft_variants.py
+//   mix_kernels.hip                  cpq_diag_direct_head, _agc, _ring_chunks, _convproc_mix, _tail_reader, _rows    test_gpu_mix_kernels.py
+//   chained EQ spans of an engine    cpq_diag_eq_chain_status                                             tests/test_gpu_eq_chained.py
+// One convention for all but the last: host pointers, own device buffers of exactly the documented sizes (Scope), the null
+// stream, no engine; what a kernel may write is filled with 0xFF bytes (NaN) unless the caller supplies its contents, and comes
+// back whole; every argument set with which a kernel would leave a buffer is refused (CPQ_ERR_INVALID_ARG) before a device is
+// looked for (CPQ_ERR_NO_DEVICE) and before anything is allocated; an allocation or HIP failure is CPQ_ERR_DEVICE.  An entry
+// reads: validate, put, launch, get.
 #include "engine_internal.hpp"
 
 namespace {
 
 using cpqi::DeviceBuffer;
+using cpqi::fail;
 
 constexpr size_t kMaxElems = (size_t)1 << 28;      // per buffer: test tools
 constexpr long long kMaxPos = 1LL << 62;           // ring positions, cursors and schedule entries
 
 bool pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
+bool partition(int P) { return P >= 64 && P <= 131072 && pow2(P); }
 bool fits(long long a, long long b) { return a >= 0 && b >= 0 && (b == 0 || a <= (long long)kMaxElems / b); }      // a * b <= 2^28
 bool haveDevice()
 {
@@ -56,6 +63,22 @@ struct Scope {
 
 const long long* ll(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
 static_assert(sizeof(long long) == sizeof(int64_t), "tables travel as long long");
+const double2* c2(const double* p) { return reinterpret_cast<const double2*>(p); }      // spectra travel as [..][2] doubles
+double2* c2(double* p) { return reinterpret_cast<double2*>(p); }
+
+// the twiddle tables of one partition size on the device; second halves (P > 4096): the reordered tables of the four-step transforms
+cpq::FftTables twiddles(Scope& d, int P)
+{
+    std::vector<double2> w1, w2;
+    cpqi::hostTwiddles(P, w1, w2);
+    w1.resize((size_t)2 * P);
+    w2.resize((size_t)2 * P);
+    if (P > 4096) cpq::fill_big_twiddles(w1.data(), w2.data(), P, w1.data() + P, w2.data() + P);
+    const double2* tw = d.put(w1.data(), w1.size());
+    const double2* tw2 = d.put(w2.data(), w2.size());
+    if (d.rc != CPQ_OK || P <= 4096) return cpq::FftTables{ tw, tw2 };
+    return cpq::FftTables{ tw, tw2, tw + P, tw2 + P };
+}
 
 // chMap: every entry -1 or a row below `rows`, no row named twice
 bool chMapValid(const int32_t* chMap, int nCh, int rows)
@@ -72,6 +95,272 @@ bool chMapValid(const int32_t* chMap, int nCh, int rows)
 
 extern "C" {
 
+// The partition FFT kernels in isolation (tests/test_gpu_fft.py): forward of every overlap-save frame from a silent history,
+// inverse of the same spectra.
+int32_t cpq_diag_partition_fft(int32_t P, int32_t nCh, int32_t T, const double* in, double* spectra, double* out)
+{
+    return cpq_diag_partition_fft_split(P, nCh, T, 0, in, spectra, out);
+}
+
+// split > 0 at P = 4096: that many workgroups walk the frames of a channel (at most one per frame), so that a small test decides
+// how many consecutive frames one workgroup transforms; otherwise the launchers' own choice
+int32_t cpq_diag_partition_fft_split(int32_t P, int32_t nCh, int32_t T, int32_t split, const double* in, double* spectra, double* out)
+{
+    if (P != 4096 || split < 0) split = 0;
+    if (split > T || !partition(P) || nCh <= 0 || T <= 0 || !in || !spectra || !out) return CPQ_ERR_INVALID_ARG;
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    const int ringSlots = cpqi::nextPow2(T);
+    const size_t nTime = (size_t)nCh * T * P, nSpec = (size_t)nCh * ringSlots * P;
+    const cpq::FftTables tw = twiddles(d, P);
+    const double* dIn = d.put(in, nTime);
+    double* dHist = d.put<double>(nullptr, (size_t)2 * nCh * P, 0);
+    double2* dX = d.put<double2>(nullptr, nSpec, 0);
+    double2* dXdn = d.put<double2>(nullptr, (size_t)nCh * ringSlots);
+    double2* dScratch = d.put<double2>(nullptr, P > 4096 ? nTime : 0);
+    double2* dY = d.put<double2>(nullptr, nTime);
+    double* dOut = d.put<double>(nullptr, nTime);
+    if (d.rc == CPQ_OK) {
+        cpq::launch_rfft_fwd_ols(nullptr, dIn, (int64_t)T * P, dHist, dHist + (size_t)nCh * P, dX, dXdn, tw, P, nCh, T, 0, ringSlots, dScratch, split);
+        // the ring holds block t of channel c at [c][t] of ringSlots slots: [c][t] of T slots for the inverse and the caller
+        for (int c = 0; c < nCh && d.rc == CPQ_OK; ++c)
+            d.ok(hipMemcpyAsync(dY + (size_t)c * T * P, dX + (size_t)c * ringSlots * P, (size_t)T * P * sizeof(double2), hipMemcpyDeviceToDevice, nullptr));
+        cpq::launch_rfft_inv_ols(nullptr, dY, dOut, (int64_t)T * P, tw, P, nCh, T, dScratch, split);
+        d.launched();
+    }
+    d.get(c2(spectra), dY, nTime);
+    d.get(out, dOut, nTime);
+    return d.rc;
+}
+
+// The FDL multiply-accumulate kernels in isolation (tests/test_gpu_fdl_mac.py): what engine_conv.cpp / engine_native.cpp launch
+// for one call -- launch_fdl_mac, then launch_fdl_mac_dcnyq when the variant leaves packed bin 0 to it -- on buffers the caller
+// fills in the kernels' own layouts (extents: kernels.hpp, launch_fdl_mac).
+int32_t cpq_diag_fdl_mac(int32_t P, int32_t nCh, int32_t K, int32_t T, int32_t tile, int32_t head, int32_t ringSlots,
+                         int32_t nIrSlots, int32_t hRows, int32_t hPrivate, const double* x, const double* h,
+                         const int32_t* irSlot, double* y, int32_t* variantUsed)
+{
+    if (!x || !h || !irSlot || !y || !variantUsed) return CPQ_ERR_INVALID_ARG;
+    if (!partition(P) || P > 4096 || nCh < 1 || K < 1 || T < 1 || nIrSlots < 1) return CPQ_ERR_INVALID_ARG;
+    if (tile != 0 && tile != 4 && tile != 8 && tile != 16 && tile != 32 && tile != cpq::kMacTileCoop) return CPQ_ERR_INVALID_ARG;
+    // the engines' own sizing rules (engine_core.cpp: ringSlots; engine_native.cpp layerGeometry: hRows, the smaller of the two)
+    const int64_t kPad32 = cpqi::alignUp(K, cpq::kMacMaxTile);
+    int64_t ringMin = 1;
+    while (ringMin < kPad32 + cpq::kMacMaxTile + T) ringMin <<= 1;
+    if (!pow2(ringSlots) || ringSlots < ringMin) return CPQ_ERR_INVALID_ARG;
+    if (hRows < kPad32 + 16) return CPQ_ERR_INVALID_ARG;
+    if (head < 0 || head >= ringSlots) return CPQ_ERR_INVALID_ARG;
+    for (int c = 0; c < nCh; ++c)
+        if (irSlot[c] < 0 || irSlot[c] >= nIrSlots) return CPQ_ERR_INVALID_ARG;
+    const size_t nX = (size_t)nCh * ringSlots * P, nH = (size_t)nIrSlots * hRows * P, nY = (size_t)nCh * T * P;
+    if (nX > kMaxElems || nH > kMaxElems || nY > kMaxElems) return CPQ_ERR_INVALID_ARG;
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+    *variantUsed = cpq::fdl_mac_variant(tile, T);
+
+    // compact (DC, Nyquist) rows: element 0 of every spectrum, which is what the forward FFT and launch_ir_spectra store there
+    std::vector<double2> xdn((size_t)nCh * ringSlots), hdn((size_t)nIrSlots * hRows);
+    for (size_t i = 0; i < xdn.size(); ++i) xdn[i] = c2(x)[i * P];
+    for (size_t i = 0; i < hdn.size(); ++i) hdn[i] = c2(h)[i * P];
+
+    Scope d;
+    const double2* dX = d.put(c2(x), nX);
+    const double2* dH = d.put(c2(h), nH);
+    const double2* dXdn = d.put(xdn.data(), xdn.size());
+    const double2* dHdn = d.put(hdn.data(), hdn.size());
+    const int* dSlot = d.put(irSlot, nCh);
+    double2* dY = d.put<double2>(nullptr, nY);          // NaN: an element no kernel stores cannot pass for a result
+    if (d.rc == CPQ_OK) {
+        cpq::launch_fdl_mac(nullptr, tile, dX, dH, dSlot, dY, P, nCh, K, ringSlots, head, T, (int64_t)hRows * P, hPrivate != 0);
+        if (cpq::fdl_mac_needs_dcnyq(tile, T))
+            cpq::launch_fdl_mac_dcnyq(nullptr, dXdn, dHdn, dSlot, dY, P, nCh, K, ringSlots, head, T, hRows);
+        d.launched();
+    }
+    d.get(c2(y), dY, nY);
+    return d.rc;
+}
+
+// The forward transform launches in isolation (tests/test_gpu_fft_variants.py): launch_rfft_fwd_ols, or with side != 0
+// launch_rfft_fwd_ols_side, as engine_conv.cpp / engine_native.cpp make them -- a moving head, a carried history, a ring that
+// wraps.
+int32_t cpq_diag_fft_forward(int32_t P, int32_t nCh, int32_t T, int32_t head, int32_t ringSlots, int32_t tailLen, const double* in,
+                             const double* histOld, int32_t side, int32_t nSide, const int64_t* sideStride, const int64_t* sideOff,
+                             const int64_t* tab, int32_t nTab, int32_t tailStride, double* ring, double* xdn, double* histNew,
+                             double* sideOut0, double* sideOut1, int64_t* tabOut, double* tailOut)
+{
+    if (!in || !histOld || !ring || !xdn || !histNew) return CPQ_ERR_INVALID_ARG;
+    if (!partition(P) || nCh < 1 || T < 1 || tailLen < 0) return CPQ_ERR_INVALID_ARG;
+    if (!pow2(ringSlots) || ringSlots < T || head < 0 || head >= ringSlots) return CPQ_ERR_INVALID_ARG;
+    const size_t rowLen = (size_t)T * P + (size_t)tailLen;
+    const size_t inStride = rowLen + (rowLen & 1);          // even: every channel's row starts on 16 bytes (the kernels load double2)
+    const size_t nRing = (size_t)nCh * ringSlots * P, nHist = (size_t)nCh * P, nTail = side ? (size_t)nCh * tailStride : 0;
+    if (nRing > kMaxElems || (size_t)nCh * inStride > kMaxElems) return CPQ_ERR_INVALID_ARG;
+    size_t nSideElems[2] = { 0, 0 };
+    double* sideOut[2] = { sideOut0, sideOut1 };
+    if (side) {
+        // the launcher's own precondition first (P = 512, at most two even-placed destinations, a table of <= 64 entries)
+        if (nSide < 0 || nSide > 2 || (nSide > 0 && (!sideStride || !sideOff))) return CPQ_ERR_INVALID_ARG;
+        if (!cpq::rfft_fwd_can_carry_side(P, nSide, sideStride, sideOff, nTab)) return CPQ_ERR_INVALID_ARG;
+        if (nTab > 0 && (!tab || !tabOut)) return CPQ_ERR_INVALID_ARG;
+        if (!tailOut || tailStride < 1 || tailLen > tailStride || nTail > kMaxElems) return CPQ_ERR_INVALID_ARG;
+        for (int a = 0; a < nSide; ++a) {          // destination a: [nCh][stride] doubles, the T blocks at off inside every row
+            if (!sideOut[a] || sideStride[a] < 1 || sideOff[a] < 0 || sideOff[a] + (int64_t)T * P > sideStride[a]) return CPQ_ERR_INVALID_ARG;
+            if ((uint64_t)sideStride[a] > kMaxElems / (size_t)nCh) return CPQ_ERR_INVALID_ARG;
+            nSideElems[a] = (size_t)nCh * (size_t)sideStride[a];
+        }
+    } else if (tailLen != 0) return CPQ_ERR_INVALID_ARG;      // only the side launch moves a tail
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    const cpq::FftTables tw = twiddles(d, P);
+    double* dIn = d.put<double>(nullptr, (size_t)nCh * inStride);      // (the pad element of an odd row stays NaN)
+    for (int c = 0; c < nCh && d.rc == CPQ_OK; ++c)
+        d.ok(hipMemcpy(dIn + (size_t)c * inStride, in + (size_t)c * rowLen, rowLen * sizeof(double), hipMemcpyHostToDevice));
+    const double* dHistOld = d.put(histOld, nHist);
+    double* dHistNew = d.put<double>(nullptr, nHist);
+    double2* dX = d.put<double2>(nullptr, nRing);
+    double2* dXdn = d.put<double2>(nullptr, (size_t)nCh * ringSlots);
+    double2* dScratch = d.put<double2>(nullptr, P > 4096 ? (size_t)nCh * T * P : 0);
+    double* dSide[2] = { d.put<double>(nullptr, nSideElems[0]), d.put<double>(nullptr, nSideElems[1]) };
+    double* dTail = d.put<double>(nullptr, nTail);
+    long long* dTab = d.put<long long>(nullptr, cpq::kGatherTabMax);
+    if (d.rc == CPQ_OK) {
+        if (side)
+            cpq::launch_rfft_fwd_ols_side(nullptr, dIn, (int64_t)inStride, dHistOld, dHistNew, dX, dXdn, tw, nCh, T, head, ringSlots, nSide,
+                                          dSide, sideStride, sideOff, nTab > 0 ? dTab : nullptr, ll(tab), nTab, dTail, tailStride, tailLen);
+        else
+            cpq::launch_rfft_fwd_ols(nullptr, dIn, (int64_t)inStride, dHistOld, dHistNew, dX, dXdn, tw, P, nCh, T, head, ringSlots, dScratch);
+        d.launched();
+    }
+    d.get(c2(ring), dX, nRing);
+    d.get(c2(xdn), dXdn, (size_t)nCh * ringSlots);
+    d.get(histNew, dHistNew, nHist);
+    if (side) {
+        for (int a = 0; a < nSide; ++a) d.get(sideOut[a], dSide[a], nSideElems[a]);
+        d.get(reinterpret_cast<long long*>(tabOut), dTab, cpq::kGatherTabMax);
+        d.get(tailOut, dTail, nTail);
+    }
+    return d.rc;
+}
+
+// The inverse transform's store modes in isolation: launch_rfft_inv_ols_ring (mode 1), launch_rfft_inv_ols_tail (mode 2) and
+// launch_rfft_inv_ols_add (mode 3) on spectra, rings, position tables and schedules the caller fills.
+int32_t cpq_diag_fft_inverse_store(int32_t mode, int32_t P, int32_t nCh, int32_t T, const double* spectra, double* ringA,
+                                   int32_t ringSizeA, const int64_t* posA, int64_t pos0, double* ringB, int32_t ringSizeB,
+                                   const int64_t* posB, const double* layerOut, const double* tailRing, int32_t tailRingSize,
+                                   const int64_t* tailState, const int64_t* sched, int32_t B, int32_t nTail, double g1, double g2,
+                                   double* out)
+{
+    if (mode < 1 || mode > 3 || !spectra) return CPQ_ERR_INVALID_ARG;
+    if (!partition(P) || nCh < 1 || T < 1) return CPQ_ERR_INVALID_ARG;
+    const size_t nTime = (size_t)nCh * T * P;
+    if (nTime > kMaxElems) return CPQ_ERR_INVALID_ARG;
+    int nCb = 0;
+    if (mode == 1) {
+        // a ring of at least one block and of two elements, so that i and i + 1 are distinct; blocks that are written lie at
+        // least P apart on the ring (two workgroups never store to one element: every engine's positions advance by P)
+        if (!ringA || !pow2(ringSizeA) || ringSizeA < P || ringSizeA < 2 || (size_t)nCh * ringSizeA > kMaxElems) return CPQ_ERR_INVALID_ARG;
+        if (!posA && (pos0 < 0 || pos0 > kMaxPos)) return CPQ_ERR_INVALID_ARG;
+        for (int t = 0; t < T; ++t) {
+            const long long pt = posA ? posA[t] : pos0 + (long long)t * P;
+            if (pt > kMaxPos) return CPQ_ERR_INVALID_ARG;
+            if (pt < 0) continue;
+            for (int u = 0; u < t; ++u) {
+                const long long pu = posA ? posA[u] : pos0 + (long long)u * P;
+                if (pu < 0) continue;
+                const long long gap = (pt - pu) & (ringSizeA - 1);
+                if (gap < P || ringSizeA - gap < P) return CPQ_ERR_INVALID_ARG;
+            }
+        }
+    } else if (mode == 2) {
+        if (P > 4096 || !out || !layerOut || !tailRing || !tailState || !sched) return CPQ_ERR_INVALID_ARG;
+        if (nTail < 1 || nTail > 2 || !pow2(B) || ((int64_t)T * P) % B != 0) return CPQ_ERR_INVALID_ARG;
+        if (!pow2(tailRingSize) || tailRingSize < 2 || (size_t)nTail * nCh * tailRingSize > kMaxElems) return CPQ_ERR_INVALID_ARG;
+        if ((size_t)nTail * nTime > kMaxElems) return CPQ_ERR_INVALID_ARG;
+        const long long g0 = tailState[3], nSamples = (long long)T * P;
+        if (g0 < 0 || g0 > kMaxPos) return CPQ_ERR_INVALID_ARG;
+        nCb = (int)(nSamples / B);
+        // an entry's B samples end inside the call (samples at or behind g0 come from layerOut[.. nSamples); older ones from the ring)
+        for (long long i = 0; i < (long long)nTail * nCb; ++i)
+            if (sched[i] >= 0 && sched[i] + B > g0 + nSamples) return CPQ_ERR_INVALID_ARG;
+    } else {
+        if (P != cpq::kP || !out || !ringA || !posA) return CPQ_ERR_INVALID_ARG;
+        if (!pow2(ringSizeA) || ringSizeA < P || ringSizeA < 2 || (size_t)nCh * ringSizeA > kMaxElems) return CPQ_ERR_INVALID_ARG;
+        if (ringB && (!posB || !pow2(ringSizeB) || ringSizeB < P || ringSizeB < 2 || (size_t)nCh * ringSizeB > kMaxElems)) return CPQ_ERR_INVALID_ARG;
+        for (int t = 0; t < T; ++t)
+            if (posA[t] > kMaxPos || (ringB && posB[t] > kMaxPos)) return CPQ_ERR_INVALID_ARG;
+    }
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    const cpq::FftTables tw = twiddles(d, P);
+    const int64_t stride = (int64_t)T * P;
+    const size_t nRingA = (size_t)nCh * ringSizeA, nRingB = (size_t)nCh * ringSizeB;
+    const double2* dY = d.put(c2(spectra), nTime);
+    double2* dScratch = d.put<double2>(nullptr, P > 4096 ? nTime : 0);
+    double* dOut = mode != 1 ? d.put<double>(nullptr, nTime) : nullptr;
+    double* dRingA = mode != 2 ? d.put(ringA, nRingA) : nullptr;          // initial contents: the caller's
+    if (mode == 1) {
+        const long long* dPosA = posA ? d.put(ll(posA), T) : nullptr;
+        if (d.rc == CPQ_OK) { cpq::launch_rfft_inv_ols_ring(nullptr, dY, dRingA, ringSizeA, dPosA, pos0, tw, P, nCh, T, dScratch); d.launched(); }
+    } else if (mode == 2) {
+        const double* dLayer = d.put(layerOut, (size_t)nTail * nTime);
+        const double* dTailRing = d.put(tailRing, (size_t)nTail * nCh * tailRingSize);
+        const long long* dSched = d.put(ll(sched), (size_t)nTail * nCb);
+        const long long* dState = d.put(ll(tailState), 4);
+        if (d.rc == CPQ_OK) {
+            cpq::launch_rfft_inv_ols_tail(nullptr, dY, dOut, stride, tw, P, nCh, T, dScratch, dLayer, dTailRing, tailRingSize, dState, dSched,
+                                          nCb, B, nTail, g1, g2);
+            d.launched();
+        }
+    } else {
+        const long long* dPosA = d.put(ll(posA), T);
+        double* dRingB = ringB ? d.put(ringB, nRingB) : nullptr;
+        const long long* dPosB = ringB ? d.put(ll(posB), T) : nullptr;
+        if (d.rc == CPQ_OK) {
+            cpq::launch_rfft_inv_ols_add(nullptr, dY, dOut, stride, tw, nCh, T, dRingA, ringSizeA, dPosA, g1, dRingB, ringB ? ringSizeB : 2,
+                                         dPosB, g2);
+            d.launched();
+        }
+        d.get(ringB, dRingB, nRingB);
+    }
+    if (mode != 1) d.get(out, dOut, nTime);
+    if (mode != 2) d.get(ringA, dRingA, nRingA);
+    return d.rc;
+}
+
+// launch_ir_spectra and, with a gain, launch_spectrum_gain behind it, on one h_eff.  The device copy of h_eff holds
+// nParts * P elements, NaN from heffLen on: a load past the end cannot pass for a zero.
+int32_t cpq_diag_ir_spectra(int32_t P, int32_t nParts, const double* heff, int32_t heffLen, const double* gain, double* H, double* HDN,
+                            double* Hg, double* HDNg)
+{
+    if (!heff || !H || !HDN || (gain && (!Hg || !HDNg))) return CPQ_ERR_INVALID_ARG;
+    if (!partition(P) || nParts < 1) return CPQ_ERR_INVALID_ARG;
+    const size_t n = (size_t)nParts * P;
+    if (n > kMaxElems || heffLen < 1 || (size_t)heffLen > n) return CPQ_ERR_INVALID_ARG;
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    const cpq::FftTables tw = twiddles(d, P);
+    double* dHeff = d.put<double>(nullptr, n);
+    if (d.rc == CPQ_OK) d.ok(hipMemcpy(dHeff, heff, (size_t)heffLen * sizeof(double), hipMemcpyHostToDevice));
+    const double* dGain = gain ? d.put(gain, (size_t)P + 1) : nullptr;
+    double2* dH = d.put<double2>(nullptr, n);
+    double2* dHdn = d.put<double2>(nullptr, nParts);
+    double2* dScratch = d.put<double2>(nullptr, P > 4096 ? n : 0);
+    if (d.rc == CPQ_OK) { cpq::launch_ir_spectra(nullptr, dHeff, heffLen, dH, dHdn, tw, P, nParts, dScratch); d.launched(); }
+    d.get(c2(H), dH, n);
+    d.get(c2(HDN), dHdn, nParts);
+    if (gain && d.rc == CPQ_OK) {          // only now: the ungained spectra are with the caller
+        cpq::launch_spectrum_gain(nullptr, dH, dHdn, dGain, P, nParts);
+        d.launched();
+        d.get(c2(Hg), dH, n);
+        d.get(c2(HDNg), dHdn, nParts);
+    }
+    return d.rc;
+}
+
+// ---------------------------------------------------------------- the launchers of mix_kernels.hip (tests/test_gpu_mix_kernels.py)
 int32_t cpq_diag_direct_head(int32_t nCh, int32_t n, int64_t inStride, int32_t nSlots, const double* in, const double* irRev,
                              const int32_t* taps, const int32_t* irSlot, const double* histOld, const int32_t* wetOn, double* dout,
                              double* histNew, double* out, int64_t outStride)
@@ -365,6 +654,22 @@ int32_t cpq_diag_rows(int32_t op, int32_t nCh, int32_t n, const double* src, int
     }
     d.get(dst, dDst, nDst);
     return d.rc;
+}
+
+// needs the engine: the header of its chained-span launches
+int32_t cpq_diag_eq_chain_status(cpq_engine* e, uint32_t* launches, uint32_t* gaveUp)
+{
+    if (!e || !launches || !gaveUp) return CPQ_ERR_INVALID_ARG;
+    *launches = 0;
+    *gaveUp = 0;
+    if (!e->svfChain || e->svfChainSpans <= 0) return CPQ_OK;
+    (void)hipSetDevice(e->device);
+    uint32_t hdr[4] = { 0, 0, 0, 0 };          // generation, finished workgroups, ticket, error (svf_kernels.hip: TpvChainHeader)
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    CPQ_HIP(e, hipMemcpy(hdr, e->svfChain, sizeof(hdr), hipMemcpyDeviceToHost));
+    *launches = hdr[0];
+    *gaveUp = hdr[3];
+    return CPQ_OK;
 }
 
 }  // extern "C"

@@ -1,10 +1,14 @@
 // engine_internal.hpp -- the engine object behind the C ABI and the helpers its translation units share:
 //   engine_core.cpp  create / destroy / prepare, status and profiling entry points, DSPCore routing (whole path)
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
+//   engine_native.cpp  plan groups: streams whose convolver runs on the reference's own layer plan, replayed per chunk
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
 //   engine_eq.cpp    EQ and output filter: design, device tables, bypass / band-reset state machine
+//   engine_os.cpp    half-band oversampler around the routing: stage buffers, per-stream state machine
 //   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
 //   engine_out.cpp   output stage: DC blocker, headroom, limiter and clamp on the delivered rows
+//   engine_meter.cpp  loudness and true-peak metering of the delivered rows
+//   engine_diag.cpp  every cpq_diag_* entry point: single launchers on caller-filled buffers, no engine
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per

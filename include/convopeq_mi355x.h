@@ -661,7 +661,7 @@ int32_t     cpq_profile_reset(cpq_engine* e);
 int32_t     cpq_profile_read(cpq_engine* e, int32_t kernel_id, int64_t* launches, double* total_ms);
 const char* cpq_kernel_name(int32_t kernel_id);
 
-/* ---------------------------------------------------------------- diagnostics */
+/* ---------------------------------------------------------------- diagnostics (all defined in csrc/engine_diag.cpp) */
 /* The partition FFT on its own (what replaces ProductionFft::forwardRealToCCS / inverseCCSToR, src/FFTBackend.cpp:123-150,
  * inside processLayerBlock): for n_channels x n_blocks blocks of `partition` samples (host, [channel][block][sample]; the
  * history before block 0 is silence) the forward transform of every overlap-save frame [previous block | block]

@@ -58,6 +58,8 @@ import fractions
 import numpy as np
 import pytest
 
+from mac_fft_calls import INVALID_ARG, MAC_BAD as BAD_ARGS, MAC_GOOD as GOOD, MAC_POINTERS, mac_buffers, mac_call
+
 pytestmark = pytest.mark.gpu
 
 COOP = -1                       # tile value of the diagnostic that forces the workgroup-cooperative kernel at any T
@@ -66,7 +68,6 @@ VID = {4: "4", 8: "8", 16: "16", 32: "32", COOP: "coop"}
 K_SWEEP = list(range(1, 26)) + [31, 32, 33, 63, 64, 65, 259]
 K_ANCHORS = [3, 9, 16, 33]
 POISON = float(2 ** 40)
-INVALID_ARG = -1
 
 
 @pytest.fixture(scope="module")
@@ -375,61 +376,23 @@ def test_one_call_equals_two(lib, tile, T, T1):
 
 
 # ---------------------------------------------------------------------------------------------- d. argument errors
-GOOD = dict(P=64, n_ch=2, K=5, T=3, tile=4, head=1, ring=128, n_slots=2, h_rows=48, slots=(0, 1))
-BAD_ARGS = {
-    "ring not a power of two": dict(ring=96),
-    "ring below the engines' rule": dict(ring=64),                  # nextPow2(32 + 32 + 3) = 128
-    "ring zero": dict(ring=0),
-    "h_rows below alignUp(K, 32) + 16": dict(h_rows=47),
-    "ir_slot negative": dict(slots=(0, -1)),
-    "ir_slot = n_ir_slots": dict(slots=(2, 0)),
-    "head negative": dict(head=-1),
-    "head = ring_slots": dict(head=128),
-    "P below 64": dict(P=32),
-    "P above 4096": dict(P=8192),
-    "P not a power of two": dict(P=96),
-    "K zero": dict(K=0),
-    "T zero": dict(T=0),
-    "no channels": dict(n_ch=0),
-    "no IR slots": dict(n_slots=0),
-    "unknown tile": dict(tile=5),
-}
-
-
+# (the table and its caller: tests/mac_fft_calls.py, which tests/test_host_and_abi_cpu.py walks without a device)
 @pytest.mark.parametrize("what", list(BAD_ARGS))
 def test_argument_errors(lib, what):
     a = dict(GOOD, **BAD_ARGS[what])
-    # buffers sized for the good arguments or the bad ones, whichever is larger: a refusal must not depend on reading them
-    P, n_ch, ring = max(a["P"], 64), max(a["n_ch"], 2), max(a["ring"], 128)
-    X = np.ones((n_ch, ring, P, 2))
-    H = np.ones((max(a["n_slots"], 2), max(a["h_rows"], 48), P, 2))
-    Y = np.full((n_ch, max(a["T"], 3), P, 2), -7.0)
-    used = C.c_int32(-99)
-    dp = lambda arr: arr.ctypes.data_as(C.POINTER(C.c_double))
-
-    def call(v, x=X, h=H):
-        slots = np.array(v["slots"], dtype=np.int32)
-        return lib.cpq_diag_fdl_mac(v["P"], v["n_ch"], v["K"], v["T"], v["tile"], v["head"], v["ring"], v["n_slots"], v["h_rows"], 0,
-                                    dp(x), dp(h), slots.ctypes.data_as(C.POINTER(C.c_int32)), dp(Y), C.byref(used))
-
-    assert call(a) == INVALID_ARG, what
+    X, H, Y, used = mac_buffers(a)
+    assert mac_call(lib, a, X, H, Y, used) == INVALID_ARG, what
     assert used.value == -99 and (Y == -7.0).all()                  # refused before anything ran
     # the call after it, with good arguments, succeeds and computes K = 5 ones times ones
     Xg, Hg = np.ones((2, 128, 64, 2)), np.ones((2, 48, 64, 2))
-    assert call(GOOD, Xg, Hg) == 0
+    assert mac_call(lib, GOOD, Xg, Hg, Y, used) == 0
     assert used.value == 4
     got = Y.reshape(-1)[:2 * 3 * 64 * 2].reshape(2, 3, 64, 2)
     assert (got[:, :, 1:, 0] == 0.0).all() and (got[:, :, 1:, 1] == 10.0).all() and (got[:, :, 0] == 5.0).all()
 
 
 def test_null_pointers_are_refused(lib):
-    X, H = np.ones((2, 128, 64, 2)), np.ones((2, 48, 64, 2))
-    Y = np.empty((2, 3, 64, 2))
-    slots = np.array([0, 1], dtype=np.int32)
-    used = C.c_int32(0)
-    dp = lambda arr: arr.ctypes.data_as(C.POINTER(C.c_double))
-    sp = slots.ctypes.data_as(C.POINTER(C.c_int32))
-    for args in ((None, dp(H), sp, dp(Y), C.byref(used)), (dp(X), None, sp, dp(Y), C.byref(used)), (dp(X), dp(H), None, dp(Y), C.byref(used)),
-                 (dp(X), dp(H), sp, None, C.byref(used)), (dp(X), dp(H), sp, dp(Y), None)):
-        assert lib.cpq_diag_fdl_mac(64, 2, 5, 3, 4, 1, 128, 2, 48, 0, *args) == INVALID_ARG
-    assert lib.cpq_diag_fdl_mac(64, 2, 5, 3, 4, 1, 128, 2, 48, 0, dp(X), dp(H), sp, dp(Y), C.byref(used)) == 0
+    X, H, Y, used = mac_buffers()
+    for name in MAC_POINTERS:
+        assert mac_call(lib, GOOD, X, H, Y, used, null=name) == INVALID_ARG
+    assert mac_call(lib, GOOD, X, H, Y, used) == 0

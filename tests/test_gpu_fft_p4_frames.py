@@ -25,6 +25,7 @@ import pytest
 
 import fft_layout
 from fft_layout import dp
+from mac_fft_calls import FFT_BAD, FFT_GOOD, FFT_VALID, INVALID_ARG, fft_split_call
 
 pytestmark = pytest.mark.gpu
 
@@ -95,19 +96,23 @@ def test_p4_frame_ranges(lib, n_ch, n_blocks, split):
 
 def test_split_argument(lib):
     """split <= 0 is the engine's own choice (the result of cpq_diag_partition_fft); more workgroups than frames are refused;
-    other partitions ignore the argument"""
-    x = _input(3, 5)
-    spec0, out0 = np.empty((3, 5, P, 2)), np.empty((3, 5, P))
-    assert lib.cpq_diag_partition_fft(P, 3, 5, dp(x), dp(spec0), dp(out0)) == 0
-    for split in (0, -3, 5):
-        spec, out = _run(lib, x, split)
-        assert np.array_equal(spec, spec0) and np.array_equal(out, out0), split
-    assert lib.cpq_diag_partition_fft_split(P, 3, 5, 6, dp(x), dp(spec0), dp(out0)) != 0
+    other partitions ignore the argument.  The argument sets: tests/mac_fft_calls.py, walked without a device too"""
+    n_ch, T = FFT_GOOD["n_ch"], FFT_GOOD["T"]
+    x = _input(n_ch, T)
+    spec0, out0 = np.empty((n_ch, T, P, 2)), np.empty((n_ch, T, P))
+    assert lib.cpq_diag_partition_fft(P, n_ch, T, dp(x), dp(spec0), dp(out0)) == 0
     y = np.ascontiguousarray(x[:, :, :512])
-    a, b = (np.empty((3, 5, 512, 2)), np.empty((3, 5, 512))), (np.empty((3, 5, 512, 2)), np.empty((3, 5, 512)))
-    assert lib.cpq_diag_partition_fft(512, 3, 5, dp(y), dp(a[0]), dp(a[1])) == 0
-    assert lib.cpq_diag_partition_fft_split(512, 3, 5, 4, dp(y), dp(b[0]), dp(b[1])) == 0
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    a = np.empty((n_ch, T, 512, 2)), np.empty((n_ch, T, 512))
+    assert lib.cpq_diag_partition_fft(512, n_ch, T, dp(y), dp(a[0]), dp(a[1])) == 0
+    for what, override in FFT_VALID.items():
+        v = dict(FFT_GOOD, **override)
+        rc, spec, out = fft_split_call(lib, v, x if v["P"] == P else y)
+        assert rc == 0, what
+        want = (spec0, out0) if v["P"] == P else a
+        assert np.array_equal(spec, want[0]) and np.array_equal(out, want[1]), what
+    assert fft_split_call(lib, dict(FFT_GOOD, **FFT_BAD["split = T + 1"]), x)[0] == INVALID_ARG
+    rc, spec, out = fft_split_call(lib, dict(FFT_GOOD, P=512, split=4), y)
+    assert rc == 0 and np.array_equal(spec, a[0]) and np.array_equal(out, a[1])
 
 
 def test_engine_two_calls_of_3_and_5_partitions(lib, oracle):

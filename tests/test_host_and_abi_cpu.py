@@ -181,6 +181,24 @@ def test_mix_kernel_diagnostics_refuse_before_looking_for_a_device(amd):
         assert {rc for _, rc, _, _ in K.valid_calls(lib)} == {K.NO_DEVICE}
 
 
+def test_mac_and_partition_fft_diagnostics_refuse_before_looking_for_a_device(amd):
+    """cpq_diag_fdl_mac / cpq_diag_partition_fft_split: every refusal rule and every null pointer once (tests/mac_fft_calls.py,
+    the tables the device tests import) is CPQ_ERR_INVALID_ARG without a device, with the outputs and *variant_used as they
+    were; the valid sets get past the checks and, without a GPU, end at CPQ_ERR_NO_DEVICE with the outputs as they were"""
+    import torch
+    import mac_fft_calls as M
+    from convopeq_amd import _capi
+    lib = _capi.load()
+    res = M.walk_refusals(lib)
+    assert len(res) == len(M.MAC_BAD) + len(M.MAC_POINTERS) + len(M.FFT_BAD) + len(M.FFT_POINTERS) >= 30
+    assert {k for k, _, _, _ in res} == {"fdl_mac", "partition_fft_split"}
+    assert [r for r in res if r[2:] != (_capi.CPQ_ERR_INVALID_ARG, True)] == []
+    if not torch.cuda.is_available():
+        valid = M.valid_calls(lib)
+        assert len(valid) == 1 + len(M.FFT_VALID) == 5
+        assert [r for r in valid if r[2:] != (M.NO_DEVICE, True)] == []
+
+
 def test_outfilter_design_matches_oracle_and_rbj(amd, oracle):
     """N2: OutputFilter::prepare coefficient design through the C ABI == oracle restatement; sanity vs scipy."""
     from scipy.signal import freqz
