@@ -1,17 +1,46 @@
-// fft_kernels.hip -- wave-level fp64 real FFT kernels for gfx950 (CDNA4, wave64).
+// fft_kernels.hip -- fp64 real FFT kernels for gfx950 (CDNA4, wave64): the partition transforms of the convolver.
 //
-// One wavefront computes one 1024-point real transform as a 512-point complex FFT: 8 complex points
-// per lane in registers, three radix-8 passes, two exchanges through 9 KB of LDS whose strides (72 and
-// 66 complex) keep every ds_read_b128/ds_write_b128 lane group on distinct banks, then the real-FFT
-// split.  The overlap-save framing of the reference (copy [prev|cur], src/MKLNonUniformConvolver.cpp:
-// 1256-1258), its CCS de-interleave (:132-139, :1270-1283) and the output half selection (:1332) are
-// fused into the loads/stores, so a frame is read once from HBM and a spectrum written once.
+// A P-sample partition is transformed as the 2P-point real FFT of an overlap-save frame, computed as a P-point complex
+// FFT of z[n] = x[2n] + i x[2n+1] followed by the real-FFT split.  The overlap-save framing of the reference (copy
+// [prev|cur], src/MKLNonUniformConvolver.cpp:1256-1258), its CCS de-interleave (:132-139, :1270-1283) and the output half
+// selection (:1332) are fused into the loads/stores, so a frame is read once from HBM and a spectrum written once.
 //
 // Replaces ippsFFTFwd_RToCCS_64f / ippsFFTInv_CCSToR_64f (src/FFTBackend.cpp:123-150) with the same
 // scaling convention (IPP_FFT_DIV_INV_BY_N: forward unscaled, inverse 1/N, :33-35).
 //
-// Spectrum layout ("packed"): 512 complex per transform; bin k (1..511) = X[k]; bin 0 = (X[0], X[512])
-// (DC and Nyquist are both real), so a spectrum is exactly 8 KB and a wave stores 1 KB per instruction.
+// Spectrum layout ("packed"): P complex per transform; bin k (1..P-1) = X[k]; bin 0 = (X[0], X[P]) (DC and Nyquist are
+// both real).  Up to P = 2048 element k is bin k; from P = 4096 up the spectrum is stored PERMUTED, element
+// k1 * 512 + k2 = bin k1 + (P / 512) k2 (the MAC is element-wise; forward, IR and inverse transforms agree on it).
+//
+// Five families, chosen from P by fftFamily() for all three launchers (forward, IR spectra, inverse):
+//
+//   P              family       kernels                                             complex FFT
+//   64, 128, 256   Stockham     k_rfft_fwd_lds<StockhamFft, FRAME>,                 radix-2 Stockham, two LDS buffers
+//                               k_rfft_inv_lds<MODE, StockhamFft>
+//   512            Wave512      k_rfft_fwd_ols<SIDE>, k_ir_spectra,                 wave_cfft512: one wave, 8 points per lane
+//                               k_rfft_inv_ols<MODE>
+//   1024, 2048     MixedRadix   k_rfft_fwd_lds<MixedRadixFft, FRAME>,               wg_cfft: radix 8 (+ 4 or 2), one padded
+//                               k_rfft_inv_lds<MODE, MixedRadixFft>                 LDS buffer
+//   4096           P4           k_rfft_fwd_ols_p4, k_ir_spectra_p4,                 four-step inside a workgroup: dft8, then
+//                               k_rfft_inv_ols_p4<MODE>                             wave_cfft512 per wave
+//   8192 ... 2^17  FourStep     k_big_cols_fwd<FRAME>, k_big_rows_fwd,              four-step through scratch: col_fft, then
+//                               k_big_rows_inv, k_big_cols_inv<MODE>                wave_cfft512 per row (FourStepGeom)
+//
+// (FRAME = true: overlap-save frames; false: zero-padded IR partitions.  MODE: where store_block2 puts a block.)
+//
+// Written once and shared by every family, so that they stay bit-identical to one another (the engine mixes families
+// inside one plan group; tests/test_gpu_fft_variants.py and tests/test_gpu_fft_p4_frames.py compare the launch paths bit
+// for bit, tests/test_gpu_fft_bits.py every size with a recorded digest):
+//   rfft_split / pack_dcnyq       Z[k], Z[M-k], w -> X[k]; the packed element 0
+//   rfft_unsplit / unpack_dcnyq   the inverse of the two
+//                                 (Stockham, MixedRadix, FourStep call them; Wave512 and P4 carry the same expressions as
+//                                 inline text, marked at the four sites: through the helpers the compiler orders those
+//                                 unrolled loops differently, and the P4 kernels sit at their register limit -- RESULTS.md)
+//   OlsFrame::load, ir_part_load  complex element n of a frame (with the history store) / of an IR partition
+//                                 (Stockham, MixedRadix, FourStep; Wave512 and P4 load whole register halves instead)
+//   stage8 / stage_small          one Stockham radix-8 / radix-2,4 stage over an LDS index map (wg_cfft: WgMap, col_fft: ColMap)
+//   dft8, mul_powers, wave_cfft512, store_block2
+// Each site keeps its own way of finding the partner element and the twiddle.
 #include "kernels.hpp"
 
 namespace cpq {
@@ -50,6 +79,66 @@ __device__ __forceinline__ double2 cmulw(double2 a, double2 w)
 {
     if (INV) return make_double2(fma(a.x, w.x, a.y * w.y), fma(a.y, w.x, -(a.x * w.y)));
     return make_double2(fma(a.x, w.x, -(a.y * w.y)), fma(a.x, w.y, a.y * w.x));
+}
+
+// real-FFT split: Z = M-point FFT of (even + i odd) samples -> bin k of the 2M-point real frame,
+// X[k] = E + w O with E = (Z[k] + conj Z[M-k]) / 2, O = -i (Z[k] - conj Z[M-k]) / 2, w = exp(-2 pi i k / 2M); zm = Z[M-k]
+// (twiddle() gives w: a callable, so that w is fetched where the sites fetched it, between the sums and the product)
+template <typename W>
+__device__ __forceinline__ double2 rfft_split(double2 zk, double2 zm, W twiddle)
+{
+    const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));   // (Z[k] + conj Z[M-k]) / 2
+    const double2 d = make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y));   // (Z[k] - conj Z[M-k]) / 2
+    const double2 o = make_double2(d.y, -d.x);                                  // -i d
+    const double2 w = twiddle();
+    return make_double2(e.x + fma(o.x, w.x, -(o.y * w.y)), e.y + fma(o.x, w.y, o.y * w.x));
+}
+// element 0 of a packed spectrum from Z[0]: (DC, Nyquist), both real
+__device__ __forceinline__ double2 pack_dcnyq(double2 z0) { return make_double2(z0.x + z0.y, z0.x - z0.y); }
+
+// inverse of the split: packed spectrum Y -> z[k] = E + i O, the input of the M-point inverse FFT; ym = Y[M-k], same w
+template <typename W>
+__device__ __forceinline__ double2 rfft_unsplit(double2 yk, double2 ym, W twiddle)
+{
+    const double2 e = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y - ym.y));
+    const double2 d = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y + ym.y));
+    const double2 w = twiddle();
+    const double2 o = make_double2(fma(d.x, w.x, d.y * w.y), fma(d.y, w.x, -(d.x * w.y)));   // d * conj(w)
+    return make_double2(e.x - o.y, e.y + o.x);                                               // E + i O
+}
+// z[0] from the packed element 0 = (DC, Nyquist)
+__device__ __forceinline__ double2 unpack_dcnyq(double2 y0) { return make_double2(0.5 * (y0.x + y0.y), 0.5 * (y0.x - y0.y)); }
+
+// The overlap-save frame [previous block | block t] of channel c as P complex points (copy [prev|cur],
+// src/MKLNonUniformConvolver.cpp:1256-1258); the previous block of t = 0 is the history of the call before
+struct OlsFrame {
+    const double* cur; const double* prev; double* hist; int halfP; bool last;
+    __device__ __forceinline__ OlsFrame(const double* in, int64_t chStride, const double* histOld, double* histNew, int P, int T,
+                                        int c, int t)
+        : cur(in + (int64_t)c * chStride + (int64_t)t * P), prev((t > 0) ? (cur - P) : (histOld + (int64_t)c * P)),
+          hist(histNew + (int64_t)c * P), halfP(P >> 1), last(t == T - 1)
+    {
+    }
+    // element n into dst (a register or LDS: written first, the kernels' loops were timed in that order); the call's last block
+    // also goes to the overlap history of the next call (prevInputBuf, NUC.cpp:1258)
+    __device__ __forceinline__ void load(int n, double2& dst) const
+    {
+        const double* src = (n < halfP) ? (prev + 2 * n) : (cur + 2 * (n - halfP));
+        const double2 v = *reinterpret_cast<const double2*>(src);
+        dst = v;
+        if (last && n >= halfP) *reinterpret_cast<double2*>(hist + 2 * (n - halfP)) = v;
+    }
+};
+
+// complex element n (< P) of the zero-padded IR partition `part` of heff: [h[part P .. (part+1) P) | 0] (NUC.cpp:921-928)
+__device__ __forceinline__ double2 ir_part_load(const double* __restrict__ heff, int heffLen, int part, int P, int n)
+{
+    double2 v = make_double2(0.0, 0.0);
+    if (n < (P >> 1)) {
+        const int64_t i = (int64_t)part * P + 2 * n;
+        v = make_double2(i < heffLen ? heff[i] : 0.0, (i + 1) < heffLen ? heff[i + 1] : 0.0);
+    }
+    return v;
 }
 
 // 4-point DFT of (t0..t3) -> (t0..t3), natural order
@@ -161,6 +250,7 @@ __device__ __forceinline__ void wave_split_store(double2 (&v)[8], double2* lds, 
         const int k = lane + 64 * r;
         const double2 zk = v[r];
         const double2 zm = lds[(512 - k) & 511];
+        // rfft_split / pack_dcnyq, inline: through the helpers the compiler orders this loop's instructions differently (RESULTS.md)
         const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));   // (Z[k] + conj Z[512-k]) / 2
         const double2 d = make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y));   // (Z[k] - conj Z[512-k]) / 2
         const double2 o = make_double2(d.y, -d.x);                                  // -i d
@@ -339,6 +429,7 @@ __global__ __launch_bounds__(64) void k_rfft_inv_ols(const double2* __restrict__
         const int k = lane + 64 * j;
         const double2 yk = y[k];
         const double2 ym = y[(512 - k) & 511];
+        // rfft_unsplit / unpack_dcnyq, inline (as in wave_split_store)
         const double2 e = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y - ym.y));
         const double2 d = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y + ym.y));
         const double2 w = cmul(wl, w16(j));                                                     // exp(-2 pi i (lane + 64 j) / 1024)
@@ -357,11 +448,15 @@ __global__ __launch_bounds__(64) void k_rfft_inv_ols(const double2* __restrict__
 
 
 // ---------------------------------------------------------------------------------------------------------
-// Generic partition sizes (P = 64 ... 2048 except 512): one workgroup per transform, radix-2 Stockham
-// autosort between two LDS buffers (2 x P complex), then the same real-FFT split.  Slower per byte than the
-// wave-level 512-point kernels above; covers the block-size sweep of BASELINE.json configs[2].
+// P = 64 ... 2048 except 512: one workgroup per transform with the whole transform in LDS.  Two complex FFTs, one set
+// of kernels (k_rfft_fwd_lds, k_rfft_inv_lds) over a policy type F that supplies
+//   F::at(i)              LDS address of logical element i
+//   F::cfft<INV>(lds, M, twM)   the M-point FFT of the elements in LDS; returns the buffer that holds the result
+//   F::kMaxThreads, F::threads(P), F::ldsBytes(P)     launch geometry
+// Slower per byte than the wave-level 512-point kernels above; P <= 256 covers the block-size sweep of BASELINE.json configs[2].
 // tw.tw512 holds exp(-2 pi i m / P) (m < P), tw.tw1024 holds exp(-2 pi i k / 2P) (k < P) for the engine's P.
 
+// radix-2 Stockham autosort between two buffers a, b of M complex
 template <bool INV>
 __device__ __forceinline__ double2* stockham(double2* a, double2* b, int M, const double2* __restrict__ twM)
 {
@@ -383,153 +478,60 @@ __device__ __forceinline__ double2* stockham(double2* a, double2* b, int M, cons
     return a;      // buffer holding the result, natural order
 }
 
-__device__ __forceinline__ void split_store_generic(const double2* Z, int M, const double2* __restrict__ tw2M,
-                                                    double2* __restrict__ spec, double2* __restrict__ dcnyq)
-{
-    for (int k = threadIdx.x; k < M; k += blockDim.x) {
-        const double2 zk = Z[k];
-        const double2 zm = Z[(M - k) & (M - 1)];
-        const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
-        const double2 d = make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y));
-        const double2 o = make_double2(d.y, -d.x);
-        const double2 w = tw2M[k];
-        double2 xk = make_double2(e.x + fma(o.x, w.x, -(o.y * w.y)), e.y + fma(o.x, w.y, o.y * w.x));
-        if (k == 0) {
-            xk = make_double2(zk.x + zk.y, zk.x - zk.y);
-            *dcnyq = xk;
-        }
-        spec[k] = xk;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_rfft_fwd_ols_generic(const double* __restrict__ in, int64_t chStride,
-                                                              const double* __restrict__ histOld,
-                                                              double* __restrict__ histNew, double2* __restrict__ X,
-                                                              double2* __restrict__ XDN, FftTables tw, int P, int T,
-                                                              int head, int ringMask)
-{
-    extern __shared__ double2 dyn[];
-    double2* a = dyn;
-    double2* b = dyn + P;
-    const int c = blockIdx.x / T;
-    const int t = blockIdx.x - c * T;
-    const double* cur = in + (int64_t)c * chStride + (int64_t)t * P;
-    const double* prev = (t > 0) ? (cur - P) : (histOld + (int64_t)c * P);
-    const int halfP = P >> 1;
-    for (int n = threadIdx.x; n < P; n += blockDim.x) {
-        const double* src = (n < halfP) ? (prev + 2 * n) : (cur + 2 * (n - halfP));
-        const double2 v = *reinterpret_cast<const double2*>(src);
-        a[n] = v;
-        if (t == T - 1 && n >= halfP) *reinterpret_cast<double2*>(histNew + (int64_t)c * P + 2 * (n - halfP)) = v;
-    }
-    __syncthreads();
-    const double2* Z = stockham<false>(a, b, P, tw.tw512);
-    const int slot = (head + t) & ringMask;
-    const int64_t row = (int64_t)c * (ringMask + 1) + slot;
-    split_store_generic(Z, P, tw.tw1024, X + row * P, XDN + row);
-}
-
-__global__ __launch_bounds__(256) void k_ir_spectra_generic(const double* __restrict__ heff, int heffLen,
-                                                            double2* __restrict__ H, double2* __restrict__ HDN,
-                                                            FftTables tw, int P)
-{
-    extern __shared__ double2 dyn[];
-    double2* a = dyn;
-    double2* b = dyn + P;
-    const int k = blockIdx.x;
-    const int halfP = P >> 1;
-    for (int n = threadIdx.x; n < P; n += blockDim.x) {
-        double2 v = make_double2(0.0, 0.0);
-        if (n < halfP) {
-            const int i = k * P + 2 * n;
-            v = make_double2(i < heffLen ? heff[i] : 0.0, (i + 1) < heffLen ? heff[i + 1] : 0.0);
-        }
-        a[n] = v;
-    }
-    __syncthreads();
-    const double2* Z = stockham<false>(a, b, P, tw.tw512);
-    split_store_generic(Z, P, tw.tw1024, H + (int64_t)k * P, HDN + k);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void k_rfft_inv_ols_generic(const double2* __restrict__ Y, double* __restrict__ out,
-                                                              int64_t chStride, FftTables tw, int P, int T, OutSpec ro)
-{
-    extern __shared__ double2 dyn[];
-    double2* a = dyn;
-    double2* b = dyn + P;
-    const int c = blockIdx.x / T;
-    const int t = blockIdx.x - c * T;
-    const double2* y = Y + (int64_t)blockIdx.x * P;
-    const double2 y0 = y[0];
-    for (int k = threadIdx.x; k < P; k += blockDim.x) {
-        const double2 yk = y[k];
-        const double2 ym = y[(P - k) & (P - 1)];
-        const double2 e = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y - ym.y));
-        const double2 d = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y + ym.y));
-        const double2 w = tw.tw1024[k];
-        const double2 o = make_double2(fma(d.x, w.x, d.y * w.y), fma(d.y, w.x, -(d.x * w.y)));
-        double2 z = make_double2(e.x - o.y, e.y + o.x);
-        if (k == 0) z = make_double2(0.5 * (y0.x + y0.y), 0.5 * (y0.x - y0.y));
-        a[k] = z;
-    }
-    __syncthreads();
-    const double2* z = stockham<true>(a, b, P, tw.tw512);
-    const double s = 1.0 / (double)P;
-    const int halfP = P >> 1;
-    for (int n = halfP + threadIdx.x; n < P; n += blockDim.x)      // second half of the 2P-sample frame
-        store_block2<MODE>(out, chStride, ro, c, t, P, 2 * (n - halfP), make_double2(z[n].x * s, z[n].y * s));
-}
-
-}  // namespace
-
-namespace {
-
-// ---------------------------------------------------------------------------------------------------------
-// Large partitions (P = 1024, 2048, 4096): one workgroup of P/8 threads per transform, 8 points per thread,
-// mixed-radix Stockham (radix-8 stages, then one radix-4 or radix-2 stage when P is not a power of 8) through
-// ONE P-complex LDS buffer: every thread reads its 8 inputs, barrier, butterflies in registers, writes its 8
-// outputs, barrier.  Stage with radix R and Ns = product of earlier radices, butterfly j in [0, P/R):
-//   k = j mod Ns,  in[j + q P/R] * exp(-2 pi i q k / (R Ns))  ->  out[(j - k) R + k + q Ns].
-// LDS element index with one pad element per 8: the first radix-8 stage writes elements 8 j + q from consecutive lanes j
-// (stride 128 B: an 8-way bank conflict unpadded, conflict-free at stride 9), the second one 64 a + b
+// Mixed-radix Stockham stages through ONE LDS buffer: every thread reads its 8 inputs, butterflies in registers, barrier,
+// writes its 8 outputs, barrier.  Stage with radix R and Ns = product of earlier radices, butterfly j in [0, M/R):
+//   k = j mod Ns,  in[j + q M/R] * exp(-2 pi i q k / (R Ns))  ->  out[(j - k) R + k + q Ns].
+// MAP says where the M logical elements live and which butterflies the thread has:
+//   m.at(i)     LDS address of element i
+//   m.j, m.nj   the thread's first butterfly index and the number of threads along the element axis (M / 8)
+//   kTwStep     exp(-2 pi i m / M) = twM[m * kTwStep]
+// WgMap: one transform per workgroup (wg_cfft); ColMap: one transform per column of a tile (col_fft, below).
+// WgMap pads one element per 8: the first radix-8 stage writes elements 8 j + q from consecutive lanes j (stride 128 B: an
+// 8-way bank conflict unpadded, conflict-free at stride 9), the second one 64 a + b
 __device__ __forceinline__ int wgp(int i) { return i + (i >> 3); }
+struct WgMap {
+    static constexpr int kTwStep = 1;
+    int j, nj;
+    __device__ __forceinline__ int at(int i) const { return wgp(i); }
+};
 
-template <bool INV>
-__device__ __forceinline__ void wg_stage8(double2* lds, int M, int ns, const double2* __restrict__ twM)
+// radix-8 stage; the first stage of a transform (ns = 1) has no twiddles
+template <bool INV, typename MAP>
+__device__ __forceinline__ void stage8(double2* lds, int M, int ns, const double2* __restrict__ twM, MAP m)
 {
-    const int j = threadIdx.x;
+    const int j = m.j;
     const int stride = M >> 3;
     const int k = j & (ns - 1);
     double2 v[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = lds[wgp(j + q * stride)];
-    if (ns > 1) mul_powers<INV>(v, twM[k * (M / (8 * ns))]);      // one root per lane and stage, its powers by multiplication
+    for (int q = 0; q < 8; ++q) v[q] = lds[m.at(j + q * stride)];
+    const int tstep = (M / (8 * ns)) * MAP::kTwStep;
+    if (ns > 1) mul_powers<INV>(v, twM[k * tstep]);      // one root per lane and stage, its powers by multiplication
     dft8<INV>(v);
     __syncthreads();
     const int o = ((j - k) << 3) + k;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) lds[wgp(o + q * ns)] = v[q];
+    for (int q = 0; q < 8; ++q) lds[m.at(o + q * ns)] = v[q];
     __syncthreads();
 }
 
-// final radix-R stage (R = 2 or 4) over all P points with P/8 threads: each thread does 8/R butterflies
-template <bool INV, int R>
-__device__ __forceinline__ void wg_stage_small(double2* lds, int M, int ns, const double2* __restrict__ twM)
+// final radix-R stage (R = 2 or 4) over all M points with M/8 threads: each thread does 8/R butterflies
+template <bool INV, int R, typename MAP>
+__device__ __forceinline__ void stage_small(double2* lds, int M, int ns, const double2* __restrict__ twM, MAP m)
 {
     constexpr int NB = 8 / R;
     const int stride = M / R;
-    const int tstep = M / (R * ns);
+    const int tstep = (M / (R * ns)) * MAP::kTwStep;
     double2 v[NB][R];
     int outBase[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const int j = threadIdx.x + b * blockDim.x;
+        const int j = m.j + b * m.nj;
         const int k = j & (ns - 1);
         outBase[b] = (j - k) * R + k;
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-            v[b][q] = lds[wgp(j + q * stride)];
+            v[b][q] = lds[m.at(j + q * stride)];
             if (q > 0) v[b][q] = cmulw<INV>(v[b][q], twM[q * k * tstep]);
         }
         if (R == 4) dft4<INV>(v[b][0], v[b][1], v[b][2], v[b][3]);
@@ -539,87 +541,83 @@ __device__ __forceinline__ void wg_stage_small(double2* lds, int M, int ns, cons
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int q = 0; q < R; ++q) lds[wgp(outBase[b] + q * ns)] = v[b][q];
+        for (int q = 0; q < R; ++q) lds[m.at(outBase[b] + q * ns)] = v[b][q];
     __syncthreads();
 }
 
+// M = 1024, 2048 (P/8 threads, 8 points per thread): radix-8 stages, then one radix-4 or radix-2 stage when M is not a power of 8
 template <bool INV>
 __device__ __forceinline__ void wg_cfft(double2* lds, int M, const double2* __restrict__ twM)
 {
+    const WgMap m{ (int)threadIdx.x, (int)blockDim.x };
     int ns = 1;
-    while (ns * 8 <= M) { wg_stage8<INV>(lds, M, ns, twM); ns *= 8; }
-    if (ns * 4 == M) wg_stage_small<INV, 4>(lds, M, ns, twM);
-    else if (ns * 2 == M) wg_stage_small<INV, 2>(lds, M, ns, twM);
+    while (ns * 8 <= M) { stage8<INV>(lds, M, ns, twM, m); ns *= 8; }
+    if (ns * 4 == M) stage_small<INV, 4>(lds, M, ns, twM, m);
+    else if (ns * 2 == M) stage_small<INV, 2>(lds, M, ns, twM, m);
 }
 
-// real-FFT split of the padded LDS buffer (same arithmetic as split_store_generic)
-__device__ __forceinline__ void split_store_wg(const double2* Z, int M, const double2* __restrict__ tw2M,
-                                               double2* __restrict__ spec, double2* __restrict__ dcnyq)
+struct StockhamFft {        // P <= 256: two buffers of P complex, natural order
+    static constexpr int kMaxThreads = 256;
+    static int threads(int P) { return P / 2 < 64 ? 64 : (P / 2 > 256 ? 256 : P / 2); }
+    static size_t ldsBytes(int P) { return 2 * P * sizeof(double2); }
+    static __device__ __forceinline__ int at(int i) { return i; }
+    template <bool INV>
+    static __device__ __forceinline__ double2* cfft(double2* lds, int M, const double2* __restrict__ twM)
+    {
+        return stockham<INV>(lds, lds + M, M, twM);
+    }
+};
+struct MixedRadixFft {      // P = 1024, 2048: one padded buffer, in place
+    static constexpr int kMaxThreads = 512;
+    static int threads(int P) { return P / 8; }
+    static size_t ldsBytes(int P) { return (size_t)(P + (P >> 3)) * sizeof(double2); }
+    static __device__ __forceinline__ int at(int i) { return wgp(i); }
+    template <bool INV>
+    static __device__ __forceinline__ double2* cfft(double2* lds, int M, const double2* __restrict__ twM)
+    {
+        wg_cfft<INV>(lds, M, twM);
+        return lds;
+    }
+};
+
+// forward.  FRAME = true: overlap-save frame of (channel, block) = blockIdx.x, spectrum into the FDL ring at slot head + t;
+// FRAME = false: zero-padded IR partition blockIdx.x of heff (in), spectrum into row blockIdx.x
+template <typename F, bool FRAME>
+__global__ __launch_bounds__(F::kMaxThreads) void k_rfft_fwd_lds(const double* __restrict__ in, int64_t chStride,
+                                                                 const double* __restrict__ histOld,
+                                                                 double* __restrict__ histNew, int heffLen,
+                                                                 double2* __restrict__ X, double2* __restrict__ XDN,
+                                                                 FftTables tw, int P, int T, int head, int ringMask)
 {
-    for (int k = threadIdx.x; k < M; k += blockDim.x) {
-        const double2 zk = Z[wgp(k)];
-        const double2 zm = Z[wgp((M - k) & (M - 1))];
-        const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
-        const double2 d = make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y));
-        const double2 o = make_double2(d.y, -d.x);
-        const double2 w = tw2M[k];
-        double2 xk = make_double2(e.x + fma(o.x, w.x, -(o.y * w.y)), e.y + fma(o.x, w.y, o.y * w.x));
+    extern __shared__ double2 dyn[];
+    const int nthr = blockDim.x;
+    const int c = FRAME ? blockIdx.x / T : 0;
+    const int t = FRAME ? blockIdx.x - c * T : 0;
+    if (FRAME) {
+        const OlsFrame frame(in, chStride, histOld, histNew, P, T, c, t);
+        for (int n = threadIdx.x; n < P; n += nthr) frame.load(n, dyn[F::at(n)]);
+    } else {
+        for (int n = threadIdx.x; n < P; n += nthr) dyn[F::at(n)] = ir_part_load(in, heffLen, blockIdx.x, P, n);
+    }
+    __syncthreads();
+    const double2* Z = F::template cfft<false>(dyn, P, tw.tw512);
+    const int64_t row = FRAME ? (int64_t)c * (ringMask + 1) + ((head + t) & ringMask) : (int64_t)blockIdx.x;
+    double2* spec = X + row * P;
+    for (int k = threadIdx.x; k < P; k += nthr) {
+        const double2 zk = Z[F::at(k)];
+        const double2 zm = Z[F::at((P - k) & (P - 1))];
+        double2 xk = rfft_split(zk, zm, [&] { return tw.tw1024[k]; });
         if (k == 0) {
-            xk = make_double2(zk.x + zk.y, zk.x - zk.y);
-            *dcnyq = xk;
+            xk = pack_dcnyq(zk);
+            XDN[row] = xk;
         }
         spec[k] = xk;
     }
 }
 
-__global__ __launch_bounds__(512) void k_rfft_fwd_ols_wg(const double* __restrict__ in, int64_t chStride,
-                                                         const double* __restrict__ histOld,
-                                                         double* __restrict__ histNew, double2* __restrict__ X,
-                                                         double2* __restrict__ XDN, FftTables tw, int P, int T,
-                                                         int head, int ringMask)
-{
-    extern __shared__ double2 dyn[];
-    const int c = blockIdx.x / T;
-    const int t = blockIdx.x - c * T;
-    const double* cur = in + (int64_t)c * chStride + (int64_t)t * P;
-    const double* prev = (t > 0) ? (cur - P) : (histOld + (int64_t)c * P);
-    const int halfP = P >> 1;
-    for (int n = threadIdx.x; n < P; n += blockDim.x) {
-        const double* src = (n < halfP) ? (prev + 2 * n) : (cur + 2 * (n - halfP));
-        const double2 v = *reinterpret_cast<const double2*>(src);
-        dyn[wgp(n)] = v;
-        if (t == T - 1 && n >= halfP) *reinterpret_cast<double2*>(histNew + (int64_t)c * P + 2 * (n - halfP)) = v;
-    }
-    __syncthreads();
-    wg_cfft<false>(dyn, P, tw.tw512);
-    const int slot = (head + t) & ringMask;
-    const int64_t row = (int64_t)c * (ringMask + 1) + slot;
-    split_store_wg(dyn, P, tw.tw1024, X + row * P, XDN + row);
-}
-
-__global__ __launch_bounds__(512) void k_ir_spectra_wg(const double* __restrict__ heff, int heffLen,
-                                                       double2* __restrict__ H, double2* __restrict__ HDN,
-                                                       FftTables tw, int P)
-{
-    extern __shared__ double2 dyn[];
-    const int k = blockIdx.x;
-    const int halfP = P >> 1;
-    for (int n = threadIdx.x; n < P; n += blockDim.x) {
-        double2 v = make_double2(0.0, 0.0);
-        if (n < halfP) {
-            const int i = k * P + 2 * n;
-            v = make_double2(i < heffLen ? heff[i] : 0.0, (i + 1) < heffLen ? heff[i + 1] : 0.0);
-        }
-        dyn[wgp(n)] = v;
-    }
-    __syncthreads();
-    wg_cfft<false>(dyn, P, tw.tw512);
-    split_store_wg(dyn, P, tw.tw1024, H + (int64_t)k * P, HDN + k);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(512) void k_rfft_inv_ols_wg(const double2* __restrict__ Y, double* __restrict__ out,
-                                                         int64_t chStride, FftTables tw, int P, int T, OutSpec ro)
+template <int MODE, typename F>
+__global__ __launch_bounds__(F::kMaxThreads) void k_rfft_inv_lds(const double2* __restrict__ Y, double* __restrict__ out,
+                                                                 int64_t chStride, FftTables tw, int P, int T, OutSpec ro)
 {
     extern __shared__ double2 dyn[];
     const int c = blockIdx.x / T;
@@ -629,20 +627,16 @@ __global__ __launch_bounds__(512) void k_rfft_inv_ols_wg(const double2* __restri
     for (int k = threadIdx.x; k < P; k += blockDim.x) {
         const double2 yk = y[k];
         const double2 ym = y[(P - k) & (P - 1)];
-        const double2 e = make_double2(0.5 * (yk.x + ym.x), 0.5 * (yk.y - ym.y));
-        const double2 d = make_double2(0.5 * (yk.x - ym.x), 0.5 * (yk.y + ym.y));
-        const double2 w = tw.tw1024[k];
-        const double2 o = make_double2(fma(d.x, w.x, d.y * w.y), fma(d.y, w.x, -(d.x * w.y)));
-        double2 z = make_double2(e.x - o.y, e.y + o.x);
-        if (k == 0) z = make_double2(0.5 * (y0.x + y0.y), 0.5 * (y0.x - y0.y));
-        dyn[wgp(k)] = z;
+        double2 z = rfft_unsplit(yk, ym, [&] { return tw.tw1024[k]; });
+        if (k == 0) z = unpack_dcnyq(y0);
+        dyn[F::at(k)] = z;
     }
     __syncthreads();
-    wg_cfft<true>(dyn, P, tw.tw512);
+    const double2* z = F::template cfft<true>(dyn, P, tw.tw512);
     const double s = 1.0 / (double)P;
     const int halfP = P >> 1;
-    for (int n = halfP + threadIdx.x; n < P; n += blockDim.x)
-        store_block2<MODE>(out, chStride, ro, c, t, P, 2 * (n - halfP), make_double2(dyn[wgp(n)].x * s, dyn[wgp(n)].y * s));
+    for (int n = halfP + threadIdx.x; n < P; n += blockDim.x)      // second half of the 2P-sample frame
+        store_block2<MODE>(out, chStride, ro, c, t, P, 2 * (n - halfP), make_double2(z[F::at(n)].x * s, z[F::at(n)].y * s));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -720,6 +714,7 @@ __device__ __forceinline__ void p4_forward_frame(double2 (&v)[8], double2* dyn, 
         const int k2 = lane + 64 * r;
         const double2 zk = v[r];
         const double2 zm = dyn[p4_partner(w, k2)];
+        // rfft_split / pack_dcnyq, inline: the kernel sits at its register limit and the helpers change its instruction order
         const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));   // (Z[k] + conj Z[4096-k]) / 2
         const double2 d = make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y));   // (Z[k] - conj Z[4096-k]) / 2
         const double2 o = make_double2(d.y, -d.x);                                  // -i d
@@ -838,6 +833,7 @@ __global__ __launch_bounds__(512, 4) void k_rfft_inv_ols_p4(const double2* __res
         for (int r = 0; r < 8; ++r) {
             const int k2 = lane + 64 * r;
             const double2 a = pa[r], b = pb[r];
+            // rfft_unsplit / unpack_dcnyq, inline (as in p4_forward_frame)
             const double2 e = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
             const double2 d = make_double2(0.5 * (a.x - b.x), 0.5 * (a.y + b.y));
             const double2 tk = cmul(wk, w16(r));
@@ -887,70 +883,29 @@ __global__ __launch_bounds__(512, 4) void k_rfft_inv_ols_p4(const double2* __res
 // 128- / 256-point columns of 65536- / 131072-sample partitions so that the tile stays at 64 KB and the workgroup at 512 threads
 __host__ __device__ constexpr int bigCols(int M1) { return M1 <= 64 ? 64 : (M1 == 128 ? 32 : 16); }
 
-// Stockham stages over the element axis of a [element][column] LDS tile; thread = (column, j), j < M1 / 8
-template <bool INV>
-__device__ __forceinline__ void col_stage8(double2* lds, int M1, int ns, const double2* __restrict__ twP, int j, int col, int kBigCols)
-{
-    const int stride = M1 >> 3;
-    const int k = j & (ns - 1);
-    double2 v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = lds[(j + q * stride) * kBigCols + col];
-    const int tstep = (M1 / (8 * ns)) * 512;             // exp(-2 pi i m / M1) = twP[m * 512]
-    mul_powers<INV>(v, twP[k * tstep]);
-    dft8<INV>(v);
-    __syncthreads();
-    const int o = ((j - k) << 3) + k;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) lds[(o + q * ns) * kBigCols + col] = v[q];
-    __syncthreads();
-}
-
-template <bool INV, int R>
-__device__ __forceinline__ void col_stage_small(double2* lds, int M1, int ns, const double2* __restrict__ twP, int j, int col, int kBigCols)
-{
-    constexpr int NB = 8 / R;
-    const int nthr = M1 >> 3;
-    const int stride = M1 / R;
-    const int tstep = (M1 / (R * ns)) * 512;
-    double2 v[NB][R];
-    int outBase[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int jj = j + b * nthr;
-        const int k = jj & (ns - 1);
-        outBase[b] = (jj - k) * R + k;
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            v[b][q] = lds[(jj + q * stride) * kBigCols + col];
-            if (q > 0) v[b][q] = cmulw<INV>(v[b][q], twP[q * k * tstep]);
-        }
-        if (R == 4) dft4<INV>(v[b][0], v[b][1], v[b][2], v[b][3]);
-        else { const double2 a = v[b][0], c = v[b][1]; v[b][0] = cadd(a, c); v[b][1] = csub(a, c); }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int q = 0; q < R; ++q) lds[(outBase[b] + q * ns) * kBigCols + col] = v[b][q];
-    __syncthreads();
-}
+// the M1 elements of a column in a [element][column] LDS tile of `cols` columns; thread = (column, j), j < M1 / 8;
+// exp(-2 pi i m / M1) = twP[m * 512]
+struct ColMap {
+    static constexpr int kTwStep = 512;
+    int j, nj, col, cols;
+    __device__ __forceinline__ int at(int i) const { return i * cols + col; }
+};
 
 // M1-point FFT of the thread's column: the first radix-8 stage takes its inputs from registers (v[q] = element
 // j + q M1/8), the result ends in LDS in natural order
 template <bool INV>
-__device__ __forceinline__ void col_fft(double2 (&v)[8], double2* lds, int M1, const double2* __restrict__ twP, int j, int col, int kBigCols)
+__device__ __forceinline__ void col_fft(double2 (&v)[8], double2* lds, int M1, const double2* __restrict__ twP, ColMap m)
 {
     dft8<INV>(v);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) lds[(8 * j + q) * kBigCols + col] = v[q];
+    for (int q = 0; q < 8; ++q) lds[m.at(8 * m.j + q)] = v[q];
     __syncthreads();
     if (M1 >= 64) {                  // 64 = 8 x 8, 128 = 8 x 8 x 2, 256 = 8 x 8 x 4
-        col_stage8<INV>(lds, M1, 8, twP, j, col, kBigCols);
-        if (M1 == 128) col_stage_small<INV, 2>(lds, M1, 64, twP, j, col, kBigCols);
-        else if (M1 == 256) col_stage_small<INV, 4>(lds, M1, 64, twP, j, col, kBigCols);
-    } else if (M1 == 32) col_stage_small<INV, 4>(lds, M1, 8, twP, j, col, kBigCols);
-    else col_stage_small<INV, 2>(lds, M1, 8, twP, j, col, kBigCols);
+        stage8<INV>(lds, M1, 8, twP, m);
+        if (M1 == 128) stage_small<INV, 2>(lds, M1, 64, twP, m);
+        else if (M1 == 256) stage_small<INV, 4>(lds, M1, 64, twP, m);
+    } else if (M1 == 32) stage_small<INV, 4>(lds, M1, 8, twP, m);
+    else stage_small<INV, 2>(lds, M1, 8, twP, m);
 }
 
 // column pass, forward.  FRAME = true: overlap-save frame [previous P | current P] of (channel c, block t);
@@ -966,39 +921,24 @@ __global__ __launch_bounds__(512) void k_big_cols_fwd(const double* __restrict__
     const int tr = blockIdx.x / nTiles, tile = blockIdx.x - tr * nTiles;
     const int col = threadIdx.x & (kBigCols - 1), j = threadIdx.x / kBigCols;
     const int n2 = tile * kBigCols + col;
-    const int halfM = P >> 1;
     const int stride = M1 >> 3;
+    const ColMap m{ j, stride, col, kBigCols };
     double2 v[8];
     if (FRAME) {
         const int c = tr / T, t = tr - c * T;
-        const double* cur = in + (int64_t)c * chStride + (int64_t)t * P;
-        const double* prev = (t > 0) ? (cur - P) : (histOld + (int64_t)c * P);
+        const OlsFrame frame(in, chStride, histOld, histNew, P, T, c, t);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int n = (j + q * stride) * 512 + n2;
-            const double* src = (n < halfM) ? (prev + 2 * n) : (cur + 2 * (n - halfM));
-            v[q] = *reinterpret_cast<const double2*>(src);
-            if (t == T - 1 && n >= halfM)      // overlap history for the next call (prevInputBuf, NUC.cpp:1258)
-                *reinterpret_cast<double2*>(histNew + (int64_t)c * P + 2 * (n - halfM)) = v[q];
-        }
+        for (int q = 0; q < 8; ++q) frame.load((j + q * stride) * 512 + n2, v[q]);
     } else {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int n = (j + q * stride) * 512 + n2;
-            double2 x = make_double2(0.0, 0.0);
-            if (n < halfM) {
-                const int64_t i = (int64_t)tr * P + 2 * n;
-                x = make_double2(i < heffLen ? in[i] : 0.0, (i + 1) < heffLen ? in[i + 1] : 0.0);
-            }
-            v[q] = x;
-        }
+        for (int q = 0; q < 8; ++q) v[q] = ir_part_load(in, heffLen, tr, P, (j + q * stride) * 512 + n2);
     }
-    col_fft<false>(v, dyn, M1, tw.tw512, j, col, kBigCols);
+    col_fft<false>(v, dyn, M1, tw.tw512, m);
     double2* a = A + (int64_t)tr * P;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int k1 = j + q * stride;
-        a[k1 * 512 + n2] = cmulw<false>(dyn[k1 * kBigCols + col], tw.twCol[k1 * 512 + n2]);       // W_M^(n2 k1)
+        a[k1 * 512 + n2] = cmulw<false>(dyn[m.at(k1)], tw.twCol[k1 * 512 + n2]);       // W_M^(n2 k1)
     }
 }
 
@@ -1034,13 +974,9 @@ __global__ __launch_bounds__(128) void k_big_rows_fwd(const double2* __restrict_
         const int k2 = lane + 64 * r;
         const double2 zk = v[r];
         const double2 zm = rows[w ^ 1][krow == 0 ? ((512 - k2) & 511) : (511 - k2)];
-        const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
-        const double2 d = make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y));
-        const double2 o = make_double2(d.y, -d.x);
-        const double2 wk = tw.twSplit[krow * 512 + k2];
-        double2 xk = make_double2(e.x + fma(o.x, wk.x, -(o.y * wk.y)), e.y + fma(o.x, wk.y, o.y * wk.x));
+        double2 xk = rfft_split(zk, zm, [&] { return tw.twSplit[krow * 512 + k2]; });
         if (krow == 0 && k2 == 0) {
-            xk = make_double2(zk.x + zk.y, zk.x - zk.y);   // (DC, Nyquist)
+            xk = pack_dcnyq(zk);
             XDN[row] = xk;
         }
         x[k2] = xk;
@@ -1072,12 +1008,8 @@ __global__ __launch_bounds__(128) void k_big_rows_inv(const double2* __restrict_
         const int k2 = lane + 64 * r;
         const double2 yk = own[r];
         const double2 yp = rows[w ^ 1][krow == 0 ? ((512 - k2) & 511) : (511 - k2)];
-        const double2 e = make_double2(0.5 * (yk.x + yp.x), 0.5 * (yk.y - yp.y));
-        const double2 d = make_double2(0.5 * (yk.x - yp.x), 0.5 * (yk.y + yp.y));
-        const double2 wk = tw.twSplit[krow * 512 + k2];
-        const double2 o = make_double2(fma(d.x, wk.x, d.y * wk.y), fma(d.y, wk.x, -(d.x * wk.y)));   // d * conj(w)
-        double2 z = make_double2(e.x - o.y, e.y + o.x);
-        if (krow == 0 && k2 == 0) z = make_double2(0.5 * (y0.x + y0.y), 0.5 * (y0.x - y0.y));
+        double2 z = rfft_unsplit(yk, yp, [&] { return tw.twSplit[krow * 512 + k2]; });
+        if (krow == 0 && k2 == 0) z = unpack_dcnyq(y0);
         v[r] = z;
     }
     wave_cfft512<true>(v, lds[w], lane, tw.tw512[lane * M1], tw.tw512[8 * (lane & 7) * M1]);
@@ -1101,11 +1033,12 @@ __global__ __launch_bounds__(512) void k_big_cols_inv(const double2* __restrict_
     const int col = threadIdx.x & (kBigCols - 1), j = threadIdx.x / kBigCols;
     const int n2 = tile * kBigCols + col;
     const int stride = M1 >> 3;
+    const ColMap m{ j, stride, col, kBigCols };
     const double2* a = A + (int64_t)tr * P;
     double2 v[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) v[q] = a[(j + q * stride) * 512 + n2];
-    col_fft<true>(v, dyn, M1, tw.tw512, j, col, kBigCols);
+    col_fft<true>(v, dyn, M1, tw.tw512, m);
     const int c = tr / T, t = tr - c * T;
     const double s = 1.0 / (double)P;
     const int halfM = P >> 1;
@@ -1113,7 +1046,7 @@ __global__ __launch_bounds__(512) void k_big_cols_inv(const double2* __restrict_
     for (int q = 0; q < 8; ++q) {
         const int n1 = j + q * stride;
         if (n1 >= (M1 >> 1)) {
-            const double2 z = dyn[n1 * kBigCols + col];
+            const double2 z = dyn[m.at(n1)];
             const int n = n1 * 512 + n2;
             store_block2<MODE>(out, chStride, ro, c, t, P, 2 * (n - halfM), make_double2(z.x * s, z.y * s));
         }
@@ -1162,7 +1095,32 @@ void allowLargeLds(K kernel, size_t bytes)
 
 }  // namespace
 
-static size_t wgLdsBytes(int P) { return (size_t)(P + (P >> 3)) * sizeof(double2); }   // padded buffer of the *_wg kernels
+// which kernels transform partitions of P samples (the table at the head of this file)
+enum class Family { Stockham, Wave512, MixedRadix, P4, FourStep };
+static Family fftFamily(int P)
+{
+    if (P > 4096) return Family::FourStep;
+    if (P == kP) return Family::Wave512;
+    if (P == kP4) return Family::P4;
+    return P >= 1024 ? Family::MixedRadix : Family::Stockham;
+}
+
+// launch geometry of the two passes of n four-step transforms (P > 4096); the scratch between them is [n][P]
+struct FourStepGeom {
+    dim3 colGrid, colBlock, rowGrid, rowBlock;
+    size_t colLds;
+    FourStepGeom(int P, int n)
+    {
+        const int M1 = P >> 9, cols = bigCols(M1);
+        colGrid = dim3(n * (512 / cols));             // column tiles of every transform
+        colBlock = dim3(cols * M1 / 8);
+        colLds = (size_t)M1 * cols * sizeof(double2);
+        rowGrid = dim3(n * ((M1 >> 1) + 1));          // row pairs (k1, M1 - k1) of every transform
+        rowBlock = dim3(128);
+    }
+};
+
+static size_t p4LdsBytes() { return 8 * kP4Row * sizeof(double2); }      // the exchange buffer: eight rows of kP4Row complex
 // frames of one channel are walked by `split` workgroups (contiguous ranges): one per channel when the channels alone
 // fill the chip (2 workgroups per CU), more for few channels
 static int p4Split(int nCh, int T)
@@ -1171,35 +1129,46 @@ static int p4Split(int nCh, int T)
     while (nCh * split < 2048 && split * 2 <= T) split *= 2;
     return split;
 }
-static int genericThreads(int P) { return P / 2 < 64 ? 64 : (P / 2 > 256 ? 256 : P / 2); }
+
+// the LDS families: n workgroups, one per transform
+template <typename F, bool FRAME, typename... Args>
+static void launch_fwd_lds(hipStream_t stream, int n, int P, Args... args)
+{
+    allowLargeLds(k_rfft_fwd_lds<F, FRAME>, F::ldsBytes(P));
+    hipLaunchKernelGGL((k_rfft_fwd_lds<F, FRAME>), dim3(n), dim3(F::threads(P)), F::ldsBytes(P), stream, args...);
+}
 
 void launch_rfft_fwd_ols(hipStream_t stream, const double* in, int64_t chStride, const double* histOld,
                          double* histNew, double2* X, double2* XDN, FftTables tw, int P, int nCh, int T, int head,
                          int ringSlots, double2* scratch, int forceSplit)
 {
-    if (P > 4096) {         // four-step: column pass into scratch [nCh * T][P], then row pass + split into the FDL ring
-        const int M1 = P >> 9;
-        hipLaunchKernelGGL(k_big_cols_fwd<true>, dim3(nCh * T * (512 / bigCols(M1))), dim3(bigCols(M1) * M1 / 8), (size_t)M1 * bigCols(M1) * sizeof(double2),
-                           stream, in, chStride, histOld, histNew, 0, scratch, tw, P, T);
-        hipLaunchKernelGGL(k_big_rows_fwd, dim3(nCh * T * ((M1 >> 1) + 1)), dim3(128), 0, stream, scratch, X, XDN, tw, P,
-                           T, head, ringSlots - 1, ringSlots);
-        return;
+    switch (fftFamily(P)) {
+    case Family::FourStep: {      // column pass into scratch [nCh * T][P], then row pass + split into the FDL ring
+        const FourStepGeom g(P, nCh * T);
+        hipLaunchKernelGGL(k_big_cols_fwd<true>, g.colGrid, g.colBlock, g.colLds, stream, in, chStride, histOld, histNew, 0,
+                           scratch, tw, P, T);
+        hipLaunchKernelGGL(k_big_rows_fwd, g.rowGrid, g.rowBlock, 0, stream, scratch, X, XDN, tw, P, T, head, ringSlots - 1,
+                           ringSlots);
+        break;
     }
-    if (P == kP)
+    case Family::Wave512:
         hipLaunchKernelGGL(k_rfft_fwd_ols<false>, dim3(nCh * T), dim3(64), 0, stream, in, chStride, histOld, histNew, X, XDN,
                            tw, T, head, ringSlots - 1, FwdSide{});
-    else if (P == kP4) {
+        break;
+    case Family::P4: {
         const int split = forceSplit > 0 ? forceSplit : p4Split(nCh, T);
-        allowLargeLds(k_rfft_fwd_ols_p4, wgLdsBytes(P));
-        hipLaunchKernelGGL(k_rfft_fwd_ols_p4, dim3(nCh * split), dim3(512), wgLdsBytes(P), stream, in, chStride, histOld,
+        allowLargeLds(k_rfft_fwd_ols_p4, p4LdsBytes());
+        hipLaunchKernelGGL(k_rfft_fwd_ols_p4, dim3(nCh * split), dim3(512), p4LdsBytes(), stream, in, chStride, histOld,
                            histNew, X, XDN, tw, T, split, head, ringSlots - 1);
-    } else if (P >= 1024) {
-        allowLargeLds(k_rfft_fwd_ols_wg, wgLdsBytes(P));
-        hipLaunchKernelGGL(k_rfft_fwd_ols_wg, dim3(nCh * T), dim3(P / 8), wgLdsBytes(P), stream, in, chStride,
-                           histOld, histNew, X, XDN, tw, P, T, head, ringSlots - 1);
-    } else
-        hipLaunchKernelGGL(k_rfft_fwd_ols_generic, dim3(nCh * T), dim3(genericThreads(P)), 2 * P * sizeof(double2),
-                           stream, in, chStride, histOld, histNew, X, XDN, tw, P, T, head, ringSlots - 1);
+        break;
+    }
+    case Family::MixedRadix:
+        launch_fwd_lds<MixedRadixFft, true>(stream, nCh * T, P, in, chStride, histOld, histNew, 0, X, XDN, tw, P, T, head, ringSlots - 1);
+        break;
+    case Family::Stockham:
+        launch_fwd_lds<StockhamFft, true>(stream, nCh * T, P, in, chStride, histOld, histNew, 0, X, XDN, tw, P, T, head, ringSlots - 1);
+        break;
+    }
 }
 
 bool rfft_fwd_can_carry_side(int P, int nSide, const int64_t* stride, const int64_t* off, int nTab)
@@ -1226,26 +1195,28 @@ void launch_rfft_fwd_ols_side(hipStream_t stream, const double* in, int64_t chSt
 void launch_ir_spectra(hipStream_t stream, const double* heff, int heffLen, double2* H, double2* HDN, FftTables tw,
                        int P, int nParts, double2* scratch)
 {
-    if (P > 4096) {         // scratch [nParts][P]
-        const int M1 = P >> 9;
-        hipLaunchKernelGGL(k_big_cols_fwd<false>, dim3(nParts * (512 / bigCols(M1))), dim3(bigCols(M1) * M1 / 8), (size_t)M1 * bigCols(M1) * sizeof(double2),
-                           stream, heff, 0, nullptr, nullptr, heffLen, scratch, tw, P, 1);
-        hipLaunchKernelGGL(k_big_rows_fwd, dim3(nParts * ((M1 >> 1) + 1)), dim3(128), 0, stream, scratch, H, HDN, tw, P, 1, 0,
-                           0, 0);
-        return;
+    switch (fftFamily(P)) {
+    case Family::FourStep: {      // scratch [nParts][P]
+        const FourStepGeom g(P, nParts);
+        hipLaunchKernelGGL(k_big_cols_fwd<false>, g.colGrid, g.colBlock, g.colLds, stream, heff, 0, nullptr, nullptr, heffLen,
+                           scratch, tw, P, 1);
+        hipLaunchKernelGGL(k_big_rows_fwd, g.rowGrid, g.rowBlock, 0, stream, scratch, H, HDN, tw, P, 1, 0, 0, 0);
+        break;
     }
-    if (P == kP)
+    case Family::Wave512:
         hipLaunchKernelGGL(k_ir_spectra, dim3(nParts), dim3(64), 0, stream, heff, heffLen, H, HDN, tw);
-    else if (P == kP4) {
-        allowLargeLds(k_ir_spectra_p4, wgLdsBytes(P));
-        hipLaunchKernelGGL(k_ir_spectra_p4, dim3(nParts), dim3(512), wgLdsBytes(P), stream, heff, heffLen, H, HDN, tw);
-    } else if (P >= 1024) {
-        allowLargeLds(k_ir_spectra_wg, wgLdsBytes(P));
-        hipLaunchKernelGGL(k_ir_spectra_wg, dim3(nParts), dim3(P / 8), wgLdsBytes(P), stream, heff, heffLen, H, HDN,
-                           tw, P);
-    } else
-        hipLaunchKernelGGL(k_ir_spectra_generic, dim3(nParts), dim3(genericThreads(P)), 2 * P * sizeof(double2), stream,
-                           heff, heffLen, H, HDN, tw, P);
+        break;
+    case Family::P4:
+        allowLargeLds(k_ir_spectra_p4, p4LdsBytes());
+        hipLaunchKernelGGL(k_ir_spectra_p4, dim3(nParts), dim3(512), p4LdsBytes(), stream, heff, heffLen, H, HDN, tw);
+        break;
+    case Family::MixedRadix:
+        launch_fwd_lds<MixedRadixFft, false>(stream, nParts, P, heff, 0, nullptr, nullptr, heffLen, H, HDN, tw, P, 1, 0, 0);
+        break;
+    case Family::Stockham:
+        launch_fwd_lds<StockhamFft, false>(stream, nParts, P, heff, 0, nullptr, nullptr, heffLen, H, HDN, tw, P, 1, 0, 0);
+        break;
+    }
 }
 
 void launch_spectrum_gain(hipStream_t stream, double2* H, double2* HDN, const double* gain, int P, int nParts)
@@ -1254,31 +1225,41 @@ void launch_spectrum_gain(hipStream_t stream, double2* H, double2* HDN, const do
 }
 
 namespace {
+template <int MODE, typename F, typename... Args>
+void launch_inv_lds(hipStream_t stream, int n, int P, Args... args)
+{
+    allowLargeLds(k_rfft_inv_lds<MODE, F>, F::ldsBytes(P));
+    hipLaunchKernelGGL((k_rfft_inv_lds<MODE, F>), dim3(n), dim3(F::threads(P)), F::ldsBytes(P), stream, args...);
+}
+
 template <int MODE>
 void launch_inv(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw, int P, int nCh, int T,
                 double2* scratch, OutSpec ro, int forceSplit = 0)
 {
-    if (P > 4096) {         // scratch [nCh * T][P]
-        const int M1 = P >> 9;
-        hipLaunchKernelGGL(k_big_rows_inv, dim3(nCh * T * ((M1 >> 1) + 1)), dim3(128), 0, stream, Y, scratch, tw, P);
-        hipLaunchKernelGGL(k_big_cols_inv<MODE>, dim3(nCh * T * (512 / bigCols(M1))), dim3(bigCols(M1) * M1 / 8), (size_t)M1 * bigCols(M1) * sizeof(double2), stream,
-                           scratch, out, chStride, tw, P, T, ro);
-        return;
+    switch (fftFamily(P)) {
+    case Family::FourStep: {      // scratch [nCh * T][P]
+        const FourStepGeom g(P, nCh * T);
+        hipLaunchKernelGGL(k_big_rows_inv, g.rowGrid, g.rowBlock, 0, stream, Y, scratch, tw, P);
+        hipLaunchKernelGGL(k_big_cols_inv<MODE>, g.colGrid, g.colBlock, g.colLds, stream, scratch, out, chStride, tw, P, T, ro);
+        break;
     }
-    if (P == kP)
+    case Family::Wave512:
         hipLaunchKernelGGL(k_rfft_inv_ols<MODE>, dim3(nCh * T), dim3(64), 0, stream, Y, out, chStride, tw, T, ro);
-    else if (P == kP4) {
+        break;
+    case Family::P4: {
         const int split = forceSplit > 0 ? forceSplit : p4Split(nCh, T);
-        allowLargeLds(k_rfft_inv_ols_p4<MODE>, wgLdsBytes(P));
-        hipLaunchKernelGGL(k_rfft_inv_ols_p4<MODE>, dim3(nCh * split), dim3(512), wgLdsBytes(P), stream, Y, out, chStride, tw, T,
+        allowLargeLds(k_rfft_inv_ols_p4<MODE>, p4LdsBytes());
+        hipLaunchKernelGGL(k_rfft_inv_ols_p4<MODE>, dim3(nCh * split), dim3(512), p4LdsBytes(), stream, Y, out, chStride, tw, T,
                            split, ro);
-    } else if (P >= 1024) {
-        allowLargeLds(k_rfft_inv_ols_wg<MODE>, wgLdsBytes(P));
-        hipLaunchKernelGGL(k_rfft_inv_ols_wg<MODE>, dim3(nCh * T), dim3(P / 8), wgLdsBytes(P), stream, Y, out, chStride,
-                           tw, P, T, ro);
-    } else
-        hipLaunchKernelGGL(k_rfft_inv_ols_generic<MODE>, dim3(nCh * T), dim3(genericThreads(P)), 2 * P * sizeof(double2),
-                           stream, Y, out, chStride, tw, P, T, ro);
+        break;
+    }
+    case Family::MixedRadix:
+        launch_inv_lds<MODE, MixedRadixFft>(stream, nCh * T, P, Y, out, chStride, tw, P, T, ro);
+        break;
+    case Family::Stockham:
+        launch_inv_lds<MODE, StockhamFft>(stream, nCh * T, P, Y, out, chStride, tw, P, T, ro);
+        break;
+    }
 }
 }  // namespace
 

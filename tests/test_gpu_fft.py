@@ -4,9 +4,9 @@ cpq_diag_partition_fft: forward transform of every overlap-save frame [previous 
 fp64, inverse of the same spectra against the input (the second half of the inverse of a frame's spectrum is the block
 itself), and the round trip.  One case per kernel family:
 
-  P = 64 / 128 / 256      k_rfft_*_ols_generic   (radix-2 Stockham through LDS)
+  P = 64 / 128 / 256      k_rfft_*_lds over StockhamFft     (one workgroup per transform, radix-2 Stockham through LDS)
   P = 512                 k_rfft_*_ols           (wave-level 512-point transform, 8 points per lane)
-  P = 1024 / 2048         k_rfft_*_ols_wg        (one workgroup per transform, mixed radix)
+  P = 1024 / 2048         k_rfft_*_lds over MixedRadixFft   (the same kernels, mixed radix through one padded buffer)
   P = 4096                k_rfft_*_ols_p4        (four-step inside a workgroup; spectra stored permuted)
   P = 8192 ... 131072     k_big_cols_* / k_big_rows_*   (four-step through a scratch buffer; spectra stored permuted;
                           65536 / 131072: 128- / 256-point columns, 32 / 16 columns per workgroup)

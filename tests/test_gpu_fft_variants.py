@@ -9,7 +9,7 @@ that cpq_diag_partition_fft (tests/test_gpu_fft.py) covers --
   add store      launch_rfft_inv_ols_add  (MODE 3, P = 512): one or two delay-line rings added to the rows
   IR spectra     launch_ir_spectra at the edges of h_eff's length, launch_spectrum_gain with a factor of its own per bin
 
-per kernel family: P = 64, 256 generic; 512 wave-level; 1024, 2048 one workgroup; 4096 four-step in a workgroup; 8192 four-step
+per kernel family: P = 64, 256 radix-2 Stockham in LDS; 512 wave-level; 1024, 2048 mixed radix in LDS; 4096 four-step in a workgroup; 8192 four-step
 through scratch with 16-point columns; 65536, 131072 the 128- and 256-point column variants.  3 channels x 5 blocks up to
 P = 4096, 2 x 2 above.
 
