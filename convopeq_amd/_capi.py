@@ -30,7 +30,7 @@ CPQ_ORDER_CONV_THEN_EQ = 0
 CPQ_ORDER_EQ_THEN_CONV = 1
 KERNEL_IDS = {"k_rfft_fwd_ols": 0, "k_fdl_mac": 1, "k_fdl_mac_dcnyq": 2, "k_rfft_inv_ols": 3, "k_svf_cascade": 4,
               "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8, "k_meter": 9,
-              "k_pcm": 10, "k_out": 11}
+              "k_pcm": 10, "k_out": 11, "k_dither": 12}
 CPQ_LEVEL_NUC = 0
 CPQ_LEVEL_PROCESSOR = 1
 CPQ_EQ_MODE_AUTO = 0
@@ -48,6 +48,10 @@ CPQ_OUT_HEADROOM = 2
 CPQ_OUT_LIMITER = 4
 CPQ_OUT_CLAMP = 8
 CPQ_OUT_ALL = 15
+CPQ_DITHER_OFF = 0
+CPQ_DITHER_FIXED4 = 1
+CPQ_DITHER_FIXED15 = 2
+CPQ_DITHER_TILE = 64
 CPQ_PCM_F64 = 0
 CPQ_PCM_F32 = 1
 CPQ_PCM_S16 = 2
@@ -217,6 +221,11 @@ SYMBOLS = {
     "cpq_out_process": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32]),
     "cpq_out_process_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
     "cpq_out_read_envelope": (C.c_int32, [_E, C.c_int32, c_double_p]),
+    "cpq_dither_design": (C.c_int32, [C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p]),
+    "cpq_engine_set_dither": (C.c_int32, [_E, C.c_int32, C.c_int32]),
+    "cpq_dither_reset": (C.c_int32, [_E]),
+    "cpq_dither_process": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32]),
+    "cpq_dither_process_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
     "cpq_pcm_bytes_per_sample": (C.c_int32, [C.c_int32]),
     "cpq_pcm_unpack": (C.c_int32, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32]),
     "cpq_pcm_unpack_device": (C.c_int32, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32]),

@@ -162,6 +162,7 @@ const char* cpq_kernel_name(int32_t id)
         case CPQ_K_METER: return "k_meter";
         case CPQ_K_PCM: return "k_pcm";
         case CPQ_K_OUT: return "k_out";
+        case CPQ_K_DITHER: return "k_dither";
         default: return "?";
     }
 }
@@ -471,6 +472,7 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
         if (rc != CPQ_OK) return rc;
     }
     CPQ_TRY(refreshOutStage(e));        // dcBlockers().output*.init / peakLimiter.prepare + reset at the new base rate
+    CPQ_TRY(refreshDither(e));          // the shaper's prepare(rate, bits)
     return zeroRuntimeState(e, true, true);
 }
 
@@ -583,7 +585,9 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed)
 int cpqi::meteredChain(cpq_engine* e, const double* a, double* b, int n)
 {
     int rc = e->osFactor > 1 ? enqueueOsChain(e, a, b, n) : enqueueBoth(e, a, b, n);
-    if (rc == CPQ_OK) rc = enqueueOutPre(e, b, n, b, n, n);           // each half returns at once when its flags are off
+    const bool dither = e->ditherShaper != CPQ_DITHER_OFF;            // the shaper then applies the headroom and the scrub itself
+    if (rc == CPQ_OK) rc = enqueueOutPre(e, b, n, b, n, n, !dither);  // each half returns at once when its flags are off
+    if (rc == CPQ_OK && dither) rc = enqueueDither(e, b, n, b, n, n);
     if (rc == CPQ_OK && e->meterFlags) rc = enqueueMeters(e, b, n, n);
     if (rc == CPQ_OK) rc = enqueueOutPost(e, b, n, b, n, n);
     return rc;

@@ -1,0 +1,134 @@
+// engine_dither.cpp -- the dither stage: processOutputDouble's ditherBitDepth > 0 branch (DSPCoreDouble.cpp:644-654) for the
+// reference's two deterministic shapers, FixedNoiseShaper and Fixed15TapNoiseShaper.  The kernel is in dither_kernels.hip, the
+// design and the seeds in dither_design.cpp; the host owns the coefficients and the per-channel state (error taps, generator
+// words).  Every stream is a DSPCore of its own, so every stream starts from the same two generator states (L, R).  In the
+// whole-chain call the stage sits between the DC blocker and the meters (engine_core.cpp, meteredChain).
+#include "engine_internal.hpp"
+
+namespace cpqi {
+
+namespace {
+
+int callbackLen(const cpq_engine* e) { return std::max(1, e->B / e->osFactor); }
+double baseRate(const cpq_engine* e) { return e->sampleRate / e->osFactor; }
+
+int clearErrors(cpq_engine* e)
+{
+    CPQ_HIP(e, hipSetDevice(e->device));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    CPQ_HIP(e, hipMemset(e->ditherErr, 0, sizeof(double) * cpq::kDitherMaxOrder * (size_t)e->nCh));
+    return CPQ_OK;
+}
+
+int seed(cpq_engine* e)
+{
+    std::vector<unsigned long long> words(4 * (size_t)e->nCh);
+    for (int side = 0; side < 2; ++side) {
+        unsigned long long s[4];
+        cpq::ditherSeed(e->ditherShaper, baseRate(e), e->ditherBits, side, s);
+        for (int k = 0; k < 4; ++k)
+            for (int ch = side; ch < e->nCh; ch += 2) words[(size_t)k * e->nCh + ch] = s[k];
+    }
+    CPQ_HIP(e, hipMemcpy(e->ditherRng, words.data(), sizeof(unsigned long long) * words.size(), hipMemcpyHostToDevice));
+    return CPQ_OK;
+}
+
+void design(cpq_engine* e)
+{
+    cpq::DitherParams& p = e->ditherParams;
+    cpq::ditherDesign(baseRate(e), e->ditherShaper, e->ditherBits, p.c, &p.scale);     // arguments checked by cpq_engine_set_dither
+    p.invScale = std::ldexp(1.0, e->ditherBits - 1);
+    p.maxV = 1.0 - (1.0 / p.invScale);
+}
+
+int checkRows(cpq_engine* e, const void* in, const void* out, int n)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    if (e->ditherShaper == CPQ_DITHER_OFF) return fail(e, CPQ_ERR_NOT_READY, "dither is off (cpq_engine_set_dither)");
+    if (!in || !out) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (n <= 0 || n > e->maxCall / e->osFactor)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, e->maxCall / e->osFactor);
+    if (!e->anyCalls && n % callbackLen(e) != 0)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d is not a multiple of the callback length %d", n, callbackLen(e));
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
+        return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    return CPQ_OK;
+}
+
+}  // namespace
+
+int refreshDither(cpq_engine* e)
+{
+    if (e->ditherShaper == CPQ_DITHER_OFF) return CPQ_OK;
+    design(e);
+    CPQ_TRY(clearErrors(e));                    // synchronises the stream
+    return e->ditherShaper == CPQ_DITHER_FIXED15 ? seed(e) : CPQ_OK;
+}
+
+int enqueueDither(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int n)
+{
+    if (e->ditherShaper == CPQ_DITHER_OFF) return CPQ_OK;
+    cpq::DitherParams p = e->ditherParams;
+    p.scrub = (e->outFlags & CPQ_OUT_HEADROOM) != 0;
+    p.headroom = p.scrub ? cpq::kOutHeadroom : 1.0;
+    ProfScope ps(e, CPQ_K_DITHER);
+    if (!cpq::launch_dither(e->stream, in, inStride, out, outStride, n, e->nCh, cpq::ditherOrder(e->ditherShaper), p, e->ditherErr, e->ditherRng))
+        return fail(e, CPQ_ERR_UNSUPPORTED, "no dither kernel for shaper %d", e->ditherShaper);       // a missing kernel is an error
+    CPQ_HIP(e, hipGetLastError());
+    return CPQ_OK;
+}
+
+}  // namespace cpqi
+
+using namespace cpqi;
+
+extern "C" {
+
+int32_t cpq_engine_set_dither(cpq_engine* e, int32_t shaper, int32_t bitDepth)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    if (shaper != CPQ_DITHER_OFF && !cpq::ditherOrder(shaper)) return fail(e, CPQ_ERR_INVALID_ARG, "unknown dither shaper %d", shaper);
+    if (shaper != CPQ_DITHER_OFF && (bitDepth < 1 || bitDepth > 32)) return fail(e, CPQ_ERR_INVALID_ARG, "dither bit depth %d outside 1..32", bitDepth);
+    if (shaper == CPQ_DITHER_OFF) bitDepth = 0;
+    if (shaper == e->ditherShaper && bitDepth == e->ditherBits) return CPQ_OK;
+    CPQ_HIP(e, hipSetDevice(e->device));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    if (shaper != CPQ_DITHER_OFF && !e->ditherErr)
+        CPQ_TRY(allocAll(e, { { e->ditherErr, cpq::kDitherMaxOrder * (size_t)e->nCh }, { e->ditherRng, 4 * (size_t)e->nCh } },
+                         "dither state buffers could not be allocated"));
+    e->ditherShaper = shaper;
+    e->ditherBits = bitDepth;
+    if (shaper == CPQ_DITHER_OFF) return CPQ_OK;
+    design(e);
+    CPQ_TRY(clearErrors(e));
+    return seed(e);
+}
+
+int32_t cpq_dither_reset(cpq_engine* e)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    if (e->ditherShaper == CPQ_DITHER_OFF) return fail(e, CPQ_ERR_NOT_READY, "dither is off (cpq_engine_set_dither)");
+    return clearErrors(e);
+}
+
+int32_t cpq_dither_process_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
+{
+    CPQ_TRY(checkRows(e, dIn, dOut, nSamples));
+    CPQ_HIP(e, hipSetDevice(e->device));
+    return enqueueDither(e, dIn, nSamples, dOut, nSamples, nSamples);
+}
+
+int32_t cpq_dither_process(cpq_engine* e, const double* in, double* out, int32_t nSamples)
+{
+    CPQ_TRY(checkRows(e, in, out, nSamples));
+    CPQ_HIP(e, hipSetDevice(e->device));
+    CPQ_TRY(ensureCallBuffer(e, e->stageIn, "upload staging"));
+    const size_t bytes = sizeof(double) * (size_t)e->nCh * nSamples;
+    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, bytes, hipMemcpyHostToDevice, e->stream));
+    CPQ_TRY(enqueueDither(e, e->stageIn, nSamples, e->stageIn, nSamples, nSamples));
+    CPQ_HIP(e, hipMemcpyAsync(out, e->stageIn, bytes, hipMemcpyDeviceToHost, e->stream));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    return CPQ_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 //   engine_os.cpp    half-band oversampler around the routing: stage buffers, per-stream state machine
 //   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
 //   engine_out.cpp   output stage: DC blocker, headroom, limiter and clamp on the delivered rows
+//   engine_dither.cpp  dither stage: the fixed 4- and 15-tap noise shapers between the output stage's two halves
 //   engine_meter.cpp  loudness and true-peak metering of the delivered rows
 //   engine_diag.cpp  every cpq_diag_* entry point: single launchers on caller-filled buffers, no engine
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
@@ -321,6 +322,12 @@ struct cpq_engine {
     cpqi::DeviceBuffer<double> outEnv;                  // [streams] limiter envelopes
     double outRelease = 0.0;                            // SimplePeakLimiter::releaseCoeff at the base rate
 
+    // dither stage (engine_dither.cpp): per channel the shaper's error taps and its generator's words; one group
+    int ditherShaper = CPQ_DITHER_OFF, ditherBits = 0;
+    cpq::DitherParams ditherParams{};                   // coefficients and scales at the present base rate
+    cpqi::DeviceBuffer<double> ditherErr;               // [kDitherMaxOrder][nCh]
+    cpqi::DeviceBuffer<unsigned long long> ditherRng;   // [4][nCh]
+
     // packed PCM entry points (engine_pcm.cpp): the call's packed input and output on the device, one group
     cpqi::DeviceBuffer<char> pcmIn, pcmOut;
     size_t pcmInCap = 0, pcmOutCap = 0;
@@ -420,8 +427,13 @@ int enqueueMeters(cpq_engine* e, const double* rows, int64_t stride, int nBase);
 int refreshOutStage(cpq_engine* e);             // redesign for the present base rate and reset; nothing while the stage is off
 // the steps before the meters (DC blocker, headroom + scrub) and after them (limiter, clamp); in == out allowed.  A half whose
 // flags are off launches nothing and leaves out untouched
-int enqueueOutPre(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
+// headroom = false: the DC blocker alone (the whole-chain call with dither on, where the shaper applies headroom and scrub)
+int enqueueOutPre(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase, bool headroom = true);
 int enqueueOutPost(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
+// engine_dither.cpp
+int refreshDither(cpq_engine* e);               // prepare() at the present base rate: coefficients, errors cleared, the 15-tap shaper reseeded
+// headroom, shaper and (with CPQ_OUT_HEADROOM) the scrub; launches nothing while dither is off
+int enqueueDither(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
 // engine_core.cpp: DSPCore's routing of one block (conv / EQ in the configured order, output filter, makeup)
 int enqueueBoth(cpq_engine* e, const double* a, double* b, int n);
 // the whole-chain call behind cpq_engine_process_block: oversampling around the routing, then the output stage with the meters

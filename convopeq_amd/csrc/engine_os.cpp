@@ -188,7 +188,7 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
     CPQ_HIP(e, hipMemset(e->osFlags, 0, sizeof(int) * 4 * S));
     e->osFactor = factor;
     e->osType = type;
-    if (nStages == 0) { CPQ_TRY(refreshMeters(e)); return refreshOutStage(e); }     // the meters and the output stage follow the base rate
+    if (nStages == 0) { CPQ_TRY(refreshMeters(e)); CPQ_TRY(refreshOutStage(e)); return refreshDither(e); }     // the meters and the output stage follow the base rate
     cpq::OsStage st[3];
     size_t bytes = 0;
     for (int i = 0; i < nStages; ++i) {
@@ -223,7 +223,8 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
     if (rc != CPQ_OK) return rc;
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     CPQ_TRY(refreshMeters(e));
-    return refreshOutStage(e);
+    CPQ_TRY(refreshOutStage(e));
+    return refreshDither(e);
 }
 
 int32_t cpq_os_up_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nBase)

@@ -64,12 +64,13 @@ int refreshOutStage(cpq_engine* e)
     return CPQ_OK;
 }
 
-int enqueueOutPre(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int n)
+int enqueueOutPre(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int n, bool headroom)
 {
-    if (!(e->outFlags & kPreFlags)) return CPQ_OK;
+    const int flags = e->outFlags & (headroom ? kPreFlags : CPQ_OUT_DC_BLOCK);
+    if (!flags) return CPQ_OK;
     ProfScope p(e, CPQ_K_OUT);
-    cpq::launch_out_pre(e->stream, in, inStride, out, outStride, n, callbackLen(e), e->nCh, (e->outFlags & CPQ_OUT_DC_BLOCK) != 0,
-                        (e->outFlags & CPQ_OUT_HEADROOM) != 0, e->outTab, e->outDc);
+    cpq::launch_out_pre(e->stream, in, inStride, out, outStride, n, callbackLen(e), e->nCh, (flags & CPQ_OUT_DC_BLOCK) != 0,
+                        (flags & CPQ_OUT_HEADROOM) != 0, e->outTab, e->outDc);
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;
 }

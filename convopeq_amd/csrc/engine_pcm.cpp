@@ -16,8 +16,8 @@ int checkFormat(cpq_engine* e, int format, int layout, bool output)
 {
     if (pcm::bytesPerSample(format) < 0) return fail(e, CPQ_ERR_INVALID_ARG, "unknown PCM format %d", format);
     if (!pcm::validLayout(layout)) return fail(e, CPQ_ERR_INVALID_ARG, "unknown PCM layout %d", layout);
-    if (output && format == CPQ_PCM_S16)
-        return fail(e, CPQ_ERR_UNSUPPORTED, "16-bit output needs the dither stage, which this engine does not have");
+    if (output && format == CPQ_PCM_S16 && !(e->ditherShaper != CPQ_DITHER_OFF && e->ditherBits <= 16))
+        return fail(e, CPQ_ERR_UNSUPPORTED, "16-bit output needs the dither stage at 16 bits or fewer (cpq_engine_set_dither)");
     return CPQ_OK;
 }
 

@@ -77,4 +77,23 @@ struct OutStageHost {
     void process(double* l, double* r, int n, int flags);   // flags: CPQ_OUT_*
 };
 
+// dither stage (dither_design.cpp): FixedNoiseShaper / Fixed15TapNoiseShaper of the reference
+constexpr int kDitherMaxOrder = 16;
+inline int ditherOrder(int shaper) { return shaper == CPQ_DITHER_FIXED4 ? 4 : shaper == CPQ_DITHER_FIXED15 ? 16 : 0; }
+// prepare(rate, bits): coeffs[16] (unused taps 0.0), scale = 2^-(bits - 1); false for an unknown shaper or bits outside 1..32
+bool   ditherDesign(double rate, int shaper, int bits, double coeffs[kDitherMaxOrder], double* scale);
+// xoshiro256++ state of channel ch (0 = L, 1 = R): the 4-tap header's constants, or initializeRandomStates(rate, bits)
+void   ditherSeed(int shaper, double rate, int bits, int ch, unsigned long long s[4]);
+// one stream of the stage, sequential, in the reference's operation order: processStereoBlock(l, r, n, headroom)
+struct DitherHost {
+    int shaper = CPQ_DITHER_OFF, order = 0, bits = 0;
+    double coeffs[kDitherMaxOrder] = {}, scale = 1.0, invScale = 1.0;
+    double err[2][kDitherMaxOrder] = {};        // [channel][k], k = 0 the newest
+    unsigned long long rng[2][4] = {};
+    bool configure(double rate, int shaperId, int bitDepth);    // a new shaper object + prepare(): errors cleared, seeded
+    void prepare(double rate);                                  // prepare() again: errors cleared, the 15-tap shaper reseeded
+    void reset();                                               // errors only
+    void process(double* l, double* r, int n, double headroom);
+};
+
 }  // namespace cpq

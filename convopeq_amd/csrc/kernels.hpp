@@ -269,6 +269,19 @@ void launch_out_pre(hipStream_t stream, const double* in, int64_t inStride, doub
 void launch_out_post(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nStreams,
                      bool limiter, bool clamp, double release, double* env);
 
+// ---- dither stage (dither_kernels.hip): headroom, the 4- or 15-tap noise shaper and (scrub) the scrub on rows [nCh][n]; in and
+// out may be the same rows.  err [kDitherMaxOrder][nCh] (tap k of channel c at k * nCh + c, k = 0 the newest) and rng [4][nCh]
+// are carried across calls.  order: 4 or 16; false: no kernel for that order.
+constexpr int kDitherTile = CPQ_DITHER_TILE;    // samples of a row a wave stages in LDS at a time
+struct DitherParams {
+    double c[kDitherMaxOrder];
+    double scale, invScale, maxV;               // 2^-(bits-1), 2^(bits-1), 1 - scale
+    double headroom;                            // kOutHeadroom or 1.0
+    int scrub;
+};
+bool launch_dither(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nCh, int order,
+                   const DitherParams& p, double* err, unsigned long long* rng);
+
 // ---- packed PCM converters (pcm_kernels.hip): cpq_pcm_format x cpq_pcm_layout <-> fp64 rows [2 nStreams][n]
 constexpr int kPcmTile = 4096;     // samples of the packed side per workgroup: 4096 of a planar row, 2048 stereo frames
 // pcm aligned to its element (S24: any byte), rows to 8 bytes; sanitizeCb > 0: CPQ_PCM_SANITIZE with callbacks of that many

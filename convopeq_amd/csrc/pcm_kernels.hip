@@ -93,8 +93,9 @@ __device__ __forceinline__ void pcmEncode(unsigned char* img, int k, double x)
     if constexpr (FMT == CPQ_PCM_F64) *reinterpret_cast<double*>(img + 8 * k) = x;
     else if constexpr (FMT == CPQ_PCM_F32) *reinterpret_cast<float*>(img + 4 * k) = (float)x;
     else if constexpr (FMT == CPQ_PCM_S32) *reinterpret_cast<int*>(img + 4 * k) = pcmQuantize<32>(x);
+    else if constexpr (FMT == CPQ_PCM_S16) *reinterpret_cast<short*>(img + 2 * k) = (short)pcmQuantize<16>(x);
     else {
-        static_assert(FMT == CPQ_PCM_S24, "no 16-bit output");
+        static_assert(FMT == CPQ_PCM_S24, "unknown format");
         const unsigned q = (unsigned)pcmQuantize<24>(x);
         img[3 * k] = (unsigned char)q;
         img[3 * k + 1] = (unsigned char)(q >> 8);
@@ -232,9 +233,10 @@ bool launch_pcm_pack(hipStream_t stream, const double* rows, void* pcm, int form
     switch (format) {
     case CPQ_PCM_F64: packLayout<CPQ_PCM_F64>(stream, rows, pcm, layout, n, nStreams); return true;
     case CPQ_PCM_F32: packLayout<CPQ_PCM_F32>(stream, rows, pcm, layout, n, nStreams); return true;
+    case CPQ_PCM_S16: packLayout<CPQ_PCM_S16>(stream, rows, pcm, layout, n, nStreams); return true;     // the callers refuse it without dither
     case CPQ_PCM_S24: packLayout<CPQ_PCM_S24>(stream, rows, pcm, layout, n, nStreams); return true;
     case CPQ_PCM_S32: packLayout<CPQ_PCM_S32>(stream, rows, pcm, layout, n, nStreams); return true;
-    default: return false;               // S16 included: no 16-bit output without a dither stage
+    default: return false;
     }
 }
 

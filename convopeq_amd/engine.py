@@ -122,6 +122,15 @@ def out_design(rate):
     return alpha, rel.value
 
 
+def dither_design(rate, shaper, bit_depth):
+    """cpq_dither_design: (coefficients float64[16], scale) of a noise shaper's prepare(rate, bit_depth)."""
+    coeffs, scale = np.empty(16), C.c_double()
+    rc = K.load().cpq_dither_design(float(rate), int(shaper), int(bit_depth), _dp(coeffs), C.byref(scale))
+    if rc != 0:
+        raise CpqError(rc, "cpq_dither_design")
+    return coeffs, scale.value
+
+
 def pcm_bytes_per_sample(fmt):
     """cpq_pcm_bytes_per_sample: bytes of one packed sample, -1 for an unknown format."""
     return K.load().cpq_pcm_bytes_per_sample(int(fmt))
@@ -427,6 +436,20 @@ class BatchedEngine:
         self._ck(self._lib.cpq_out_read_envelope(self._h, int(stream), C.byref(v)))
         return v.value
 
+    # ---- dither stage (the fixed 4- and 15-tap noise shapers; headroom and scrub follow the output-stage flags)
+    def set_dither(self, shaper, bit_depth=0):
+        self._ck(self._lib.cpq_engine_set_dither(self._h, int(shaper), int(bit_depth)))
+
+    def dither_reset(self):
+        self._ck(self._lib.cpq_dither_reset(self._h))
+
+    def dither_process(self, x):
+        """The stage alone on rows [n_channels, n]."""
+        return self._host(self._lib.cpq_dither_process, x)
+
+    def dither_process_device(self, d_in, d_out, n_samples):
+        self._ck(self._lib.cpq_dither_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_samples))
+
     # ---- host-buffer processing: x is [n_channels, n_samples] float64
     def _host(self, fn, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -504,8 +527,8 @@ class BatchedEngine:
             n = C.c_int64()
             ms = C.c_double()
             self._ck(self._lib.cpq_profile_read(self._h, kid, C.byref(n), C.byref(ms)))
-            if name in ("k_os_halfband", "k_meter", "k_pcm", "k_out") and n.value == 0:
-                continue        # listed only for engines that oversample / meter / take packed PCM / run the output stage
+            if name in ("k_os_halfband", "k_meter", "k_pcm", "k_out", "k_dither") and n.value == 0:
+                continue        # listed only for engines that oversample / meter / take packed PCM / run the output stage / dither
             out[name] = (n.value, ms.value)
         return out
 

@@ -35,6 +35,8 @@ extern "C" {
  * (cpq_engine_set_output_stage, cpq_out_*) exist.  cpq_abi_revision() does not count them, so at run time a caller that may
  * meet an older library finds out by looking the symbol up (dlsym) */
 #define CPQ_HAS_OUTPUT_STAGE 1
+/* likewise: defined when the dither stage (cpq_engine_set_dither, cpq_dither_*) and 16-bit PCM output exist */
+#define CPQ_HAS_DITHER 1
 
 typedef enum {
     CPQ_OK               =  0,
@@ -566,7 +568,7 @@ int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t max_b
  * The stage runs on the base-rate rows at the end of cpq_engine_process_block[_device] and of the PCM calls: after the
  * oversampler's down stages, before the pack, one callback = block_size / factor samples (the ragged last chunk of a
  * CPQ_CALLS_ANY call is a callback of its own length).  With the stage on the meters read where the reference's do: after the
- * scrub, before the limiter.  Not built: dither and the noise shapers, the soft clipper, the fade-in, the fixed latency delay. */
+ * scrub, before the limiter.  Not built: the soft clipper, the fade-in, the fixed latency delay (dither: the next section). */
 #define CPQ_OUT_DC_BLOCK 1
 #define CPQ_OUT_HEADROOM 2
 #define CPQ_OUT_LIMITER  4
@@ -592,6 +594,44 @@ int32_t cpq_out_process_device(cpq_engine* e, const double* d_in, double* d_out,
 /* synchronises the engine's stream; *envelope = the limiter's envelope of one stream */
 int32_t cpq_out_read_envelope(cpq_engine* e, int32_t stream, double* envelope);
 
+/* ---------------------------------------------------------------- dither stage */
+/* processOutputDouble's ditherBitDepth > 0 branch (DSPCoreDouble.cpp:644-654) for the reference's two deterministic shapers:
+ * the shaper's processStereoBlock(l, r, n, headroom) takes the place of the plain headroom multiply; scrub, meters, limiter and
+ * clamp follow as without it, so the limiter acts after quantisation and a limited sample leaves the grid.
+ *   CPQ_DITHER_FIXED4   FixedNoiseShaper (src/FixedNoiseShaper.h): 4 error taps, xoshiro256++ seeded with the header's constants
+ *                       (channel 0 for L, channel 1 for R); its prepare() / reset() do not reseed
+ *   CPQ_DITHER_FIXED15  Fixed15TapNoiseShaper (src/Fixed15TapNoiseShaper.h): ORDER 16 (the sixteenth coefficient is 0.0), seeded
+ *                       by splitmix64 over (rate, bit depth) in every prepare()
+ * Per sample and channel: x = in * headroom; fb = sum c[k] e[k] (e[0] the newest stored error; 4 taps: one expression, left to
+ * right; 15 taps: fb = 0.0, fb += c[k] e[k]; no contraction); y = x - fb; v = clamp(y, -1, 1 - scale) + (u1 + u2 - 1) * scale
+ * with u = (xoshiro256++ >> 11) * 2^-53, u1 drawn first; yq = rint(v * invScale) (ties to even) * scale; the stored error is
+ * yq - y clamped to +-2 scale.  scale = 2^-(bits - 1).  Non-finite values: the 4-tap shaper replaces a non-finite y by 0 before
+ * the clamp and a non-finite result by 0, its stored error passes std::clamp (a NaN stays) and then becomes 0 when not finite;
+ * the 15-tap shaper has no such guards (a NaN in is a NaN out), clamps the rounded code to [-invScale, invScale - 1] with
+ * std::clamp, and its stored error passes max_sd / min_sd, which turn a NaN into -2 scale.  The coefficients are prepare()'s: ten
+ * presets (44.1 ... 768 kHz), linear interpolation in the rate between them, the first and the last preset outside.
+ * Every stream is a DSPCore of its own: all streams draw the same two sequences (L, R).
+ * Headroom is 0.8912509381337456 with CPQ_OUT_HEADROOM in the output-stage flags, else 1.0; the scrub runs only with that flag.
+ * Not built: the psychoacoustic and the adaptive shaper, the shapers' diagnostics, the 15-tap errorEnvelope / needsReset
+ * handshake (finite input cannot raise it). */
+#define CPQ_DITHER_OFF     0
+#define CPQ_DITHER_FIXED4  1
+#define CPQ_DITHER_FIXED15 2
+#define CPQ_DITHER_TILE    64   /* samples a workgroup of k_dither moves through LDS at a time (tests walk its edges) */
+/* prepare(rate, bit_depth) of the shaper: coeffs[16] (the 4-tap shaper fills 4, the rest 0.0) and *scale.  bit_depth 1 .. 32.
+ * Host only. */
+int32_t cpq_dither_design(double rate, int32_t shaper, int32_t bit_depth, double coeffs[16], double* scale);
+/* shaper CPQ_DITHER_OFF (the default: nothing is launched, bit_depth ignored) or one of the two shapers with bit_depth 1 .. 32;
+ * anything else is CPQ_ERR_INVALID_ARG before any state moves.  The same arguments again change nothing; any change clears the
+ * errors and reseeds.  The rate is sample_rate / oversampling factor: cpq_engine_prepare and cpq_engine_set_oversampling
+ * redesign the coefficients and clear the errors; they reseed the 15-tap shaper only, as the reference's prepare() does. */
+int32_t cpq_engine_set_dither(cpq_engine* e, int32_t shaper, int32_t bit_depth);
+/* the shaper's reset(): errors to 0, the generators run on.  CPQ_ERR_NOT_READY while dither is off (so for the calls below). */
+int32_t cpq_dither_reset(cpq_engine* e);
+/* The stage alone (headroom, shaper, scrub if flagged) on caller rows, with the argument rules of cpq_out_process. */
+int32_t cpq_dither_process(cpq_engine* e, const double* in, double* out, int32_t n_samples);
+int32_t cpq_dither_process_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_samples);
+
 /* ------------------------------------------------------- packed PCM in and out */
 /* The whole-chain call with a converter at each end: float32 or integer PCM, planar or interleaved, instead of fp64 rows.
  * What the reference does around its chain in float (DSPCore::processInput -> convertFloatToDoubleHighQuality,
@@ -612,7 +652,9 @@ int32_t cpq_out_read_envelope(cpq_engine* e, int32_t stream, double* envelope);
  *   out, S24/S32      rint(x * 2^(b-1)), ties to even, saturated to [-2^(b-1), 2^(b-1) - 1], NaN -> 0; S24 as three
  *                     little-endian bytes
  *   out, F64          a copy or an interleave
- *   out, S16          CPQ_ERR_UNSUPPORTED: a 16-bit result wants the dither stage, which this engine does not have
+ *   out, S16          only while the dither stage is on with bit_depth <= 16 (cpq_engine_set_dither): the S24 rule at 16 bits,
+ *                     which is exact on rows the shaper quantised and the limiter left alone; otherwise CPQ_ERR_UNSUPPORTED
+ *                     and the destination is untouched
  * Packed buffers are aligned to their element (S24: any byte), fp64 rows to 8 bytes; the buffers of
  * cpq_engine_process_block_pcm[_device] to 16 bytes like those of cpq_engine_process_block.  No byte outside
  * [base, base + bytes) of a buffer is read or written. */
@@ -653,7 +695,8 @@ typedef enum {
     CPQ_K_METER    = 9,   /* loudness and true-peak meters (k_meter_kweight / k_meter_true_peak / k_meter_finish) */
     CPQ_K_PCM      = 10,  /* packed PCM converters (k_pcm_unpack / k_pcm_pack) */
     CPQ_K_OUT      = 11,  /* output stage (k_out_pre / k_out_headroom / k_out_post) */
-    CPQ_K_COUNT    = 12
+    CPQ_K_DITHER   = 12,  /* dither stage (k_dither) */
+    CPQ_K_COUNT    = 13
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);
 int32_t     cpq_profile_reset(cpq_engine* e);

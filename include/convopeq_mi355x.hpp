@@ -382,4 +382,22 @@ private:
     int status_ = CPQ_OK;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// The reference's fixed noise shapers (FixedNoiseShaper, Fixed15TapNoiseShaper) for every stream of an engine: once prepared,
+// cpq_engine_process_block quantises its output to bitDepth bits between the output stage's DC blocker and its limiter, and
+// the PCM calls accept CPQ_PCM_S16 output when bitDepth <= 16.
+class BatchedDither {
+public:
+    explicit BatchedDither(Engine& e) : e_(e) {}
+    // shaper: CPQ_DITHER_FIXED4 / CPQ_DITHER_FIXED15; CPQ_DITHER_OFF switches the stage off
+    bool prepare(int shaper, int bitDepth) { return (status_ = cpq_engine_set_dither(e_.get(), shaper, bitDepth)) == CPQ_OK; }
+    void reset() { status_ = cpq_dither_reset(e_.get()); }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return e_.lastError(); }
+
+private:
+    Engine& e_;
+    int status_ = CPQ_OK;
+};
+
 }  // namespace cpq
