@@ -51,6 +51,7 @@ CPQ_OUT_ALL = 15
 CPQ_DITHER_OFF = 0
 CPQ_DITHER_FIXED4 = 1
 CPQ_DITHER_FIXED15 = 2
+CPQ_DITHER_ADAPTIVE9 = 4
 CPQ_DITHER_TILE = 64
 CPQ_PCM_F64 = 0
 CPQ_PCM_F32 = 1
@@ -224,6 +225,8 @@ SYMBOLS = {
     "cpq_dither_design": (C.c_int32, [C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p]),
     "cpq_engine_set_dither": (C.c_int32, [_E, C.c_int32, C.c_int32]),
     "cpq_dither_reset": (C.c_int32, [_E]),
+    "cpq_dither_set_adaptive_coeffs": (C.c_int32, [_E, C.c_int32, c_double_p, C.c_int32]),
+    "cpq_dither_get_adaptive_coeffs": (C.c_int32, [_E, C.c_int32, c_double_p]),
     "cpq_dither_process": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32]),
     "cpq_dither_process_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32]),
     "cpq_pcm_bytes_per_sample": (C.c_int32, [C.c_int32]),

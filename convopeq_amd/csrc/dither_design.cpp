@@ -1,8 +1,10 @@
-// dither_design.cpp -- host side of the dither stage: prepare() of the reference's two deterministic noise shapers
-// (src/FixedNoiseShaper.h:70-108, 299-342; src/Fixed15TapNoiseShaper.h:88-134, 344-426), their generators' seeds, and the stage
-// itself, sequentially, in the reference's operation order (processSample / quantize of either header).  No GPU.
+// dither_design.cpp -- host side of the dither stage: prepare() of the reference's three deterministic noise shapers
+// (src/FixedNoiseShaper.h:70-108, 299-342; src/Fixed15TapNoiseShaper.h:88-134, 344-426; src/LatticeNoiseShaper.h:26-66), their
+// generators' seeds, and the stage itself, sequentially, in the reference's operation order (processSample / quantize of each
+// header).  No GPU.
 // killDenormal is the identity, as in the reference's release build (src/DspNumericPolicy.h:189-204).  The 4-tap header leaves
-// the contraction of its feedback sum to its compiler: here, as everywhere in this project, nothing is contracted.
+// the contraction of its feedback sum to its compiler: here, as everywhere in this project, nothing is contracted.  The lattice
+// header fuses four terms of its feedback sum itself (computeFeedback's _mm256_fmadd_pd): those are std::fma here.
 #include "host_design.hpp"
 
 #include <cmath>
@@ -35,6 +37,9 @@ constexpr double kPresets15[kPresets][16] = {
 constexpr unsigned long long kSeeds4[2][4] = {
     { 0x123456789ABCDEF0ULL, 0xFEDCBA9876543210ULL, 0x0123456789ABCDEFULL, 0xEFCDAB8967452301ULL },
     { 0x89ABCDEF01234567ULL, 0x76543210FEDCBA98ULL, 0xABCDEF0123456789ULL, 0x67452301EFCDAB89ULL } };
+
+// kDefaultAdaptiveNoiseShaperCoeffs (src/audioengine/AudioEngine.Processing.DSPCoreLifecycle.cpp:32-35)
+constexpr double kAdaptiveDefault[kLatticeOrder] = { -0.003796, -0.006752, 0.008418, -0.010546, 0.004716, -0.007624, -0.020750, -0.002049, -0.003632 };
 
 // selectPresetWithInterpolation: a NaN rate matches no branch and leaves the caller's zeros (preset 0, t = 0)
 void selectPreset(double rate, int& lo, int& hi, double& t)
@@ -83,6 +88,11 @@ bool ditherDesign(double rate, int shaper, int bits, double coeffs[kDitherMaxOrd
 {
     const int order = ditherOrder(shaper);
     if (!order || bits < 1 || bits > 32) return false;
+    *scale = 1.0 / std::ldexp(1.0, bits - 1);
+    if (shaper == CPQ_DITHER_ADAPTIVE9) {       // LatticeNoiseShaper::prepare(bitDepth) takes no rate
+        for (int i = 0; i < kDitherMaxOrder; ++i) coeffs[i] = i < kLatticeOrder ? kAdaptiveDefault[i] : 0.0;
+        return true;
+    }
     int lo, hi;
     double t;
     selectPreset(rate, lo, hi, t);
@@ -96,7 +106,6 @@ bool ditherDesign(double rate, int shaper, int bits, double coeffs[kDitherMaxOrd
     // 48 kHz preset
     if (order == 4 && std::fabs(coeffs[0] + coeffs[1] + coeffs[2] + coeffs[3] - 1.0) > 1.0e-12)
         for (int i = 0; i < 4; ++i) coeffs[i] = kPresets4[1][i];
-    *scale = 1.0 / std::ldexp(1.0, bits - 1);
     return true;
 }
 
@@ -111,6 +120,14 @@ void ditherSeed(int shaper, double rate, int bits, int ch, unsigned long long s[
     unsigned long long stream = seed ^ (0x9E3779B97F4A7C15ULL * (unsigned long long)(ch + 1));
     for (int i = 0; i < 4; ++i) s[i] = splitmix64(stream);
     if ((s[0] | s[1] | s[2] | s[3]) == 0ULL) s[0] = 1ULL;
+}
+
+void ditherClampAdaptive(const double* k, int n, double out[kLatticeOrder])
+{
+    for (int i = 0; i < kLatticeOrder; ++i) {
+        const double v = i < n ? k[i] : 0.0;
+        out[i] = !std::isfinite(v) ? 0.0 : v > 0.85 ? 0.85 : v < -0.85 ? -0.85 : v;
+    }
 }
 
 bool DitherHost::configure(double rate, int shaperId, int bitDepth)
@@ -131,7 +148,7 @@ bool DitherHost::configure(double rate, int shaperId, int bitDepth)
 void DitherHost::prepare(double rate)
 {
     if (!order) return;
-    ditherDesign(rate, shaper, bits, coeffs, &scale);
+    if (shaper != CPQ_DITHER_ADAPTIVE9) ditherDesign(rate, shaper, bits, coeffs, &scale);
     if (shaper == CPQ_DITHER_FIXED15)
         for (int ch = 0; ch < 2; ++ch) ditherSeed(shaper, rate, bits, ch, rng[ch]);
     reset();
@@ -139,11 +156,59 @@ void DitherHost::prepare(double rate)
 
 void DitherHost::reset() { std::memset(err, 0, sizeof(err)); }
 
+bool DitherHost::setAdaptiveCoeffs(const double* k, int n)
+{
+    if (shaper != CPQ_DITHER_ADAPTIVE9 || n < 0 || n > kLatticeOrder || (n > 0 && !k)) return false;
+    ditherClampAdaptive(k, n, coeffs);
+    reset();
+    return true;
+}
+
+// LatticeNoiseShaper::processStereoBlock.  Its closing clampStateSIMD (+-1e12) cannot act on states that advanceState already
+// holds to +-2 and is left out
+static void latticeProcess(DitherHost& h, double* const rows[2], int n, double headroom)
+{
+    const double scale = h.scale, invScale = h.invScale;
+    const double minV = -1.0, maxV = 1.0 - (1.0 / invScale), lim = 2.0 * scale;
+    for (int ch = 0; ch < 2; ++ch) {
+        double* st = h.err[ch];
+        const double* c = h.coeffs;
+        unsigned long long* rng = h.rng[ch];
+        for (int i = 0; i < n; ++i) {
+            const double x = rows[ch][i] * headroom;
+            double p[4];
+            for (int j = 0; j < 4; ++j) p[j] = std::fma(st[4 + j], c[4 + j], st[j] * c[j]);
+            const double fb = ((p[0] + p[2]) + (p[1] + p[3])) + st[8] * c[8];
+            const double y = x + fb;
+            double v = y;                                       // a NaN passes both comparisons
+            if (v < minV) v = minV;
+            else if (v > maxV) v = maxV;
+            const double u1 = uniform(rng);
+            const double u2 = uniform(rng);
+            v += (u1 + u2 - 1.0) * scale;
+            const double q = std::nearbyint(v * invScale);
+            const double minQ = -invScale, maxQ = invScale - 1.0;
+            const double yq = (q < minQ ? minQ : (maxQ < q ? maxQ : q)) * scale;       // std::clamp: a NaN stays
+            const double error = finiteOrZero(yq - y);
+            double f = error < -lim ? -lim : (lim < error ? lim : error);
+            for (int k = 0; k < kLatticeOrder; ++k) {           // advanceState
+                const double b = st[k];
+                const double nf = f + c[k] * b;
+                const double nb = c[k] * f + b;
+                st[k] = nb < -2.0 ? -2.0 : (2.0 < nb ? 2.0 : nb);
+                f = nf;
+            }
+            rows[ch][i] = yq;
+        }
+    }
+}
+
 void DitherHost::process(double* l, double* r, int n, double headroom)
 {
     if (!order || n <= 0) return;
     double* rows[2] = { l, r };
     const double minV = -1.0, maxV = 1.0 - (1.0 / invScale), lim = 2.0 * scale;
+    if (shaper == CPQ_DITHER_ADAPTIVE9) { latticeProcess(*this, rows, n, headroom); return; }
     for (int ch = 0; ch < 2; ++ch) {
         double* e = err[ch];
         for (int i = 0; i < n; ++i) {

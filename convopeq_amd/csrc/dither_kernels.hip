@@ -1,5 +1,6 @@
-// dither_kernels.hip -- the dither stage on gfx950: FixedNoiseShaper / Fixed15TapNoiseShaper::processStereoBlock of the reference
-// (src/FixedNoiseShaper.h:162-184, 272-297; src/Fixed15TapNoiseShaper.h:204-230, 318-342) on rows [channel][sample].
+// dither_kernels.hip -- the dither stage on gfx950: FixedNoiseShaper / Fixed15TapNoiseShaper / LatticeNoiseShaper::processStereoBlock
+// of the reference (src/FixedNoiseShaper.h:162-184, 272-297; src/Fixed15TapNoiseShaper.h:204-230, 318-342;
+// src/LatticeNoiseShaper.h:73-111, 203-293) on rows [channel][sample].
 //
 // The quantiser sits inside the error feedback loop, so a channel is one sequential chain and no scan reproduces it: the only
 // parallelism is across channels.  k_dither<ORDER> runs one wave per workgroup; a lane owns kDitherCpl consecutive channels (1: a
@@ -13,6 +14,13 @@
 // 64, distinct for the 32 lanes an 8-byte LDS access serves together; the staging writes are consecutive doubles.  Loads and
 // stores are single doubles, so a row on an odd double or with any stride is nothing special, and a tile is read whole before any
 // of it is written, so in and out may be the same rows.
+//
+// k_dither_lattice is the adaptive 9th-order shaper on the same tile: the stored error runs through nine lattice stages, each
+// depending on the one before, and the coefficients belong to the stream, so a lane loads its channel's nine from coef [9][nCh]
+// once and keeps them beside the nine states and the generator words (22 doubles a channel).  The feedback sum holds the file's
+// only fused multiply-adds, the four computeFeedback writes as _mm256_fmadd_pd; the file is built with -ffp-contract=off, so
+// nothing else fuses.  processStereoBlock's closing clampStateSIMD (+-1e12) cannot act on states advanceState already holds to
+// +-2 and is not built.
 #include "kernels.hpp"
 
 namespace cpq {
@@ -42,6 +50,25 @@ __device__ __forceinline__ double dUniform(unsigned long long (&s)[4])
 }
 
 __device__ __forceinline__ double dFiniteOrZero(double v) { return fabs(v) < __builtin_huge_val() ? v : 0.0; }
+
+// the wave's rows x len samples from t0 on, into the tile and back: lane = sample
+__device__ __forceinline__ void dTileLoad(double* tile, const double* in, int64_t inStride, int row0, int rows, int t0, int len, int lane)
+{
+    if (lane < len) {
+#pragma unroll 8
+        for (int r = 0; r < rows; ++r) tile[r * kDitherPitch + lane] = in[(row0 + r) * inStride + t0 + lane];
+    }
+}
+
+__device__ __forceinline__ void dTileStore(const double* tile, double* out, int64_t outStride, int row0, int rows, int t0, int len, int lane)
+{
+    if (lane < len) {
+#pragma unroll 8
+        for (int r = 0; r < rows; ++r) out[(row0 + r) * outStride + t0 + lane] = tile[r * kDitherPitch + lane];
+    }
+}
+
+__device__ __forceinline__ double dScrub(double yq, int scrub) { return scrub ? (fabs(yq) < 1.0e300 ? yq : 0.0) : yq; }
 
 // processSample: x in, yq out; e and s are the channel's state
 template <int ORDER>
@@ -106,10 +133,7 @@ k_dither(const double* in, int64_t inStride, double* out, int64_t outStride, int
     }
     for (int t0 = 0; t0 < n; t0 += kDitherStep) {
         const int len = min(kDitherStep, n - t0);
-        if (lane < len) {
-#pragma unroll 8
-            for (int r = 0; r < rows; ++r) tile[r * kDitherPitch + lane] = in[(row0 + r) * inStride + t0 + lane];
-        }
+        dTileLoad(tile, in, inStride, row0, rows, t0, len, lane);
         __syncthreads();
         double* mine = tile + lane * kDitherCpl * kDitherPitch;
         if (lane * kDitherCpl < rows) {
@@ -120,7 +144,7 @@ k_dither(const double* in, int64_t inStride, double* out, int64_t outStride, int
 #pragma unroll
                     for (int c = 0; c < kDitherCpl; ++c) {
                         const double yq = dSample<ORDER>(mine[c * kDitherPitch + t + k] * p.headroom, e[c], s[c], p);
-                        mine[c * kDitherPitch + t + k] = p.scrub ? (fabs(yq) < 1.0e300 ? yq : 0.0) : yq;
+                        mine[c * kDitherPitch + t + k] = dScrub(yq, p.scrub);
                     }
                 }
             }
@@ -128,15 +152,12 @@ k_dither(const double* in, int64_t inStride, double* out, int64_t outStride, int
 #pragma unroll
                 for (int c = 0; c < kDitherCpl; ++c) {
                     const double yq = dSample<ORDER>(mine[c * kDitherPitch + t] * p.headroom, e[c], s[c], p);
-                    mine[c * kDitherPitch + t] = p.scrub ? (fabs(yq) < 1.0e300 ? yq : 0.0) : yq;
+                    mine[c * kDitherPitch + t] = dScrub(yq, p.scrub);
                 }
             }
         }
         __syncthreads();
-        if (lane < len) {
-#pragma unroll 8
-            for (int r = 0; r < rows; ++r) out[(row0 + r) * outStride + t0 + lane] = tile[r * kDitherPitch + lane];
-        }
+        dTileStore(tile, out, outStride, row0, rows, t0, len, lane);
         __syncthreads();                                            // the tile is free again
     }
 #pragma unroll
@@ -151,14 +172,103 @@ k_dither(const double* in, int64_t inStride, double* out, int64_t outStride, int
     }
 }
 
+// LatticeNoiseShaper::processSample: x in, yq out; st, c and s are the channel's states, coefficients and generator
+__device__ __forceinline__ double dLatticeSample(double x, double (&st)[kLatticeOrder], const double (&c)[kLatticeOrder],
+                                                 unsigned long long (&s)[4], const DitherParams& p)
+{
+    // computeFeedback: lanes j = 0..3 of mul_pd then fmadd_pd, the horizontal add, then state[8] on its own
+    const double p0 = __builtin_fma(st[4], c[4], st[0] * c[0]);
+    const double p1 = __builtin_fma(st[5], c[5], st[1] * c[1]);
+    const double p2 = __builtin_fma(st[6], c[6], st[2] * c[2]);
+    const double p3 = __builtin_fma(st[7], c[7], st[3] * c[3]);
+    const double fb = ((p0 + p2) + (p1 + p3)) + st[8] * c[8];
+    const double y = x + fb;
+    double v = y;                                                           // quantize: a NaN passes both comparisons
+    if (v < -1.0) v = -1.0;
+    else if (v > p.maxV) v = p.maxV;
+    const double u1 = dUniform(s);
+    const double u2 = dUniform(s);
+    v += (u1 + u2 - 1.0) * p.scale;
+    const double q = __builtin_rint(v * p.invScale);
+    const double minQ = -p.invScale, maxQ = p.invScale - 1.0;
+    const double yq = (q < minQ ? minQ : (maxQ < q ? maxQ : q)) * p.scale;  // std::clamp: a NaN stays
+    const double lim = 2.0 * p.scale;
+    const double error = dFiniteOrZero(yq - y);
+    double f = error < -lim ? -lim : (lim < error ? lim : error);
+#pragma unroll
+    for (int i = 0; i < kLatticeOrder; ++i) {                               // advanceState
+        const double b = st[i];
+        const double nf = f + c[i] * b;
+        const double nb = c[i] * f + b;
+        st[i] = nb < -2.0 ? -2.0 : (2.0 < nb ? 2.0 : nb);
+        f = nf;
+    }
+    return yq;
+}
+
+// grid and rows as k_dither.  coef [kLatticeOrder][nCh]; the states are err's rows 0 .. kLatticeOrder - 1
+__global__ void __launch_bounds__(64)
+k_dither_lattice(const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nCh, DitherParams p,
+                 const double* __restrict__ coef, double* __restrict__ err, unsigned long long* __restrict__ rng)
+{
+    __shared__ double tile[kDitherRows * kDitherPitch];
+    const int lane = threadIdx.x;
+    const int row0 = blockIdx.x * kDitherRows;
+    const int rows = min(kDitherRows, nCh - row0);                  // >= 1
+    double st[kDitherCpl][kLatticeOrder], c[kDitherCpl][kLatticeOrder];
+    unsigned long long s[kDitherCpl][4];
+#pragma unroll
+    for (int ch = 0; ch < kDitherCpl; ++ch) {
+        const int r = lane * kDitherCpl + ch;
+        const bool live = r < rows;
+#pragma unroll
+        for (int k = 0; k < kLatticeOrder; ++k) {
+            st[ch][k] = live ? err[(size_t)k * nCh + row0 + r] : 0.0;
+            c[ch][k] = live ? coef[(size_t)k * nCh + row0 + r] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[ch][k] = live ? rng[(size_t)k * nCh + row0 + r] : 1ull;
+    }
+    for (int t0 = 0; t0 < n; t0 += kDitherStep) {
+        const int len = min(kDitherStep, n - t0);
+        dTileLoad(tile, in, inStride, row0, rows, t0, len, lane);
+        __syncthreads();
+        double* mine = tile + lane * kDitherCpl * kDitherPitch;
+        if (lane * kDitherCpl < rows) {
+            for (int t = 0; t < len; ++t) {
+#pragma unroll
+                for (int ch = 0; ch < kDitherCpl; ++ch) {
+                    const double yq = dLatticeSample(mine[ch * kDitherPitch + t] * p.headroom, st[ch], c[ch], s[ch], p);
+                    mine[ch * kDitherPitch + t] = dScrub(yq, p.scrub);
+                }
+            }
+        }
+        __syncthreads();
+        dTileStore(tile, out, outStride, row0, rows, t0, len, lane);
+        __syncthreads();                                            // the tile is free again
+    }
+#pragma unroll
+    for (int ch = 0; ch < kDitherCpl; ++ch) {
+        const int r = lane * kDitherCpl + ch;
+        if (r < rows) {
+#pragma unroll
+            for (int k = 0; k < kLatticeOrder; ++k) err[(size_t)k * nCh + row0 + r] = st[ch][k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rng[(size_t)k * nCh + row0 + r] = s[ch][k];
+        }
+    }
+}
+
 }  // namespace
 
 bool launch_dither(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nCh, int order,
-                   const DitherParams& p, double* err, unsigned long long* rng)
+                   const DitherParams& p, const double* coef, double* err, unsigned long long* rng)
 {
     const dim3 grid((unsigned)((nCh + kDitherRows - 1) / kDitherRows)), block(64);
     if (order == 4) hipLaunchKernelGGL(k_dither<4>, grid, block, 0, stream, in, inStride, out, outStride, n, nCh, p, err, rng);
     else if (order == 16) hipLaunchKernelGGL(k_dither<16>, grid, block, 0, stream, in, inStride, out, outStride, n, nCh, p, err, rng);
+    else if (order == kLatticeOrder && coef)
+        hipLaunchKernelGGL(k_dither_lattice, grid, block, 0, stream, in, inStride, out, outStride, n, nCh, p, coef, err, rng);
     else return false;
     return true;
 }

@@ -7,7 +7,7 @@
 //   engine_os.cpp    half-band oversampler around the routing: stage buffers, per-stream state machine
 //   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
 //   engine_out.cpp   output stage: DC blocker, headroom, limiter and clamp on the delivered rows
-//   engine_dither.cpp  dither stage: the fixed 4- and 15-tap noise shapers between the output stage's two halves
+//   engine_dither.cpp  dither stage: the fixed 4- and 15-tap and the adaptive lattice noise shaper between the output stage's two halves
 //   engine_meter.cpp  loudness and true-peak metering of the delivered rows
 //   engine_diag.cpp  every cpq_diag_* entry point: single launchers on caller-filled buffers, no engine
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
@@ -327,6 +327,8 @@ struct cpq_engine {
     cpq::DitherParams ditherParams{};                   // coefficients and scales at the present base rate
     cpqi::DeviceBuffer<double> ditherErr;               // [kDitherMaxOrder][nCh]
     cpqi::DeviceBuffer<unsigned long long> ditherRng;   // [4][nCh]
+    cpqi::DeviceBuffer<double> ditherCoef;              // [kLatticeOrder][nCh] adaptive shaper: the stream's set in both of its channels
+    std::vector<double> ditherCoefHost;                 // what ditherCoef holds
 
     // packed PCM entry points (engine_pcm.cpp): the call's packed input and output on the device, one group
     cpqi::DeviceBuffer<char> pcmIn, pcmOut;
@@ -431,7 +433,9 @@ int refreshOutStage(cpq_engine* e);             // redesign for the present base
 int enqueueOutPre(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase, bool headroom = true);
 int enqueueOutPost(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
 // engine_dither.cpp
-int refreshDither(cpq_engine* e);               // prepare() at the present base rate: coefficients, errors cleared, the 15-tap shaper reseeded
+// prepare() at the present base rate: coefficients, errors cleared, the 15-tap shaper reseeded; the adaptive shaper's per-stream
+// coefficients stay
+int refreshDither(cpq_engine* e);
 // headroom, shaper and (with CPQ_OUT_HEADROOM) the scrub; launches nothing while dither is off
 int enqueueDither(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
 // engine_core.cpp: DSPCore's routing of one block (conv / EQ in the configured order, output filter, makeup)

@@ -77,22 +77,32 @@ struct OutStageHost {
     void process(double* l, double* r, int n, int flags);   // flags: CPQ_OUT_*
 };
 
-// dither stage (dither_design.cpp): FixedNoiseShaper / Fixed15TapNoiseShaper of the reference
+// dither stage (dither_design.cpp): FixedNoiseShaper / Fixed15TapNoiseShaper / LatticeNoiseShaper of the reference
 constexpr int kDitherMaxOrder = 16;
-inline int ditherOrder(int shaper) { return shaper == CPQ_DITHER_FIXED4 ? 4 : shaper == CPQ_DITHER_FIXED15 ? 16 : 0; }
-// prepare(rate, bits): coeffs[16] (unused taps 0.0), scale = 2^-(bits - 1); false for an unknown shaper or bits outside 1..32
+constexpr int kLatticeOrder = 9;        // LatticeNoiseShaper::kOrder
+inline int ditherOrder(int shaper)
+{
+    return shaper == CPQ_DITHER_FIXED4 ? 4 : shaper == CPQ_DITHER_FIXED15 ? 16 : shaper == CPQ_DITHER_ADAPTIVE9 ? kLatticeOrder : 0;
+}
+// prepare(rate, bits): coeffs[16] (unused taps 0.0), scale = 2^-(bits - 1); false for an unknown shaper or bits outside 1..32.
+// The adaptive shaper: kDefaultAdaptiveNoiseShaperCoeffs whatever the rate
 bool   ditherDesign(double rate, int shaper, int bits, double coeffs[kDitherMaxOrder], double* scale);
-// xoshiro256++ state of channel ch (0 = L, 1 = R): the 4-tap header's constants, or initializeRandomStates(rate, bits)
+// xoshiro256++ state of channel ch (0 = L, 1 = R): the 4-tap and the lattice header's constants, or initializeRandomStates(rate, bits)
 void   ditherSeed(int shaper, double rate, int bits, int ch, unsigned long long s[4]);
+// LatticeNoiseShaper::setCoefficients: out[9] = clampCoeff of k[0 .. n - 1] (not finite -> 0, else clamped to +-0.85), the rest 0
+void   ditherClampAdaptive(const double* k, int n, double out[kLatticeOrder]);
 // one stream of the stage, sequential, in the reference's operation order: processStereoBlock(l, r, n, headroom)
 struct DitherHost {
     int shaper = CPQ_DITHER_OFF, order = 0, bits = 0;
     double coeffs[kDitherMaxOrder] = {}, scale = 1.0, invScale = 1.0;
-    double err[2][kDitherMaxOrder] = {};        // [channel][k], k = 0 the newest
+    double err[2][kDitherMaxOrder] = {};        // [channel][k], k = 0 the newest; the lattice's states in k = 0 .. 8
     unsigned long long rng[2][4] = {};
     bool configure(double rate, int shaperId, int bitDepth);    // a new shaper object + prepare(): errors cleared, seeded
-    void prepare(double rate);                                  // prepare() again: errors cleared, the 15-tap shaper reseeded
+    // prepare() again: errors cleared, the 15-tap shaper reseeded; the adaptive shaper keeps its coefficients (the published set
+    // is applied again at the first callback)
+    void prepare(double rate);
     void reset();                                               // errors only
+    bool setAdaptiveCoeffs(const double* k, int n);             // applyMatchedCoefficients; false unless adaptive, n in 0..9
     void process(double* l, double* r, int n, double headroom);
 };
 

@@ -269,9 +269,10 @@ void launch_out_pre(hipStream_t stream, const double* in, int64_t inStride, doub
 void launch_out_post(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nStreams,
                      bool limiter, bool clamp, double release, double* env);
 
-// ---- dither stage (dither_kernels.hip): headroom, the 4- or 15-tap noise shaper and (scrub) the scrub on rows [nCh][n]; in and
-// out may be the same rows.  err [kDitherMaxOrder][nCh] (tap k of channel c at k * nCh + c, k = 0 the newest) and rng [4][nCh]
-// are carried across calls.  order: 4 or 16; false: no kernel for that order.
+// ---- dither stage (dither_kernels.hip): headroom, the 4- or 15-tap or the 9th-order lattice noise shaper and (scrub) the scrub
+// on rows [nCh][n]; in and out may be the same rows.  err [kDitherMaxOrder][nCh] (tap k of channel c at k * nCh + c, k = 0 the
+// newest; the lattice's states in rows 0 .. 8) and rng [4][nCh] are carried across calls.  order: 4, 16 or kLatticeOrder, which
+// reads coef [kLatticeOrder][nCh] (the channel's own reflection coefficients) and not p.c; false: no kernel for that order.
 constexpr int kDitherTile = CPQ_DITHER_TILE;    // samples of a row a wave stages in LDS at a time
 struct DitherParams {
     double c[kDitherMaxOrder];
@@ -280,7 +281,7 @@ struct DitherParams {
     int scrub;
 };
 bool launch_dither(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nCh, int order,
-                   const DitherParams& p, double* err, unsigned long long* rng);
+                   const DitherParams& p, const double* coef, double* err, unsigned long long* rng);
 
 // ---- packed PCM converters (pcm_kernels.hip): cpq_pcm_format x cpq_pcm_layout <-> fp64 rows [2 nStreams][n]
 constexpr int kPcmTile = 4096;     // samples of the packed side per workgroup: 4096 of a planar row, 2048 stereo frames

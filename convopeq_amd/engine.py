@@ -436,12 +436,22 @@ class BatchedEngine:
         self._ck(self._lib.cpq_out_read_envelope(self._h, int(stream), C.byref(v)))
         return v.value
 
-    # ---- dither stage (the fixed 4- and 15-tap noise shapers; headroom and scrub follow the output-stage flags)
+    # ---- dither stage (the fixed 4- and 15-tap and the adaptive lattice noise shaper; headroom and scrub follow the output-stage flags)
     def set_dither(self, shaper, bit_depth=0):
         self._ck(self._lib.cpq_engine_set_dither(self._h, int(shaper), int(bit_depth)))
 
     def dither_reset(self):
         self._ck(self._lib.cpq_dither_reset(self._h))
+
+    def dither_set_adaptive_coeffs(self, stream, k):
+        """applyMatchedCoefficients of one stream or CPQ_ALL_STREAMS: up to nine reflection coefficients, clamped; states cleared."""
+        k = np.ascontiguousarray(k, dtype=np.float64).reshape(-1)
+        self._ck(self._lib.cpq_dither_set_adaptive_coeffs(self._h, int(stream), _dp(k) if k.size else None, k.size))
+
+    def dither_get_adaptive_coeffs(self, stream):
+        k = np.empty(9)
+        self._ck(self._lib.cpq_dither_get_adaptive_coeffs(self._h, int(stream), _dp(k)))
+        return k
 
     def dither_process(self, x):
         """The stage alone on rows [n_channels, n]."""

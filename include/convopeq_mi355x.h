@@ -37,6 +37,8 @@ extern "C" {
 #define CPQ_HAS_OUTPUT_STAGE 1
 /* likewise: defined when the dither stage (cpq_engine_set_dither, cpq_dither_*) and 16-bit PCM output exist */
 #define CPQ_HAS_DITHER 1
+/* likewise: defined when the adaptive 9th-order lattice shaper (CPQ_DITHER_ADAPTIVE9, cpq_dither_*_adaptive_coeffs) exists */
+#define CPQ_HAS_ADAPTIVE_DITHER 1
 
 typedef enum {
     CPQ_OK               =  0,
@@ -595,7 +597,7 @@ int32_t cpq_out_process_device(cpq_engine* e, const double* d_in, double* d_out,
 int32_t cpq_out_read_envelope(cpq_engine* e, int32_t stream, double* envelope);
 
 /* ---------------------------------------------------------------- dither stage */
-/* processOutputDouble's ditherBitDepth > 0 branch (DSPCoreDouble.cpp:644-654) for the reference's two deterministic shapers:
+/* processOutputDouble's ditherBitDepth > 0 branch (DSPCoreDouble.cpp:644-654) for the reference's three deterministic shapers:
  * the shaper's processStereoBlock(l, r, n, headroom) takes the place of the plain headroom multiply; scrub, meters, limiter and
  * clamp follow as without it, so the limiter acts after quantisation and a limited sample leaves the grid.
  *   CPQ_DITHER_FIXED4   FixedNoiseShaper (src/FixedNoiseShaper.h): 4 error taps, xoshiro256++ seeded with the header's constants
@@ -612,22 +614,49 @@ int32_t cpq_out_read_envelope(cpq_engine* e, int32_t stream, double* envelope);
  * presets (44.1 ... 768 kHz), linear interpolation in the rate between them, the first and the last preset outside.
  * Every stream is a DSPCore of its own: all streams draw the same two sequences (L, R).
  * Headroom is 0.8912509381337456 with CPQ_OUT_HEADROOM in the output-stage flags, else 1.0; the scrub runs only with that flag.
- * Not built: the psychoacoustic and the adaptive shaper, the shapers' diagnostics, the 15-tap errorEnvelope / needsReset
- * handshake (finite input cannot raise it). */
-#define CPQ_DITHER_OFF     0
-#define CPQ_DITHER_FIXED4  1
-#define CPQ_DITHER_FIXED15 2
+ *   CPQ_DITHER_ADAPTIVE9  LatticeNoiseShaper (src/LatticeNoiseShaper.h), NoiseShaperType::Adaptive9thOrder: a 9-stage lattice on
+ *                       the stored error, the 4-tap header's two constant generator states (prepare() / reset() do not reseed),
+ *                       and nine reflection coefficients of the stream's own
+ * Per sample and channel, with states s[0..8] and the stream's coefficients c[0..8]: x = in * headroom;
+ * p_j = fma(s[4+j], c[4+j], s[j] * c[j]) for j = 0..3 (computeFeedback's _mm256_fmadd_pd, a real fused multiply-add);
+ * fb = ((p_0 + p_2) + (p_1 + p_3)) + s[8] * c[8] (nothing else contracted); y = x + fb; v = y clamped to [-1, 1 - scale] by two
+ * comparisons (a NaN passes both), plus (u1 + u2 - 1) * scale; q = rint(v * invScale) clamped to [-invScale, invScale - 1] with
+ * std::clamp (a NaN stays); yq = q * scale is the output; err = yq - y, 0 when not finite, clamped to +-2 scale; then f = err and
+ * for i = 0..8: b = s[i], nf = f + c[i] * b, s[i] = clamp(c[i] * f + b, -2, 2), f = nf.  A NaN input is a NaN output for that
+ * sample only, +-inf clamps to the rails, and in both cases the stored error is 0, so the states stay finite.
+ * processStereoBlock's closing clampStateSIMD (+-1e12) cannot act on states already held to +-2 and is not built.
+ * Coefficients: every stream starts from kDefaultAdaptiveNoiseShaperCoeffs (DSPCoreLifecycle.cpp:32-35);
+ * cpq_dither_set_adaptive_coeffs is the learner's published set reaching the shaper (applyMatchedCoefficients at the start of a
+ * callback, DSPCoreDouble.cpp:617-628).  Which set to publish -- the reference keeps one per sample-rate bank
+ * (kAdaptiveNoiseShaperSampleRateBankCount = 10, 44.1 ... 768 kHz), bit depth and learning mode -- is the caller's lookup.
+ * Not built: the psychoacoustic shaper (it draws from MKL's SFMT19937 stream), the learner itself, the shapers' diagnostics, the
+ * 15-tap errorEnvelope / needsReset handshake (finite input cannot raise it). */
+#define CPQ_DITHER_OFF       0
+#define CPQ_DITHER_FIXED4    1
+#define CPQ_DITHER_FIXED15   2
+#define CPQ_DITHER_ADAPTIVE9 4  /* 3 stays unassigned and refused */
 #define CPQ_DITHER_TILE    64   /* samples a workgroup of k_dither moves through LDS at a time (tests walk its edges) */
 /* prepare(rate, bit_depth) of the shaper: coeffs[16] (the 4-tap shaper fills 4, the rest 0.0) and *scale.  bit_depth 1 .. 32.
+ * CPQ_DITHER_ADAPTIVE9: the default set in coeffs[0..8], the rest 0.0; the rate is ignored, as its prepare(bitDepth) takes none.
  * Host only. */
 int32_t cpq_dither_design(double rate, int32_t shaper, int32_t bit_depth, double coeffs[16], double* scale);
-/* shaper CPQ_DITHER_OFF (the default: nothing is launched, bit_depth ignored) or one of the two shapers with bit_depth 1 .. 32;
+/* shaper CPQ_DITHER_OFF (the default: nothing is launched, bit_depth ignored) or one of the three shapers with bit_depth 1 .. 32;
  * anything else is CPQ_ERR_INVALID_ARG before any state moves.  The same arguments again change nothing; any change clears the
- * errors and reseeds.  The rate is sample_rate / oversampling factor: cpq_engine_prepare and cpq_engine_set_oversampling
- * redesign the coefficients and clear the errors; they reseed the 15-tap shaper only, as the reference's prepare() does. */
+ * errors and reseeds, and gives every stream of the adaptive shaper the default set.  The rate is sample_rate / oversampling
+ * factor: cpq_engine_prepare and cpq_engine_set_oversampling redesign the coefficients and clear the errors; they reseed the
+ * 15-tap shaper only, as the reference's prepare() does.  The adaptive shaper keeps each stream's coefficients across them (the
+ * reference applies the published set again at the first callback after DSPCore::prepare) and its states are cleared. */
 int32_t cpq_engine_set_dither(cpq_engine* e, int32_t shaper, int32_t bit_depth);
-/* the shaper's reset(): errors to 0, the generators run on.  CPQ_ERR_NOT_READY while dither is off (so for the calls below). */
+/* the shaper's reset(): errors (the lattice's states) to 0, the generators run on, coefficients stay.  CPQ_ERR_NOT_READY while
+ * dither is off (so for the calls below). */
 int32_t cpq_dither_reset(cpq_engine* e);
+/* applyMatchedCoefficients(k, n) for one stream or CPQ_ALL_STREAMS: the coefficients become clampCoeff(k[i]) (not finite -> 0,
+ * else clamped to +-0.85) for i < n and 0 from n on, and those streams' states are cleared; other streams and every generator
+ * are left alone.  Acts on the next call.  CPQ_ERR_NOT_READY unless the adaptive shaper is on; CPQ_ERR_INVALID_ARG for a stream
+ * out of range, n outside 0 .. 9 or a null k with n > 0; every refusal happens before any state moves. */
+int32_t cpq_dither_set_adaptive_coeffs(cpq_engine* e, int32_t stream, const double* k, int32_t n);
+/* k[0..8] = the clamped coefficients stream `stream` (an index, not CPQ_ALL_STREAMS) runs with; refusals as above */
+int32_t cpq_dither_get_adaptive_coeffs(const cpq_engine* e, int32_t stream, double k[9]);
 /* The stage alone (headroom, shaper, scrub if flagged) on caller rows, with the argument rules of cpq_out_process. */
 int32_t cpq_dither_process(cpq_engine* e, const double* in, double* out, int32_t n_samples);
 int32_t cpq_dither_process_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_samples);
@@ -695,7 +724,7 @@ typedef enum {
     CPQ_K_METER    = 9,   /* loudness and true-peak meters (k_meter_kweight / k_meter_true_peak / k_meter_finish) */
     CPQ_K_PCM      = 10,  /* packed PCM converters (k_pcm_unpack / k_pcm_pack) */
     CPQ_K_OUT      = 11,  /* output stage (k_out_pre / k_out_headroom / k_out_post) */
-    CPQ_K_DITHER   = 12,  /* dither stage (k_dither) */
+    CPQ_K_DITHER   = 12,  /* dither stage (k_dither, k_dither_lattice) */
     CPQ_K_COUNT    = 13
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);

@@ -383,15 +383,24 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// The reference's fixed noise shapers (FixedNoiseShaper, Fixed15TapNoiseShaper) for every stream of an engine: once prepared,
+// The reference's deterministic noise shapers (FixedNoiseShaper, Fixed15TapNoiseShaper, LatticeNoiseShaper) for every stream of
+// an engine: once prepared,
 // cpq_engine_process_block quantises its output to bitDepth bits between the output stage's DC blocker and its limiter, and
 // the PCM calls accept CPQ_PCM_S16 output when bitDepth <= 16.
 class BatchedDither {
 public:
     explicit BatchedDither(Engine& e) : e_(e) {}
-    // shaper: CPQ_DITHER_FIXED4 / CPQ_DITHER_FIXED15; CPQ_DITHER_OFF switches the stage off
+    // shaper: CPQ_DITHER_FIXED4 / CPQ_DITHER_FIXED15 / CPQ_DITHER_ADAPTIVE9; CPQ_DITHER_OFF switches the stage off
     bool prepare(int shaper, int bitDepth) { return (status_ = cpq_engine_set_dither(e_.get(), shaper, bitDepth)) == CPQ_OK; }
     void reset() { status_ = cpq_dither_reset(e_.get()); }
+    // LatticeNoiseShaper::applyMatchedCoefficients for one stream or CPQ_ALL_STREAMS: the learner's published set (its
+    // sample-rate bank, bit depth and mode chosen by the caller), numCoeffs 0 .. 9; those streams' states are cleared
+    bool applyMatchedCoefficients(int stream, const double* coeffs, int numCoeffs)
+    {
+        return (status_ = cpq_dither_set_adaptive_coeffs(e_.get(), stream, coeffs, numCoeffs)) == CPQ_OK;
+    }
+    // LatticeNoiseShaper::getCoefficients of one stream: the nine clamped values in use
+    bool getCoefficients(int stream, double coeffs[9]) { return (status_ = cpq_dither_get_adaptive_coeffs(e_.get(), stream, coeffs)) == CPQ_OK; }
     int lastStatus() const noexcept { return status_; }
     const char* lastError() const noexcept { return e_.lastError(); }
 
