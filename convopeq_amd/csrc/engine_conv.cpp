@@ -16,7 +16,7 @@ int enqueueConv(cpq_engine* e, const double* dIn, double* dOut, int n)
     if (e->mainActive && (int64_t)T * e->P != n)
         return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d is not a multiple of the partition size %d (streams on the uniform path)", n, e->P);
     // before anything writes dOut, which may alias dIn: the call's input joins the plan groups' accumulators and the direct head runs
-    if (!e->groups.empty()) { const int rc = groupsAppend(e, dIn, n); if (rc != CPQ_OK) return rc; }
+    if (!e->groups.empty()) CPQ_TRY(groupsAppend(e, dIn, n));
     if (e->anyDirect) {
         ProfScope p(e, CPQ_K_MIX);
         // a stream whose convolver rests (per-stream bypass / dry-only at the processor level) keeps its head history: the
@@ -114,7 +114,7 @@ int enqueueConv(cpq_engine* e, const double* dIn, double* dOut, int n)
         e->histSel ^= 1;
     }
     // Get(): ring output of layer 0, then the direct output, then the tail layers (src/MKLNonUniformConvolver.cpp:1606-1633)
-    if (!e->groups.empty()) { const int rc = groupsRunLayer0(e, dOut, n); if (rc != CPQ_OK) return rc; }
+    if (!e->groups.empty()) CPQ_TRY(groupsRunLayer0(e, dOut, n));
     addDirect();
     if (!e->groups.empty()) return groupsRunTails(e, dOut, n);
     CPQ_HIP(e, hipGetLastError());
@@ -161,10 +161,9 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
     if (direct && !e->directIr) {
         const size_t callSamples = (size_t)e->tMax * e->P;
         const size_t taps = (size_t)32 * e->nCh;
-        const int rc = allocAll(e, { { e->directIr, taps, true }, { e->directTaps, (size_t)e->nCh, true }, { e->directHist[0], taps, true },
-                                     { e->directHist[1], taps, true }, { e->directOut, e->nCh * callSamples } },
-                                "direct-head buffers could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { e->directIr, taps, true }, { e->directTaps, (size_t)e->nCh, true }, { e->directHist[0], taps, true },
+                              { e->directHist[1], taps, true }, { e->directOut, e->nCh * callSamples } },
+                         "direct-head buffers could not be allocated"));
         e->directTapsHost.assign(e->nCh, 0);
     }
     const double* irs[2] = { irL, irR };
@@ -200,10 +199,9 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
                 for (int l = 1; l < probe.num_layers; ++l) span = std::max(span, probe.output_delay[l] + 2 * probe.part_size[l]);
                 const int tailRingSlots = nextPow2(span + 2 * e->B + e->tMax * e->P);
                 const size_t callSamples = (size_t)e->tMax * e->P;
-                const int rc = allocAll(e, { { e->layerOut, nTail * e->nCh * callSamples }, { e->tailRing, (size_t)nTail * e->nCh * tailRingSlots, true },
-                                             { e->tailState, 4, true }, { e->tailSched, 2 * ((size_t)e->tMax * e->P / e->B) } },      // per tail layer and callback
-                                        "layered-mode buffers could not be allocated");
-                if (rc != CPQ_OK) return rc;
+                CPQ_TRY(allocAll(e, { { e->layerOut, nTail * e->nCh * callSamples }, { e->tailRing, (size_t)nTail * e->nCh * tailRingSlots, true },
+                                      { e->tailState, 4, true }, { e->tailSched, 2 * ((size_t)e->tMax * e->P / e->B) } },      // per tail layer and callback
+                                 "layered-mode buffers could not be allocated"));
                 e->tailRingSlots = tailRingSlots;
                 e->layerPlan = probe;
                 std::copy(layerRow, layerRow + 3, e->layerRow);
@@ -251,19 +249,16 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
                 CPQ_HIP(e, hipMemsetAsync(e->HDN + (int64_t)slot * e->hRows, 0, (size_t)e->irParts[slot] * sizeof(double2), e->stream));
                 e->irParts[slot] = 0;
             }
-            const int rc = setDirect(slot, irs[ch]);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(setDirect(slot, irs[ch]));
         }
-        const int rc = nativeSetImpulse(e, stream, irL, irR, irLen, scale, headTaps, spec, sp);
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(nativeSetImpulse(e, stream, irL, irR, irLen, scale, headTaps, spec, sp));
         e->plan = sp;
         e->planValid = true;
         e->directHead = direct != 0;
     } else {
         for (int s = sFirst; s < sEnd; ++s)
             if (e->groupOf[(size_t)s] >= 0) {        // back from a plan group to the main path
-                const int rc = leaveNativeGroup(e, s);
-                if (rc != CPQ_OK) return rc;
+                CPQ_TRY(leaveNativeGroup(e, s));
             }
     }
     for (int ch = 0; ch < 2 && !native; ++ch) {
@@ -282,8 +277,7 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
                 if (scaled) for (double& v : heff) v *= scale;
                 if (l == 0 && e->directIr) {
                     for (int i = 0; i < headTaps && i < (int)heff.size(); ++i) heff[(size_t)i] = 0.0;
-                    rc = setDirect(slot, irs[ch]);
-                    if (rc != CPQ_OK) return rc;
+                    CPQ_TRY(setDirect(slot, irs[ch]));
                 }
                 CPQ_HIP(e, hipMemcpyAsync(e->heffDev, heff.data(), heff.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
                 cpq::launch_ir_spectra(e->stream, e->heffDev, (int)heff.size(), Hs + (int64_t)e->layerRow[l] * e->P,
@@ -312,8 +306,7 @@ int32_t cpq_conv_set_impulse(cpq_engine* e, int32_t stream, const double* irL, c
         }
         if (e->directIr) {
             for (int i = 0; i < headTaps && i < (int)heff.size(); ++i) heff[(size_t)i] = 0.0;     // the head leaves the FFT path
-            rc = setDirect(slot, irs[ch]);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(setDirect(slot, irs[ch]));
         }
         const int parts = ((int)heff.size() + e->P - 1) / e->P;
         if (parts > e->kCap) return fail(e, CPQ_ERR_INVALID_ARG, "h_eff needs %d partitions, capacity %d", parts, e->kCap);
@@ -383,8 +376,7 @@ int32_t cpq_conv_reset(cpq_engine* e) { return e ? zeroRuntimeState(e, true, fal
 
 int32_t cpq_conv_process_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
-    const int rc = checkCall(e, dIn, dOut, nSamples);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkCall(e, dIn, dOut, nSamples));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueConv(e, dIn, dOut, nSamples);
 }

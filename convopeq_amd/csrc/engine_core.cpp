@@ -55,6 +55,27 @@ int checkCall(cpq_engine* e, const void* in, const void* out, int nSamples)
     return CPQ_OK;
 }
 
+int checkBaseRows(cpq_engine* e, const void* in, const void* out, int n, bool on, const char* offText, bool wholeCallbacks)
+{
+    if (!e) return CPQ_ERR_INVALID_ARG;
+    if (!on) return fail(e, CPQ_ERR_NOT_READY, "%s", offText);
+    if (!in || !out) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (n <= 0 || n > e->maxCall / e->osFactor)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, e->maxCall / e->osFactor);
+    if (wholeCallbacks && !e->anyCalls && n % callbackLen(e) != 0)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d is not a multiple of the callback length %d", n, callbackLen(e));
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
+        return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    return CPQ_OK;
+}
+
+int refreshBaseRateStages(cpq_engine* e)
+{
+    CPQ_TRY(refreshMeters(e));          // truePeakDetector.prepare / loudnessMeter.prepare: coefficients for the base rate, everything cleared
+    CPQ_TRY(refreshOutStage(e));        // dcBlockers().output*.init / peakLimiter.prepare + reset at the base rate
+    return refreshDither(e);            // the shaper's prepare(rate, bits)
+}
+
 
 // Call-sized buffers that only some entry points need are allocated when first used: the staging pair of the host-pointer
 // entry points, the hand-off buffer of the EQ -> convolver order (3 x 2 GB at 256 streams and 524288-sample calls).
@@ -63,6 +84,20 @@ int ensureCallBuffer(cpq_engine* e, DeviceBuffer<double>& buf, const char* what)
     if (buf) return CPQ_OK;
     const size_t count = (size_t)e->nCh * e->tMax * e->P;
     return allocAll(e, { { buf, count } }, "%s buffer of %zu bytes could not be allocated", what, count * sizeof(double));
+}
+
+int hostRoundTrip(cpq_engine* e, const double* in, size_t inLen, double* out, size_t outLen, bool inPlace,
+                  const std::function<int(const double*, double*)>& body)
+{
+    CPQ_HIP(e, hipSetDevice(e->device));
+    CPQ_TRY(ensureCallBuffer(e, e->stageIn, "upload staging"));
+    if (!inPlace) CPQ_TRY(ensureCallBuffer(e, e->stageOut, "download staging"));
+    double* dst = inPlace ? e->stageIn : e->stageOut;
+    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, sizeof(double) * (size_t)e->nCh * inLen, hipMemcpyHostToDevice, e->stream));
+    CPQ_TRY(body(e->stageIn, dst));
+    if (outLen) CPQ_HIP(e, hipMemcpyAsync(out, dst, sizeof(double) * (size_t)e->nCh * outLen, hipMemcpyDeviceToHost, e->stream));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    return CPQ_OK;
 }
 
 void hostTwiddles(int P, std::vector<double2>& w1, std::vector<double2>& w2)
@@ -96,7 +131,7 @@ int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
         CPQ_HIP(e, hipMemsetAsync(e->hist[1], 0, (size_t)e->nCh * e->P * sizeof(double), e->stream));
         e->head = 0;
         e->histSel = 0;
-        { const int rc = resetGroups(e); if (rc != CPQ_OK) return rc; }
+        CPQ_TRY(resetGroups(e));
         for (const auto& h : e->directHist)
             if (h) CPQ_HIP(e, hipMemsetAsync(h, 0, sizeof(double) * 32 * e->nCh, e->stream));
         if (e->tailState) CPQ_HIP(e, hipMemsetAsync(e->tailState, 0, 4 * sizeof(long long), e->stream));
@@ -108,7 +143,7 @@ int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
     if (eq) {
         CPQ_HIP(e, hipMemsetAsync(e->svfState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
         CPQ_HIP(e, hipMemsetAsync(e->ofState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
-        if (e->agcState) { const int rc = agcStateReset(e, 0, e->desc.n_streams); if (rc != CPQ_OK) return rc; }
+        if (e->agcState) CPQ_TRY(agcStateReset(e, 0, e->desc.n_streams));
     }
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;
@@ -180,8 +215,7 @@ int32_t cpq_nuc_heff(const double* ir, int32_t irLen, int32_t blockSize, double 
     if (!ir) return CPQ_ERR_INVALID_ARG;
     std::vector<double> h;
     cpq_nuc_plan p;
-    const int rc = cpq::buildHeff(ir, irLen, blockSize, scale, spec, h, &p);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(cpq::buildHeff(ir, irLen, blockSize, scale, spec, h, &p));
     if (heff && cap > 0) std::memcpy(heff, h.data(), sizeof(double) * (size_t)std::min<int>(cap, (int)h.size()));
     return (int32_t)h.size();
 }
@@ -441,21 +475,18 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
             same = e->eqParamsSet[s] && std::memcmp(&e->eqParamsHost[s], &e->eqParamsHost[0], sizeof(cpq_eq_params)) == 0;
         if (same) {
             const cpq_eq_params p = e->eqParamsHost[0];
-            const int rc = cpq_eq_set_params(e, CPQ_ALL_STREAMS, &p);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(cpq_eq_set_params(e, CPQ_ALL_STREAMS, &p));
         } else {
             for (int s = 0; s < S; ++s)
                 if (e->eqParamsSet[s]) {
                     const cpq_eq_params p = e->eqParamsHost[s];
-                    const int rc = cpq_eq_set_params(e, s, &p);
-                    if (rc != CPQ_OK) return rc;
+                    CPQ_TRY(cpq_eq_set_params(e, s, &p));
                 }
         }
         for (int s = 0; s < S; ++s)
             if (e->ofModesSet[s]) {
                 const auto m = e->ofModesHost[s];
-                const int rc = cpq_outfilter_set_params(e, s, m.convIsLast, m.hc, m.lc, m.lp);
-                if (rc != CPQ_OK) return rc;
+                CPQ_TRY(cpq_outfilter_set_params(e, s, m.convIsLast, m.hc, m.lc, m.lp));
             }
     }
     e->eqProcessed = false;
@@ -463,16 +494,8 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
     syncEqBypass(e);
     for (size_t s = 0; s < e->mixRamp.size(); ++s) e->mixRamp[s].ramp.setCurrentAndTargetValue((double)e->procParams[s].mix);   // Lifecycle.cpp:370-371
     for (auto& r : e->gainRamp) r.snap();       // setCurrentAndTargetValue (Core.cpp:765)
-    {   // oversampling.prepare -> release(): histories and flags cleared, counters kept
-        const int rc = resetOversampler(e);
-        if (rc != CPQ_OK) return rc;
-    }
-    {   // truePeakDetector.prepare / loudnessMeter.prepare: coefficients for the new base rate, everything cleared
-        const int rc = refreshMeters(e);
-        if (rc != CPQ_OK) return rc;
-    }
-    CPQ_TRY(refreshOutStage(e));        // dcBlockers().output*.init / peakLimiter.prepare + reset at the new base rate
-    CPQ_TRY(refreshDither(e));          // the shaper's prepare(rate, bits)
+    CPQ_TRY(resetOversampler(e));       // oversampling.prepare -> release(): histories and flags cleared, counters kept
+    CPQ_TRY(refreshBaseRateStages(e));
     return zeroRuntimeState(e, true, true);
 }
 
@@ -555,8 +578,7 @@ int32_t cpq_engine_set_gains(cpq_engine* e, int32_t stream, double convInputTrim
     CPQ_HIP(e, hipSetDevice(e->device));
     const int S = e->desc.n_streams;
     if (!e->trimDev) {
-        const int rc = allocAll(e, { { e->trimDev, (size_t)S }, { e->makeupDev, (size_t)S } }, "gain buffers could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { e->trimDev, (size_t)S }, { e->makeupDev, (size_t)S } }, "gain buffers could not be allocated"));
     }
     for (int s = s0; s < s1; ++s) {
         // the trim is applied only when it differs from 1 by more than 1e-12 (:440)
@@ -593,35 +615,37 @@ int cpqi::meteredChain(cpq_engine* e, const double* a, double* b, int n)
     return rc;
 }
 
+// n_samples of the whole-chain call are base-rate samples: the routing runs on n_samples * factor, which the call limit bounds
+static int checkOversampledLimit(cpq_engine* e, int nSamples)
+{
+    if (e && e->osFactor > 1 && nSamples > e->maxCall / e->osFactor)
+        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
+                    e->osFactor, e->maxCall);
+    return CPQ_OK;
+}
+
 int cpqi::checkBlockCall(cpq_engine* e, const void* in, const void* out, int nSamples)
 {
-    const int factor = e ? e->osFactor : 1;
-    if (factor > 1 && nSamples > e->maxCall / factor)   // n_samples are base-rate samples: the routing runs on n_samples * factor
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
-                    factor, e->maxCall);
-    int rc = checkCall(e, in, out, nSamples * factor);
-    if (rc == CPQ_OK) rc = checkMeterCall(e, nSamples);
-    return rc;
+    CPQ_TRY(checkOversampledLimit(e, nSamples));
+    CPQ_TRY(checkCall(e, in, out, nSamples * (e ? e->osFactor : 1)));
+    return checkMeterCall(e, nSamples);
 }
 
 extern "C" {
 
 int32_t cpq_engine_process_block_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
-    const int rc = checkBlockCall(e, dIn, dOut, nSamples);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkBlockCall(e, dIn, dOut, nSamples));
     CPQ_HIP(e, hipSetDevice(e->device));
     return meteredChain(e, dIn, dOut, nSamples);
 }
 
 int32_t cpq_engine_process_block(cpq_engine* e, const double* in, double* out, int32_t nSamples)
 {
-    const int factor = e ? e->osFactor : 1;
-    if (factor > 1 && nSamples > e->maxCall / factor)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d times the oversampling factor %d exceeds the call limit %d", nSamples,
-                    factor, e->maxCall);
-    if (e && nSamples > 0) { const int rc = checkMeterCall(e, nSamples); if (rc != CPQ_OK) return rc; }
-    return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return meteredChain(e, a, b, n); }, factor);
+    CPQ_TRY(checkOversampledLimit(e, nSamples));
+    if (e && nSamples > 0) CPQ_TRY(checkMeterCall(e, nSamples));    // before checkCall here, after it in the device variant
+    return viaStaging(e, in, out, nSamples, [e](const double* a, double* b, int n) { return meteredChain(e, a, b, n); },
+                      e ? e->osFactor : 1);
 }
 
 // -------------------------------------------------------------------------- profiling
@@ -672,8 +696,7 @@ int32_t cpq_profile_reset(cpq_engine* e)
 int32_t cpq_profile_read(cpq_engine* e, int32_t id, int64_t* launches, double* totalMs)
 {
     if (!e || id < 0 || id >= CPQ_K_COUNT) return CPQ_ERR_INVALID_ARG;
-    const int rc = drainProfile(e);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(drainProfile(e));
     if (launches) *launches = e->prof[id].launches;
     if (totalMs) *totalMs = e->prof[id].totalMs;
     return CPQ_OK;

@@ -4,15 +4,13 @@
 // (error taps or lattice states, generator words).  Every stream is a DSPCore of its own, so every stream starts from the same
 // two generator states (L, R).  The adaptive shaper's coefficients are the stream's: cpq_dither_set_adaptive_coeffs is
 // applyMatchedCoefficients at the start of a callback (DSPCoreDouble.cpp:617-628).  In the whole-chain call the stage sits
-// between the DC blocker and the meters (engine_core.cpp, meteredChain).
+// between the DC blocker and the meters (engine_core.cpp, meteredChain).  cpq_dither_process takes the refusals of
+// checkBaseRows and the in-place hostRoundTrip; baseRate is the engine's (engine_internal.hpp).
 #include "engine_internal.hpp"
 
 namespace cpqi {
 
 namespace {
-
-int callbackLen(const cpq_engine* e) { return std::max(1, e->B / e->osFactor); }
-double baseRate(const cpq_engine* e) { return e->sampleRate / e->osFactor; }
 
 int clearErrors(cpq_engine* e)
 {
@@ -54,16 +52,7 @@ void design(cpq_engine* e)
 
 int checkRows(cpq_engine* e, const void* in, const void* out, int n)
 {
-    if (!e) return CPQ_ERR_INVALID_ARG;
-    if (e->ditherShaper == CPQ_DITHER_OFF) return fail(e, CPQ_ERR_NOT_READY, "dither is off (cpq_engine_set_dither)");
-    if (!in || !out) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (n <= 0 || n > e->maxCall / e->osFactor)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, e->maxCall / e->osFactor);
-    if (!e->anyCalls && n % callbackLen(e) != 0)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d is not a multiple of the callback length %d", n, callbackLen(e));
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
-    return CPQ_OK;
+    return checkBaseRows(e, in, out, n, e && e->ditherShaper != CPQ_DITHER_OFF, "dither is off (cpq_engine_set_dither)", true);
 }
 
 }  // namespace
@@ -164,14 +153,8 @@ int32_t cpq_dither_process_device(cpq_engine* e, const double* dIn, double* dOut
 int32_t cpq_dither_process(cpq_engine* e, const double* in, double* out, int32_t nSamples)
 {
     CPQ_TRY(checkRows(e, in, out, nSamples));
-    CPQ_HIP(e, hipSetDevice(e->device));
-    CPQ_TRY(ensureCallBuffer(e, e->stageIn, "upload staging"));
-    const size_t bytes = sizeof(double) * (size_t)e->nCh * nSamples;
-    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, bytes, hipMemcpyHostToDevice, e->stream));
-    CPQ_TRY(enqueueDither(e, e->stageIn, nSamples, e->stageIn, nSamples, nSamples));
-    CPQ_HIP(e, hipMemcpyAsync(out, e->stageIn, bytes, hipMemcpyDeviceToHost, e->stream));
-    CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    return CPQ_OK;
+    return hostRoundTrip(e, in, (size_t)nSamples, out, (size_t)nSamples, true,
+                         [&](const double* a, double* b) { return enqueueDither(e, a, nSamples, b, nSamples, nSamples); });
 }
 
 }  // extern "C"

@@ -190,15 +190,14 @@ int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride
     }
     bool midSide = false;
     for (char m : e->eqMidSide) midSide = midSide || m;
-    const int rc = enqueueCascade(e, dIn, dOut, stride, n, tp, CPQ_K_SVF_TP, CPQ_K_SVF, e->svfCoef, e->svfFlags, e->svfSatGain,
-                                  e->svfState, e->svfTp, midSide);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(enqueueCascade(e, dIn, dOut, stride, n, tp, CPQ_K_SVF_TP, CPQ_K_SVF, e->svfCoef, e->svfFlags, e->svfSatGain,
+                           e->svfState, e->svfTp, midSide));
     if (anyRamp) {
         ProfScope p(e, CPQ_K_MIX);
         cpq::launch_gain_ramp(e->stream, dOut, stride, e->desc.n_streams, e->B, cbs, e->rampGains, e->rampOn);
         CPQ_HIP(e, hipGetLastError());
     }
-    if (!e->anyAgc) return rc;
+    if (!e->anyAgc) return CPQ_OK;
     {
         ProfScope p(e, CPQ_K_MIX);
         // block coefficients of the tables prepareToPlay builds (src/eqprocessor/EQProcessor.Core.cpp:776-784)
@@ -226,13 +225,13 @@ static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_
     if (!e->eqSet) return fail(e, CPQ_ERR_NOT_READY, "cpq_eq_set_params has not been called");
     const int S = e->desc.n_streams;
     auto agcReset = [e](int s) -> int {        // rtAgcCurrentGainShadow = 1, envelopes = 0 (Processing.cpp:586-593, 1070-1077)
-        if (e->agcState) { const int rc = agcStateReset(e, s, 1); if (rc != CPQ_OK) return rc; }
+        if (e->agcState) CPQ_TRY(agcStateReset(e, s, 1));
         e->agcResetPending[s] = 0;
         return CPQ_OK;
     };
     if (!e->anyEqBypass && !e->anyEqReset) {
         for (int s = 0; s < S; ++s)
-            if (e->agcResetPending[s]) { const int rc = agcReset(s); if (rc != CPQ_OK) return rc; }
+            if (e->agcResetPending[s]) CPQ_TRY(agcReset(s));
         e->eqProcessed = true;
         return enqueueEqCore(e, dIn, dOut, stride, n, nullptr);
     }
@@ -377,9 +376,7 @@ int enqueueEq(cpq_engine* e, const double* dIn, double* dOut, int n)
     bool perCallback = e->anyAgc || e->anyEqBypass || e->anyEqReset;
     for (size_t s = 0; s < e->gainRamp.size() && !perCallback; ++s) perCallback = !e->agcOnHost[s] && e->gainRamp[s].moving();
     if (r == 0 || !perCallback) return enqueueEqRange(e, dIn, dOut, (int64_t)n, n);
-    int rc = CPQ_OK;
-    if (n - r > 0) rc = enqueueEqRange(e, dIn, dOut, (int64_t)n, n - r);
-    if (rc != CPQ_OK) return rc;
+    if (n - r > 0) CPQ_TRY(enqueueEqRange(e, dIn, dOut, (int64_t)n, n - r));
     struct QuantumOf {            // the short callback is a callback of r samples to everything below
         cpq_engine* e; int saved;
         QuantumOf(cpq_engine* e_, int b) : e(e_), saved(e_->B) { e->B = b; }
@@ -457,9 +454,8 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
         const int S = e->desc.n_streams;
         const size_t cbMax = (size_t)e->tMax * e->P / e->B;
         if (!e->agcOn) {
-            const int rc = allocAll(e, { { e->agcOn, (size_t)S }, { e->agcState, (size_t)3 * S, true }, { e->agcRmsIn, e->nCh * cbMax },
-                                         { e->agcRmsOut, e->nCh * cbMax }, { e->agcGains, 2 * S * cbMax } }, "AGC buffers could not be allocated");
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(allocAll(e, { { e->agcOn, (size_t)S }, { e->agcState, (size_t)3 * S, true }, { e->agcRmsIn, e->nCh * cbMax },
+                                  { e->agcRmsOut, e->nCh * cbMax }, { e->agcGains, 2 * S * cbMax } }, "AGC buffers could not be allocated"));
             const int rs = agcStateReset(e, 0, S);
             if (rs != CPQ_OK) return rs;
             CPQ_HIP(e, hipStreamSynchronize(e->stream));
@@ -526,8 +522,7 @@ int32_t cpq_eq_reset(cpq_engine* e)
 
 int32_t cpq_eq_process_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
-    const int rc = checkCall(e, dIn, dOut, nSamples);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkCall(e, dIn, dOut, nSamples));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueEq(e, dIn, dOut, nSamples);
 }
@@ -600,8 +595,7 @@ int32_t cpq_outfilter_reset(cpq_engine* e)
 
 int32_t cpq_outfilter_process_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
-    const int rc = checkCall(e, dIn, dOut, nSamples);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkCall(e, dIn, dOut, nSamples));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueOutFilter(e, dIn, dOut, nSamples);
 }

@@ -1,5 +1,6 @@
 // engine_internal.hpp -- the engine object behind the C ABI and the helpers its translation units share:
-//   engine_core.cpp  create / destroy / prepare, status and profiling entry points, DSPCore routing (whole path)
+//   engine_core.cpp  create / destroy / prepare, status and profiling entry points, DSPCore routing (whole path); what the stage
+//                    files below share: checkCall, checkBaseRows, hostRoundTrip, refreshBaseRateStages
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
 //   engine_native.cpp  plan groups: streams whose convolver runs on the reference's own layer plan, replayed per chunk
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
@@ -25,6 +26,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -395,6 +397,22 @@ struct ProfScope {
 
 int checkCall(cpq_engine* e, const void* in, const void* out, int nSamples);
 int ensureCallBuffer(cpq_engine* e, DeviceBuffer<double>& buf, const char* what);
+
+// The stages after the routing (meters, output stage, dither, PCM sanitise) run at the base rate, one callback of block_size /
+// factor samples at a time.  The quotient is never 0: cpq_engine_create wants block_size >= 64 outside CPQ_CALLS_ANY, and
+// cpq_engine_set_oversampling refuses a factor that does not divide block_size inside it.
+inline int callbackLen(const cpq_engine* e) { return e->B / e->osFactor; }
+inline double baseRate(const cpq_engine* e) { return e->sampleRate / e->osFactor; }
+// what follows the base rate, redesigned and reset after it changed: meters, output stage, dither (each nothing while it is off)
+int refreshBaseRateStages(cpq_engine* e);
+// The refusals of a stage's own entry point on base-rate rows [nCh][n], in this order: null handle (no message), stage off
+// (CPQ_ERR_NOT_READY with offText), null buffer, n outside 1..maxCall / factor, part callbacks outside CPQ_CALLS_ANY (only
+// with wholeCallbacks: the oversampler's calls have no such rule), 16-byte alignment.  One buffer: pass it for both.
+int checkBaseRows(cpq_engine* e, const void* in, const void* out, int n, bool on, const char* offText, bool wholeCallbacks);
+// The host-pointer call of one stage, on the engine's stream: inLen samples per channel up into stageIn, body(src, dst), outLen
+// samples per channel down from dst (0: nothing comes back), synchronise.  inPlace: dst is stageIn and stageOut is not allocated.
+int hostRoundTrip(cpq_engine* e, const double* in, size_t inLen, double* out, size_t outLen, bool inPlace,
+                  const std::function<int(const double*, double*)>& body);
 // exp(-2 pi i m / P) and exp(-2 pi i m / 2P), m < P: extended precision on the host, rounded once (SURVEY.md section 7 "hard parts")
 void hostTwiddles(int P, std::vector<double2>& w1, std::vector<double2>& w2);
 int zeroRuntimeState(cpq_engine* e, bool conv, bool eq);
@@ -423,7 +441,7 @@ int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase);
 // engine_meter.cpp
 constexpr int kMeterRing = 4096;                // LockFreeRingBuffer<BlockPower, 4096>
 int refreshMeters(cpq_engine* e);               // redesign for the present base rate and reset; nothing while metering is off
-int checkMeterCall(cpq_engine* e, int nBase);   // the refusals, before anything is enqueued
+int checkMeterCall(cpq_engine* e, int nBase);   // true peak's own refusals, before anything is enqueued
 int enqueueMeters(cpq_engine* e, const double* rows, int64_t stride, int nBase);
 // engine_out.cpp
 int refreshOutStage(cpq_engine* e);             // redesign for the present base rate and reset; nothing while the stage is off
@@ -463,12 +481,10 @@ int enqueueOutFilter(cpq_engine* e, const double* dIn, double* dOut, int n);
 template <typename Io, typename F>
 int stagedCall(cpq_engine* e, Io& io, int nSamples, F&& body, int factor = 1)
 {
-    int rc = checkCall(e, io.hostIn(), io.hostOut(), nSamples * factor);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkCall(e, io.hostIn(), io.hostOut(), nSamples * factor));
     CPQ_HIP(e, hipSetDevice(e->device));
-    rc = ensureCallBuffer(e, e->stageIn, "upload staging");
-    if (rc == CPQ_OK) rc = ensureCallBuffer(e, e->stageOut, "download staging");
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(ensureCallBuffer(e, e->stageIn, "upload staging"));
+    CPQ_TRY(ensureCallBuffer(e, e->stageOut, "download staging"));
     constexpr int kChunks = 4;
     const int T = nSamples * factor / e->P;                             // partitions in the call (whole ones outside CPQ_CALLS_ANY)
     auto pinned = [](const void* p) {
@@ -480,8 +496,7 @@ int stagedCall(cpq_engine* e, Io& io, int nSamples, F&& body, int factor = 1)
     // (measured 1157 vs 1230 M samples/s); one upload, one download
     if (e->anyCalls || T < 32 || T % kChunks != 0 || !pinned(io.hostIn()) || !pinned(io.hostOut())) {
         CPQ_TRY(io.uploadAll(e, nSamples));
-        rc = body(e->stageIn, e->stageOut, nSamples);
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(body(e->stageIn, e->stageOut, nSamples));
         CPQ_TRY(io.downloadAll(e, nSamples));
         CPQ_HIP(e, hipStreamSynchronize(e->stream));
         return CPQ_OK;
@@ -506,13 +521,12 @@ int stagedCall(cpq_engine* e, Io& io, int nSamples, F&& body, int factor = 1)
         CPQ_TRY(io.uploadChunk(e, i, chunkLen, nSamples));
         CPQ_HIP(e, hipEventRecord(e->evIn[i], e->copyIn));
         CPQ_HIP(e, hipStreamWaitEvent(e->stream, e->evIn[i], 0));
-        rc = body(dIn, dOut, (int)chunkLen);
-        if (rc != CPQ_OK) { (void)hipDeviceSynchronize(); return rc; }
+        const int rc = body(dIn, dOut, (int)chunkLen);
+        if (rc != CPQ_OK) { (void)hipDeviceSynchronize(); return rc; }      // nothing of the other chunks stays in flight
         CPQ_HIP(e, hipEventRecord(e->evDone[i], e->stream));
-        if (i > 0) { rc = download(i - 1); if (rc != CPQ_OK) return rc; }
+        if (i > 0) CPQ_TRY(download(i - 1));
     }
-    rc = download(kChunks - 1);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(download(kChunks - 1));
     CPQ_HIP(e, hipStreamSynchronize(e->copyOut));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;

@@ -2,6 +2,8 @@
 // TruePeakDetector, src/TruePeakDetector.{h,cpp}; run at the end of DSPCore::processOutputDouble, DSPCoreDouble.cpp:695-701).
 // The kernels are in meter_kernels.hip; the host designs the filters for the base rate, owns the buffers and keeps the ring's
 // counters: every stream sees the same callbacks, so one write / read pair and one block counter serve all of them.
+// cpq_meter_process takes the refusals of checkBaseRows, then true peak's own (checkMeterCall), and the hostRoundTrip that
+// brings nothing back.
 #include "engine_internal.hpp"
 
 namespace cpqi {
@@ -9,8 +11,6 @@ namespace cpqi {
 namespace {
 
 constexpr size_t kTabDoubles = 2 * (size_t)cpq::kMeterSectionDoubles + 32 + 16;
-
-int callbackLen(const cpq_engine* e) { return e->B / e->osFactor; }
 
 int resetMeters(cpq_engine* e)
 {
@@ -28,7 +28,7 @@ int designMeters(cpq_engine* e)
 {
     std::vector<double> tab(kTabDoubles, 0.0);
     double pre[5], rlb[5];
-    cpq::meterKWeighting(e->sampleRate / e->osFactor, pre, rlb);
+    cpq::meterKWeighting(baseRate(e), pre, rlb);
     cpq::meterSectionTables(pre, tab.data());
     cpq::meterSectionTables(rlb, tab.data() + cpq::kMeterSectionDoubles);
     cpq::OsStage s0, s1;
@@ -47,14 +47,7 @@ int designMeters(cpq_engine* e)
 
 int checkRows(cpq_engine* e, const void* in, int n)
 {
-    if (!e) return CPQ_ERR_INVALID_ARG;
-    if (!e->meterFlags) return fail(e, CPQ_ERR_NOT_READY, "metering is off (cpq_engine_set_metering)");
-    if (!in) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (n <= 0 || n > e->maxCall / e->osFactor)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, e->maxCall / e->osFactor);
-    if (!e->anyCalls && n % callbackLen(e) != 0)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d is not a multiple of the callback length %d", n, callbackLen(e));
-    if (reinterpret_cast<uintptr_t>(in) & 15u) return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    CPQ_TRY(checkBaseRows(e, in, in, n, e && e->meterFlags, "metering is off (cpq_engine_set_metering)", true));
     return checkMeterCall(e, n);
 }
 
@@ -63,9 +56,8 @@ int checkRows(cpq_engine* e, const void* in, int n)
 int refreshMeters(cpq_engine* e)
 {
     if (!e->meterFlags) return CPQ_OK;
-    int rc = designMeters(e);
-    if (rc == CPQ_OK) rc = resetMeters(e);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(designMeters(e));
+    CPQ_TRY(resetMeters(e));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;
 }
@@ -132,11 +124,10 @@ int32_t cpq_engine_set_metering(cpq_engine* e, int32_t flags)
     if (flags && !e->meterTab) {
         const size_t S = (size_t)e->desc.n_streams, nCh = (size_t)e->nCh;
         const int cbCap = (e->maxCall + e->B - 1) / e->B;          // callbacks of the longest call, at any factor
-        const int rc = allocAll(e, { { e->meterTab, kTabDoubles }, { e->meterState, 8 * nCh }, { e->meterHist[0], 32 * nCh },
-                                     { e->meterHist[1], 32 * nCh }, { e->meterHold, S }, { e->meterChSum, nCh * cbCap },
-                                     { e->meterChPeak, nCh * cbCap }, { e->meterTp, S * cbCap }, { e->meterRing, S * kMeterRing } },
-                                "meter buffers could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { e->meterTab, kTabDoubles }, { e->meterState, 8 * nCh }, { e->meterHist[0], 32 * nCh },
+                              { e->meterHist[1], 32 * nCh }, { e->meterHold, S }, { e->meterChSum, nCh * cbCap },
+                              { e->meterChPeak, nCh * cbCap }, { e->meterTp, S * cbCap }, { e->meterRing, S * kMeterRing } },
+                         "meter buffers could not be allocated"));
         e->meterCbCap = cbCap;
     }
     e->meterFlags = flags;
@@ -147,32 +138,23 @@ int32_t cpq_meter_reset(cpq_engine* e)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
     if (!e->meterFlags) return fail(e, CPQ_ERR_NOT_READY, "metering is off (cpq_engine_set_metering)");
-    const int rc = resetMeters(e);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(resetMeters(e));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;
 }
 
 int32_t cpq_meter_process_device(cpq_engine* e, const double* dIn, int32_t nSamples)
 {
-    const int rc = checkRows(e, dIn, nSamples);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkRows(e, dIn, nSamples));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueMeters(e, dIn, nSamples, nSamples);
 }
 
 int32_t cpq_meter_process(cpq_engine* e, const double* in, int32_t nSamples)
 {
-    int rc = checkRows(e, in, nSamples);
-    if (rc != CPQ_OK) return rc;
-    CPQ_HIP(e, hipSetDevice(e->device));
-    rc = ensureCallBuffer(e, e->stageIn, "upload staging");
-    if (rc != CPQ_OK) return rc;
-    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, sizeof(double) * (size_t)e->nCh * nSamples, hipMemcpyHostToDevice, e->stream));
-    rc = enqueueMeters(e, e->stageIn, nSamples, nSamples);
-    if (rc != CPQ_OK) return rc;
-    CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    return CPQ_OK;
+    CPQ_TRY(checkRows(e, in, nSamples));
+    return hostRoundTrip(e, in, (size_t)nSamples, nullptr, 0, true,
+                         [&](const double* a, double*) { return enqueueMeters(e, a, nSamples, nSamples); });
 }
 
 int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t maxBlocks, int32_t* nBlocks, int64_t* nDropped)

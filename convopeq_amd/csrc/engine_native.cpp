@@ -57,9 +57,8 @@ int allocLayer(cpq_engine* e, NativeLayer& t, int capCh, int hSlots)
     const bool big = t.P > 4096;          // four-step transforms: + the two reordered tables (kernels.hpp: FftTables)
     total += (big ? 4 : 2) * twBytes + gainBytes + scratchBytes;
     {
-        const int rc = allocAll(e, { { t.mem, (size_t)total } }, "plan group layer (partition %d, %d channels): %lld bytes could not be allocated",
-                                t.P, capCh, (long long)total);
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { t.mem, (size_t)total } }, "plan group layer (partition %d, %d channels): %lld bytes could not be allocated",
+                         t.P, capCh, (long long)total));
     }
     char* const mem = t.mem;
     CPQ_HIP(e, hipMemsetAsync(mem, 0, (size_t)total, e->stream));
@@ -222,8 +221,7 @@ int stageUpload(cpq_engine* e, void* dst, const void* src, size_t bytes)
     PinnedRing& r = e->pinned;
     if (!r.host) {
         r.cap = (size_t)8 << 20;
-        const int rc = allocAll(e, { { r.host, r.cap } }, "pinned staging ring could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { r.host, r.cap } }, "pinned staging ring could not be allocated"));
     }
     const size_t need = (bytes + 255) & ~(size_t)255;
     if (need > r.cap / 4) {
@@ -296,8 +294,7 @@ int leaveNativeGroup(cpq_engine* e, int stream)
     for (size_t p = 0; p < g.streamOfPair.size(); ++p)
         if (g.streamOfPair[p] == stream) {
             g.streamOfPair[p] = -1;
-            const int rc = zeroPairState(e, g, (int)p);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(zeroPairState(e, g, (int)p));
         }
     e->groupOf[(size_t)stream] = -1;
     bool empty = true;
@@ -335,8 +332,7 @@ static int isolateStream(cpq_engine* e, int stream)
     n->samplesSinceReset = std::max<long long>(g.samplesSinceReset, 1);        // not fresh: nobody else may join its phase
     n->lastGot = g.lastGot;
     n->lastCall = g.lastCall;
-    int rc = sizeGroup(e, *n, 1);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(sizeGroup(e, *n, 1));
     for (size_t l = 0; l < g.layers.size(); ++l) {
         const NativeLayer& src = g.layers[l];
         NativeLayer& dst = n->layers[l];
@@ -358,11 +354,9 @@ static int isolateStream(cpq_engine* e, int stream)
     PlanGroup& isolated = *n;
     e->groups.push_back(std::move(n));
     e->groupOf[(size_t)stream] = (int)e->groups.size() - 1;
-    rc = zeroPairState(e, g, pair);
-    if (rc != CPQ_OK) return rc;
-    rc = uploadGroupMaps(e, g);
-    if (rc == CPQ_OK) rc = uploadGroupMaps(e, isolated);
-    return rc;
+    CPQ_TRY(zeroPairState(e, g, pair));
+    CPQ_TRY(uploadGroupMaps(e, g));
+    return uploadGroupMaps(e, isolated);
 }
 
 // frozen: the stream's convolver is not called (bypass / dry-only at the processor level); its state waits as it is
@@ -373,8 +367,7 @@ int setStreamFrozen(cpq_engine* e, int stream, bool frozen)
                                                    "(CPQ_CALLS_ANY, CPQ_SCHED_REFERENCE_NUC or a FilterSpec plan with tail layers); "
                                                    "on the uniform path set it for CPQ_ALL_STREAMS");
     if (e->groups[(size_t)gi]->frozen == frozen) return CPQ_OK;      // (a frozen group has one member: it was isolated first)
-    const int rc = isolateStream(e, stream);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(isolateStream(e, stream));
     gi = e->groupOf[(size_t)stream];
     e->groups[(size_t)gi]->frozen = frozen;
     return CPQ_OK;
@@ -397,7 +390,7 @@ int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double*
     const int S = e->desc.n_streams;
     const bool shared = stream == CPQ_ALL_STREAMS;
     const int s0 = shared ? 0 : stream, s1 = shared ? S : stream + 1;
-    for (int s = s0; s < s1; ++s) { const int rc = leaveNativeGroup(e, s); if (rc != CPQ_OK) return rc; }
+    for (int s = s0; s < s1; ++s) CPQ_TRY(leaveNativeGroup(e, s));
 
     // a fresh group with the same plan takes the stream(s); anything else would put them on another group's phase
     PlanGroup* g = nullptr;
@@ -416,8 +409,7 @@ int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double*
         g->hasSpec = spec != nullptr;
         if (spec) g->spec = *spec;
         g->shared = shared;
-        const int rc = sizeGroup(e, *g, shared ? S : 1);       // one pair, doubled as members join: 256 one-member groups (256 IR lengths) cost what they use
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(sizeGroup(e, *g, shared ? S : 1));     // one pair, doubled as members join: 256 one-member groups (256 IR lengths) cost what they use
         e->groups.push_back(std::move(made));
         gi = (int)e->groups.size() - 1;
     }
@@ -428,14 +420,13 @@ int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double*
         for (size_t p = 0; p < g->streamOfPair.size() && pair < 0; ++p) if (g->streamOfPair[p] < 0) pair = (int)p;
         if (pair < 0) {
             pair = (int)g->streamOfPair.size();
-            const int rc = sizeGroup(e, *g, std::min(S, std::max(2 * pair, 2)));
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(sizeGroup(e, *g, std::min(S, std::max(2 * pair, 2))));
         }
         g->streamOfPair[(size_t)pair] = s;
         e->groupOf[(size_t)s] = gi;
         pairOf.push_back(pair);
     }
-    { const int rc = uploadGroupMaps(e, *g); if (rc != CPQ_OK) return rc; }
+    CPQ_TRY(uploadGroupMaps(e, *g));
 
     // partition spectra of every layer (:919-946), the direct head's taps left out of the FFT path (:730-731), scaled
     // (:939-940), FilterSpec gains at the layer's own FFT size (:336-443), air absorption on the tail layers (:1060-1097)
@@ -680,7 +671,7 @@ int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
         PlanGroup& g = *gp;
         if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
         const long long w0 = g.callW0, r0 = g.callR0;        // (replayed in groupsAppend)
-        if (!g.tabOnDevice) { const int rc = stageUpload(e, g.tabDev, g.tabHost.data(), g.tabHost.size() * sizeof(long long)); if (rc != CPQ_OK) return rc; }
+        if (!g.tabOnDevice) CPQ_TRY(stageUpload(e, g.tabDev, g.tabHost.data(), g.tabHost.size() * sizeof(long long)));
         // Whole-block call on an empty ring, every chunk's Get() taking exactly the chunk this call's blocks produce, members =
         // all channels in order: the inverse FFT writes the output rows directly, no ring put / get (two passes and two
         // launches less; the ring stays empty, its positions advanced on the host by the replay above)
@@ -699,12 +690,11 @@ int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
         const bool addTails = direct && g.layers.size() >= 2 && g.layers.size() <= 3 && g.layers[0].P == cpq::kP && e->B == cpq::kP && !e->anyDirect;
         if (addTails) {
             for (size_t l = 1; l < g.layers.size(); ++l) {
-                const int rc = runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0);
-                if (rc != CPQ_OK) return rc;
+                CPQ_TRY(runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0));
             }
             g.tailsDone = true;
         }
-        { const int rc = runLayerBlocks(e, g, g.layers[0], n, nullptr, w0, direct ? dOut : nullptr, addTails); if (rc != CPQ_OK) return rc; }
+        CPQ_TRY(runLayerBlocks(e, g, g.layers[0], n, nullptr, w0, direct ? dOut : nullptr, addTails));
         // Get() reads layer 0's ring chunk by chunk and then adds the tail layers' delay-line blocks: with nothing in between (no
         // direct head) the read waits for groupsRunTails, whose pass over the output does both
         g.getDeferred = !direct && !e->anyDirect && g.layers.size() >= 2 && g.layers.size() <= 3;
@@ -730,8 +720,7 @@ int groupsRunTails(cpq_engine* e, double* dOut, int n)
         if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
         if (g.tailsDone) { g.tailsDone = false; continue; }     // (ran ahead of layer 0, whose transform added their blocks: groupsRunLayer0)
         for (size_t l = 1; l < g.layers.size(); ++l) {
-            const int rc = runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0));
         }
         ProfScope p(e, CPQ_K_MIX);
         if (g.getDeferred) {

@@ -1,7 +1,8 @@
 // engine_os.cpp -- the half-band oversampler around the routing (CustomInputOversampler, src/CustomInputOversampler.cpp, as
 // DSPCore::processDouble runs it: processUp, the chain at F x the rate, processDown; DSPCoreDouble.cpp:359-376, :477-531).
 // The stage kernels, guards and per-stream state machine are in os_kernels.hip; the host sizes the buffers, uploads the
-// coefficients and flips the history ping-pong selectors.
+// coefficients and flips the history ping-pong selectors.  cpq_os_up / cpq_os_down take the refusals of checkBaseRows (any
+// call length) and the two-buffer hostRoundTrip; a new factor ends in refreshBaseRateStages (all three: engine_core.cpp).
 #include "engine_internal.hpp"
 
 namespace cpqi {
@@ -34,8 +35,7 @@ static int ensureOsTmp(cpq_engine* e)
     for (auto& b : e->osTmp) {
         if (b) continue;
         const size_t count = (size_t)e->nCh * (size_t)(e->maxCall / 2);
-        const int rc = allocAll(e, { { b, count } }, "oversampler stage buffer of %zu bytes could not be allocated", count * sizeof(double));
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { b, count } }, "oversampler stage buffer of %zu bytes could not be allocated", count * sizeof(double)));
     }
     return CPQ_OK;
 }
@@ -56,7 +56,7 @@ static cpq::OsStageArgs stageArgs(cpq_engine* e, int i)
 // processUp: in [nCh][inStride] (nBase samples) -> out [nCh][outStride] (nBase * F samples)
 static int enqueueUp(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
 {
-    if (e->osStages > 1) { const int rc = ensureOsTmp(e); if (rc != CPQ_OK) return rc; }
+    if (e->osStages > 1) CPQ_TRY(ensureOsTmp(e));
     ProfScope p(e, CPQ_K_OS);
     const double* src = in;
     int64_t srcStride = inStride;
@@ -82,7 +82,7 @@ static int enqueueUp(cpq_engine* e, const double* in, int64_t inStride, double* 
 // processDown: in [nCh][inStride] (nBase * F samples) -> out [nCh][outStride] (nBase samples)
 static int enqueueDown(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
 {
-    if (e->osStages > 1) { const int rc = ensureOsTmp(e); if (rc != CPQ_OK) return rc; }
+    if (e->osStages > 1) CPQ_TRY(ensureOsTmp(e));
     ProfScope p(e, CPQ_K_OS);
     cpq::OsHistories hs{};
     for (int i = 0; i < e->osStages; ++i) {
@@ -119,48 +119,21 @@ static int enqueueDown(cpq_engine* e, const double* in, int64_t inStride, double
 // whole path with factor > 1: up -> routing on nBase * F samples in the internal work buffer (in place) -> down
 int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase)
 {
-    int rc = ensureCallBuffer(e, e->osWork, "oversampled block");
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(ensureCallBuffer(e, e->osWork, "oversampled block"));
     const int n = nBase * e->osFactor;
-    rc = enqueueUp(e, dIn, nBase, e->osWork, n, nBase);
-    if (rc == CPQ_OK) rc = enqueueBoth(e, e->osWork, e->osWork, n);
-    if (rc == CPQ_OK) rc = enqueueDown(e, e->osWork, n, dOut, nBase, nBase);
-    return rc;
+    CPQ_TRY(enqueueUp(e, dIn, nBase, e->osWork, n, nBase));
+    CPQ_TRY(enqueueBoth(e, e->osWork, e->osWork, n));
+    return enqueueDown(e, e->osWork, n, dOut, nBase, nBase);
 }
 
 }  // namespace cpqi
 
 using namespace cpqi;
 
-// the stand-alone entry points: nBase * F within the engine's call limit, 16-byte aligned buffers
+// the stand-alone entry points: nBase * F within the engine's call limit, 16-byte aligned buffers; any call length
 static int checkOsCall(cpq_engine* e, const void* in, const void* out, int nBase)
 {
-    if (!e) return CPQ_ERR_INVALID_ARG;
-    if (e->osFactor == 1) return fail(e, CPQ_ERR_NOT_READY, "oversampling is not set (factor 1)");
-    if (!in || !out) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (nBase <= 0 || nBase > e->maxCall / e->osFactor)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_base=%d outside 1..%d (n_base * factor beyond the call limit %d)", nBase,
-                    e->maxCall / e->osFactor, e->maxCall);
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
-    return CPQ_OK;
-}
-
-template <typename F>
-static int osHost(cpq_engine* e, const double* in, double* out, int nBase, size_t inLen, size_t outLen, F&& body)
-{
-    int rc = checkOsCall(e, in, out, nBase);
-    if (rc != CPQ_OK) return rc;
-    CPQ_HIP(e, hipSetDevice(e->device));
-    rc = ensureCallBuffer(e, e->stageIn, "upload staging");
-    if (rc == CPQ_OK) rc = ensureCallBuffer(e, e->stageOut, "download staging");
-    if (rc != CPQ_OK) return rc;
-    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, sizeof(double) * (size_t)e->nCh * inLen, hipMemcpyHostToDevice, e->stream));
-    rc = body(e->stageIn, e->stageOut);
-    if (rc != CPQ_OK) return rc;
-    CPQ_HIP(e, hipMemcpyAsync(out, e->stageOut, sizeof(double) * (size_t)e->nCh * outLen, hipMemcpyDeviceToHost, e->stream));
-    CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    return CPQ_OK;
+    return checkBaseRows(e, in, out, nBase, e && e->osFactor > 1, "oversampling is not set (factor 1)", false);
 }
 
 extern "C" {
@@ -180,15 +153,14 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
     freeOversampler(e);
     const int S = e->desc.n_streams;
     if (!e->osFlags) {
-        const int rc = allocAll(e, { { e->osFlags, (size_t)4 * S }, { e->osCounts, (size_t)2 * S }, { e->osNonSilent, (size_t)3 * e->nCh } },
-                                "oversampler state could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { e->osFlags, (size_t)4 * S }, { e->osCounts, (size_t)2 * S }, { e->osNonSilent, (size_t)3 * e->nCh } },
+                         "oversampler state could not be allocated"));
     }
     CPQ_HIP(e, hipMemset(e->osCounts, 0, sizeof(unsigned long long) * 2 * S));
     CPQ_HIP(e, hipMemset(e->osFlags, 0, sizeof(int) * 4 * S));
     e->osFactor = factor;
     e->osType = type;
-    if (nStages == 0) { CPQ_TRY(refreshMeters(e)); CPQ_TRY(refreshOutStage(e)); return refreshDither(e); }     // the meters and the output stage follow the base rate
+    if (nStages == 0) return refreshBaseRateStages(e);
     cpq::OsStage st[3];
     size_t bytes = 0;
     for (int i = 0; i < nStages; ++i) {
@@ -219,51 +191,45 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
         for (int b = 0; b < 2; ++b) { d.down[b] = p; p += (size_t)e->nCh * alignUp(d.downKeep, 32); }
     }
     e->osStages = nStages;
-    const int rc = resetOversampler(e);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(resetOversampler(e));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    CPQ_TRY(refreshMeters(e));
-    CPQ_TRY(refreshOutStage(e));
-    return refreshDither(e);
+    return refreshBaseRateStages(e);
 }
 
 int32_t cpq_os_up_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nBase)
 {
-    const int rc = checkOsCall(e, dIn, dOut, nBase);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkOsCall(e, dIn, dOut, nBase));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueUp(e, dIn, nBase, dOut, (int64_t)nBase * e->osFactor, nBase);
 }
 
 int32_t cpq_os_down_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nBase)
 {
-    const int rc = checkOsCall(e, dIn, dOut, nBase);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkOsCall(e, dIn, dOut, nBase));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueDown(e, dIn, (int64_t)nBase * e->osFactor, dOut, nBase, nBase);
 }
 
 int32_t cpq_os_up(cpq_engine* e, const double* in, double* out, int32_t nBase)
 {
-    const size_t nOut = e ? (size_t)nBase * e->osFactor : 0;
-    return osHost(e, in, out, nBase, (size_t)nBase, nOut, [&](const double* a, double* b) {
-        return enqueueUp(e, a, nBase, b, (int64_t)nOut, nBase);
-    });
+    CPQ_TRY(checkOsCall(e, in, out, nBase));
+    const size_t nOut = (size_t)nBase * e->osFactor;
+    return hostRoundTrip(e, in, (size_t)nBase, out, nOut, false,
+                         [&](const double* a, double* b) { return enqueueUp(e, a, nBase, b, (int64_t)nOut, nBase); });
 }
 
 int32_t cpq_os_down(cpq_engine* e, const double* in, double* out, int32_t nBase)
 {
-    const size_t nIn = e ? (size_t)nBase * e->osFactor : 0;
-    return osHost(e, in, out, nBase, nIn, (size_t)nBase, [&](const double* a, double* b) {
-        return enqueueDown(e, a, (int64_t)nIn, b, nBase, nBase);
-    });
+    CPQ_TRY(checkOsCall(e, in, out, nBase));
+    const size_t nIn = (size_t)nBase * e->osFactor;
+    return hostRoundTrip(e, in, nIn, out, (size_t)nBase, false,
+                         [&](const double* a, double* b) { return enqueueDown(e, a, (int64_t)nIn, b, nBase, nBase); });
 }
 
 int32_t cpq_os_reset(cpq_engine* e)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
-    const int rc = resetOversampler(e);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(resetOversampler(e));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;
 }

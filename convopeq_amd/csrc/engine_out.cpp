@@ -2,7 +2,8 @@
 // is off (DSPCoreDouble.cpp:577-744): the 3 Hz output UltraHighRateDCBlocker, the kOutputHeadroom multiply with the scrub, the
 // SimplePeakLimiter and the hard clamp.  The kernels are in out_kernels.hip, the design in out_design.cpp; the host owns the
 // tables and the carried states (two one-pole states per channel, one envelope per stream).  The whole-chain call runs the
-// first two steps before the meters and the last two after them (engine_core.cpp, meteredChain).
+// first two steps before the meters and the last two after them (engine_core.cpp, meteredChain).  cpq_out_process takes the
+// refusals of checkBaseRows and the in-place hostRoundTrip, callbackLen and baseRate are the engine's (engine_internal.hpp).
 #include "engine_internal.hpp"
 
 namespace cpqi {
@@ -10,8 +11,6 @@ namespace cpqi {
 namespace {
 
 constexpr int kPreFlags = CPQ_OUT_DC_BLOCK | CPQ_OUT_HEADROOM, kPostFlags = CPQ_OUT_LIMITER | CPQ_OUT_CLAMP;
-
-int callbackLen(const cpq_engine* e) { return std::max(1, e->B / e->osFactor); }
 
 int resetOutStage(cpq_engine* e)
 {
@@ -26,16 +25,7 @@ int resetOutStage(cpq_engine* e)
 
 int checkRows(cpq_engine* e, const void* in, const void* out, int n)
 {
-    if (!e) return CPQ_ERR_INVALID_ARG;
-    if (!e->outFlags) return fail(e, CPQ_ERR_NOT_READY, "the output stage is off (cpq_engine_set_output_stage)");
-    if (!in || !out) return fail(e, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (n <= 0 || n > e->maxCall / e->osFactor)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, e->maxCall / e->osFactor);
-    if (!e->anyCalls && n % callbackLen(e) != 0)
-        return fail(e, CPQ_ERR_INVALID_ARG, "n_samples=%d is not a multiple of the callback length %d", n, callbackLen(e));
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(e, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
-    return CPQ_OK;
+    return checkBaseRows(e, in, out, n, e && e->outFlags, "the output stage is off (cpq_engine_set_output_stage)", true);
 }
 
 // both halves on rows of n samples; a half that is off copies nothing, so the first half that runs takes in -> out
@@ -56,7 +46,7 @@ int refreshOutStage(cpq_engine* e)
 {
     if (!e->outFlags) return CPQ_OK;
     double alpha[2], tab[2 * cpq::kOutSectionDoubles];
-    cpq::outDesign(e->sampleRate / e->osFactor, alpha, &e->outRelease);
+    cpq::outDesign(baseRate(e), alpha, &e->outRelease);
     cpq::outSectionTable(alpha[0], tab);
     cpq::outSectionTable(alpha[1], tab + cpq::kOutSectionDoubles);
     CPQ_TRY(resetOutStage(e));              // synchronises the stream: nothing in flight reads the tables
@@ -122,14 +112,8 @@ int32_t cpq_out_process_device(cpq_engine* e, const double* dIn, double* dOut, i
 int32_t cpq_out_process(cpq_engine* e, const double* in, double* out, int32_t nSamples)
 {
     CPQ_TRY(checkRows(e, in, out, nSamples));
-    CPQ_HIP(e, hipSetDevice(e->device));
-    CPQ_TRY(ensureCallBuffer(e, e->stageIn, "upload staging"));
-    const size_t bytes = sizeof(double) * (size_t)e->nCh * nSamples;
-    CPQ_HIP(e, hipMemcpyAsync(e->stageIn, in, bytes, hipMemcpyHostToDevice, e->stream));
-    CPQ_TRY(enqueueOutRows(e, e->stageIn, e->stageIn, nSamples));
-    CPQ_HIP(e, hipMemcpyAsync(out, e->stageIn, bytes, hipMemcpyDeviceToHost, e->stream));
-    CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    return CPQ_OK;
+    return hostRoundTrip(e, in, (size_t)nSamples, out, (size_t)nSamples, true,
+                         [&](const double* a, double* b) { return enqueueOutRows(e, a, b, nSamples); });
 }
 
 int32_t cpq_out_read_envelope(cpq_engine* e, int32_t stream, double* envelope)

@@ -1,7 +1,8 @@
 // engine_pcm.cpp -- packed PCM in and out (include/convopeq_mi355x.h): cpq_pcm_unpack / cpq_pcm_pack and the whole-chain call
 // with a converter at each end.  The host-pointer call is viaStaging's loop (stagedCall, engine_internal.hpp) with copies that
 // carry packed bytes: upload packed, unpack into the staging rows, the unchanged body, pack from the staging rows, download
-// packed.  Layout arithmetic: pcm_layout.hpp; kernels: pcm_kernels.hip.
+// packed.  Layout arithmetic: pcm_layout.hpp; kernels: pcm_kernels.hip.  cpq_pcm_unpack / cpq_pcm_pack keep their own
+// round trips: packed bytes on one side and, for the pack, rows that go up into stageOut -- hostRoundTrip would need both.
 #include "engine_internal.hpp"
 #include "pcm_layout.hpp"
 
@@ -9,8 +10,6 @@ using namespace cpqi;
 namespace pcm = cpq::pcm;
 
 namespace {
-
-int callbackLen(const cpq_engine* e) { return std::max(1, e->B / e->osFactor); }
 
 int checkFormat(cpq_engine* e, int format, int layout, bool output)
 {

@@ -42,8 +42,7 @@ int uploadProcParams(cpq_engine* e)
     CPQ_HIP(e, hipSetDevice(e->device));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     if (!e->procGains) {
-        const int rc = allocAll(e, { { e->procGains, (size_t)2 * S }, { e->procDelay, (size_t)S } }, "processor-level gain buffers could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { e->procGains, (size_t)2 * S }, { e->procDelay, (size_t)S } }, "processor-level gain buffers could not be allocated"));
     }
     // delay ring: the longest delay in sight (any IR that fits the engine: irPeakLatency < irLen) plus one call; a larger
     // request later grows it, keeping what it holds
@@ -51,8 +50,7 @@ int uploadProcParams(cpq_engine* e)
     if (need > e->dryRingSize) {
         const int size = nextPow2((int)std::min<int64_t>(need, (int64_t)1 << 30));
         DeviceBuffer<double> ring;
-        const int rc = allocAll(e, { { ring, (size_t)e->nCh * size, true } }, "dry delay line of %d samples per channel could not be allocated", size);
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { ring, (size_t)e->nCh * size, true } }, "dry delay line of %d samples per channel could not be allocated", size));
         if (e->dryRing) {
             cpq::launch_ring_regrow(e->stream, e->dryRing, e->dryRingSize, ring, size, e->dryPos, e->nCh);
             CPQ_HIP(e, hipStreamSynchronize(e->stream));
@@ -61,8 +59,7 @@ int uploadProcParams(cpq_engine* e)
         e->dryRingSize = size;
     }
     if (!e->latNew) {
-        const int rc = allocAll(e, { { e->latNew, (size_t)S }, { e->latOld, (size_t)S }, { e->latLen, (size_t)S } }, "latency buffers could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(allocAll(e, { { e->latNew, (size_t)S }, { e->latOld, (size_t)S }, { e->latLen, (size_t)S } }, "latency buffers could not be allocated"));
     }
     CPQ_HIP(e, hipMemcpy(e->procGains, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice));
     CPQ_HIP(e, hipMemcpy(e->procDelay, d.data(), sizeof(int) * d.size(), hipMemcpyHostToDevice));
@@ -71,7 +68,7 @@ int uploadProcParams(cpq_engine* e)
 
 int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
 {
-    if (!e->procGains) { const int rc = uploadProcParams(e); if (rc != CPQ_OK) return rc; }
+    if (!e->procGains) CPQ_TRY(uploadProcParams(e));
     {
         // feasibility first, before the ramp replay below consumes samples: resting ONE convolver needs that stream in a plan
         // group.  Which convolvers rest in THIS call is what the replay below will decide, asked of a copy of each ramp (a
@@ -122,10 +119,9 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     }
     if (anyRamp) {
         if (!e->mixRampLen) {
-            const int rc = allocAll(e, { { e->mixRampLen, (size_t)S } }, "mix-ramp buffers could not be allocated");
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(allocAll(e, { { e->mixRampLen, (size_t)S } }, "mix-ramp buffers could not be allocated"));
         }
-        { const int rc = grow(e, e->mixRampGains, e->mixRampCap, rampStride, (size_t)2 * S, "mix-ramp buffers could not be allocated"); if (rc != CPQ_OK) return rc; }
+        CPQ_TRY(grow(e, e->mixRampGains, e->mixRampCap, rampStride, (size_t)2 * S, "mix-ramp buffers could not be allocated"));
         CPQ_TRY(stageUpload(e, e->mixRampLen, mixRampLenHost.data(), sizeof(int) * S));
         CPQ_TRY(stageUpload(e, e->mixRampGains, rampHost.data(), sizeof(double) * rampHost.size()));
     }
@@ -145,8 +141,7 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     if (!allRest && (anyRest || !e->groups.empty()))
         for (int s = 0; s < S; ++s) {
             if (e->groupOf[(size_t)s] < 0) { if (rest[s]) return setStreamFrozen(e, s, true); continue; }     // reports why not
-            const int rc = setStreamFrozen(e, s, rest[s] != 0);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(setStreamFrozen(e, s, rest[s] != 0));
         }
     {
         std::vector<int> wetOn((size_t)S);
@@ -154,8 +149,7 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
         if (wetOn != e->procWetOnHost) {
             if (!e->procWetOn)
                 CPQ_TRY(allocAll(e, { { e->procWetOn, (size_t)S } }, "processor-level flags could not be allocated"));
-            const int rc = stageUpload(e, e->procWetOn, wetOn.data(), sizeof(int) * S);
-            if (rc != CPQ_OK) return rc;
+            CPQ_TRY(stageUpload(e, e->procWetOn, wetOn.data(), sizeof(int) * S));
             e->procWetOnHost = wetOn;
         }
     }
@@ -231,8 +225,7 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n)
     bool anyFadeValues = false;            // a fade of ONE value (a one-sample call) needs the buffer as well
     for (int r = 0; r < R; ++r) anyFadeValues = anyFadeValues || !xg[r].empty();
     if (anyFadeValues) {
-        const int rc = grow(e, e->latGains, e->latCap, xTotal + e->B, (size_t)S, "latency cross-fade buffer could not be allocated");
-        if (rc != CPQ_OK) return rc;
+        CPQ_TRY(grow(e, e->latGains, e->latCap, xTotal + e->B, (size_t)S, "latency cross-fade buffer could not be allocated"));
     }
     for (int r = 0; r < R; ++r) {
         const int off = ranges[r].c0 * e->B, len = std::min(ranges[r].c1 * e->B, n) - off;
@@ -308,8 +301,7 @@ int32_t cpq_engine_set_conv_level(cpq_engine* e, int32_t level)
 
 int32_t cpq_convproc_process_device(cpq_engine* e, const double* dIn, double* dOut, int32_t nSamples)
 {
-    const int rc = checkCall(e, dIn, dOut, nSamples);
-    if (rc != CPQ_OK) return rc;
+    CPQ_TRY(checkCall(e, dIn, dOut, nSamples));
     CPQ_HIP(e, hipSetDevice(e->device));
     return enqueueConvProc(e, dIn, dOut, nSamples);
 }
