@@ -53,6 +53,17 @@ CPQ_DITHER_FIXED4 = 1
 CPQ_DITHER_FIXED15 = 2
 CPQ_DITHER_ADAPTIVE9 = 4
 CPQ_DITHER_TILE = 64
+CPQ_SCORE_RNG_FRESH = 0
+CPQ_SCORE_RNG_CHAINED = 1
+CPQ_SCORE_SEGMENT_LEN = 4096
+CPQ_SCORE_MAX_SEGMENTS = 16
+CPQ_SCORE_RECENT = 4096 + 2048 * 15
+CPQ_SCORE_BINS = 2049
+CPQ_SCORE_MAX_CANDIDATES = 1024
+CPQ_SCORE_UNSTABLE = 1e18
+CPQ_SEGMENT_BROADBAND = 0
+CPQ_SEGMENT_TONAL = 1
+CPQ_SEGMENT_TRANSIENT = 2
 CPQ_PCM_F64 = 0
 CPQ_PCM_F32 = 1
 CPQ_PCM_S16 = 2
@@ -136,6 +147,21 @@ class OsTelemetry(C.Structure):
 class MeterBlock(C.Structure):
     _fields_ = [("mean_square", C.c_double), ("peak_linear", C.c_double), ("true_peak", C.c_double),
                 ("true_peak_hold", C.c_double), ("block_index", C.c_uint64)]
+
+
+class ScorerDesc(C.Structure):
+    _fields_ = [("n_learners", C.c_int32), ("max_candidates", C.c_int32), ("sample_rate_hz", C.c_double), ("bit_depth", C.c_int32),
+                ("level_weights", C.c_double * 4), ("coeff_safety_margin", C.c_double), ("stability_check", C.c_int32),
+                ("rng_mode", C.c_int32)]
+
+
+class ScoreParts(C.Structure):
+    _fields_ = [("noise_power", C.c_double), ("spectral_flatness_penalty", C.c_double), ("hf_penalty", C.c_double),
+                ("time_domain_rms", C.c_double), ("composite_score", C.c_double)]
+
+
+class ScoreSegment(C.Structure):
+    _fields_ = [("start", C.c_int32), ("level", C.c_int32), ("type", C.c_int32), ("reserved", C.c_int32), ("gain", C.c_double)]
 
 
 class EngineDesc(C.Structure):
@@ -274,6 +300,20 @@ SYMBOLS = {
                                   c_double_p, _i32p, _i32p, c_double_p, c_double_p, C.c_int32]),
     "cpq_diag_eq_chain_status": (C.c_int32, [_E, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "cpq_kernel_name": (C.c_char_p, [C.c_int32]),
+    "cpq_scorer_create": (C.c_int32, [C.POINTER(ScorerDesc), C.POINTER(C.c_void_p)]),
+    "cpq_scorer_destroy": (None, [C.c_void_p]),
+    "cpq_scorer_last_error": (C.c_char_p, [C.c_void_p]),
+    "cpq_scorer_set_audio": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int32, _i32p]),
+    "cpq_scorer_set_audio_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, _i32p]),
+    "cpq_scorer_get_segments": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(ScoreSegment), _i32p, _i32p]),
+    "cpq_scorer_read_thresholds": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_double_p]),
+    "cpq_scorer_score": (C.c_int32, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.POINTER(ScoreParts)]),
+    "cpq_scorer_score_raw": (C.c_int32, [C.c_void_p, c_double_p, C.c_int32, c_double_p, C.POINTER(ScoreParts)]),
+    "cpq_scorer_set_rng_start": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cpq_scorer_read_error": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p]),
+    "cpq_scorer_last_timing": (C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
+    "cpq_score_design": (C.c_int32, [C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, _i32p, _i32p, _i32p, c_double_p]),
+    "cpq_score_select_segments": (C.c_int32, [c_double_p, c_double_p, C.c_int32, C.POINTER(ScoreSegment), _i32p, _i32p]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@
 // nothing else fuses.  processStereoBlock's closing clampStateSIMD (+-1e12) cannot act on states advanceState already holds to
 // +-2 and is not built.
 #include "kernels.hpp"
+#include "lattice_device.hpp"
 
 namespace cpq {
 namespace {
@@ -33,23 +34,6 @@ constexpr int kDitherCpl = CPQ_DITHER_CPL;          // channels per lane (measur
 constexpr int kDitherRows = 64 * kDitherCpl;        // rows per wave
 constexpr int kDitherStep = kDitherTile / kDitherCpl;   // samples per tile: rows x (step + 1) doubles stay below 64 KiB of LDS
 constexpr int kDitherPitch = kDitherStep + 1;
-
-__device__ __forceinline__ unsigned long long dRotl(unsigned long long x, int k) { return (x << k) | (x >> (64 - k)); }
-
-__device__ __forceinline__ double dUniform(unsigned long long (&s)[4])
-{
-    const unsigned long long result = dRotl(s[0] + s[3], 23) + s[0];
-    const unsigned long long t = s[1] << 17;
-    s[2] ^= s[0];
-    s[3] ^= s[1];
-    s[1] ^= s[2];
-    s[0] ^= s[3];
-    s[2] ^= t;
-    s[3] = dRotl(s[3], 45);
-    return (double)(result >> 11) * (1.0 / 9007199254740992.0);
-}
-
-__device__ __forceinline__ double dFiniteOrZero(double v) { return fabs(v) < __builtin_huge_val() ? v : 0.0; }
 
 // the wave's rows x len samples from t0 on, into the tile and back: lane = sample
 __device__ __forceinline__ void dTileLoad(double* tile, const double* in, int64_t inStride, int row0, int rows, int t0, int len, int lane)
@@ -170,40 +154,6 @@ k_dither(const double* in, int64_t inStride, double* out, int64_t outStride, int
             for (int k = 0; k < 4; ++k) rng[(size_t)k * nCh + row0 + r] = s[c][k];
         }
     }
-}
-
-// LatticeNoiseShaper::processSample: x in, yq out; st, c and s are the channel's states, coefficients and generator
-__device__ __forceinline__ double dLatticeSample(double x, double (&st)[kLatticeOrder], const double (&c)[kLatticeOrder],
-                                                 unsigned long long (&s)[4], const DitherParams& p)
-{
-    // computeFeedback: lanes j = 0..3 of mul_pd then fmadd_pd, the horizontal add, then state[8] on its own
-    const double p0 = __builtin_fma(st[4], c[4], st[0] * c[0]);
-    const double p1 = __builtin_fma(st[5], c[5], st[1] * c[1]);
-    const double p2 = __builtin_fma(st[6], c[6], st[2] * c[2]);
-    const double p3 = __builtin_fma(st[7], c[7], st[3] * c[3]);
-    const double fb = ((p0 + p2) + (p1 + p3)) + st[8] * c[8];
-    const double y = x + fb;
-    double v = y;                                                           // quantize: a NaN passes both comparisons
-    if (v < -1.0) v = -1.0;
-    else if (v > p.maxV) v = p.maxV;
-    const double u1 = dUniform(s);
-    const double u2 = dUniform(s);
-    v += (u1 + u2 - 1.0) * p.scale;
-    const double q = __builtin_rint(v * p.invScale);
-    const double minQ = -p.invScale, maxQ = p.invScale - 1.0;
-    const double yq = (q < minQ ? minQ : (maxQ < q ? maxQ : q)) * p.scale;  // std::clamp: a NaN stays
-    const double lim = 2.0 * p.scale;
-    const double error = dFiniteOrZero(yq - y);
-    double f = error < -lim ? -lim : (lim < error ? lim : error);
-#pragma unroll
-    for (int i = 0; i < kLatticeOrder; ++i) {                               // advanceState
-        const double b = st[i];
-        const double nf = f + c[i] * b;
-        const double nb = c[i] * f + b;
-        st[i] = nb < -2.0 ? -2.0 : (2.0 < nb ? 2.0 : nb);
-        f = nf;
-    }
-    return yq;
 }
 
 // grid and rows as k_dither.  coef [kLatticeOrder][nCh]; the states are err's rows 0 .. kLatticeOrder - 1

@@ -11,6 +11,8 @@
 //   engine_dither.cpp  dither stage: the fixed 4- and 15-tap and the adaptive lattice noise shaper between the output stage's two halves
 //   engine_meter.cpp  loudness and true-peak metering of the delivered rows
 //   engine_diag.cpp  every cpq_diag_* entry point: single launchers on caller-filled buffers, no engine
+//   engine_score.cpp  cpq_scorer, an object of its own: the fitness function of the adaptive shaper's learner (uses only fail and
+//                    the device buffers of this header)
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per

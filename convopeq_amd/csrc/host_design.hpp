@@ -106,4 +106,42 @@ struct DitherHost {
     void process(double* l, double* r, int n, double headroom);
 };
 
+// shaper scorer (score_design.cpp): the deterministic host parts of NoiseShaperLearner's fitness function
+constexpr int kScoreLen = 4096;                 // AudioSegment::kLength = MklFftEvaluator::kFftLength
+constexpr int kScoreBins = kScoreLen / 2 + 1;   // kSpectrumBins
+constexpr int kScoreHop = kScoreLen / 2;        // kSegmentHop
+constexpr int kScoreLevels = 4, kScorePerLevel = 4, kScoreMaxSegments = kScoreLevels * kScorePerLevel;
+constexpr int kScoreRecent = kScoreLen + kScoreHop * (kScoreMaxSegments - 1);       // kRecentSampleRequest
+constexpr int kScoreBands = 24;                 // kBarkBandCount
+constexpr int kScoreSpreadBins = 1601;          // kSpreadTableBins
+constexpr int kScoreWordsPerSegment = 2 * kScoreLen;    // generator words one channel draws over one segment
+constexpr double kScoreLevelsDb[kScoreLevels] = { -40.0, -30.0, -20.0, -10.0 };    // kTargetLevelsDB
+// MklFftEvaluator::configureForSampleRate (src/MklFftEvaluator.h:143-242) and what evaluate() derives from it per bin
+struct ScoreTables {
+    double rate = 0.0;
+    std::vector<double> weight;         // weights[bin] * computeJndWeight(computeJndDb(freqHz[bin])): the factor of the psycho sum
+    std::vector<double> bark, athDb, athPow, width;     // barkHz, athThresholdDb, athThresholdPower, getBinWidth(bin)
+    std::vector<double> thrSpread;      // computeMaskingThreshold's dbToPower(-12 - 0.6 bark) at bin * binWidth
+    std::vector<int> band, range;       // binToBand, neighborRangeBins
+    std::vector<double> spreadTonal, spreadNoise;       // kSpreadTableTonal / kSpreadTableNoise
+    int bandStart[kScoreBands + 1] = {};        // bins of band b: [bandStart[b], bandStart[b + 1]); binToBand never decreases
+    int flatStart = 0, flatEnd = 0, highStart = 0, ultraStart = 0;
+    double ultraShare = 0.0, flatWeight = 0.35, hfWeight = 0.2;
+    double weightSum = 0.0;             // the psycho sum's psychoWeightSum, added bin after bin as evaluate() does
+};
+bool scoreTables(double rate, ScoreTables& t);   // false: binToBand is not monotonic (no rate above 1 Hz gives that)
+// buildTrainingSegments (src/NoiseShaperLearner.cpp:1185-1270) on the last min(n, kScoreRecent) samples, without the levelling
+// itself: which windows enter which level bucket, with what gain.  out is in evaluation order (level-major, then bucket order)
+struct ScoreSegment { int start, level, type; double gain, targetRms; };      // start counts from the first sample used; type: cpq_segment_type
+int scoreSelectSegments(const double* l, const double* r, int n, ScoreSegment out[kScoreMaxSegments], int counts[kScoreLevels]);
+// table[j][ch][4]: start[ch] advanced by j * kScoreWordsPerSegment draws, j < count
+void scoreRngTable(const unsigned long long start[2][4], int count, std::vector<unsigned long long>& table);
+// index into that table of segment s of nSeg of the candidate with c candidates run before it
+inline int scoreRngIndex(int mode, int c, int nSeg, int s) { return mode == CPQ_SCORE_RNG_CHAINED ? c * nSeg + s : s; }
+inline double scoreAlpha(int level) { return kScoreLevelsDb[level] < -30.0 ? 0.3 : kScoreLevelsDb[level] > -15.0 ? 0.7 : 0.5; }
+// LatticeNoiseShaper::isStable
+bool scoreStable(const double* k, int n);
+// evaluateCandidate's mapping: clampCoeff(std::tanh(raw[i]), margin)
+void scoreMapRaw(const double* raw, double margin, double out[kLatticeOrder]);
+
 }  // namespace cpq

@@ -290,4 +290,35 @@ constexpr int kPcmTile = 4096;     // samples of the packed side per workgroup: 
 bool launch_pcm_unpack(hipStream_t stream, const void* pcm, int format, int layout, double* rows, int n, int nStreams, int sanitizeCb);
 bool launch_pcm_pack(hipStream_t stream, const double* rows, void* pcm, int format, int layout, int n, int nStreams);
 
+// ---- shaper scorer (score_kernels.hip): NoiseShaperLearner::evaluateCandidateMapped for many learners and candidates at once.
+// Rows are kScoreLen doubles.  Nothing here checks an index: every table below is built by engine_score.cpp from validated counts.
+// one lattice chain (a lane): segment row read, error row written, coefficient set [9], generator start [4]
+struct ScoreChain { int src, dst, coef, rng; };
+// seg rows -> err rows: a fresh LatticeNoiseShaper (p: scale, invScale, maxV, headroom) over every chain, err = yq - x * headroom
+void launch_score_lattice(hipStream_t stream, const double* seg, double* err, const ScoreChain* chains, int nChains, const double* coef,
+                          const unsigned long long* rng, const DitherParams& p);
+// levelled segment rows of one learner: seg[row][i] = recent[row & 1][start[row >> 1] + i] * gain[row >> 1]; recent rows of
+// `stride` doubles
+void launch_score_level(hipStream_t stream, const double* recent, int64_t stride, const int* start, const double* gain, double* seg,
+                        int nSegments);
+// the per-bin tables of ScoreTables on the device, twiddles exp(-2 pi i k / 4096), k < 2048
+struct ScoreDeviceTables {
+    const double *weight, *bark, *athDb, *athPow, *width, *thrSpread, *spreadTonal, *spreadNoise;
+    const int *band, *range, *bandStart;
+    const double2* tw;
+    int flatStart, flatEnd, highStart, ultraStart;
+    double ultraShare, flatWeight, hfWeight, weightSum;
+};
+// one evaluation (a workgroup): rows 2 row and 2 row + 1 of `rows` are L and R; thr: the segment's masking thresholds row
+// (thresholds mode: the row written); slot: where parts and blended land; alpha: the level's blend factor
+struct ScoreEval { int row, thr, slot; double alpha; };
+// thresholdsOnly: precomputeMaskingThresholds of segment rows (thr written).  Otherwise MklFftEvaluator::evaluate of error rows:
+// parts[slot] and blended[slot] = alpha * sqrt(composite / 4096) * 1000 + (1 - alpha) * rms * 1000
+void launch_score_spectrum(hipStream_t stream, const double* rows, double* thr, const ScoreEval* evals, int nEvals,
+                           const ScoreDeviceTables& t, cpq_score_parts* parts, double* blended, bool thresholdsOnly);
+// per (learner, candidate) pair: state 1 -> CPQ_SCORE_UNSTABLE, no segments or no weight -> DBL_MAX, else the level-weighted mean
+// of the level means of blended[pair][16] (segments in evaluation order), counts [learner][4], in the reference's order
+void launch_score_reduce(hipStream_t stream, const double* blended, const int* counts, const int* state, int nLearners, int nCand,
+                         const double* levelWeights, double* scores);
+
 }  // namespace cpq

@@ -914,6 +914,110 @@ int32_t     cpq_diag_rows(int32_t op, int32_t n_ch, int32_t n, const double* src
  * hand-over ever ran into its poll bound (a defect: results of that launch are not valid).  For tests. */
 int32_t     cpq_diag_eq_chain_status(cpq_engine* e, uint32_t* launches, uint32_t* gave_up);
 
+/* ------------------------------------------------------- shaper scorer: the fitness function of the adaptive shaper's learner */
+/* cpq_scorer reproduces the deterministic part of NoiseShaperLearner (src/NoiseShaperLearner.cpp): configureForSampleRate,
+ * buildTrainingSegments with precomputeMaskingThresholds, evaluateCandidate / evaluateCandidateMapped, and
+ * MklFftEvaluator::evaluate / computeMaskingThreshold (src/MklFftEvaluator.h).  It is an object of its own, independent of
+ * cpq_engine, with the same device rules: CPQ_ERR_NO_DEVICE without a gfx950 device, no CPU fallback.  One scorer serves
+ * n_learners learners, each with its own training segments; one call scores every candidate of every learner.  The optimiser
+ * (CMA-ES), the capture queue and AudioSegmentBuffer, phases and modes, elite re-evaluation (call score again) and persistence
+ * are the caller's.  A scored set reaches the shaper through cpq_dither_set_adaptive_coeffs.
+ *
+ * Generator semantics.  reset() of the reference's shaper clears the lattice states and not the generator, so within one
+ * EvaluationContext the dither stream runs on across segments and candidates, and which worker scores which candidate is a race:
+ * the reference's population scores are not a function of their inputs.  Two deterministic modes are offered; segment s counts in
+ * evaluation order (level-major, then bucket order), a segment draws 8192 words per channel, and rng_start is
+ * LatticeNoiseShaper::rngState (src/LatticeNoiseShaper.h:297-300) unless cpq_scorer_set_rng_start changed it:
+ *   CPQ_SCORE_RNG_FRESH    every candidate is scored by a freshly constructed context: candidate c, segment s starts from
+ *                          rng_start advanced by 8192 * s words (the default)
+ *   CPQ_SCORE_RNG_CHAINED  one context scores candidates 0 .. C - 1 in order, the reference with no auxiliary workers:
+ *                          rng_start advanced by 8192 * (c' * n_segments + s) words, c' the number of candidates of that
+ *                          learner before c that ran: a set the stability check refuses is not run and draws nothing, so
+ *                          c' = c while every candidate is stable.
+ * Nothing is carried from one score call to the next.
+ * The 4096-point transform is the device's own (FFT parity unpinned: IPP's and the device's spectra differ by their own rounding
+ * only); sums over bins are tree-shaped; every data-dependent decision is the reference's comparison on the reference's quantity. */
+#define CPQ_HAS_SHAPER_SCORING 1
+#define CPQ_SCORE_RNG_FRESH   0
+#define CPQ_SCORE_RNG_CHAINED 1
+#define CPQ_SCORE_SEGMENT_LEN  4096     /* AudioSegment::kLength */
+#define CPQ_SCORE_MAX_SEGMENTS 16       /* kMaxTrainingSegments: 4 levels x 4 */
+#define CPQ_SCORE_RECENT (4096 + 2048 * 15)     /* kRecentSampleRequest */
+#define CPQ_SCORE_MAX_CANDIDATES 1024   /* per learner and call: the start-state table (16 entries of 8192 words a candidate,
+                                         * stepped on the host at create and set_rng_start) stays below a second of host work */
+#define CPQ_SCORE_UNSTABLE 1e18        /* evaluateCandidateMapped's penalty of a set isStable refuses */
+typedef enum { CPQ_SEGMENT_BROADBAND = 0, CPQ_SEGMENT_TONAL = 1, CPQ_SEGMENT_TRANSIENT = 2 } cpq_segment_type;   /* SpectralType */
+typedef struct cpq_scorer cpq_scorer;
+typedef struct {
+    int32_t n_learners;             /* >= 1 */
+    int32_t max_candidates;         /* 1 .. CPQ_SCORE_MAX_CANDIDATES; the reference's population is 18 */
+    double  sample_rate_hz;         /* finite, > 0: configureForSampleRate and precomputeMaskingThresholds */
+    int32_t bit_depth;              /* evaluationBitDepth, 1 .. 32 */
+    double  level_weights[4];       /* currentLevelWeights; reference default {0.4, 0.3, 0.2, 0.1}; finite, >= 0 */
+    double  coeff_safety_margin;    /* settings.coeffSafetyMargin (0.85), in (0, 1]: cpq_scorer_score_raw only */
+    int32_t stability_check;        /* settings.enableStabilityCheck (1) */
+    int32_t rng_mode;               /* CPQ_SCORE_RNG_* */
+} cpq_scorer_desc;
+typedef struct {                    /* MklFftEvaluator::Result (src/MklFftEvaluator.h:40-47) */
+    double noise_power, spectral_flatness_penalty, hf_penalty, time_domain_rms, composite_score;
+} cpq_score_parts;
+typedef struct {                    /* one LeveledSegment of a learner, in evaluation order */
+    int32_t start;                  /* first sample of the window, counted from the first of the samples used */
+    int32_t level;                  /* 0 .. 3: -40, -30, -20, -10 dBFS */
+    int32_t type;                   /* cpq_segment_type (crest factor > 5: transient, < 1.6: tonal) */
+    int32_t reserved;
+    double  gain;                   /* appliedGain: targetRMS / rms, or 0.95 / peak where that is smaller */
+} cpq_score_segment;
+/* CPQ_ERR_INVALID_ARG for a desc outside the ranges above or a null argument; CPQ_ERR_NO_DEVICE; CPQ_ERR_OOM. */
+int32_t cpq_scorer_create(const cpq_scorer_desc* desc, cpq_scorer** out);
+void    cpq_scorer_destroy(cpq_scorer* s);
+/* the text of the scorer's last refusal or failure ("" when there was none) */
+const char* cpq_scorer_last_error(const cpq_scorer* s);
+/* buildTrainingSegments (src/NoiseShaperLearner.cpp:1185-1270) of one learner on the most recent min(n, CPQ_SCORE_RECENT) of the
+ * samples given, replacing what the learner held: hop 2048, windows with RMS below 1e-5 gated out, gain limited by the peak
+ * headroom 0.95, targets -40 / -30 / -20 / -10 dBFS, a bucket full at 4.  The selection runs on the host in the reference's order;
+ * the levelling multiply and precomputeMaskingThresholds (:1377-1398: transform of the levelled segment, computeMaskingThreshold
+ * per bin) run on the device and stay there.  *n_segments (may be NULL) = segments held afterwards; n < 4096 gives 0 and CPQ_OK.
+ * The _device variant takes device pointers (the selection reads a copy).  CPQ_ERR_INVALID_ARG: learner out of range, n < 0,
+ * a null row with n > 0. */
+int32_t cpq_scorer_set_audio(cpq_scorer* s, int32_t learner, const double* left, const double* right, int32_t n, int32_t* n_segments);
+int32_t cpq_scorer_set_audio_device(cpq_scorer* s, int32_t learner, const double* d_left, const double* d_right, int32_t n, int32_t* n_segments);
+/* segments[0 .. *n_segments - 1] of a learner (room for CPQ_SCORE_MAX_SEGMENTS) and counts[4] per level; either may be NULL */
+int32_t cpq_scorer_get_segments(const cpq_scorer* s, int32_t learner, cpq_score_segment* segments, int32_t* n_segments, int32_t counts[4]);
+/* thresholds[2049] = LeveledSegment::maskingThresholds of segment `segment` (evaluation order) of a learner.  Synchronises. */
+int32_t cpq_scorer_read_thresholds(cpq_scorer* s, int32_t learner, int32_t segment, double* thresholds);
+/* evaluateCandidateMapped (src/NoiseShaperLearner.cpp:1289-1375) for every learner and candidate: mapped [n_learners]
+ * [n_candidates][9] reflection coefficients, scores [n_learners][n_candidates], parts (may be NULL) [n_learners][n_candidates]
+ * [16] per segment in evaluation order, zero where nothing was evaluated.  1 <= n_candidates <= max_candidates.  Per candidate:
+ * with the stability check on, a set isStable refuses (some |k| >= 1 - 1e-12) scores CPQ_SCORE_UNSTABLE and is not run; otherwise
+ * a fresh shaper (prepare(bit_depth), setCoefficients: clampCoeff to +-0.85) runs every segment from cleared states with headroom
+ * 0.8912509381337456, the error yq - x * headroom goes through evaluate() with the segment's masking thresholds, and the score is
+ * sum_level(w_level * mean_segments(alpha * sqrt(composite / 4096) * 1000 + (1 - alpha) * rms * 1000)) / sum_level(w_level) over
+ * the levels that hold segments, alpha 0.3 / 0.5 / 0.5 / 0.7.  A learner without segments (or with zero total weight) scores
+ * DBL_MAX.  The lattice stage is bit-exact; the rest differs from the reference by rounding alone.  Host pointers; synchronises. */
+int32_t cpq_scorer_score(cpq_scorer* s, const double* mapped, int32_t n_candidates, double* scores, cpq_score_parts* parts);
+/* evaluateCandidate (:1272-1287): mapped = clampCoeff(tanh(raw), coeff_safety_margin) on the host with std::tanh, then the above.
+ * The reference's population path maps with MKL's vdTanh, which may differ from std::tanh in the last place: cpq_scorer_score is
+ * the exact entry point. */
+int32_t cpq_scorer_score_raw(cpq_scorer* s, const double* raw, int32_t n_candidates, double* scores, cpq_score_parts* parts);
+/* the two generator states (L, R) every evaluation counts from; rebuilds the start-state tables.  Acts on the next score call. */
+int32_t cpq_scorer_set_rng_start(cpq_scorer* s, const uint64_t state[2][4]);
+/* Diagnostic: the error rows (4096 doubles each; either may be NULL) the lattice stage of the last score call stored for one
+ * (learner, candidate, segment).  CPQ_ERR_NOT_READY when that call did not run this chain (no call yet, candidate refused or
+ * beyond its n_candidates, segment beyond the learner's). */
+int32_t cpq_scorer_read_error(cpq_scorer* s, int32_t learner, int32_t candidate, int32_t segment, double* left, double* right);
+/* Diagnostic: events around the two stages of the last score call, in milliseconds */
+int32_t cpq_scorer_last_timing(cpq_scorer* s, double* lattice_ms, double* spectrum_ms);
+/* configureForSampleRate on the host, for tests and tuning: any of the outputs may be NULL.  weight[2049] = weights[bin] *
+ * jndWeight(bin), bark / ath_db / width (getBinWidth) [2049], band / range (binToBand, neighborRangeBins) [2049], bins[4] =
+ * flatnessStartBin, flatnessEndBin, highBandStartBin, ultraHighStartBin, scalars[4] = expectedUltraHighShare,
+ * flatnessPenaltyWeight, hfPenaltyWeight, sum of weight. */
+int32_t cpq_score_design(double sample_rate_hz, double* weight, double* bark, double* ath_db, double* width, int32_t* band,
+                         int32_t* range, int32_t bins[4], double scalars[4]);
+/* buildTrainingSegments' selection alone, on the host: as cpq_scorer_get_segments after cpq_scorer_set_audio would report */
+int32_t cpq_score_select_segments(const double* left, const double* right, int32_t n, cpq_score_segment* segments,
+                                  int32_t* n_segments, int32_t counts[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -409,4 +409,47 @@ private:
     int status_ = CPQ_OK;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// The fitness function of the adaptive shaper's learner (NoiseShaperLearner::buildTrainingSegments, evaluateCandidate,
+// evaluateCandidateMapped; MklFftEvaluator::evaluate) for nLearners learners at once; independent of Engine.  The optimiser,
+// the capture queue and persistence are the caller's.
+class ShaperScorer {
+public:
+    explicit ShaperScorer(const cpq_scorer_desc& desc) { status_ = cpq_scorer_create(&desc, &s_); }
+    // the reference's settings: 18 candidates, level weights {0.4, 0.3, 0.2, 0.1}, margin 0.85, stability check on
+    static cpq_scorer_desc defaults(int nLearners, double sampleRateHz, int evaluationBitDepth)
+    {
+        return cpq_scorer_desc{ nLearners, 18, sampleRateHz, evaluationBitDepth, { 0.4, 0.3, 0.2, 0.1 }, 0.85, 1, CPQ_SCORE_RNG_FRESH };
+    }
+    ~ShaperScorer() { cpq_scorer_destroy(s_); }
+    ShaperScorer(const ShaperScorer&) = delete;
+    ShaperScorer& operator=(const ShaperScorer&) = delete;
+    bool valid() const noexcept { return s_ != nullptr; }
+    // the learner's segments from the most recent samples (what AudioSegmentBuffer::copyLatest returns); returns their number
+    int buildTrainingSegments(int learner, const double* left, const double* right, int numSamples)
+    {
+        int32_t n = 0;
+        status_ = cpq_scorer_set_audio(s_, learner, left, right, numSamples, &n);
+        return status_ == CPQ_OK ? n : 0;
+    }
+    // mapped [nLearners][numCandidates][9] -> scores [nLearners][numCandidates]; parts may be null
+    bool evaluateCandidateMapped(const double* mapped, int numCandidates, double* scores, cpq_score_parts* parts = nullptr)
+    {
+        return (status_ = cpq_scorer_score(s_, mapped, numCandidates, scores, parts)) == CPQ_OK;
+    }
+    // the same from raw optimiser coordinates: tanh and clampCoeff(k, coeffSafetyMargin) first
+    bool evaluateCandidate(const double* raw, int numCandidates, double* scores, cpq_score_parts* parts = nullptr)
+    {
+        return (status_ = cpq_scorer_score_raw(s_, raw, numCandidates, scores, parts)) == CPQ_OK;
+    }
+    bool setRngStart(const uint64_t state[2][4]) { return (status_ = cpq_scorer_set_rng_start(s_, state)) == CPQ_OK; }
+    cpq_scorer* get() const noexcept { return s_; }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return cpq_scorer_last_error(s_); }
+
+private:
+    cpq_scorer* s_ = nullptr;
+    int status_ = CPQ_OK;
+};
+
 }  // namespace cpq

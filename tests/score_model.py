@@ -1,0 +1,514 @@
+"""numpy restatement of the shaper scorer (convopeq_amd/csrc/score_design.cpp, score_kernels.hip): the deterministic part of the
+reference's NoiseShaperLearner -- configureForSampleRate, buildTrainingSegments with precomputeMaskingThresholds,
+evaluateCandidateMapped, MklFftEvaluator::evaluate -- in the reference's operation order, with numpy's FFT and the host's libm.
+
+evaluate() branches on comparisons.  evaluate() here also reports, per evaluation, the smallest distance of any data-dependent
+comparison from its threshold (Result.margin), each relative to the threshold itself:
+    peak test         avg > 6 localAvg                    |avg - 6 localAvg| / (6 localAvg)
+    tonal test        centerDb - neighbourDb >= 7         a peak: the closest neighbour; no peak: the clearest failure; / 7
+    spread cut        |bark_i - masker.bark| > 8          ||delta| - 8| / 8
+    spread table      round(delta / 0.01 + 800)           distance of the index from the half-way point, in table steps
+Comparisons on tables alone (the 0.5-Bark absorb radius, band membership, the bin ranges) are made on the same bits everywhere.
+sumEnergy <= 1e-24, count <= 0 and the caps of 128 are reported as Result.caps: a case that comes near them is not recorded."""
+import ctypes
+import ctypes.util
+import math
+
+import numpy as np
+
+from dither_model import SEEDS4
+
+LEN, BINS, HOP, LEVELS, PER_LEVEL, MAX_SEG = 4096, 2049, 2048, 4, 4, 16
+RECENT = LEN + HOP * (MAX_SEG - 1)
+LEVELS_DB = (-40.0, -30.0, -20.0, -10.0)
+WEIGHTS = (0.4, 0.3, 0.2, 0.1)
+H = 0.8912509381337456
+MIN_POWER = 1.0e-24
+DB_PER_LN = 10.0 * 0.43429448190325182765
+FRESH, CHAINED = 0, 1
+UNSTABLE = 1e18
+D_REF = 2.5e-14           # measured 2.41e-14: RESULTS.md, "shaper scorer" (the model against the recorded reference, members and scores)
+GPU_BAR = max(8.0 * D_REF, 2049.0 * 2.0 ** -52)
+# the model's masking thresholds against the recorded ones, largest relative deviation per run (RESULTS.md): not part of D_REF.
+# C16 is two tones over a noise floor far below them, so most of its bins hold leakage and with it the transform's own rounding
+D_THR = {"A16": 1.2e-14, "B24": 2.0e-15, "C16": 2.6e-13}
+
+
+def deviation(got, want):
+    """[.., 5] Result members: relative, but absolute (natural scale 1) for the two penalties, which are differences of
+    near-equal quantities near 0, and for a member recorded as exactly 0"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    scale = np.abs(want)
+    scale[..., 1:3] = 1.0
+    return np.abs(got - want) / np.where(scale == 0.0, 1.0, scale)
+
+_libm = ctypes.CDLL(ctypes.util.find_library("m"))
+_libm.fma.restype = ctypes.c_double
+_libm.fma.argtypes = [ctypes.c_double] * 3
+_fma = np.frompyfunc(_libm.fma, 3, 1)          # a correctly rounded fused multiply-add, element by element
+
+
+def fma(a, b, c):
+    return _fma(a, b, c).astype(np.float64)
+
+
+def alpha(level):
+    return 0.3 if LEVELS_DB[level] < -30.0 else 0.7 if LEVELS_DB[level] > -15.0 else 0.5
+
+
+# ---------------------------------------------------------------- configureForSampleRate
+def _pow(a, b):
+    try:
+        return math.pow(a, b)
+    except OverflowError:           # std::pow returns +inf (the threshold in quiet above 40 kHz)
+        return math.inf
+
+
+def _bark(f):
+    f = max(0.0, f)
+    return 13.0 * math.atan(0.00076 * f) + 3.5 * math.atan(math.pow(f / 7500.0, 2.0))
+
+
+def _ath_spl(f):
+    k = max(0.01, f / 1000.0)
+    f2 = k * k
+    return 3.64 * math.pow(k, -0.8) + -6.5 * math.exp(-0.6 * math.pow(k - 3.3, 2.0)) + 0.001 * f2 * f2
+
+
+def _spread_table(down):
+    t = np.empty(1601)
+    for i in range(1601):
+        d = -8.0 + float(i) * 0.01
+        if d >= 0.0:
+            t[i] = -27.0 * d
+        else:
+            x = d + 0.474
+            t[i] = (15.81 + 7.5 * x - 17.5 * math.sqrt(1.0 + (x * x))) + (down + 27.0) * abs(d)
+    return t
+
+
+class Tables:
+    def __init__(self, rate):
+        rate = max(1.0, rate)
+        nyq = 0.5 * rate
+        bw = nyq / float(BINS - 1)
+        to_bin = lambda hz: min(max(int(math.floor(hz / bw + 0.5)) if hz / bw >= 0 else int(math.ceil(hz / bw - 0.5)), 0), BINS - 1)
+        self.rate, self.flat_weight = rate, 0.35
+        self.hf_weight = min(max(0.20 * math.sqrt(48000.0 / rate), 0.05), 0.20)
+        fs, fe = min(12000.0, nyq * 0.60), min(18000.0, nyq * 0.82)
+        if fe <= fs + (bw * 8.0):
+            fs, fe = nyq * 0.50, nyq * 0.80
+        self.flat_start = to_bin(fs)
+        self.flat_end = max(self.flat_start + 1, to_bin(fe))
+        hs = max(14000.0, nyq * 0.60)
+        if hs >= nyq:
+            hs = nyq * 0.60
+        us = nyq * 0.85
+        if us <= hs + (bw * 8.0):
+            us = hs + (bw * 8.0)
+        self.high_start = to_bin(hs)
+        self.ultra_start = max(self.high_start + 1, to_bin(us))
+        self.ultra_share = float(max(1, BINS - self.ultra_start)) / float(max(1, BINS - self.high_start))
+        step = max(1.0e-9, _bark(nyq) / 24.0)
+        self.freq = np.array([float(b) * bw for b in range(BINS)])
+        self.bark, self.ath_db, self.ath_pow, self.weight, self.thr_spread = (np.empty(BINS) for _ in range(5))
+        self.band, self.range = np.empty(BINS, dtype=np.int32), np.empty(BINS, dtype=np.int32)
+        self.weight_sum = 0.0
+        for b in range(BINS):
+            f = float(self.freq[b])
+            bark = _bark(f)
+            ath = _ath_spl(f) - 90.0 + 0.0
+            self.bark[b], self.ath_db[b], self.ath_pow[b] = bark, ath, _pow(10.0, ath / 10.0)
+            k = max(0.0, f / 1000.0)
+            self.range[b] = min(max(int((25.0 + 75.0 * math.pow(1.0 + 1.4 * k * k, 0.69)) / max(1.0, bw) * 0.5), 1), 24)
+            self.band[b] = min(max(int(bark / step), 0), 23)
+            g = max(f, 1.0)
+            g2 = g * g
+            h1 = -4.737338981378384e-24 * g2 * g2 * g2 + 2.043828333606125e-15 * g2 * g2 - 1.363894795463638e-7 * g2 + 1.0
+            h2 = 1.306612257402824e-19 * g2 * g2 * g - 2.118150887541247e-11 * g2 * g + 5.559488023498642e-4 * g
+            r = (1.246332637532143e-4 * g) / math.sqrt(h1 * h1 + h2 * h2)
+            w = r * r
+            if g > 18000.0:
+                ro = math.pow(10.0, -12.0 * (g - 18000.0) / max(1000.0, nyq - 18000.0) / 20.0)
+                w *= ro * ro
+            w = max(1.0e-6, w)
+            jnd = min(max(0.5 + 1.0 * math.exp(-0.5 * (k - 0.5) * (k - 0.5)) + 0.2 * (k - 3.0) * (k - 3.0), 0.5), 3.0)
+            self.weight[b] = w * (1.0 / max(1.0e-6, jnd + 0.3))
+            self.weight_sum += float(self.weight[b])
+            self.thr_spread[b] = math.pow(10.0, (-12.0 - (0.6 * bark)) / 10.0)
+        self.width = np.empty(BINS)
+        self.width[1:-1] = 0.5 * (self.freq[2:] - self.freq[:-2])
+        self.width[0], self.width[-1] = self.freq[1] - self.freq[0], self.freq[-1] - self.freq[-2]
+        self.spread = (_spread_table(-24.0), _spread_table(-27.0))
+
+
+# ---------------------------------------------------------------- buildTrainingSegments
+def select_segments(left, right):
+    """-> ([(start, level, type, gain)] in evaluation order, counts per level); start counts from the first sample used"""
+    n = len(left)
+    usable = min(n, RECENT)
+    counts = [0] * LEVELS
+    if usable < LEN:
+        return [], counts
+    l, r = np.asarray(left[n - usable:], dtype=np.float64), np.asarray(right[n - usable:], dtype=np.float64)
+    buckets = [[] for _ in range(LEVELS)]
+    total, start = 0, 0
+    while start + LEN <= usable and total < MAX_SEG:
+        a, b = l[start:start + LEN], r[start:start + LEN]
+        sum_squares = 0.0
+        for v in (0.5 * (a * a + b * b)).tolist():      # sequential, as the reference adds
+            sum_squares += v
+        peak = float(max(np.abs(a).max(), np.abs(b).max()))
+        rms = math.sqrt(sum_squares / float(LEN))
+        if rms >= 1.0e-5:
+            crest = peak / rms if rms > 1e-9 else 1.0
+            kind = 2 if crest > 5.0 else 1 if crest < 1.6 else 0
+            for lv in range(LEVELS):
+                if counts[lv] < PER_LEVEL:
+                    gain = math.pow(10.0, LEVELS_DB[lv] / 20.0) / rms
+                    if peak * gain > 0.95:
+                        gain = 0.95 / peak
+                    buckets[lv].append((start, lv, kind, gain))
+                    counts[lv] += 1
+                    total += 1
+        start += HOP
+    return [s for b in buckets for s in b], counts
+
+
+def level(left, right, seg):
+    """the levelled rows [2, 4096] of one segment"""
+    n = len(left)
+    o = n - min(n, RECENT) + seg[0]
+    return np.stack([np.asarray(left[o:o + LEN]) * seg[3], np.asarray(right[o:o + LEN]) * seg[3]])
+
+
+def power_spectrum(rows):
+    """0.5 (|L|^2 + |R|^2) of rows [2, 4096], without the clamp"""
+    s = np.fft.rfft(rows, axis=1)
+    m = s.real * s.real + s.imag * s.imag
+    return 0.5 * (m[0] + m[1])
+
+
+def masking_thresholds(rows, t):
+    return np.maximum(t.ath_pow, np.maximum(power_spectrum(rows), MIN_POWER) * t.thr_spread)
+
+
+def threshold_deviation(got, want, t):
+    """masking thresholds [2049] against recorded ones: (the bins where the recording is the threshold in quiet are the same
+    bits, largest relative deviation over the other bins).  A threshold above the floor is one bin's power times a table entry,
+    so its relative deviation is the transform's in that bin: D_REF, which is taken over Result members and scores, does not
+    cover it.  The model's own figures against the recording are D_THR below; both sides are held to GPU_BAR."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    floor = want == t.ath_pow
+    return bool(np.array_equal(got[floor], want[floor])), float(np.abs(got[~floor] / want[~floor] - 1.0).max())
+
+
+# ---------------------------------------------------------------- the generator
+_M = (1 << 64) - 1
+
+
+def _step(s):
+    t = (s[1] << 17) & _M
+    s[2] ^= s[0]
+    s[3] ^= s[1]
+    s[1] ^= s[2]
+    s[0] ^= s[3]
+    s[2] ^= t
+    s[3] = ((s[3] << 45) | (s[3] >> 19)) & _M
+
+
+_RNG_CACHE = {}
+
+
+def rng_table(count, start=SEEDS4):
+    """[count][2][4]: start advanced by 8192 j draws, word by word"""
+    key = tuple(tuple(int(v) for v in ch) for ch in start)
+    have = _RNG_CACHE.setdefault(key, [])
+    if not have:
+        have.append([list(ch) for ch in key])
+    while len(have) < count:
+        nxt = [list(ch) for ch in have[-1]]
+        for ch in nxt:
+            for _ in range(2 * LEN):
+                _step(ch)
+        have.append(nxt)
+    return np.array(have[:count], dtype=np.uint64)
+
+
+def rng_index(mode, c, n_seg, s):
+    return c * n_seg + s if mode == CHAINED else s
+
+
+# ---------------------------------------------------------------- the lattice stage
+def clamp_coeffs(k):
+    return [0.0 if not math.isfinite(v) else 0.85 if v > 0.85 else -0.85 if v < -0.85 else float(v) for v in k]
+
+
+def is_stable(k):
+    return all(not (abs(v) >= 1.0 - 1e-12) for v in k)
+
+
+def lattice_errors(rows, coef, rng, bits, n=LEN, peak=None):
+    """rows [chains, >= n] levelled input, coef [chains, 9] (clamped), rng [chains, 4] uint64 -> error rows yq - x H [chains, n];
+    fresh states.  LatticeNoiseShaper::processSample, as tests/lattice_model.py states it; peak: list that receives max |state|"""
+    rows = np.asarray(rows, dtype=np.float64)
+    c = np.ascontiguousarray(np.asarray(coef, dtype=np.float64).T)
+    s = [np.array(rng[:, k], dtype=np.uint64) for k in range(4)]
+    st = np.zeros_like(c)
+    inv = math.ldexp(1.0, bits - 1)
+    sc = 1.0 / inv
+    max_v, lim = 1.0 - (1.0 / inv), 2.0 * sc
+    out = np.empty((rows.shape[0], n))
+    top = 0.0
+
+    def uniform():
+        result = (((s[0] + s[3]) << np.uint64(23)) | ((s[0] + s[3]) >> np.uint64(41))) + s[0]
+        t = s[1] << np.uint64(17)
+        s[2] ^= s[0]
+        s[3] ^= s[1]
+        s[1] ^= s[2]
+        s[0] ^= s[3]
+        s[2] ^= t
+        s[3] = (s[3] << np.uint64(45)) | (s[3] >> np.uint64(19))
+        return (result >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+    with np.errstate(over="ignore"):
+        for i in range(n):
+            xh = rows[:, i] * H
+            p = [fma(st[4 + j], c[4 + j], st[j] * c[j]) for j in range(4)]
+            y = xh + (((p[0] + p[2]) + (p[1] + p[3])) + st[8] * c[8])
+            v = np.where(y < -1.0, -1.0, np.where(y > max_v, max_v, y))
+            u1 = uniform()
+            u2 = uniform()
+            v = v + (u1 + u2 - 1.0) * sc
+            q = np.rint(v * inv)
+            yq = np.where(q < -inv, -inv, np.where(inv - 1.0 < q, inv - 1.0, q)) * sc
+            e = yq - y
+            e = np.where(np.isfinite(e), e, 0.0)
+            f = np.where(e < -lim, -lim, np.where(lim < e, lim, e))
+            for k in range(9):
+                b = st[k].copy()
+                nf = f + c[k] * b
+                nb = c[k] * f + b
+                st[k] = np.where(nb < -2.0, -2.0, np.where(2.0 < nb, 2.0, nb))
+                f = nf
+            if peak is not None:
+                top = max(top, float(np.abs(st).max()))
+            out[:, i] = yq - xh
+    if peak is not None:
+        peak.append(top)
+    return out
+
+
+def lattice_model_errors(rows, coef, rng, bits):
+    """the same chains (an even number) through tests/lattice_model.py, whose rows are the reference's bit for bit: every chain
+    a channel of its Lattice.  Its fused terms are exact rationals, so it is slow: about 50 us a chain and sample"""
+    import lattice_model as L
+    st = L.Lattice(len(rows) // 2, bits)
+    st.coef[:] = np.asarray(coef, dtype=np.float64).T
+    st.rng = np.ascontiguousarray(np.asarray(rng, dtype=np.uint64).T)
+    st.reset()
+    rows = np.asarray(rows, dtype=np.float64)
+    return st.process(rows, H) - rows * H
+
+
+# ---------------------------------------------------------------- MklFftEvaluator::evaluate
+class Result:
+    MEMBERS = ("noise_power", "spectral_flatness_penalty", "hf_penalty", "time_domain_rms", "composite_score")
+
+    def array(self):
+        return np.array([getattr(self, m) for m in self.MEMBERS])
+
+
+def _db(p):
+    return np.log(np.maximum(p, MIN_POWER)) * DB_PER_LN
+
+
+def evaluate(err, thr, t):
+    """err [2, 4096], thr [2049] or None -> Result with .margin and .caps"""
+    res = Result()
+    margin = math.inf
+    sum_sq = 0.0
+    for v in (0.5 * (err[0] * err[0] + err[1] * err[1])).tolist():
+        sum_sq += v
+    res.time_domain_rms = math.sqrt(sum_sq / LEN)
+    raw = power_spectrum(err)
+    power = np.maximum(MIN_POWER, raw)
+    safe = power + MIN_POWER
+    total = float(np.sum(power))
+    fl = slice(t.flat_start, min(t.flat_end, BINS - 1) + 1)
+    flat_bins = fl.stop - fl.start
+    flat_log, flat_pow = float(np.sum(np.log(safe[fl]))), float(np.sum(safe[fl]))
+    high, ultra = float(np.sum(power[t.high_start:])), float(np.sum(power[t.ultra_start:]))
+    local = 0.5 * (raw[:-2] + raw[2:]) + MIN_POWER
+    inner = power[1:-1]
+    is_pk = inner > 6.0 * local
+    peak = float(inner[is_pk].max()) if is_pk.any() else 0.0
+    margin = min(margin, float(np.min(np.abs(inner - 6.0 * local) / (6.0 * local))))
+
+    pdb = _db(power)
+    consumed = np.zeros(BINS, dtype=bool)
+    maskers = []                                    # (levelDb with the noise correction, bark, type)
+    n_tonal_found, min_energy = 0, math.inf
+    ks = np.arange(1, 25)
+    bins = np.arange(BINS)
+    deltas = []
+    for side in (-1, 1):
+        at = bins[:, None] + side * ks[None, :]
+        valid = (at >= 0) & (at < BINS) & (ks[None, :] <= t.range[:, None])
+        deltas.append(np.where(valid, pdb[:, None] - pdb[np.clip(at, 0, BINS - 1)], np.inf))
+    closest = np.concatenate(deltas, axis=1).min(axis=1)[3:BINS - 3]       # a peak: the closest neighbour; else the clearest failure
+    margin = min(margin, float(np.min(np.abs(closest - 7.0) / 7.0)))
+    for i in (np.nonzero(closest >= 7.0)[0] + 3).tolist():
+        sum_e = sum_bw = 0.0
+        for j in range(max(0, i - 8), min(BINS - 1, i + 8) + 1):
+            if abs(t.bark[j] - t.bark[i]) > 0.5:
+                continue
+            e = float(power[j]) * float(t.width[j])
+            sum_e += e
+            sum_bw += float(t.bark[j]) * e
+            consumed[j] = True
+        min_energy = min(min_energy, sum_e)
+        if sum_e <= MIN_POWER:
+            continue
+        n_tonal_found += 1
+        if len(maskers) < 128:
+            maskers.append((float(_db(np.float64(sum_e))), sum_bw / sum_e, 0))
+    for band in range(24):
+        sel = (t.band == band) & ~consumed
+        count = int(sel.sum())
+        e = power[sel] * t.width[sel]
+        sum_e = float(np.sum(e))
+        if count <= 0 or sum_e <= MIN_POWER:
+            continue
+        min_energy = min(min_energy, sum_e)
+        pf = np.maximum(power[sel], 1.0e-15)
+        sfm = math.exp(float(np.sum(np.log(pf))) / float(count)) / max(float(np.sum(pf)) / float(count), 1.0e-15)
+        tonality = min(max(-0.299 + (-0.43 * math.log(max(sfm, 1.0e-12)) * 0.43429448190325182765), 0.0), 1.0)
+        if len(maskers) < 128:
+            maskers.append((float(_db(np.float64(sum_e))) + (-5.0 * (1.0 - tonality)), float(np.sum(t.bark[sel] * e)) / sum_e, 1))
+    res.caps = {"tonal": n_tonal_found, "maskers": len(maskers), "min_energy": min_energy}
+
+    masking = t.ath_pow.copy()
+    if maskers:
+        lv = np.array([m[0] for m in maskers])
+        mb = np.array([m[1] for m in maskers])
+        ty = np.array([m[2] for m in maskers])
+        d = t.bark[:, None] - mb[None, :]                           # [bin, masker]
+        near = ~(np.abs(d) > 8.0)
+        margin = min(margin, float(np.min(np.abs(np.abs(d) - 8.0) / 8.0)))
+        idx = (d / 0.01) + 800.0
+        ii = np.where(idx >= 0.0, np.floor(idx + 0.5), np.ceil(idx - 0.5)).astype(np.int64)     # std::round
+        margin = min(margin, float(np.min(np.abs(np.abs(idx[near] - np.floor(idx[near])) - 0.5))))
+        ok = (ii >= 0) & (ii < 1601)
+        ic = np.clip(ii, 0, 1600)
+        sp = np.where(ok, np.where(ty[None, :] == 0, t.spread[0][ic], t.spread[1][ic]), 0.0)
+        tot = np.where(near, lv[None, :] + sp, -np.inf)
+        mx = tot.max(axis=1)
+        has = np.isfinite(mx)
+        ex = np.where(near, np.exp((tot - np.where(has, mx, 0.0)[:, None]) * 0.2302585093), 0.0)
+        sm = np.zeros(BINS)
+        for j in range(len(maskers)):                               # in masker order, as the reference adds
+            sm = sm + ex[:, j]
+        masking = np.where(has, np.maximum(np.exp(mx * 0.2302585093) * sm, t.ath_pow), t.ath_pow)
+    thr_db = np.maximum(_db(masking), t.ath_db)
+    if thr is not None:
+        thr_db = np.maximum(thr_db, _db(np.maximum(thr, MIN_POWER)))
+    delta = pdb - thr_db
+    z = 2.0 * delta
+    with np.errstate(over="ignore"):
+        soft = np.where(z > 50.0, delta, np.where(z < -50.0, np.exp(z) / 2.0, np.log1p(np.exp(z)) / 2.0))
+    eff = 20.0 * np.tanh(soft / 20.0)
+    eff_pow = np.maximum(0.0, np.power(10.0, eff / 10.0) - 1.0)
+    psycho = float(np.sum(t.weight * eff_pow))
+    res.noise_power = (psycho / t.weight_sum) * float(LEN) if t.weight_sum > MIN_POWER else 0.0
+    flat = min(max(math.exp(flat_log / float(flat_bins)) / max(flat_pow / float(flat_bins), MIN_POWER), 0.0), 1.0)
+    res.spectral_flatness_penalty = 1.0 - flat
+    res.hf_penalty = max(0.0, ultra / max(high + MIN_POWER, MIN_POWER) - t.ultra_share) / max(1.0 - t.ultra_share, MIN_POWER)
+    tonal_penalty = max(0.0, peak / (total + MIN_POWER) - 0.05) * 10.0
+    res.composite_score = res.noise_power * (1.0 + (t.flat_weight * res.spectral_flatness_penalty) + (t.hf_weight * res.hf_penalty) + tonal_penalty)
+    res.margin = margin
+    return res
+
+
+def blend(res, level_index):
+    a = alpha(level_index)
+    return a * (math.sqrt(res.composite_score / LEN) * 1000.0) + (1.0 - a) * (res.time_domain_rms * 1000.0)
+
+
+def combine(blended, counts, weights=WEIGHTS):
+    """blended: per segment in evaluation order -> the candidate's score"""
+    tw = ts = 0.0
+    s = 0
+    for lv in range(LEVELS):
+        if counts[lv] == 0:
+            continue
+        acc = 0.0
+        for _ in range(counts[lv]):
+            acc += blended[s]
+            s += 1
+        ts += (acc / counts[lv]) * weights[lv]
+        tw += weights[lv]
+    return np.finfo(np.float64).max if tw <= 0.0 else ts / tw
+
+
+class Learner:
+    """one learner's segments: levelled rows and masking thresholds"""
+
+    def __init__(self, left, right, t):
+        self.segs, self.counts = select_segments(left, right)
+        self.rows = [level(left, right, s) for s in self.segs]
+        self.thr = [masking_thresholds(r, t) for r in self.rows]
+
+
+def chain_inputs(learner, cands, mode, start=SEEDS4):
+    """the lattice stage's chains for stable candidates `cands` {index: mapped}: rows, coef, rng, keys [(c, s, ch)]"""
+    n_seg = len(learner.segs)
+    count = 1 + rng_index(mode, len(cands) - 1, n_seg, n_seg - 1)
+    table = rng_table(count, start)
+    rows, coef, rng, keys = [], [], [], []
+    for before, (c, k) in enumerate(sorted(cands.items())):         # a refused candidate draws nothing: the chained stream passes it by
+        for s in range(n_seg):
+            for ch in range(2):
+                rows.append(learner.rows[s][ch])
+                coef.append(clamp_coeffs(k))
+                rng.append(table[rng_index(mode, before, n_seg, s)][ch])
+                keys.append((c, s, ch))
+    return np.array(rows), np.array(coef), np.array(rng, dtype=np.uint64), keys
+
+
+def score_batch(jobs, t, bits, stability=True, weights=WEIGHTS, start=SEEDS4):
+    """evaluateCandidateMapped for every candidate of every job (learner, mapped [C, 9], mode) at one rate and bit depth: per job
+    (scores [C], results {(c, s): Result}, errors {(c, s): [2, 4096]}).  All jobs' chains go through the lattice stage together:
+    its cost here is per sample, hardly per chain"""
+    plans = []
+    for learner, mapped, mode in jobs:
+        mapped = [list(map(float, k)) for k in mapped]
+        run = {c: k for c, k in enumerate(mapped) if not (stability and not is_stable(k))}
+        plans.append((learner, mapped, run, chain_inputs(learner, run, mode, start) if learner.segs and run else None))
+    live = [p[3] for p in plans if p[3] is not None]
+    if live:
+        err = lattice_errors(*(np.concatenate([ci[k] for ci in live]) for k in range(3)), bits)
+    out, at = [], 0
+    for learner, mapped, run, ci in plans:
+        scores = np.empty(len(mapped))
+        results, errors = {}, {}
+        if ci is not None:
+            keys = ci[3]
+            for i in range(0, len(keys), 2):
+                c, s, _ = keys[i]
+                errors[c, s] = err[at + i:at + i + 2]
+                results[c, s] = evaluate(errors[c, s], learner.thr[s], t)
+            at += len(keys)
+        for c in range(len(mapped)):
+            if c not in run:
+                scores[c] = UNSTABLE
+            else:
+                scores[c] = combine([blend(results[c, s], learner.segs[s][1]) for s in range(len(learner.segs))], learner.counts, weights)
+        out.append((scores, results, errors))
+    return out
+
+
+def score(learner, mapped, t, bits, mode=FRESH, stability=True, weights=WEIGHTS, start=SEEDS4):
+    """one job of score_batch"""
+    return score_batch([(learner, mapped, mode)], t, bits, stability, weights, start)[0]
