@@ -164,6 +164,14 @@ class ScoreSegment(C.Structure):
     _fields_ = [("start", C.c_int32), ("level", C.c_int32), ("type", C.c_int32), ("reserved", C.c_int32), ("gain", C.c_double)]
 
 
+class DiagScoreEval(C.Structure):
+    _fields_ = [("row", C.c_int32), ("thr", C.c_int32), ("slot", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_double)]
+
+
+class DiagScoreChain(C.Structure):
+    _fields_ = [("src", C.c_int32), ("dst", C.c_int32), ("coef", C.c_int32), ("rng", C.c_int32)]
+
+
 class EngineDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("n_streams", C.c_int32),
                 ("block_size", C.c_int32), ("max_ir_len", C.c_int32), ("max_blocks_per_call", C.c_int32),
@@ -314,6 +322,11 @@ SYMBOLS = {
     "cpq_scorer_last_timing": (C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
     "cpq_score_design": (C.c_int32, [C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, _i32p, _i32p, _i32p, c_double_p]),
     "cpq_score_select_segments": (C.c_int32, [c_double_p, c_double_p, C.c_int32, C.POINTER(ScoreSegment), _i32p, _i32p]),
+    "cpq_diag_score_spectrum": (C.c_int32, [C.c_double, C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.POINTER(DiagScoreEval),
+                                            C.c_int32, C.c_int32, C.POINTER(ScoreParts), c_double_p]),
+    "cpq_diag_score_lattice": (C.c_int32, [C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.POINTER(DiagScoreChain),
+                                           C.c_int32, c_double_p, C.c_int32, C.POINTER(C.c_uint64)]),
+    "cpq_diag_score_reduce": (C.c_int32, [C.c_int32, C.c_int32, _i32p, _i32p, c_double_p, c_double_p, c_double_p]),
 }
 
 _lib = None

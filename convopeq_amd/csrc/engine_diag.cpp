@@ -2,6 +2,7 @@
 //   partition FFT, FDL MAC           cpq_diag_partition_fft(_split), _fdl_mac      tests/test_gpu_fft.py, _fft_p4_frames.py, _fdl_mac.py
 //   FFT launch variants, IR spectra  cpq_diag_fft_forward, _fft_inverse_store, _ir_spectra                tests/test_gpu_fft_variants.py
 //   mix_kernels.hip                  cpq_diag_direct_head, _agc, _ring_chunks, _convproc_mix, _tail_reader, _rows    test_gpu_mix_kernels.py
+//   score_kernels.hip                cpq_diag_score_spectrum, _score_lattice, _score_reduce                 tests/test_gpu_score_kernels.py
 //   chained EQ spans of an engine    cpq_diag_eq_chain_status                                             tests/test_gpu_eq_chained.py
 // One convention for all but the last: host pointers, own device buffers of exactly the documented sizes (Scope), the null
 // stream, no engine; what a kernel may write is filled with 0xFF bytes (NaN) unless the caller supplies its contents, and comes
@@ -653,6 +654,124 @@ int32_t cpq_diag_rows(int32_t op, int32_t nCh, int32_t n, const double* src, int
         }
     }
     d.get(dst, dDst, nDst);
+    return d.rc;
+}
+
+// ---------------------------------------------------------------- the scorer's kernels (tests/test_gpu_score_kernels.py)
+// launch_score_spectrum as engine_score.cpp makes it, with the tables of `rate` (the scorer's own upload), on caller-filled rows,
+// thresholds and evaluation table
+int32_t cpq_diag_score_spectrum(double rate, int32_t nRows, const double* rows, int32_t nThr, double* thr, int32_t nEvals,
+                                const cpq_diag_score_eval* evals, int32_t nSlots, int32_t thresholdsOnly, cpq_score_parts* parts,
+                                double* blended)
+{
+    if (!rows || !thr || !evals || !parts || !blended) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: null buffer");
+    if (!(rate > 0.0) || !std::isfinite(rate)) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: sample rate must be finite and > 0");
+    if (nRows < 1 || nThr < 1 || nEvals < 1 || nSlots < 1) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: n_rows, n_thr, n_evals and n_slots must be >= 1");
+    if (!fits(nRows, 2 * cpq::kScoreLen) || !fits(nThr, cpq::kScoreBins) || !fits(nEvals, 1) || !fits(nSlots, 1))
+        return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: a buffer above 2^28 elements");
+    std::vector<char> slotSeen(nSlots, 0), thrSeen(nThr, 0);
+    std::vector<cpq::ScoreEval> table(nEvals);
+    for (int i = 0; i < nEvals; ++i) {
+        const cpq_diag_score_eval& ev = evals[i];
+        if (ev.row < 0 || ev.row >= nRows) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: eval %d names row %d outside 0..%d", i, ev.row, nRows - 1);
+        if (ev.thr < 0 || ev.thr >= nThr) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: eval %d names thr %d outside 0..%d", i, ev.thr, nThr - 1);
+        if (ev.slot < 0 || ev.slot >= nSlots) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: eval %d names slot %d outside 0..%d", i, ev.slot, nSlots - 1);
+        if (slotSeen[ev.slot]) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: slot %d named twice", ev.slot);
+        if (thresholdsOnly && thrSeen[ev.thr]) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: thr %d written twice", ev.thr);
+        slotSeen[ev.slot] = thrSeen[ev.thr] = 1;
+        table[i] = cpq::ScoreEval{ ev.row, ev.thr, ev.slot, ev.alpha };
+    }
+    cpq::ScoreTables t;
+    if (!cpq::scoreTables(rate, t)) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_spectrum: no Bark band layout at %g Hz", rate);
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    cpqi::ScoreTableBuffers tables;
+    std::string error;
+    const int rc = cpqi::uploadScoreTables(t, tables, error);
+    if (rc != CPQ_OK) return fail(nullptr, CPQ_ERR_DEVICE, "score_spectrum: %s", error.c_str());
+    const double* dRows = d.put(rows, (size_t)nRows * 2 * cpq::kScoreLen);
+    double* dThr = d.put(thr, (size_t)nThr * cpq::kScoreBins);
+    const cpq::ScoreEval* dEvals = d.put(table.data(), table.size());
+    cpq_score_parts* dParts = d.put<cpq_score_parts>(nullptr, nSlots);
+    double* dBlended = d.put<double>(nullptr, nSlots);
+    if (d.rc == CPQ_OK) {
+        cpq::launch_score_spectrum(nullptr, dRows, dThr, dEvals, nEvals, tables.dev, dParts, dBlended, thresholdsOnly != 0);
+        d.launched();
+    }
+    d.get(thr, dThr, (size_t)nThr * cpq::kScoreBins);
+    d.get(parts, dParts, (size_t)nSlots);
+    d.get(blended, dBlended, (size_t)nSlots);
+    return d.rc;
+}
+
+// launch_score_lattice with the shaper parameters cpq_scorer_create derives from `bits`, on caller-filled rows and chain table
+int32_t cpq_diag_score_lattice(int32_t bits, int32_t nSrc, const double* seg, int32_t nDst, double* err, int32_t nChains,
+                               const cpq_diag_score_chain* chains, int32_t nCoef, const double* coef, int32_t nRng, const uint64_t* rng)
+{
+    if (!seg || !err || !chains || !coef || !rng) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: null buffer");
+    if (bits < 1 || bits > 32) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: bit depth %d outside 1..32", bits);
+    if (nSrc < 1 || nDst < 1 || nChains < 1 || nCoef < 1 || nRng < 1) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: n_src, n_dst, n_chains, n_coef and n_rng must be >= 1");
+    if (!fits(nSrc, cpq::kScoreLen) || !fits(nDst, cpq::kScoreLen) || !fits(nChains, 4) || !fits(nCoef, cpq::kLatticeOrder) || !fits(nRng, 4))
+        return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: a buffer above 2^28 elements");
+    std::vector<char> dstSeen(nDst, 0);
+    std::vector<cpq::ScoreChain> table(nChains);
+    for (int i = 0; i < nChains; ++i) {
+        const cpq_diag_score_chain& c = chains[i];
+        if (c.src < 0 || c.src >= nSrc) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: chain %d names src %d outside 0..%d", i, c.src, nSrc - 1);
+        if (c.dst < 0 || c.dst >= nDst) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: chain %d names dst %d outside 0..%d", i, c.dst, nDst - 1);
+        if (c.coef < 0 || c.coef >= nCoef) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: chain %d names coef %d outside 0..%d", i, c.coef, nCoef - 1);
+        if (c.rng < 0 || c.rng >= nRng) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: chain %d names rng %d outside 0..%d", i, c.rng, nRng - 1);
+        if (dstSeen[c.dst]) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_lattice: dst %d named twice", c.dst);
+        dstSeen[c.dst] = 1;
+        table[i] = cpq::ScoreChain{ c.src, c.dst, c.coef, c.rng };
+    }
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "generator words travel as unsigned long long");
+    const double* dSeg = d.put(seg, (size_t)nSrc * cpq::kScoreLen);
+    double* dErr = d.put<double>(nullptr, (size_t)nDst * cpq::kScoreLen);
+    const cpq::ScoreChain* dChains = d.put(table.data(), table.size());
+    const double* dCoef = d.put(coef, (size_t)nCoef * cpq::kLatticeOrder);
+    const unsigned long long* dRng = d.put(reinterpret_cast<const unsigned long long*>(rng), (size_t)nRng * 4);
+    if (d.rc == CPQ_OK) {
+        cpq::launch_score_lattice(nullptr, dSeg, dErr, dChains, nChains, dCoef, dRng, cpqi::scoreDitherParams(bits));
+        d.launched();
+    }
+    d.get(err, dErr, (size_t)nDst * cpq::kScoreLen);
+    return d.rc;
+}
+
+// launch_score_reduce on caller-filled counts, states and blended rows
+int32_t cpq_diag_score_reduce(int32_t nLearners, int32_t nCand, const int32_t* counts, const int32_t* state, const double* blended,
+                              const double* weights, double* scores)
+{
+    if (!counts || !state || !blended || !weights || !scores) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_reduce: null buffer");
+    if (nLearners < 1 || nCand < 1 || (int64_t)nLearners * nCand > (1 << 20))
+        return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_reduce: n_learners and n_cand must be >= 1, their product <= 2^20");
+    for (int l = 0; l < nLearners; ++l) {
+        int sum = 0;
+        for (int i = 0; i < cpq::kScoreLevels; ++i) {
+            const int c = counts[l * cpq::kScoreLevels + i];
+            if (c < 0 || c > cpq::kScoreMaxSegments) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_reduce: learner %d, level %d: count %d outside 0..%d", l, i, c, cpq::kScoreMaxSegments);
+            sum += c;
+        }
+        if (sum > cpq::kScoreMaxSegments) return fail(nullptr, CPQ_ERR_INVALID_ARG, "score_reduce: learner %d: counts sum to %d, above %d", l, sum, cpq::kScoreMaxSegments);
+    }
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    const size_t nPairs = (size_t)nLearners * nCand;
+    const double* dBlended = d.put(blended, nPairs * cpq::kScoreMaxSegments);
+    const int* dCounts = d.put(counts, (size_t)nLearners * cpq::kScoreLevels);
+    const int* dState = d.put(state, nPairs);
+    double* dScores = d.put<double>(nullptr, nPairs);
+    if (d.rc == CPQ_OK) {
+        cpq::launch_score_reduce(nullptr, dBlended, dCounts, dState, nLearners, nCand, weights, dScores);
+        d.launched();
+    }
+    d.get(scores, dScores, nPairs);
     return d.rc;
 }
 

@@ -361,6 +361,18 @@ int fail(cpq_engine* e, int code, const char* fmt, ...);
         if (rc__ != CPQ_OK) return rc__;                                                             \
     } while (0)
 
+// the scorer's tables on the device (engine_score.cpp; cpq_scorer_create and cpq_diag_score_spectrum): the eight per-bin double
+// tables and the twiddles in tabD, band / range / bandStart in tabI, dev pointing into both.  CPQ_OK, or CPQ_ERR_OOM /
+// CPQ_ERR_DEVICE with the reason in `error`
+struct ScoreTableBuffers {
+    DeviceBuffer<double> tabD;
+    DeviceBuffer<int> tabI;
+    cpq::ScoreDeviceTables dev{};
+};
+int uploadScoreTables(const cpq::ScoreTables& t, ScoreTableBuffers& b, std::string& error);
+// the scorer's shaper at `bits` (LatticeNoiseShaper::prepare) with the output stage's headroom: scale, invScale, maxV, headroom
+cpq::DitherParams scoreDitherParams(int bits);
+
 // the stream argument of an entry point, one stream or CPQ_ALL_STREAMS, as the range [s0, s1); refuses any other value
 int streamRange(cpq_engine* e, int stream, int& s0, int& s1);
 

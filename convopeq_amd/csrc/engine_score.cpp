@@ -21,10 +21,8 @@ struct cpq_scorer {
     std::string lastError;
 
     cpq::ScoreTables tab;
-    cpq::ScoreDeviceTables dev{};
+    cpqi::ScoreTableBuffers tables;             // tab on the device
     cpq::DitherParams p{};
-    cpqi::DeviceBuffer<double> tabD;            // the eight double tables, then the twiddles
-    cpqi::DeviceBuffer<int> tabI;               // band, range, bandStart
     unsigned long long rngStart[2][4] = {};
     cpqi::DeviceBuffer<unsigned long long> rng; // [max_candidates * 16][2][4]
 
@@ -44,6 +42,58 @@ struct cpq_scorer {
     std::vector<int> lastNSeg;
     bool scored = false;
 };
+
+namespace cpqi {
+
+// LatticeNoiseShaper::prepare
+cpq::DitherParams scoreDitherParams(int bits)
+{
+    cpq::DitherParams p{};
+    p.invScale = std::ldexp(1.0, bits - 1);
+    p.scale = 1.0 / p.invScale;
+    p.maxV = 1.0 - (1.0 / p.invScale);
+    p.headroom = cpq::kOutHeadroom;
+    return p;
+}
+
+int uploadScoreTables(const cpq::ScoreTables& t, ScoreTableBuffers& b, std::string& error)
+{
+    auto ship = [&error](hipError_t err, const char* what) {
+        if (err == hipSuccess) return true;
+        error = std::string(what) + " failed: " + hipGetErrorString(err);
+        return false;
+    };
+    std::vector<double2> tw(cpq::kScoreLen / 2);
+    const long double step = -2.0L * 3.14159265358979323846264338327950288L / (long double)cpq::kScoreLen;
+    for (size_t k = 0; k < tw.size(); ++k) tw[k] = make_double2((double)cosl(step * (long double)k), (double)sinl(step * (long double)k));
+    const std::vector<double>* dbl[8] = { &t.weight, &t.bark, &t.athDb, &t.athPow, &t.width, &t.thrSpread, &t.spreadTonal, &t.spreadNoise };
+    size_t nD = 0;
+    for (auto* v : dbl) nD += v->size() + (v->size() & 1);          // every table starts on 16 bytes
+    if (!b.tabD.alloc(nD + 2 * tw.size()) || !b.tabI.alloc(2 * (size_t)cpq::kScoreBins + cpq::kScoreBands + 1)) {
+        error = "scorer tables could not be allocated";
+        return CPQ_ERR_OOM;
+    }
+    const double* at[8];
+    size_t off = 0;
+    for (int i = 0; i < 8; ++i) {
+        at[i] = b.tabD.get() + off;
+        if (!ship(hipMemcpy(b.tabD.get() + off, dbl[i]->data(), dbl[i]->size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy of a scorer table"))
+            return CPQ_ERR_DEVICE;
+        off += dbl[i]->size() + (dbl[i]->size() & 1);
+    }
+    int* ip = b.tabI.get();
+    if (!ship(hipMemcpy(b.tabD.get() + off, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice), "hipMemcpy of the scorer twiddles") ||
+        !ship(hipMemcpy(ip, t.band.data(), cpq::kScoreBins * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy of a scorer table") ||
+        !ship(hipMemcpy(ip + cpq::kScoreBins, t.range.data(), cpq::kScoreBins * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy of a scorer table") ||
+        !ship(hipMemcpy(ip + 2 * cpq::kScoreBins, t.bandStart, sizeof(t.bandStart), hipMemcpyHostToDevice), "hipMemcpy of a scorer table"))
+        return CPQ_ERR_DEVICE;
+    b.dev = cpq::ScoreDeviceTables{ at[0], at[1], at[2], at[3], at[4], at[5], at[6], at[7], ip, ip + cpq::kScoreBins, ip + 2 * cpq::kScoreBins,
+                                    reinterpret_cast<const double2*>(b.tabD.get() + off), t.flatStart, t.flatEnd, t.highStart,
+                                    t.ultraStart, t.ultraShare, t.flatWeight, t.hfWeight, t.weightSum };
+    return CPQ_OK;
+}
+
+}  // namespace cpqi
 
 namespace {
 
@@ -86,35 +136,6 @@ int uploadRng(cpq_scorer* s)
     return CPQ_OK;
 }
 
-int uploadTables(cpq_scorer* s)
-{
-    const cpq::ScoreTables& t = s->tab;
-    std::vector<double2> tw(kScoreLen / 2);
-    const long double step = -2.0L * 3.14159265358979323846264338327950288L / (long double)kScoreLen;
-    for (size_t k = 0; k < tw.size(); ++k) tw[k] = make_double2((double)cosl(step * (long double)k), (double)sinl(step * (long double)k));
-    const std::vector<double>* dbl[8] = { &t.weight, &t.bark, &t.athDb, &t.athPow, &t.width, &t.thrSpread, &t.spreadTonal, &t.spreadNoise };
-    size_t nD = 0;
-    for (auto* v : dbl) nD += v->size() + (v->size() & 1);          // every table starts on 16 bytes
-    if (!s->tabD.alloc(nD + 2 * tw.size()) || !s->tabI.alloc(2 * (size_t)kScoreBins + cpq::kScoreBands + 1))
-        return sfail(s, CPQ_ERR_OOM, "scorer tables could not be allocated");
-    const double* at[8];
-    size_t off = 0;
-    for (int i = 0; i < 8; ++i) {
-        at[i] = s->tabD.get() + off;
-        CPQ_SHIP(s, hipMemcpy(s->tabD.get() + off, dbl[i]->data(), dbl[i]->size() * sizeof(double), hipMemcpyHostToDevice));
-        off += dbl[i]->size() + (dbl[i]->size() & 1);
-    }
-    CPQ_SHIP(s, hipMemcpy(s->tabD.get() + off, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-    int* ip = s->tabI.get();
-    CPQ_SHIP(s, hipMemcpy(ip, t.band.data(), kScoreBins * sizeof(int), hipMemcpyHostToDevice));
-    CPQ_SHIP(s, hipMemcpy(ip + kScoreBins, t.range.data(), kScoreBins * sizeof(int), hipMemcpyHostToDevice));
-    CPQ_SHIP(s, hipMemcpy(ip + 2 * kScoreBins, t.bandStart, sizeof(t.bandStart), hipMemcpyHostToDevice));
-    s->dev = cpq::ScoreDeviceTables{ at[0], at[1], at[2], at[3], at[4], at[5], at[6], at[7], ip, ip + kScoreBins, ip + 2 * kScoreBins,
-                                     reinterpret_cast<const double2*>(s->tabD.get() + off), t.flatStart, t.flatEnd, t.highStart,
-                                     t.ultraStart, t.ultraShare, t.flatWeight, t.hfWeight, t.weightSum };
-    return CPQ_OK;
-}
-
 int checkLearner(cpq_scorer* s, int learner)
 {
     if (learner < 0 || learner >= s->desc.n_learners) return sfail(s, CPQ_ERR_INVALID_ARG, "learner %d outside 0..%d", learner, s->desc.n_learners - 1);
@@ -142,7 +163,7 @@ int buildSegments(cpq_scorer* s, int learner, const double* l, const double* r, 
     CPQ_SHIP(s, hipMemcpyAsync(s->evals, evals, n * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, s->stream));
     cpq::launch_score_level(s->stream, s->recent, kScoreRecent, s->segStart, s->segGain,
                             s->seg.get() + (size_t)learner * kScoreMaxSegments * 2 * kScoreLen, n);
-    cpq::launch_score_spectrum(s->stream, s->seg, s->thr, s->evals, n, s->dev, nullptr, nullptr, true);
+    cpq::launch_score_spectrum(s->stream, s->seg, s->thr, s->evals, n, s->tables.dev, nullptr, nullptr, true);
     CPQ_SHIP(s, hipGetLastError());
     CPQ_SHIP(s, hipStreamSynchronize(s->stream));            // the tables above are this frame's
     return CPQ_OK;
@@ -224,7 +245,7 @@ int score(cpq_scorer* s, const double* mapped, int nCand, double* scores, cpq_sc
     CPQ_SHIP(s, hipEventRecord(s->ev[0], st));
     cpq::launch_score_lattice(st, s->seg, s->err, s->chains, (int)chains.size(), s->coef, s->rng, s->p);
     CPQ_SHIP(s, hipEventRecord(s->ev[1], st));
-    cpq::launch_score_spectrum(st, s->err, s->thr, s->evals, (int)evals.size(), s->dev, s->parts, s->blended, false);
+    cpq::launch_score_spectrum(st, s->err, s->thr, s->evals, (int)evals.size(), s->tables.dev, s->parts, s->blended, false);
     CPQ_SHIP(s, hipEventRecord(s->ev[2], st));
     cpq::launch_score_reduce(st, s->blended, s->countsDev, s->state, L, nCand, s->desc.level_weights, s->scores);
     CPQ_SHIP(s, hipGetLastError());
@@ -285,10 +306,7 @@ int32_t cpq_scorer_create(const cpq_scorer_desc* d, cpq_scorer** out)
     s->desc = *d;
     s->device = device;
     if (!cpq::scoreTables(d->sample_rate_hz, s->tab)) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "no Bark band layout at %g Hz", d->sample_rate_hz);
-    s->p.invScale = std::ldexp(1.0, d->bit_depth - 1);      // LatticeNoiseShaper::prepare
-    s->p.scale = 1.0 / s->p.invScale;
-    s->p.maxV = 1.0 - (1.0 / s->p.invScale);
-    s->p.headroom = cpq::kOutHeadroom;
+    s->p = cpqi::scoreDitherParams(d->bit_depth);
     std::memcpy(s->rngStart, kRngDefault, sizeof(kRngDefault));
     const size_t L = (size_t)d->n_learners, pairs = L * d->max_candidates;
     s->nSeg.assign(L, 0);
@@ -306,7 +324,7 @@ int32_t cpq_scorer_create(const cpq_scorer_desc* d, cpq_scorer** out)
                     s->parts.alloc(pairs * kScoreMaxSegments) && s->countsDev.alloc(L * cpq::kScoreLevels) && s->state.alloc(pairs) &&
                     s->rng.alloc((size_t)d->max_candidates * kScoreMaxSegments * 8);
     if (!ok) return sfail(nullptr, CPQ_ERR_OOM, "scorer buffers for %d learners x %d candidates could not be allocated", d->n_learners, d->max_candidates);
-    int rc = uploadTables(s.get());
+    int rc = cpqi::uploadScoreTables(s->tab, s->tables, s->lastError);
     if (rc == CPQ_OK) rc = uploadRng(s.get());
     if (rc != CPQ_OK) return sfail(nullptr, rc, "%s", s->lastError.c_str());
     *out = s.release();

@@ -1017,6 +1017,44 @@ int32_t cpq_score_design(double sample_rate_hz, double* weight, double* bark, do
 /* buildTrainingSegments' selection alone, on the host: as cpq_scorer_get_segments after cpq_scorer_set_audio would report */
 int32_t cpq_score_select_segments(const double* left, const double* right, int32_t n, cpq_score_segment* segments,
                                   int32_t* n_segments, int32_t counts[4]);
+/* The scorer's three kernels on their own (csrc/engine_diag.cpp, tests/test_gpu_score_kernels.py), for inputs cpq_scorer_score
+ * cannot produce: no scorer object.  Conventions of the other cpq_diag_* entries: all pointers are host memory; the null stream,
+ * synchronised before the entry returns; every device buffer is allocated at exactly the size stated here; every buffer a kernel
+ * may write is filled with 0xFF bytes (NaN) before the launch unless the caller supplies its contents ("in and out"), and is
+ * returned whole.  Each entry returns CPQ_ERR_INVALID_ARG, with the reason in cpq_last_error(NULL), before anything is allocated
+ * and before a device is looked for, unless the rules of its "Refused unless" hold and every pointer is non-null; no buffer may
+ * exceed 2^28 elements.  Need a gfx950 device (CPQ_ERR_NO_DEVICE); an allocation or HIP failure is CPQ_ERR_DEVICE.  Like every
+ * addition since revision 1 they leave CPQ_ABI_REVISION as it is (a caller that may meet an older library looks the symbols up),
+ * and as diagnostics of kernels no engine profiles they leave CPQ_K_COUNT at 13.
+ *
+ * cpq_diag_score_spectrum: launch_score_spectrum as cpq_scorer makes it, with the tables of sample_rate_hz (built and uploaded by
+ *   the scorer's own function).  rows: [n_rows][2][4096] (L, R); thr: [n_thr][2049], in and out; evals: [n_evals], evaluation i
+ *   reads row pair evals[i].row and, with thresholds_only == 0, the masking thresholds thr[evals[i].thr], and stores
+ *   MklFftEvaluator::evaluate's members to parts[evals[i].slot] and alpha * sqrt(composite / 4096) * 1000 + (1 - alpha) * rms * 1000
+ *   to blended[evals[i].slot]; thr comes back as given.  thresholds_only != 0: computeMaskingThreshold of every bin of 0.5 (|L|^2 +
+ *   |R|^2) to thr[evals[i].thr]; parts and blended come back as the fill.  parts, blended: [n_slots], out.
+ *   Refused unless: sample_rate_hz finite and > 0; n_rows, n_thr, n_evals, n_slots >= 1; 0 <= row < n_rows, 0 <= thr < n_thr,
+ *   0 <= slot < n_slots for every evaluation; no slot named twice; with thresholds_only no thr named twice.
+ * cpq_diag_score_lattice: launch_score_lattice with the shaper parameters cpq_scorer_create derives from bit_depth (one shared
+ *   function).  seg: [n_src][4096]; err: [n_dst][4096], out; chains: [n_chains], chain i runs a fresh shaper with the clamped
+ *   coefficients coef[chains[i].coef][9] and the generator words rng[chains[i].rng][4] over seg[chains[i].src] and stores
+ *   yq - x * headroom to err[chains[i].dst]; coef: [n_coef][9]; rng: [n_rng][4].
+ *   Refused unless: 1 <= bit_depth <= 32; n_src, n_dst, n_chains, n_coef, n_rng >= 1; every index of every chain inside its
+ *   table; no dst named twice.
+ * cpq_diag_score_reduce: launch_score_reduce.  counts: [n_learners][4] segments per level; state: [n_learners * n_cand] (1: the
+ *   pair scores CPQ_SCORE_UNSTABLE); blended: [n_learners * n_cand][16], a pair's segments in evaluation order; weights: [4];
+ *   scores: [n_learners * n_cand], out.  No level with segments, or no weight on those levels: DBL_MAX.
+ *   Refused unless: n_learners, n_cand >= 1, n_learners * n_cand <= 2^20; every count >= 0 and a learner's counts sum to <= 16. */
+typedef struct { int32_t row, thr, slot, reserved; double alpha; } cpq_diag_score_eval;
+typedef struct { int32_t src, dst, coef, rng; } cpq_diag_score_chain;
+int32_t cpq_diag_score_spectrum(double sample_rate_hz, int32_t n_rows, const double* rows, int32_t n_thr, double* thr,
+                                int32_t n_evals, const cpq_diag_score_eval* evals, int32_t n_slots, int32_t thresholds_only,
+                                cpq_score_parts* parts, double* blended);
+int32_t cpq_diag_score_lattice(int32_t bit_depth, int32_t n_src, const double* seg, int32_t n_dst, double* err, int32_t n_chains,
+                               const cpq_diag_score_chain* chains, int32_t n_coef, const double* coef, int32_t n_rng,
+                               const uint64_t* rng);
+int32_t cpq_diag_score_reduce(int32_t n_learners, int32_t n_cand, const int32_t* counts, const int32_t* state,
+                              const double* blended, const double* weights, double* scores);
 
 #ifdef __cplusplus
 }

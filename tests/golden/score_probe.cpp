@@ -11,6 +11,11 @@
 // candidate, 1: one shaper for all of them in order.  out (doubles): nSeg; per segment start, level, gain, type; per segment 2049
 // thresholds; per candidate the score; per candidate and segment the five Result members.  rows: per candidate and segment the
 // two error rows.
+// Evaluate-only mode, for tests/golden/score_edges_ref.npz (make_score_edges_ref.py):
+//   score_probe eval <rate> <in> <out> <echo>
+// in (doubles): per pair a flag, the two error rows (L, R), and with flag != 0 the 2049 masking thresholds handed to evaluate()
+// (flag 0: evaluate() gets none).  out: per pair the five Result members, then computeMaskingThreshold of every bin of the pair's
+// 0.5 (|L|^2 + |R|^2).  echo: the rows as they were read.
 #include <JuceHeader.h>
 #include "DspNumericPolicy.h"
 using namespace convo::numeric_policy;
@@ -22,6 +27,7 @@ using namespace convo::numeric_policy;
 #include <cstdlib>
 #include <limits>
 #include <memory>
+#include <string>
 #include <vector>
 
 namespace {
@@ -52,10 +58,50 @@ std::vector<double> readAll(const char* path)
     return v;
 }
 
+int evaluateOnly(int argc, char** argv)
+{
+    if (argc != 6) return 2;
+    const double rate = std::strtod(argv[2], nullptr);
+    const std::vector<double> in = readAll(argv[3]);
+    auto evaluator = std::make_unique<MklFftEvaluator>();
+    evaluator->configureForSampleRate(rate);
+    const double binWidth = (rate * 0.5) / (kBins - 1);
+    std::vector<double> out, echo;
+    auto thr = std::make_unique<std::array<double, kBins>>();
+    std::vector<MklFftEvaluator::CcsComplex> specL(kBins), specR(kBins);
+    size_t at = 0;
+    while (at < in.size()) {
+        const bool withThr = in[at] != 0.0;
+        const size_t need = 1 + 2 * (size_t)kLen + (withThr ? kBins : 0);
+        if (in.size() - at < need) return 3;
+        const double* l = in.data() + at + 1;
+        const double* r = l + kLen;
+        if (withThr) std::copy(r + kLen, r + kLen + kBins, thr->begin());
+        const auto res = evaluator->evaluate(l, r, withThr ? thr.get() : nullptr);
+        for (double v : { res.noisePower, res.spectralFlatnessPenalty, res.hfPenalty, res.timeDomainRms, res.compositeScore }) out.push_back(v);
+        evaluator->computeFft(l, r, specL.data(), specR.data());
+        for (int k = 0; k < kBins; ++k) {
+            const double magSqL = specL[k].real * specL[k].real + specL[k].imag * specL[k].imag;
+            const double magSqR = specR[k].real * specR[k].real + specR[k].imag * specR[k].imag;
+            out.push_back(evaluator->computeMaskingThreshold(0.5 * (magSqL + magSqR), k * binWidth));
+        }
+        echo.insert(echo.end(), l, l + 2 * kLen);
+        at += need;
+    }
+    FILE* f = std::fopen(argv[4], "wb");
+    if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size()) return 3;
+    std::fclose(f);
+    f = std::fopen(argv[5], "wb");
+    if (!f || std::fwrite(echo.data(), sizeof(double), echo.size(), f) != echo.size()) return 3;
+    std::fclose(f);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
+    if (argc >= 2 && std::string(argv[1]) == "eval") return evaluateOnly(argc, argv);
     if (argc != 10) return 2;
     const double rate = std::strtod(argv[1], nullptr);
     const int bits = std::atoi(argv[2]), mode = std::atoi(argv[3]), stability = std::atoi(argv[4]), nCand = std::atoi(argv[7]);

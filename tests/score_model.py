@@ -9,7 +9,9 @@ comparison from its threshold (Result.margin), each relative to the threshold it
     spread cut        |bark_i - masker.bark| > 8          ||delta| - 8| / 8
     spread table      round(delta / 0.01 + 800)           distance of the index from the half-way point, in table steps
 Comparisons on tables alone (the 0.5-Bark absorb radius, band membership, the bin ranges) are made on the same bits everywhere.
-sumEnergy <= 1e-24, count <= 0 and the caps of 128 are reported as Result.caps: a case that comes near them is not recorded."""
+sumEnergy <= 1e-24, count <= 0 and the caps of 128 are reported as Result.caps: tests/golden/score_ref.npz records no case that
+comes near them; tests/golden/score_edges_ref.npz (inputs: tests/score_edge_inputs.py) records the empty bands, the near-silent
+bands and the densest combs on purpose, and Result.branches counts the bins on each softplus branch."""
 import ctypes
 import ctypes.util
 import math
@@ -29,6 +31,11 @@ FRESH, CHAINED = 0, 1
 UNSTABLE = 1e18
 D_REF = 2.5e-14           # measured 2.41e-14: RESULTS.md, "shaper scorer" (the model against the recorded reference, members and scores)
 GPU_BAR = max(8.0 * D_REF, 2049.0 * 2.0 ** -52)
+# the edge fixture (tests/golden/score_edges_ref.npz, inputs of tests/score_edge_inputs.py): the model against the recorded members,
+# largest deviation over its cases 2.46e-14 (impulse_0 / impulse_odd; RESULTS.md), rounded up as D_REF was; the device's bar by
+# the same rule as GPU_BAR, 4.55e-13: the floor decides
+D_EDGE = 2.5e-14
+GPU_BAR_EDGE = max(8.0 * D_EDGE, 2049.0 * 2.0 ** -52)
 # the model's masking thresholds against the recorded ones, largest relative deviation per run (RESULTS.md): not part of D_REF.
 # C16 is two tones over a noise floor far below them, so most of its bins hold leakage and with it the transform's own rounding
 D_THR = {"A16": 1.2e-14, "B24": 2.0e-15, "C16": 2.6e-13}
@@ -324,8 +331,8 @@ def _db(p):
     return np.log(np.maximum(p, MIN_POWER)) * DB_PER_LN
 
 
-def evaluate(err, thr, t):
-    """err [2, 4096], thr [2049] or None -> Result with .margin and .caps"""
+def evaluate(err, thr, t, cap=128):
+    """err [2, 4096], thr [2049] or None -> Result with .margin, .caps and .branches; cap: kMaxMaskers (tests of the cap itself)"""
     res = Result()
     margin = math.inf
     sum_sq = 0.0
@@ -372,8 +379,9 @@ def evaluate(err, thr, t):
         if sum_e <= MIN_POWER:
             continue
         n_tonal_found += 1
-        if len(maskers) < 128:
+        if len(maskers) < cap:
             maskers.append((float(_db(np.float64(sum_e))), sum_bw / sum_e, 0))
+    n_bands = 0
     for band in range(24):
         sel = (t.band == band) & ~consumed
         count = int(sel.sum())
@@ -382,12 +390,14 @@ def evaluate(err, thr, t):
         if count <= 0 or sum_e <= MIN_POWER:
             continue
         min_energy = min(min_energy, sum_e)
+        n_bands += 1
         pf = np.maximum(power[sel], 1.0e-15)
         sfm = math.exp(float(np.sum(np.log(pf))) / float(count)) / max(float(np.sum(pf)) / float(count), 1.0e-15)
         tonality = min(max(-0.299 + (-0.43 * math.log(max(sfm, 1.0e-12)) * 0.43429448190325182765), 0.0), 1.0)
-        if len(maskers) < 128:
+        if len(maskers) < cap:
             maskers.append((float(_db(np.float64(sum_e))) + (-5.0 * (1.0 - tonality)), float(np.sum(t.bark[sel] * e)) / sum_e, 1))
-    res.caps = {"tonal": n_tonal_found, "maskers": len(maskers), "min_energy": min_energy}
+    res.caps = {"tonal": n_tonal_found, "maskers": len(maskers), "min_energy": min_energy, "bands": n_bands,
+                "consumed": int(consumed.sum())}
 
     masking = t.ath_pow.copy()
     if maskers:
@@ -418,6 +428,7 @@ def evaluate(err, thr, t):
     z = 2.0 * delta
     with np.errstate(over="ignore"):
         soft = np.where(z > 50.0, delta, np.where(z < -50.0, np.exp(z) / 2.0, np.log1p(np.exp(z)) / 2.0))
+    res.branches = (int((z > 50.0).sum()), int(((z <= 50.0) & ~(z < -50.0)).sum()), int((z < -50.0).sum()))       # softplus: x, log1p, exp
     eff = 20.0 * np.tanh(soft / 20.0)
     eff_pow = np.maximum(0.0, np.power(10.0, eff / 10.0) - 1.0)
     psycho = float(np.sum(t.weight * eff_pow))
