@@ -319,8 +319,8 @@ int32_t cpq_diag_fft_inverse_store(int32_t mode, int32_t P, int32_t nCh, int32_t
         double* dRingB = ringB ? d.put(ringB, nRingB) : nullptr;
         const long long* dPosB = ringB ? d.put(ll(posB), T) : nullptr;
         if (d.rc == CPQ_OK) {
-            cpq::launch_rfft_inv_ols_add(nullptr, dY, dOut, stride, tw, nCh, T, dRingA, ringSizeA, dPosA, g1, dRingB, ringB ? ringSizeB : 2,
-                                         dPosB, g2);
+            const cpq::RingTap b = ringB ? cpq::RingTap{ dRingB, ringSizeB, dPosB, g2 } : cpq::RingTap{};
+            cpq::launch_rfft_inv_ols_add(nullptr, dY, dOut, stride, tw, nCh, T, cpq::RingTap{ dRingA, ringSizeA, dPosA, g1 }, b);
             d.launched();
         }
         d.get(ringB, dRingB, nRingB);
@@ -502,14 +502,9 @@ int32_t cpq_diag_ring_chunks(int32_t op, int32_t rows, int32_t nCh, int32_t n, i
         const double* dRingB = useB ? d.put(ringB, (size_t)nCh * sizeB) : nullptr;
         const long long* dSchedB = useB ? d.put(ll(schedB), nCb) : nullptr;
         if (d.rc == CPQ_OK) {
-            if (op == 1) cpq::launch_ring_get_chunks(nullptr, dOut, outStride, dMap, n, q, dRing0, size0, dPos, dCnt, nCh);
-            else if (op == 2) cpq::launch_ring_add_chunks(nullptr, dOut, outStride, dMap, n, q, dRingA, sizeA, dSchedA, gainA, nCh);
-            else if (op == 3)
-                cpq::launch_ring_add_chunks2(nullptr, dOut, outStride, dMap, n, q, dRingA, sizeA, dSchedA, gainA, dRingB, sizeB, dSchedB,
-                                             gainB, nCh);
-            else
-                cpq::launch_ring_get_add_chunks(nullptr, dOut, outStride, dMap, n, q, dRing0, size0, dPos, dCnt, dRingA, sizeA, dSchedA,
-                                                gainA, dRingB, useB ? sizeB : 2, dSchedB, gainB, nCh);
+            const cpq::RingTap a = useA ? cpq::RingTap{ dRingA, sizeA, dSchedA, gainA } : cpq::RingTap{};
+            const cpq::RingTap b = useB ? cpq::RingTap{ dRingB, sizeB, dSchedB, gainB } : cpq::RingTap{};
+            cpq::launch_ring_chunks(nullptr, dOut, outStride, dMap, n, q, dRing0, size0, dPos, dCnt, a, b, nCh);
             d.launched();
         }
     }

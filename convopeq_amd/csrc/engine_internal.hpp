@@ -73,6 +73,7 @@ struct NativeLayer : LayerState {
     double2 *X = nullptr, *XDN = nullptr, *H = nullptr, *HDN = nullptr, *Y = nullptr, *tw = nullptr, *tw2 = nullptr, *twCol = nullptr, *twSplit = nullptr;
     double *hist[2] = { nullptr, nullptr }, *acc[2] = { nullptr, nullptr }, *ring = nullptr, *gainDev = nullptr;
     double2* scratch = nullptr;   // four-step FFT workspace (P > 4096): [max(nCh * nbMax, K)][P]
+    cpq::FftTables tables() const { return cpq::FftTables{ tw, tw2, twCol, twSplit }; }
 };
 
 // Streams that share one layer plan and one phase (loaded while the group was fresh); see engine_native.cpp
@@ -98,6 +99,12 @@ struct PlanGroup {
     bool getDeferred = false;                   // layer 0's chunk-wise ring read waits for the tails' read-add: one pass does both
     long long samplesSinceReset = 0;
     int lastGot = 0, lastCall = 0;              // Get()'s return value summed over the chunks of the last call
+    // tail layer l's delay line as Get() reads it in the call in flight (its schedule: tabOffs[2 l]); empty when the plan has no layer l
+    cpq::RingTap tap(size_t l) const
+    {
+        if (l >= layers.size()) return cpq::RingTap{};
+        return cpq::RingTap{ layers[l].ring, layers[l].outRing, tabDev + tabOffs[2 * l], layers[l].gain };
+    }
 };
 
 // pinned staging for the small host -> device tables of a call (chunk schedules, per-stream gains and flags): a byte ring;
@@ -445,6 +452,19 @@ int groupsRunLayer0(cpq_engine* e, double* dOut, int n);
 int groupsRunTails(cpq_engine* e, double* dOut, int n);
 // engine_conv.cpp
 int enqueueConv(cpq_engine* e, const double* dIn, double* dOut, int n);
+// seg = taps[0 .. len) times scale (a scale within 1e-12 of 1 is not applied) with the first headTaps taps zeroed: they leave the FFT
+// path for the direct head.  zeroThenScale: the order of the two steps, which decides the sign of the zeroed taps at a negative
+// scale -- plan groups zero first (-0.0), layered mode scales first (+0.0), and each keeps its order: the spectra's bits depend on it.
+void prepareSegment(const double* taps, int len, double scale, int headTaps, bool zeroThenScale, std::vector<double>& seg);
+void zeroHead(std::vector<double>& seg, int headTaps);      // the second step alone, for a segment that arrives scaled (buildHeff)
+// Host taps -> partition spectra of one IR slot, the one way an IR reaches the device: rows H / HDN of nParts partitions of P
+// samples, transformed with tw (and scratch where P > 4096); gainDev: P + 1 doubles for a gain table in flight.
+struct SpectraRows { double2* H; double2* HDN; cpq::FftTables tw; int P, nParts; double2* scratch; double* gainDev; };
+// Refuses a segment above the staging capacity (layer: for the message), clears the first clearRows rows (0: none), uploads seg,
+// transforms it, multiplies the spectra by gainsA and then gainsB (FilterSpec gains, air absorption; null or empty: none), checks
+// the launches and synchronises: the staging buffers and the caller's vectors are free when it returns.
+int loadSpectra(cpq_engine* e, int layer, const std::vector<double>& seg, const SpectraRows& r, int clearRows,
+                const std::vector<double>* gainsA, const std::vector<double>* gainsB);
 // engine_proc.cpp
 int uploadProcParams(cpq_engine* e);
 int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n);

@@ -431,35 +431,18 @@ int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double*
     // partition spectra of every layer (:919-946), the direct head's taps left out of the FFT path (:730-731), scaled
     // (:939-940), FilterSpec gains at the layer's own FFT size (:336-443), air absorption on the tail layers (:1060-1097)
     const double* irs[2] = { irL, irR };
-    const bool scaled = std::abs(scale - 1.0) > 1e-12;
-    std::vector<double> seg, gains;
+    std::vector<double> seg, gains, air;
     const int hPair = shared ? 0 : pairOf[0];
     for (int ch = 0; ch < 2; ++ch) {
         const int slot = shared ? ch : 2 * hPair + ch;
         for (int l = 0; l < pl.num_layers; ++l) {
             NativeLayer& t = g->layers[(size_t)l];
-            seg.assign(irs[ch] + pl.offset[l], irs[ch] + pl.offset[l] + pl.len[l]);
-            if (l == 0) for (int i = 0; i < headTaps && i < (int)seg.size(); ++i) seg[(size_t)i] = 0.0;
-            if (scaled) for (double& v : seg) v *= scale;
-            if ((int64_t)seg.size() > e->heffCap) return fail(e, CPQ_ERR_INVALID_ARG, "layer %d has %zu taps, staging capacity %lld", l, seg.size(), (long long)e->heffCap);
-            double2* Ht = t.H + (int64_t)slot * t.hRows * t.P;
-            double2* HDNt = t.HDN + (int64_t)slot * t.hRows;
-            CPQ_HIP(e, hipMemsetAsync(Ht, 0, (size_t)t.hRows * t.P * sizeof(double2), e->stream));
-            CPQ_HIP(e, hipMemsetAsync(HDNt, 0, (size_t)t.hRows * sizeof(double2), e->stream));
-            CPQ_HIP(e, hipMemcpyAsync(e->heffDev, seg.data(), seg.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-            cpq::launch_ir_spectra(e->stream, e->heffDev, (int)seg.size(), Ht, HDNt, cpq::FftTables{ t.tw, t.tw2, t.twCol, t.twSplit }, t.P, t.K, t.scratch);
-            if (spec) {
-                cpq::spectrumFilterGains(*spec, 2 * t.P, gains);
-                CPQ_HIP(e, hipMemcpyAsync(t.gainDev, gains.data(), gains.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-                cpq::launch_spectrum_gain(e->stream, Ht, HDNt, t.gainDev, t.P, t.K);
-                CPQ_HIP(e, hipStreamSynchronize(e->stream));
-                if (l > 0 && cpq::airAbsorptionGains(*spec, l, t.P + 1, gains)) {
-                    CPQ_HIP(e, hipMemcpyAsync(t.gainDev, gains.data(), gains.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-                    cpq::launch_spectrum_gain(e->stream, Ht, HDNt, t.gainDev, t.P, t.K);
-                }
-            }
-            CPQ_HIP(e, hipGetLastError());
-            CPQ_HIP(e, hipStreamSynchronize(e->stream));        // heffDev / gainDev / seg are reused
+            // the head zeroed, then scaled (:730-731 in front of :939-940): -0.0 taps at a negative scale
+            prepareSegment(irs[ch] + pl.offset[l], pl.len[l], scale, l == 0 ? headTaps : 0, true, seg);
+            if (spec) cpq::spectrumFilterGains(*spec, 2 * t.P, gains);
+            const bool damped = spec && l > 0 && cpq::airAbsorptionGains(*spec, l, t.P + 1, air);
+            const SpectraRows rows{ t.H + (int64_t)slot * t.hRows * t.P, t.HDN + (int64_t)slot * t.hRows, t.tables(), t.P, t.K, t.scratch, t.gainDev };
+            CPQ_TRY(loadSpectra(e, l, seg, rows, t.hRows, spec ? &gains : nullptr, damped ? &air : nullptr));
         }
     }
     return CPQ_OK;
@@ -527,6 +510,10 @@ static void replayCall(const cpq_engine* e, PlanGroup& g, int n, std::vector<lon
     }
 }
 
+// the group sits this call out: only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a
+// NUC-level call runs every stream
+static bool resting(const cpq_engine* e, const PlanGroup& g) { return g.frozen && e->honourFrozen; }
+
 // layer 0 had no input waiting and nothing in its output ring before this call (w0 = its write position then)
 static bool layer0WasEmpty(const PlanGroup& g, long long w0, long long r0)
 {
@@ -537,7 +524,7 @@ int groupsAppend(cpq_engine* e, const double* dIn, int n)
 {
     for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
-        if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
+        if (resting(e, g)) continue;
         // every layer accumulates the same input (Add(), :1431-1446): one pass over it.  A layer whose accumulator is
         // empty and for which the call is whole partitions needs no accumulation at all when the group's rows are the
         // call's rows: its forward transforms run right here, straight from the call's input (before anything can write
@@ -565,7 +552,7 @@ int groupsAppend(cpq_engine* e, const double* dIn, int n)
                 if (hold0 && &t == &g.layers[0]) continue;
                 ProfScope p(e, CPQ_K_RFFT_FWD);
                 cpq::launch_rfft_fwd_ols(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
-                                         cpq::FftTables{ t.tw, t.tw2, t.twCol, t.twSplit }, t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
+                                         t.tables(), t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
                 continue;
             }
             dst[nl] = t.acc[t.accSel];
@@ -580,13 +567,13 @@ int groupsAppend(cpq_engine* e, const double* dIn, int n)
             ProfScope p(e, CPQ_K_RFFT_FWD);
             if (cpq::rfft_fwd_can_carry_side(t.P, nl, stride, off, ride ? (int)g.tabHost.size() : 0)) {
                 cpq::launch_rfft_fwd_ols_side(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
-                                              cpq::FftTables{ t.tw, t.tw2, t.twCol, t.twSplit }, g.usedCh, n / t.P, t.head, t.ringSlots, nl, dst,
+                                              t.tables(), g.usedCh, n / t.P, t.head, t.ringSlots, nl, dst,
                                               stride, off, ride ? g.tabDev : nullptr, g.tabHost.data(), ride ? (int)g.tabHost.size() : 0);
                 gathered = true;
                 g.tabOnDevice = ride;
             } else {
                 cpq::launch_rfft_fwd_ols(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
-                                         cpq::FftTables{ t.tw, t.tw2, t.twCol, t.twSplit }, t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
+                                         t.tables(), t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
             }
         }
         if (!gathered) {
@@ -614,7 +601,7 @@ static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, co
     const int rem = total - nb * t.P;
     const int nCh = g.usedCh;
     if (nb > 0) {
-        const cpq::FftTables tw{ t.tw, t.tw2, t.twCol, t.twSplit };
+        const cpq::FftTables tw = t.tables();
         bool remMoved = false;
         if (t.fftAhead != nb) {        // (else: transformed straight from the call's input in groupsAppend)
             ProfScope p(e, CPQ_K_RFFT_FWD);
@@ -642,12 +629,7 @@ static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, co
             // the output ring is passed by -- read and write positions advanced together on the host), otherwise into the
             // layer's output ring / delay line at the replayed positions, written by the transform itself
             ProfScope p(e, CPQ_K_RFFT_INV);
-            if (directOut && addTails) {
-                NativeLayer& a = g.layers[1];
-                NativeLayer* b = g.layers.size() == 3 ? &g.layers[2] : nullptr;
-                cpq::launch_rfft_inv_ols_add(e->stream, t.Y, directOut, (int64_t)n, tw, nCh, nb, a.ring, a.outRing, g.tabDev + g.tabOffs[2], a.gain,
-                                             b ? b->ring : nullptr, b ? b->outRing : 2, b ? g.tabDev + g.tabOffs[4] : nullptr, b ? b->gain : 0.0);
-            }
+            if (directOut && addTails) cpq::launch_rfft_inv_ols_add(e->stream, t.Y, directOut, (int64_t)n, tw, nCh, nb, g.tap(1), g.tap(2));
             else if (directOut) cpq::launch_rfft_inv_ols(e->stream, t.Y, directOut, (int64_t)n, tw, t.P, nCh, nb, t.scratch);
             else           cpq::launch_rfft_inv_ols_ring(e->stream, t.Y, t.ring, t.outRing, putPos, ringPos0, tw, t.P, nCh, nb, t.scratch);
         }
@@ -669,7 +651,7 @@ int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
 {
     for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
-        if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
+        if (resting(e, g)) continue;
         const long long w0 = g.callW0, r0 = g.callR0;        // (replayed in groupsAppend)
         if (!g.tabOnDevice) CPQ_TRY(stageUpload(e, g.tabDev, g.tabHost.data(), g.tabHost.size() * sizeof(long long)));
         // Whole-block call on an empty ring, every chunk's Get() taking exactly the chunk this call's blocks produce, members =
@@ -700,8 +682,8 @@ int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
         g.getDeferred = !direct && !e->anyDirect && g.layers.size() >= 2 && g.layers.size() <= 3;
         if (!direct && !g.getDeferred) {
             ProfScope p(e, CPQ_K_MIX);
-            cpq::launch_ring_get_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, g.layers[0].ring, g.layers[0].outRing,
-                                        g.tabDev + g.tabOffs[0], g.tabDev + g.tabOffs[1], g.usedCh);
+            cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, g.layers[0].ring, g.layers[0].outRing,
+                                    g.tabDev + g.tabOffs[0], g.tabDev + g.tabOffs[1], cpq::RingTap{}, cpq::RingTap{}, g.usedCh);
         }
         g.samplesSinceReset += n;
         g.lastCall = n;
@@ -717,31 +699,21 @@ int groupsRunTails(cpq_engine* e, double* dOut, int n)
 {
     for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
-        if (g.frozen && e->honourFrozen) continue;      // only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a NUC-level call runs every stream
+        if (resting(e, g)) continue;
         if (g.tailsDone) { g.tailsDone = false; continue; }     // (ran ahead of layer 0, whose transform added their blocks: groupsRunLayer0)
         for (size_t l = 1; l < g.layers.size(); ++l) {
             CPQ_TRY(runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0));
         }
+        // one pass over the output: layer 0's chunk-wise ring read where it was deferred, then the delay lines (layer 1 first, as
+        // Get() adds them)
         ProfScope p(e, CPQ_K_MIX);
-        if (g.getDeferred) {
-            g.getDeferred = false;
-            NativeLayer& z = g.layers[0];
-            NativeLayer& a = g.layers[1];
-            NativeLayer* b = g.layers.size() == 3 ? &g.layers[2] : nullptr;
-            cpq::launch_ring_get_add_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, z.ring, z.outRing, g.tabDev + g.tabOffs[0], g.tabDev + g.tabOffs[1],
-                                            a.ring, a.outRing, g.tabDev + g.tabOffs[2], a.gain,
-                                            b ? b->ring : nullptr, b ? b->outRing : 2, b ? g.tabDev + g.tabOffs[4] : nullptr, b ? b->gain : 0.0, g.usedCh);
-            continue;
-        }
-        if (g.layers.size() == 3) {          // both delay lines in one pass over the output (layer 1 first, as Get() adds them)
-            NativeLayer& a = g.layers[1];
-            NativeLayer& b = g.layers[2];
-            cpq::launch_ring_add_chunks2(e->stream, dOut, n, g.chMapDev, n, e->B, a.ring, a.outRing, g.tabDev + g.tabOffs[2], a.gain,
-                                         b.ring, b.outRing, g.tabDev + g.tabOffs[4], b.gain, g.usedCh);
-        } else if (g.layers.size() == 2) {
-            NativeLayer& t = g.layers[1];
-            cpq::launch_ring_add_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, t.ring, t.outRing, g.tabDev + g.tabOffs[2], t.gain, g.usedCh);
-        }
+        const NativeLayer& z = g.layers[0];
+        if (g.getDeferred)
+            cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, z.ring, z.outRing, g.tabDev + g.tabOffs[0], g.tabDev + g.tabOffs[1],
+                                    g.tap(1), g.tap(2), g.usedCh);
+        else if (g.layers.size() == 2 || g.layers.size() == 3)
+            cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, nullptr, 0, nullptr, nullptr, g.tap(1), g.tap(2), g.usedCh);
+        g.getDeferred = false;
     }
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;

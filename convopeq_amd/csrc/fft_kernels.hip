@@ -349,7 +349,7 @@ __global__ __launch_bounds__(64) void k_ir_spectra(const double* __restrict__ he
 //           natural-time tail outputs where the sample lies inside the call, from the layer's ring where it is older) --
 //           the read-modify-write pass over the call's output that k_layer_combine would make is gone.
 //   MODE 3: the output rows PLUS the delay-line read-add of a plan group's tail layers (Get(), :1620-1633: layer 1 first, then
-//           layer 2, `dst += src` or `dst += src * gain`) where every block is one chunk of the call: what k_ring_add_chunks[2]
+//           layer 2, `dst += src` or `dst += src * gain`) where every block is one chunk of the call: what k_ring_chunks
 //           would do in a pass of its own over the output.
 struct OutSpec {
     double* ring; int mask; const long long* pos; long long pos0;                                  // MODE 1; MODE 3: ring A, its mask, its schedule
@@ -1270,12 +1270,11 @@ void launch_rfft_inv_ols(hipStream_t stream, const double2* Y, double* out, int6
 }
 
 void launch_rfft_inv_ols_add(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw, int nCh, int T,
-                             const double* ringA, int ringSizeA, const long long* schedA, double gainA,
-                             const double* ringB, int ringSizeB, const long long* schedB, double gainB)
+                             RingTap a, RingTap b)
 {
     OutSpec os{};
-    os.ring = const_cast<double*>(ringA); os.mask = ringSizeA - 1; os.pos = schedA; os.g1 = gainA;
-    os.ringB = ringB; os.maskB = ringSizeB - 1; os.schedB = schedB; os.g2 = gainB;
+    os.ring = const_cast<double*>(a.ring); os.mask = a.ringSize - 1; os.pos = a.sched; os.g1 = a.gain;
+    os.ringB = b.ring; os.maskB = b.ringSize - 1; os.schedB = b.sched; os.g2 = b.gain;
     hipLaunchKernelGGL(k_rfft_inv_ols<3>, dim3(nCh * T), dim3(64), 0, stream, Y, out, chStride, tw, T, os);
 }
 

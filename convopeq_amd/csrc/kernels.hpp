@@ -41,11 +41,19 @@ void launch_rfft_fwd_ols_side(hipStream_t stream, const double* in, int64_t chSt
                               double2* XDN, FftTables tw, int nCh, int T, int head, int ringSlots, int nSide, double* const* dst,
                               const int64_t* dstStride, const int64_t* dstOff, long long* tabDst, const long long* tab, int nTab,
                               double* tailDst = nullptr, int64_t tailStride = 0, int tailLen = 0);      // tail*: the tailLen samples behind the T blocks of every source row -> tailDst rows
+// One tail layer's tap on the output (Get(), :1620-1633): the layer's delay line ([channel][ringSize], a power of two), the ring
+// position each chunk -- or, for the inverse transform below, each block -- reads from (negative: nothing to add) and the layer's
+// gain: out = out + ring (gain within 1e-12 of 1) or out + ring * gain.  An empty tap (ring == nullptr) means "no such layer".
+struct RingTap {
+    const double* ring = nullptr;
+    int ringSize = 2;
+    const long long* sched = nullptr;
+    double gain = 0.0;
+};
 // P = 512 inverse transform that also adds the delay-line blocks of up to two tail layers to the rows it stores: block t reads
-// ring X at schedX[t] (negative: nothing to add), out = out + ring (gain within 1e-12 of 1) or out + ring * gain, A before B
+// tap x at x.sched[t], a before b (b may be empty)
 void launch_rfft_inv_ols_add(hipStream_t stream, const double2* Y, double* out, int64_t chStride, FftTables tw, int nCh, int T,
-                             const double* ringA, int ringSizeA, const long long* schedA, double gainA,
-                             const double* ringB, int ringSizeB, const long long* schedB, double gainB);
+                             RingTap a, RingTap b);
 
 // IR partition spectra: frames [h[k*P .. (k+1)*P) | 0] for k < nParts.
 void launch_ir_spectra(hipStream_t stream, const double* heff, int heffLen, double2* H, double2* HDN,
@@ -167,25 +175,18 @@ void launch_tail_schedule(hipStream_t stream, void* state, long long* sched, int
 
 // Plan groups (engine_native.cpp): chMap[local channel] = row of the call's buffers (-1 = unused slot); q = chunk length
 // (one Add / Get pair of the reference per chunk); pos / cnt / sched: per chunk, replayed on the host.
-// up to three layers' accumulators in one pass over the input; both tail layers' read-add in one pass over the output
+// up to three layers' accumulators in one pass over the input
 // tabDst / tab / nTab: a small table (<= kGatherTabMax entries) that rides along as kernel arguments and is stored to tabDst by
 // the launch -- the call's chunk schedule of a plan group without a host -> device copy of its own
 constexpr int kGatherTabMax = 64;
 void launch_rows_gather_multi(hipStream_t stream, const double* src, int64_t srcStride, const int* chMap, int nLayers,
                               double* const* dst, const int64_t* dstStride, const int64_t* dstOff, int n, int nCh,
                               long long* tabDst = nullptr, const long long* tab = nullptr, int nTab = 0);
-void launch_ring_add_chunks2(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                             const double* ringA, int ringSizeA, const long long* schedA, double gainA,
-                             const double* ringB, int ringSizeB, const long long* schedB, double gainB, int nCh);
-// launch_ring_get_chunks and launch_ring_add_chunks[2] in one pass over the output (ringB may be null)
-void launch_ring_get_add_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                                const double* ring0, int ringSize0, const long long* pos, const long long* cnt,
-                                const double* ringA, int ringSizeA, const long long* schedA, double gainA,
-                                const double* ringB, int ringSizeB, const long long* schedB, double gainB, int nCh);
-void launch_ring_get_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                            const double* ring, int ringSize, const long long* pos, const long long* cnt, int nCh);
-void launch_ring_add_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                            const double* ring, int ringSize, const long long* sched, double gain, int nCh);
+// Get() of a call in one pass over the members' output rows.  ring0 != nullptr: out = layer 0's ring read chunk by chunk
+// (cnt[chunk] samples from pos[chunk], zero-filled to the chunk's end), every sample stored; ring0 == nullptr: out is read, and a
+// sample is stored only where a tap is scheduled for its chunk.  Then tap a and tap b are added, in that order; either may be empty.
+void launch_ring_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q, const double* ring0,
+                        int ringSize0, const long long* pos, const long long* cnt, RingTap a, RingTap b, int nCh);
 
 // EQ bypass cross-fade for the streams flagged in `on`: out = out * g + dry * (1 - g); g = gains[s][i] for i < len[s], gEnd[s] after
 void launch_bypass_blend(hipStream_t stream, double* out, int64_t outStride, const double* dry, int64_t dryStride, int n,

@@ -251,8 +251,7 @@ __global__ __launch_bounds__(256) void k_ring_put(const double* __restrict__ z, 
 // ---- plan groups (engine_native.cpp): a group's channels are rows chMap[local] of the call's buffers (-1 = unused slot);
 // every Add / Get pair of the reference is one CHUNK of the call (q samples, the last one possibly shorter), whose read
 // positions the host replays (ringRead :1376-1402, delayLineReadAdd :1653-1688) and uploads per call.
-// Get() of layer 0 per chunk: cnt[cb] samples from ring position pos[cb], zero-filled to the chunk's end (:1376-1402)
-// the call's input into the accumulators of up to three layers of a plan group at once (Add(): every layer accumulates the
+// The call's input into the accumulators of up to three layers of a plan group at once (Add(): every layer accumulates the
 // same input, src/MKLNonUniformConvolver.cpp:1431-1446): the input row is read once
 struct GatherDst { double* dst[3]; long long stride[3]; long long off[3]; int n; };
 struct GatherTab { long long* dst; int n; long long v[kGatherTabMax]; };
@@ -275,91 +274,34 @@ __global__ __launch_bounds__(256) void k_rows_gather_multi(const double* __restr
     }
 }
 
-// delay-line read-add of both tail layers in one pass over the output (Get(), :1620-1633: layer 1 first, then layer 2)
-__global__ __launch_bounds__(256) void k_ring_add_chunks2(double* __restrict__ out, int64_t outStride,
-                                                          const int* __restrict__ chMap, int n, int q,
-                                                          const double* __restrict__ ringA, int maskA,
-                                                          const long long* __restrict__ schedA, double gainA,
-                                                          const double* __restrict__ ringB, int maskB,
-                                                          const long long* __restrict__ schedB, double gainB)
+// Get() of a whole call in ONE pass over the members' output rows (:1606-1633).  GET: the chunk-wise read of layer 0's ring, cnt[cb]
+// samples from ring position pos[cb], zero-filled to the chunk's end (ringRead, :1376-1402); otherwise the row is read, and a
+// sample whose chunk has nothing scheduled on either tap is not stored.  Then delayLineReadAdd of up to two tail layers, a before
+// b as Get() adds them (sched[cb] < 0: the writer is not far enough ahead, nothing is added; an empty tap: no such layer).
+template <bool GET>
+__global__ __launch_bounds__(256) void k_ring_chunks(double* __restrict__ out, int64_t outStride, const int* __restrict__ chMap,
+                                                     int n, int q, const double* __restrict__ ring0, int mask0,
+                                                     const long long* __restrict__ pos, const long long* __restrict__ cnt,
+                                                     RingTap a, RingTap b)
 {
     const int g = chMap[blockIdx.y];
     if (g < 0) return;
     double* o = out + (int64_t)g * outStride;
-    const double* ra = ringA + (int64_t)blockIdx.y * (maskA + 1);
-    const double* rb = ringB + (int64_t)blockIdx.y * (maskB + 1);
-    const bool unityA = fabs(gainA - 1.0) < 1.0e-12, unityB = fabs(gainB - 1.0) < 1.0e-12;
+    const double* r0 = GET ? ring0 + (int64_t)blockIdx.y * (mask0 + 1) : nullptr;
+    const int maskA = a.ringSize - 1, maskB = b.ringSize - 1;
+    const double* ra = a.ring ? a.ring + (int64_t)blockIdx.y * a.ringSize : nullptr;
+    const double* rb = b.ring ? b.ring + (int64_t)blockIdx.y * b.ringSize : nullptr;
+    const bool unityA = fabs(a.gain - 1.0) < 1.0e-12, unityB = fabs(b.gain - 1.0) < 1.0e-12;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const int cb = i / q, j = i - cb * q;
-        const long long sa = schedA[cb], sb = schedB[cb];
-        if (sa < 0 && sb < 0) continue;
-        double v = o[i];
-        if (sa >= 0) { const double a = ra[(sa + j) & maskA]; v = unityA ? (v + a) : (v + a * gainA); }
-        if (sb >= 0) { const double b = rb[(sb + j) & maskB]; v = unityB ? (v + b) : (v + b * gainB); }
+        const long long sa = ra ? a.sched[cb] : -1, sb = rb ? b.sched[cb] : -1;
+        if (!GET && sa < 0 && sb < 0) continue;
+        double v;
+        if (GET) v = (j < cnt[cb]) ? r0[(pos[cb] + j) & mask0] : 0.0;
+        else     v = o[i];
+        if (sa >= 0) { const double x = ra[(sa + j) & maskA]; v = unityA ? (v + x) : (v + x * a.gain); }
+        if (sb >= 0) { const double x = rb[(sb + j) & maskB]; v = unityB ? (v + x) : (v + x * b.gain); }
         o[i] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ring_get_chunks(double* __restrict__ out, int64_t outStride,
-                                                         const int* __restrict__ chMap, int n, int q,
-                                                         const double* __restrict__ ring, int mask,
-                                                         const long long* __restrict__ pos, const long long* __restrict__ cnt)
-{
-    const int g = chMap[blockIdx.y];
-    if (g < 0) return;
-    double* o = out + (int64_t)g * outStride;
-    const double* r = ring + (int64_t)blockIdx.y * (mask + 1);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int cb = i / q, j = i - cb * q;
-        o[i] = (j < cnt[cb]) ? r[(pos[cb] + j) & mask] : 0.0;
-    }
-}
-
-// Get() of a whole call in ONE pass over the members' output rows: the chunk-wise read of layer 0's ring with its zero-fill
-// (k_ring_get_chunks) and behind it the delay-line read-add of one or two tail layers (k_ring_add_chunks[2]); ringB may be null
-__global__ __launch_bounds__(256) void k_ring_get_add_chunks(double* __restrict__ out, int64_t outStride,
-                                                             const int* __restrict__ chMap, int n, int q,
-                                                             const double* __restrict__ ring0, int mask0,
-                                                             const long long* __restrict__ pos, const long long* __restrict__ cnt,
-                                                             const double* __restrict__ ringA, int maskA,
-                                                             const long long* __restrict__ schedA, double gainA,
-                                                             const double* __restrict__ ringB, int maskB,
-                                                             const long long* __restrict__ schedB, double gainB)
-{
-    const int g = chMap[blockIdx.y];
-    if (g < 0) return;
-    double* o = out + (int64_t)g * outStride;
-    const double* r0 = ring0 + (int64_t)blockIdx.y * (mask0 + 1);
-    const double* ra = ringA + (int64_t)blockIdx.y * (maskA + 1);
-    const double* rb = ringB ? ringB + (int64_t)blockIdx.y * (maskB + 1) : nullptr;
-    const bool unityA = fabs(gainA - 1.0) < 1.0e-12, unityB = fabs(gainB - 1.0) < 1.0e-12;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int cb = i / q, j = i - cb * q;
-        double v = (j < cnt[cb]) ? r0[(pos[cb] + j) & mask0] : 0.0;
-        const long long sa = schedA[cb], sb = rb ? schedB[cb] : -1;
-        if (sa >= 0) { const double a = ra[(sa + j) & maskA]; v = unityA ? (v + a) : (v + a * gainA); }
-        if (sb >= 0) { const double b = rb[(sb + j) & maskB]; v = unityB ? (v + b) : (v + b * gainB); }
-        o[i] = v;
-    }
-}
-
-// delayLineReadAdd per chunk (sched[cb] < 0: the writer is not far enough ahead, nothing is added)
-__global__ __launch_bounds__(256) void k_ring_add_chunks(double* __restrict__ out, int64_t outStride,
-                                                         const int* __restrict__ chMap, int n, int q,
-                                                         const double* __restrict__ ring, int mask,
-                                                         const long long* __restrict__ sched, double gain)
-{
-    const int g = chMap[blockIdx.y];
-    if (g < 0) return;
-    double* o = out + (int64_t)g * outStride;
-    const double* r = ring + (int64_t)blockIdx.y * (mask + 1);
-    const bool unity = fabs(gain - 1.0) < 1.0e-12;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int cb = i / q, j = i - cb * q;
-        const long long s0 = sched[cb];
-        if (s0 < 0) continue;
-        const double v = r[(s0 + j) & mask];
-        o[i] = unity ? (o[i] + v) : (o[i] + v * gain);
     }
 }
 
@@ -477,6 +419,8 @@ __global__ __launch_bounds__(256) void k_rows_scale(double* data, int64_t stride
 
 }  // namespace
 
+static dim3 rowsGrid(int n, int nCh) { int bx = (n + 255) / 256; if (bx > 64) bx = 64; if (bx < 1) bx = 1; return dim3(bx, nCh); }
+
 void launch_agc_block_rms(hipStream_t stream, const double* x, int64_t chStride, int nCh, int B, int T, double* rms)
 {
     hipLaunchKernelGGL(k_agc_block_rms, dim3((nCh * T + 15) / 16), dim3(64), 0, stream, x, chStride, nCh, B, T, rms);
@@ -507,21 +451,15 @@ void launch_convproc_mix(hipStream_t stream, const double* wet, double* out, int
                          const int* rampLen, const double* rampGains, int rampCap, int rampOff, const int* wetOn)
 {
     if (nSamples <= 0) return;
-    int bx = (nSamples + 255) / 256;
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(k_convproc_mix, dim3(bx, nCh), dim3(256), 0, stream, wet, out, chStride, nSamples, gains, ring,
+    hipLaunchKernelGGL(k_convproc_mix, rowsGrid(nSamples, nCh), dim3(256), 0, stream, wet, out, chStride, nSamples, gains, ring,
                        ringSize - 1, pos0, dNew, dOld, xLen, xGains, xCap, wetValid, rampLen, rampGains, rampCap, rampOff, wetOn);
 }
 
 void launch_ring_regrow(hipStream_t stream, const double* oldRing, int oldSize, double* newRing, int newSize, long long end,
                         int nCh)
 {
-    int bx = (oldSize + 255) / 256;
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(k_ring_regrow, dim3(bx, nCh), dim3(256), 0, stream, oldRing, oldSize - 1, newRing, newSize - 1, end);
+    hipLaunchKernelGGL(k_ring_regrow, rowsGrid(oldSize, nCh), dim3(256), 0, stream, oldRing, oldSize - 1, newRing, newSize - 1, end);
 }
-
-static dim3 rowsGrid(int n, int nCh) { int bx = (n + 255) / 256; if (bx > 64) bx = 64; if (bx < 1) bx = 1; return dim3(bx, nCh); }
 
 void launch_rows_copy(hipStream_t stream, const double* src, int64_t srcStride, int64_t srcOff, double* dst,
                       int64_t dstStride, int64_t dstOff, int n, int nCh)
@@ -570,39 +508,16 @@ void launch_rows_gather_multi(hipStream_t stream, const double* src, int64_t src
     hipLaunchKernelGGL(k_rows_gather_multi, rowsGrid(n, nCh), dim3(256), 0, stream, src, srcStride, chMap, d, n, gt);
 }
 
-void launch_ring_add_chunks2(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                             const double* ringA, int ringSizeA, const long long* schedA, double gainA,
-                             const double* ringB, int ringSizeB, const long long* schedB, double gainB, int nCh)
+void launch_ring_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q, const double* ring0,
+                        int ringSize0, const long long* pos, const long long* cnt, RingTap a, RingTap b, int nCh)
 {
     if (n <= 0 || nCh <= 0) return;
-    hipLaunchKernelGGL(k_ring_add_chunks2, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, ringA,
-                       ringSizeA - 1, schedA, gainA, ringB, ringSizeB - 1, schedB, gainB);
-}
-
-void launch_ring_get_add_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                                const double* ring0, int ringSize0, const long long* pos, const long long* cnt,
-                                const double* ringA, int ringSizeA, const long long* schedA, double gainA,
-                                const double* ringB, int ringSizeB, const long long* schedB, double gainB, int nCh)
-{
-    if (n <= 0 || nCh <= 0) return;
-    hipLaunchKernelGGL(k_ring_get_add_chunks, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, ring0, ringSize0 - 1, pos, cnt,
-                       ringA, ringSizeA - 1, schedA, gainA, ringB, ringSizeB - 1, schedB, gainB);
-}
-
-void launch_ring_get_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                            const double* ring, int ringSize, const long long* pos, const long long* cnt, int nCh)
-{
-    if (n <= 0 || nCh <= 0) return;
-    hipLaunchKernelGGL(k_ring_get_chunks, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, ring,
-                       ringSize - 1, pos, cnt);
-}
-
-void launch_ring_add_chunks(hipStream_t stream, double* out, int64_t outStride, const int* chMap, int n, int q,
-                            const double* ring, int ringSize, const long long* sched, double gain, int nCh)
-{
-    if (n <= 0 || nCh <= 0) return;
-    hipLaunchKernelGGL(k_ring_add_chunks, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, ring,
-                       ringSize - 1, sched, gain);
+    if (ring0)
+        hipLaunchKernelGGL(k_ring_chunks<true>, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, ring0,
+                           ringSize0 - 1, pos, cnt, a, b);
+    else
+        hipLaunchKernelGGL(k_ring_chunks<false>, rowsGrid(n, nCh), dim3(256), 0, stream, out, outStride, chMap, n, q, nullptr, 0,
+                           nullptr, nullptr, a, b);
 }
 
 void launch_tail_append(hipStream_t stream, const void* state, const double* layerOut, double* ring, int nCh, int nSamples,

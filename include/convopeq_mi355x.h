@@ -858,10 +858,11 @@ int32_t     cpq_diag_agc(int32_t op, int32_t n_ch, int32_t B, int32_t T, int64_t
  * channel, -1 = unused slot), n samples in chunks of q (ceil(n / q) chunks, the last one possibly shorter):
  *   op 0 launch_rows_gather_multi: out is the source; n_dst destinations dst0 .. dst2: [n_ch][dst_stride[l]] (out), the n samples
  *        at dst_off[l] of every row; tab[0 .. n_tab) stored to tab_out: [64] (out).
- *   op 1 launch_ring_get_chunks: ring0: [n_ch][size0], pos, cnt: [chunks].
- *   op 2 launch_ring_add_chunks: ring_a: [n_ch][size_a], sched_a: [chunks] (negative: nothing added), gain_a.
- *   op 3 launch_ring_add_chunks2: ring_a and ring_b with their schedules and gains.
- *   op 4 launch_ring_get_add_chunks: ring0, pos, cnt, ring_a, sched_a, gain_a; ring_b may be null.
+ *   ops 1 .. 4 are launch_ring_chunks, with or without the read of layer 0's ring in front and with no, one or two tail taps:
+ *   op 1 the read alone: ring0: [n_ch][size0], pos, cnt: [chunks].
+ *   op 2 one tap added to out: ring_a: [n_ch][size_a], sched_a: [chunks] (negative: nothing added), gain_a.
+ *   op 3 two taps added to out: ring_a and ring_b with their schedules and gains.
+ *   op 4 the read, then the taps: ring0, pos, cnt, ring_a, sched_a, gain_a; ring_b may be null.
  *   Refused unless: op in 0 .. 4; rows, n_ch, n, q >= 1; out_stride >= n; every ch_map entry -1 or < rows and no row named
  *   twice; ring sizes powers of two >= 2; 0 <= cnt <= q; 0 <= pos <= 2^62; schedule entries <= 2^62; op 0: 1 <= n_dst <= 3,
  *   0 <= dst_off[l], dst_off[l] + n <= dst_stride[l], 0 <= n_tab <= 64 (the launcher would drop a longer table silently). */

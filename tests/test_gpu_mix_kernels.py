@@ -19,10 +19,8 @@ Kernels and a case that runs each:
   k_agc_ramp             test_agc_gains_table (launch_agc_apply), test_gain_ramp[*] (launch_gain_ramp)
   k_block_silence        test_block_silence[*]
   k_rows_gather_multi    test_gather[*]
-  k_ring_get_chunks      test_ring_chunks[*] (op get)
-  k_ring_add_chunks      test_ring_chunks[*] (op add)
-  k_ring_add_chunks2     test_ring_chunks[*] (op add2)
-  k_ring_get_add_chunks  test_ring_chunks[*] (fused, with and without ring B)
+  k_ring_chunks<true>    test_ring_chunks[*] (op get; fused, with and without ring B)
+  k_ring_chunks<false>   test_ring_chunks[*] (op add, op add2)
   k_convproc_mix         test_convproc_mix[*], test_convproc_mix_null_lengths, test_put_then_mix
   k_ring_put             test_put_then_mix
   k_ring_regrow          test_ring_regrow[*]
