@@ -18,6 +18,7 @@ CPQ_ERR_OOM = -3
 CPQ_ERR_DEVICE = -4
 CPQ_ERR_UNSUPPORTED = -5
 CPQ_ERR_NOT_READY = -6
+CPQ_ERR_SILENT_IR = -7
 CPQ_ALL_STREAMS = -1
 CPQ_SEM_REFERENCE = 0
 CPQ_SEM_EXACT = 1
@@ -38,6 +39,9 @@ CPQ_EQ_MODE_SEQUENTIAL = 1
 CPQ_PHASE_AS_IS = 0
 CPQ_PHASE_MIXED = 1
 CPQ_PHASE_MINIMUM = 2
+CPQ_RESAMPLE_LINEAR_PHASE = 0
+CPQ_RESAMPLE_MINIMUM_PHASE = 1
+CPQ_RESAMPLE_MAX_FACTOR = 1280
 CPQ_OS_IIR = 0
 CPQ_OS_LINEAR_PHASE = 1
 CPQ_METER_LOUDNESS = 1
@@ -131,6 +135,11 @@ class IrScale(C.Structure):
 
 class IrPrepared(C.Structure):
     _fields_ = [("ir", IrBuffer), ("scale", IrScale), ("ir_peak_latency", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ResampleInfo(C.Structure):
+    _fields_ = [("l", C.c_int32), ("m", C.c_int32), ("taps", C.c_int32), ("reserved", C.c_int32), ("group_delay", C.c_double),
+                ("cutoff", C.c_double), ("attenuation_db", C.c_double)]
 
 
 class OsStageInfo(C.Structure):
@@ -278,6 +287,11 @@ SYMBOLS = {
     "cpq_ir_compute_scale_factor": (C.c_int32, [C.POINTER(c_double_p), C.c_int32, C.c_int32, C.POINTER(c_double_p), C.c_int32, C.c_int32, C.c_double, C.POINTER(IrScale)]),
     "cpq_ir_estimate_max_frequency_response_gain": (C.c_double, [C.POINTER(c_double_p), C.c_int32, C.c_int32]),
     "cpq_ir_estimate_peak_latency": (C.c_int32, [C.POINTER(c_double_p), C.c_int32, C.c_int32]),
+    "cpq_resample_design": (C.c_int32, [C.c_double, C.c_double, C.POINTER(ResampleInfo), c_double_p, C.c_int32]),
+    "cpq_ir_resample": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
+    "cpq_ir_resample_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
+    "cpq_ir_resample_host": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
+    "cpq_ir_resample_last_kernel_ms": (C.c_double, []),
     "cpq_profile_enable": (C.c_int32, [_E, C.c_int32]),
     "cpq_profile_reset": (C.c_int32, [_E]),
     "cpq_profile_read": (C.c_int32, [_E, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -169,6 +169,7 @@ const char* cpq_status_string(int32_t s)
         case CPQ_ERR_DEVICE: return "HIP runtime error";
         case CPQ_ERR_UNSUPPORTED: return "not supported by this engine version";
         case CPQ_ERR_NOT_READY: return "engine not ready";
+        case CPQ_ERR_SILENT_IR: return "silent impulse response";
         default: return "unknown status";
     }
 }

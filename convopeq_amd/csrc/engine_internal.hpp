@@ -13,6 +13,8 @@
 //   engine_diag.cpp  every cpq_diag_* entry point: single launchers on caller-filled buffers, no engine
 //   engine_score.cpp  cpq_scorer, an object of its own: the fitness function of the adaptive shaper's learner (uses only fail and
 //                    the device buffers of this header)
+//   engine_resample.cpp  cpq_ir_resample / _batch: the device side of the IR sample-rate conversion, no engine (uses only fail and
+//                    the device buffers of this header; design, checks, host path and tail trim are resample_design.cpp's)
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
@@ -38,6 +40,7 @@
 #include "device_buffers.hpp"
 #include "host_design.hpp"
 #include "host_replay.hpp"
+#include "resample_design.hpp"
 #include "kernels.hpp"
 
 using cpq::kBands;

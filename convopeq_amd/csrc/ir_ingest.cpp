@@ -13,8 +13,8 @@
 //   * target length + fade-out               LoaderThread.cpp:619-636, StateAndUI.cpp:942-957
 //   * scale factor                           src/IRConverter.cpp:17-196, src/IRAnalyzer.cpp:63-155
 //   * peak latency (energy centroid)         LoaderThread.cpp:149-209
-// Not restated: sample-rate conversion (third-party r8brain, not in the reference tree) -- an IR at another rate is
-// refused with CPQ_ERR_UNSUPPORTED -- and the mixed phase transform (PhaseMode::AsIs and Minimum only).
+// Not here: sample-rate conversion, a call of its own (cpq_ir_resample, resample_design.cpp / engine_resample.cpp) -- cpq_ir_prepare
+// refuses an IR at another rate with CPQ_ERR_UNSUPPORTED -- and the mixed phase transform (PhaseMode::AsIs and Minimum only).
 //   * minimum phase                          src/convolver/ConvolverProcessor.ResampleAndFallback.cpp:333-469
 #include <algorithm>
 #include <cmath>
@@ -588,7 +588,7 @@ int32_t cpq_ir_prepare(const cpq_ir_buffer* loaded, double sample_rate, float ta
     if (phase_mode != CPQ_PHASE_AS_IS && phase_mode != CPQ_PHASE_MINIMUM)
         return phase_mode == CPQ_PHASE_MIXED ? CPQ_ERR_UNSUPPORTED : CPQ_ERR_INVALID_ARG;
     if (loaded->sample_rate > 0.0 && std::fabs(loaded->sample_rate - sample_rate) > 1e-6)
-        return CPQ_ERR_UNSUPPORTED;                               // needs the r8brain resampler
+        return CPQ_ERR_UNSUPPORTED;                               // cpq_ir_resample first
     const double rate = loaded->sample_rate > 0.0 ? loaded->sample_rate : 0.0;
 
     // trailing silence, DC blocker, window: on a working copy of the kept part

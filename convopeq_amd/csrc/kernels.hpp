@@ -322,4 +322,17 @@ void launch_score_spectrum(hipStream_t stream, const double* rows, double* thr, 
 void launch_score_reduce(hipStream_t stream, const double* blended, const int* counts, const int* state, int nLearners, int nCand,
                          const double* levelWeights, double* scores);
 
+// ---- IR sample-rate conversion (resample_kernels.hip): the polyphase filter taps [L][T] over a batch of rows of one source rate.
+// x and y hold the rows back to back; row r reads x[inOff ... inOff + n) and writes y[outOff ... outOff + nOut).  A workgroup
+// takes one tile: outputs j0 ... j0 + resampleTile() - 1 of tiles[block].row (cut at nOut).  Nothing here checks an index: the
+// tables are engine_resample.cpp's, built from validated lengths.
+constexpr int kResampleTileMax = 256;       // outputs a workgroup takes while M <= 8 L; 64 beyond, so that the stage fits LDS
+constexpr int kResampleChunk = 256;         // taps a workgroup stages the row for at a time
+struct ResampleRow { long long inOff, outOff; int n, nOut; };
+struct ResampleTile { int row, j0; };
+int resampleTile(int L, int M);
+int resampleSpan(int L, int M, int tile);   // input samples the first taps of a tile's outputs spread over
+void launch_ir_resample(hipStream_t stream, const double* taps, int L, int M, int T, const double* x, double* y, const ResampleRow* rows,
+                        const ResampleTile* tiles, int nTiles);
+
 }  // namespace cpq

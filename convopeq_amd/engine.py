@@ -212,6 +212,52 @@ def ir_convert_to_minimum_phase(ir, rate=48000.0):
         K.load().cpq_ir_buffer_free(C.byref(out))
 
 
+def resample_design(in_rate, out_rate):
+    """cpq_resample_design: dict(L, M, T, group_delay, cutoff, attenuation_db, in_rate, out_rate, taps=[L][T] float64)."""
+    lib = K.load()
+    info = K.ResampleInfo()
+    n = lib.cpq_resample_design(float(in_rate), float(out_rate), C.byref(info), None, 0)
+    if n < 0:
+        raise CpqError(n, "cpq_resample_design")
+    taps = np.zeros(n)
+    rc = lib.cpq_resample_design(float(in_rate), float(out_rate), C.byref(info), _dp(taps), n)
+    if rc < 0:
+        raise CpqError(rc, "cpq_resample_design")
+    return {"L": info.l, "M": info.m, "T": info.taps, "group_delay": info.group_delay, "cutoff": info.cutoff,
+            "attenuation_db": info.attenuation_db, "in_rate": int(in_rate), "out_rate": int(out_rate), "taps": taps.reshape(info.l, info.taps)}
+
+
+def _take_ir(b):
+    try:
+        return np.ctypeslib.as_array(b.data, shape=(b.n_channels, b.n_samples)).copy()
+    finally:
+        K.load().cpq_ir_buffer_free(C.byref(b))
+
+
+def ir_resample(ir, rate, target_rate, phase=K.CPQ_RESAMPLE_LINEAR_PHASE, host=False):
+    """cpq_ir_resample (host=True: cpq_ir_resample_host, no GPU): ir [channels][samples] at rate -> planes at target_rate."""
+    lib = K.load()
+    keep, b = _ir_buffer(ir, rate)
+    out = K.IrBuffer()
+    rc = (lib.cpq_ir_resample_host if host else lib.cpq_ir_resample)(C.byref(b), float(target_rate), phase, C.byref(out))
+    if rc != 0:
+        raise CpqError(rc, "cpq_ir_resample_host" if host else lib.cpq_last_error(None).decode())
+    return _take_ir(out)
+
+
+def ir_resample_batch(irs, target_rate, phase=K.CPQ_RESAMPLE_LINEAR_PHASE):
+    """cpq_ir_resample_batch: irs a list of (ir [channels][samples], rate); one launch per source rate.  A list of planes."""
+    lib = K.load()
+    pairs = [_ir_buffer(ir, rate) for ir, rate in irs]
+    bufs = (K.IrBuffer * len(pairs))(*[b for _, b in pairs])
+    ptrs = (C.POINTER(K.IrBuffer) * len(pairs))(*[C.pointer(bufs[i]) for i in range(len(pairs))])
+    outs = (K.IrBuffer * len(pairs))()
+    rc = lib.cpq_ir_resample_batch(ptrs, len(pairs), float(target_rate), phase, outs)
+    if rc != 0:
+        raise CpqError(rc, lib.cpq_last_error(None).decode())
+    return [_take_ir(outs[i]) for i in range(len(pairs))]
+
+
 def ir_compute_scale_factor(ir, current_ir=None, current_scale=1.0):
     a, pa = _planes(ir)
     cur_ptrs, cc, cn = None, 0, 0

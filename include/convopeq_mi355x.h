@@ -47,7 +47,8 @@ typedef enum {
     CPQ_ERR_OOM          = -3,
     CPQ_ERR_DEVICE       = -4,   /* a HIP call failed; see cpq_last_error() */
     CPQ_ERR_UNSUPPORTED  = -5,   /* valid in the reference, not implemented by this engine yet */
-    CPQ_ERR_NOT_READY    = -6    /* process before set_impulse / prepare */
+    CPQ_ERR_NOT_READY    = -6,   /* process before set_impulse / prepare */
+    CPQ_ERR_SILENT_IR    = -7    /* cpq_ir_resample*: the IR's peak is below 1e-12 (the reference's ResampleResult::SilentIR) */
 } cpq_status;
 
 #define CPQ_ALL_STREAMS (-1)
@@ -493,8 +494,8 @@ typedef enum { CPQ_PHASE_AS_IS = 0, CPQ_PHASE_MIXED = 1 /* not built: CPQ_ERR_UN
 /* doTrimStep + doTransformStep (LoaderThread.cpp:490-641, 644-709): trailing-silence trim, 1 Hz DC
  * blocker, asymmetric Tukey window about the peak, zero-padded / cut to int(rate * target_ir_length_sec) samples
  * (IR_LENGTH 0.5..3 s, default 1 s; cap 2^21) with a linear fade-out, computeScaleFactor against the IR playing now
- * (current_ir may be NULL), peak latency.  An IR whose rate differs from sample_rate needs the reference's third-party
- * resampler (r8brain): CPQ_ERR_UNSUPPORTED. */
+ * (current_ir may be NULL), peak latency.  An IR whose rate differs from sample_rate is refused with CPQ_ERR_UNSUPPORTED:
+ * convert it with cpq_ir_resample() first (the reference's loader does both in one step). */
 int32_t cpq_ir_prepare(const cpq_ir_buffer* loaded, double sample_rate, float target_ir_length_sec, int32_t phase_mode,
                        const cpq_ir_buffer* current_ir, double current_scale, cpq_ir_prepared* out);
 /* ConvolverProcessorInternal::convertToMinimumPhase (src/convolver/ConvolverProcessor.ResampleAndFallback.cpp:333-469):
@@ -512,6 +513,52 @@ int32_t cpq_ir_compute_scale_factor(const double* const* ir, int32_t n_channels,
 double  cpq_ir_estimate_max_frequency_response_gain(const double* const* ir, int32_t n_channels, int32_t n_samples);
 /* LoaderThread::estimatePeakLatencySamples (LoaderThread.cpp:149-209) */
 int32_t cpq_ir_estimate_peak_latency(const double* const* ir, int32_t n_channels, int32_t n_samples);
+
+/* ---------------------------------------------------------------- IR sample-rate conversion */
+/* ConvolverProcessorInternal::resampleIR (src/convolver/ConvolverProcessor.ResampleAndFallback.cpp:18-108), which the reference's
+ * loader runs on every IR before the trim (LoaderThread.cpp:555-587) with r8brain's CDSPResampler at a 2 % transition band,
+ * 140 dB stop band, linear phase.  Here: one linear-phase Kaiser-windowed sinc of the same class, as a polyphase table, applied
+ * by k_ir_resample to a whole batch of rows (a row is one channel of one IR) in one launch per source rate.
+ *
+ * Rates are whole numbers of Hz in 8000 ... 768000; in : out reduces by its gcd to M : L (L up, M down), and L or M above 1280
+ * is refused.  Output j of a row x of n samples, for j < ceil(n out / in), is
+ *     acc = 0;  for k = 0 ... T - 1:  acc = fma(taps[(j M) mod L][k], x[floor(j M / L) + T / 2 - k], acc)
+ * in fp64, in that order, with x zero outside 0 ... n - 1: output 0 sits at input time 0, the filter's group delay (T / 2 input
+ * samples) is removed and the ringing before t = 0 is dropped, as r8brain's oneshot() does.  The device and the host path compute
+ * exactly this, so they agree bit for bit and a row's result does not depend on what else is in the batch. */
+#define CPQ_HAS_IR_RESAMPLING 1
+#define CPQ_RESAMPLE_MAX_FACTOR 1280
+typedef enum { CPQ_RESAMPLE_LINEAR_PHASE = 0, CPQ_RESAMPLE_MINIMUM_PHASE = 1 /* not built: CPQ_ERR_UNSUPPORTED */ } cpq_resample_phase;
+typedef struct {
+    int32_t l, m;                    /* out : in reduced, l up and m down */
+    int32_t taps;                    /* T: taps per phase (even); the table is [l][taps] */
+    int32_t reserved;
+    double  group_delay;             /* in input samples: taps / 2 */
+    double  cutoff;                  /* -6 dB point as a fraction of the input's Nyquist frequency: 0.98 min(in, out) / in */
+    double  attenuation_db;          /* the Kaiser window's design attenuation */
+} cpq_resample_info;
+/* The filter of a rate pair (host only, no GPU).  The pass band ends at 0.96 and the stop band begins at 1.0 of the lower of the
+ * two Nyquist frequencies; every phase sums to 1.  Returns l * taps, the number of doubles of the table, and copies it to
+ * table[phase][tap] when table is not NULL.  CPQ_ERR_UNSUPPORTED: a rate that is not a whole number, outside 8000 ... 768000, or
+ * l or m above CPQ_RESAMPLE_MAX_FACTOR; CPQ_ERR_INVALID_ARG: capacity below l * taps.  Equal rates are not an error (l = m = 1). */
+int32_t cpq_resample_design(double in_rate, double out_rate, cpq_resample_info* info, double* table, int32_t capacity);
+/* in at in->sample_rate -> out at target_rate on the current device; out is the library's (cpq_ir_buffer_free) and is zeroed on
+ * any error.  Rates no more than 1e-6 apart: a copy, without a device.  Every channel is converted to ceil(n out / in) samples,
+ * then cut after the last run of 8 samples above -160 dB of its own peak (ResampleAndFallback.cpp:66-87, on the host); the buffer
+ * is as long as the longest channel and a channel is zero beyond its own length.  Refused before anything is allocated:
+ * CPQ_ERR_INVALID_ARG for a null argument, no channels, no samples, a rate that is not positive and finite (the reference hands
+ * such a buffer back unchanged) or an unknown phase; CPQ_ERR_SILENT_IR for a peak below 1e-12; CPQ_ERR_UNSUPPORTED for
+ * CPQ_RESAMPLE_MINIMUM_PHASE and for what cpq_resample_design refuses.  CPQ_ERR_NO_DEVICE without a gfx950 device: there is no
+ * quiet fall-back, the host path is a call of its own.  The reason is in cpq_last_error(NULL). */
+int32_t cpq_ir_resample(const cpq_ir_buffer* in, double target_rate, int32_t phase, cpq_ir_buffer* out);
+/* n IRs in one call: IRs of one source rate share one launch.  out[i] is what cpq_ir_resample(in[i]) returns, bit for bit.  All
+ * or nothing: on an error every out[i] is zeroed. */
+int32_t cpq_ir_resample_batch(const cpq_ir_buffer* const* in, int32_t n, double target_rate, int32_t phase, cpq_ir_buffer* out /* [n] */);
+/* milliseconds the kernel launches of this thread's last cpq_ir_resample* call took, from device events (the call's time also
+ * holds the transfers and the trim); negative when that call launched nothing */
+double  cpq_ir_resample_last_kernel_ms(void);
+/* the same table in the same summation order on the host's threads (at most 16): what the device is checked against; no GPU */
+int32_t cpq_ir_resample_host(const cpq_ir_buffer* in, double target_rate, int32_t phase, cpq_ir_buffer* out);
 
 /* ---------------------------------------------------------------- metering */
 /* The two meters DSPCore runs on the final block of every callback (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:
