@@ -12,6 +12,19 @@ namespace {
 std::string g_createError;
 std::mutex g_createErrorMutex;
 
+struct ArenaItem { void** ptr; int64_t bytes; };
+
+// the arena slices of one cascade's tables (layouts: cpq::CascadeTables), in the order they lie in the arena
+void cascadeSlices(cpq::CascadeTables& t, int64_t nCh, std::vector<ArenaItem>& items)
+{
+    const int64_t d = (int64_t)sizeof(double);
+    items.push_back({ (void**)&t.coef, nCh * kBands * 6 * d });
+    items.push_back({ (void**)&t.flags, nCh * kBands * (int64_t)sizeof(int) });
+    items.push_back({ (void**)&t.satGain, nCh * 2 * d });
+    items.push_back({ (void**)&t.state, (int64_t)t.stateDoubles((int)nCh) * d });
+    items.push_back({ (void**)&t.tp, (nCh / 2) * kBands * cpq::kSvfTpTableDoubles * d });
+}
+
 }  // namespace
 
 namespace cpqi {
@@ -141,8 +154,8 @@ int zeroRuntimeState(cpq_engine* e, bool conv, bool eq)
         for (auto& f : e->latFade) f = LatencyFade{};
     }
     if (eq) {
-        CPQ_HIP(e, hipMemsetAsync(e->svfState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
-        CPQ_HIP(e, hipMemsetAsync(e->ofState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
+        for (const cpq::CascadeTables* t : { &e->eqTab, &e->ofTab })
+            CPQ_HIP(e, hipMemsetAsync(t->state, 0, t->stateDoubles(e->nCh) * sizeof(double), e->stream));
         if (e->agcState) CPQ_TRY(agcStateReset(e, 0, e->desc.n_streams));
     }
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
@@ -323,7 +336,6 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
     e->heffCap = std::max<int64_t>((int64_t)e->kCap * e->P, d->max_ir_len);
 
     // ---- arena layout
-    struct Item { void** ptr; int64_t bytes; };
     const int64_t nCh = e->nCh;
     {
         int nCu = 0;
@@ -340,7 +352,7 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
         const double perChannel = (double)full + (r == 0 ? 0.0 : (2 * r <= e->svfChainGrid ? 0.70 : 1.0));
         chained = 1.06 * (double)nCh / (double)e->svfChainGrid < perChannel;
     }
-    Item items[] = {
+    std::vector<ArenaItem> items = {
         { (void**)&e->X, nCh * e->ringSlots * e->P * (int64_t)sizeof(double2) },
         { (void**)&e->XDN, nCh * e->ringSlots * (int64_t)sizeof(double2) },
         { (void**)&e->H, nCh * e->hRows * e->P * (int64_t)sizeof(double2) },
@@ -353,30 +365,22 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
         { (void**)&e->tw512, e->P * (int64_t)sizeof(double2) },
         { (void**)&e->tw1024, e->P * (int64_t)sizeof(double2) },
         { (void**)&e->irSlot, nCh * (int64_t)sizeof(int) },
-        { (void**)&e->svfCoef, nCh * kBands * 6 * (int64_t)sizeof(double) },
-        { (void**)&e->svfFlags, nCh * kBands * (int64_t)sizeof(int) },
-        { (void**)&e->svfSatGain, nCh * 2 * (int64_t)sizeof(double) },
-        { (void**)&e->svfState, nCh * kBands * 2 * (int64_t)sizeof(double) },
-        { (void**)&e->svfTp, (nCh / 2) * kBands * cpq::kSvfTpTableDoubles * (int64_t)sizeof(double) },
-        { (void**)&e->ofCoef, nCh * kBands * 6 * (int64_t)sizeof(double) },
-        { (void**)&e->ofFlags, nCh * kBands * (int64_t)sizeof(int) },
-        { (void**)&e->ofSatGain, nCh * 2 * (int64_t)sizeof(double) },
-        { (void**)&e->ofState, nCh * kBands * 2 * (int64_t)sizeof(double) },
-        { (void**)&e->ofTp, (nCh / 2) * kBands * cpq::kSvfTpTableDoubles * (int64_t)sizeof(double) },
-        // scheduling words of the time-parallel cascade (svf_kernels.hip): header, the arrival counters of the CUs, and -- only
-        // for engines that chain their spans (the rule above) -- the band states handed from span to span
-        { (void**)&e->svfChain, (int64_t)cpq::svf_chain_bytes((int)nCh, chained ? e->maxCall : 0) },
     };
+    cascadeSlices(e->eqTab, nCh, items);
+    cascadeSlices(e->ofTab, nCh, items);
+    // scheduling words of the time-parallel cascade (svf_kernels.hip): header, the arrival counters of the CUs, and -- only
+    // for engines that chain their spans (the rule above) -- the band states handed from span to span
+    items.push_back({ (void**)&e->svfChain, (int64_t)cpq::svf_chain_bytes((int)nCh, chained ? e->maxCall : 0) });
     e->svfChainSpans = chained ? cpq::svf_chain_spans(e->maxCall) : 0;
     int64_t total = 0;
-    for (const Item& it : items) total += alignUp(it.bytes, 256);
+    for (const ArenaItem& it : items) total += alignUp(it.bytes, 256);
     if (!e->arena.alloc((size_t)total)) {
         delete e;
         return fail(nullptr, CPQ_ERR_OOM, "device arena of %lld bytes could not be allocated", (long long)total);
     }
     e->arenaBytes = total;
     int64_t off = 0;
-    for (const Item& it : items) { *it.ptr = e->arena + off; off += alignUp(it.bytes, 256); }
+    for (const ArenaItem& it : items) { *it.ptr = e->arena + off; off += alignUp(it.bytes, 256); }
 
     // everything starts zero: FDL, history, IR spectra (incl. padding rows), SVF state
     if (hipMemset(e->arena, 0, (size_t)total) != hipSuccess) {
@@ -552,10 +556,7 @@ int cpqi::enqueueBoth(cpq_engine* e, const double* a, double* b, int n)
             const char pass = (e->convBypassed && e->eqBypass[s].requested) ? 1 : 0;
             anyActive = anyActive || !pass;
             if (pass == e->ofPass[s] || !e->ofModesSet[s]) continue;
-            int flags[2 * kBands] = {};
-            if (!pass) for (int ch = 0; ch < 2; ++ch) for (int k = 0; k < 3; ++k) flags[ch * kBands + k] = 1 | 4;
-            CPQ_TRY(stageUpload(e, e->ofFlags + (size_t)2 * s * kBands, flags, sizeof(flags)));
-            e->ofPass[s] = pass;
+            CPQ_TRY(setOutFilterPass(e, s, pass != 0));
         }
         if (anyActive) rc = enqueueOutFilter(e, b, b, n);
     }

@@ -17,19 +17,16 @@ int agcStateReset(cpq_engine* e, int s0, int n)
 
 // one cascade launch: the time-parallel kernels over every even number of samples, the lane-skewed one over a last odd sample (or everything)
 int enqueueCascade(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int n, bool tp, int idTp, int idSeq,
-                   const double* coef, const int* flags, const double* satGain, double* state, const double* tables,
-                   bool streamPairs = false)
+                   const cpq::CascadeTables& t, bool streamPairs = false)
 {
     const int nTp = tp ? n : 0;                   // the time-parallel kernels take any number of samples
     if (nTp > 0) {
         ProfScope p(e, idTp);
-        cpq::launch_svf_cascade_tp(e->stream, dIn, dOut, stride, e->nCh, nTp, coef, flags, satGain, state, tables,
-                                   e->svfChain, e->svfChainSpans, e->svfChainGrid);
+        cpq::launch_svf_cascade_tp(e->stream, dIn, dOut, stride, e->nCh, nTp, t, e->svfChain, e->svfChainSpans, e->svfChainGrid);
     }
     if (n > nTp) {
         ProfScope p(e, idSeq);
-        cpq::launch_svf_cascade(e->stream, dIn + nTp, dOut + nTp, stride, e->nCh, n - nTp, coef, flags, satGain,
-                                state, streamPairs);
+        cpq::launch_svf_cascade(e->stream, dIn + nTp, dOut + nTp, stride, e->nCh, n - nTp, t, streamPairs);
     }
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;
@@ -51,19 +48,23 @@ void syncEqBypass(cpq_engine* e)
     }
 }
 
+// Host image of one stream's cascade tables (cpq::CascadeTables), filled by one of the three functions below and written to the
+// device by uploadCascade alone.
+struct CascadeImage {
+    enum : unsigned { kCoef = 1, kFlags = 2, kSatGain = 4, kTp = 8, kAll = 15 };
+    double coef[2][kBands][6];
+    int flags[2][kBands];
+    std::vector<double> tp;
+    double satGain[2];          // saturation, total gain: the same in both channels
+    bool tpSafe = true, midSide = false;
+    unsigned parts = kAll;      // the tables uploadCascade writes
+};
+
 // Device tables of one stream's EQ as the reference would run it: createCoeffCache (bandActive = enabled && sr > 0,
 // src/eqprocessor/EQProcessor.ProcessingCache.cpp:71-90) or, for basicPath, the band nodes of the basic process(block)
 // (inactive for non-LP/HP bands within 0.01 dB of flat: createBandNode, Coefficients.cpp:48-53).  An active Mid/Side
 // band sends the whole call through the basic path (Processing.cpp:1036-1044).
-struct EqDesign {
-    double coef[2][kBands][6];
-    int flags[2][kBands];
-    std::vector<double> tp;
-    double satGain[2];
-    bool tpSafe = true, midSide = false;
-};
-
-void designEqStream(const cpq_engine* e, const cpq_eq_params& p, bool basicPath, EqDesign& d)
+void designEqStream(const cpq_engine* e, const cpq_eq_params& p, bool basicPath, CascadeImage& d)
 {
     d.tp.assign((size_t)kBands * cpq::kSvfTpTableDoubles, 0.0);
     d.tpSafe = true;
@@ -96,6 +97,61 @@ void designEqStream(const cpq_engine* e, const cpq_eq_params& p, bool basicPath,
     if (p.filter_structure == 1 || d.midSide) d.tpSafe = false;   // parallel structure and Mid/Side bands: lane-skewed kernel
 }
 
+// the output filter's three DF-II-T sections in band slots 0 .. 2 (an identity section is run like the reference runs it)
+void outFilterFlags(CascadeImage& d)
+{
+    for (int ch = 0; ch < 2; ++ch)
+        for (int b = 0; b < kBands; ++b) d.flags[ch][b] = b < 3 ? (1 | 4) : 0;      // active, DF-II-T section
+}
+void outFilterImage(const cpq_biquad_coeffs q[3], CascadeImage& d)
+{
+    std::memset(d.coef, 0, sizeof(d.coef));
+    d.tp.assign((size_t)kBands * cpq::kSvfTpTableDoubles, 0.0);
+    d.tpSafe = true;
+    for (int b = 0; b < 3; ++b) {
+        const double v[6] = { q[b].b0, q[b].b1, q[b].b2, q[b].a1, q[b].a2, 0.0 };
+        for (int ch = 0; ch < 2; ++ch) std::memcpy(d.coef[ch][b], v, sizeof(v));
+        d.tpSafe = cpq::buildBiquadTpTables(q[b], &d.tp[(size_t)b * cpq::kSvfTpTableDoubles]) && d.tpSafe;
+    }
+    outFilterFlags(d);
+    d.satGain[0] = 0.0;
+    d.satGain[1] = 1.0;
+}
+
+// pass-through: no band active, no saturation, unity gain.  Only the flags and the saturation / gain pair are written: what
+// the stream's coefficient and time-parallel tables hold stays
+void passThroughImage(CascadeImage& d)
+{
+    std::memset(d.flags, 0, sizeof(d.flags));
+    d.satGain[0] = 0.0;
+    d.satGain[1] = 1.0;
+    d.tpSafe = true;
+    d.midSide = false;
+    d.parts = CascadeImage::kFlags | CascadeImage::kSatGain;
+}
+
+// The one place that writes cascade tables: the image to every stream of [s0, s1), table by table in the order coef, flags,
+// satGain, tp.  Blocking: plain hipMemcpy, for the setters, which have synchronised the engine's stream.  Staged: in order on the
+// engine's stream with the kernels around it.
+enum class Upload { kBlocking, kStaged };
+int uploadCascade(cpq_engine* e, const cpq::CascadeTables& t, const CascadeImage& d, int s0, int s1, Upload how)
+{
+    auto put = [e, how](void* dst, const void* src, size_t bytes) -> int {
+        if (how == Upload::kStaged) return stageUpload(e, dst, src, bytes);
+        CPQ_HIP(e, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return CPQ_OK;
+    };
+    const double sg[4] = { d.satGain[0], d.satGain[1], d.satGain[0], d.satGain[1] };
+    for (int s = s0; s < s1; ++s) {
+        const size_t c = (size_t)2 * s;
+        if (d.parts & CascadeImage::kCoef) CPQ_TRY(put(t.coef + c * kBands * 6, d.coef, sizeof(d.coef)));
+        if (d.parts & CascadeImage::kFlags) CPQ_TRY(put(t.flags + c * kBands, d.flags, sizeof(d.flags)));
+        if (d.parts & CascadeImage::kSatGain) CPQ_TRY(put(t.satGain + c * 2, sg, sizeof(sg)));
+        if (d.parts & CascadeImage::kTp) CPQ_TRY(put(t.tp + (size_t)s * d.tp.size(), d.tp.data(), d.tp.size() * sizeof(double)));
+    }
+    return CPQ_OK;
+}
+
 // Switches what the device tables of one stream hold (on the engine's stream, in order with the kernels around it):
 // 0 = the parameters as set, 1 = the basic path's band nodes, 2 = pass-through (EQ bypass in effect: nothing runs,
 // not even the total gain, the AGC or the gain ramp).
@@ -103,28 +159,14 @@ int setEqStreamMode(cpq_engine* e, int s, int mode)
 {
     auto& bp = e->eqBypass[s];
     if (bp.mode == mode) return CPQ_OK;
-    const size_t c0 = (size_t)s * 2;
-    if (mode == 2) {
-        int zeros[2 * kBands] = {};
-        const double sg[4] = { 0.0, 1.0, 0.0, 1.0 };
-        CPQ_TRY(stageUpload(e, e->svfFlags + c0 * kBands, zeros, sizeof(zeros)));
-        CPQ_TRY(stageUpload(e, e->svfSatGain + c0 * 2, sg, sizeof(sg)));
-        e->eqTpSafe[s] = 1;
-        e->eqMidSide[s] = 0;
-        e->gainRamp[s].devUnity = true;
-    } else {
-        if (!e->eqParamsSet[s]) { bp.mode = mode; return CPQ_OK; }      // no parameters: every band inactive anyway
-        EqDesign d;
-        designEqStream(e, e->eqParamsHost[s], mode == 1, d);
-        double sg[4] = { d.satGain[0], d.satGain[1], d.satGain[0], d.satGain[1] };
-        CPQ_TRY(stageUpload(e, e->svfCoef + c0 * kBands * 6, d.coef, sizeof(d.coef)));
-        CPQ_TRY(stageUpload(e, e->svfFlags + c0 * kBands, d.flags, sizeof(d.flags)));
-        CPQ_TRY(stageUpload(e, e->svfSatGain + c0 * 2, sg, sizeof(sg)));
-        CPQ_TRY(stageUpload(e, e->svfTp + (size_t)s * d.tp.size(), d.tp.data(), d.tp.size() * sizeof(double)));
-        e->eqTpSafe[s] = d.tpSafe ? 1 : 0;
-        e->eqMidSide[s] = d.midSide ? 1 : 0;
-        e->gainRamp[s].devUnity = false;          // the constant gain (or 1.0 with AGC) is on the device again
-    }
+    if (mode != 2 && !e->eqParamsSet[s]) { bp.mode = mode; return CPQ_OK; }      // no parameters: every band inactive anyway
+    CascadeImage d;
+    if (mode == 2) passThroughImage(d);
+    else designEqStream(e, e->eqParamsHost[s], mode == 1, d);
+    CPQ_TRY(uploadCascade(e, e->eqTab, d, s, s + 1, Upload::kStaged));
+    e->eqTpSafe[s] = d.tpSafe ? 1 : 0;
+    e->eqMidSide[s] = d.midSide ? 1 : 0;
+    e->gainRamp[s].devUnity = mode == 2;        // otherwise the constant gain (or 1.0 with AGC) is on the device again
     if (e->agcOn) {
         const int on = (mode != 2 && e->agcOnHost[s]) ? 1 : 0;
         CPQ_TRY(stageUpload(e, e->agcOn + s, &on, sizeof(int)));
@@ -133,82 +175,173 @@ int setEqStreamMode(cpq_engine* e, int s, int mode)
     return CPQ_OK;
 }
 
-// EQ over n samples (a multiple of the block) of rows `stride` apart.  pass: streams (or nullptr) that are bypassed for
-// the whole range -- their device tables hold pass-through flags, and the host-side gain ramp must not move either.
-int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int n, const char* pass)
+int setOutFilterPass(cpq_engine* e, int s, bool pass)
+{
+    CascadeImage d;
+    if (pass) passThroughImage(d);
+    else outFilterFlags(d);
+    d.parts = CascadeImage::kFlags;             // the filter's saturation / gain pair is 0, 1 in either state
+    CPQ_TRY(uploadCascade(e, e->ofTab, d, s, s + 1, Upload::kStaged));
+    e->ofPass[s] = pass ? 1 : 0;
+    return CPQ_OK;
+}
+
+// The total gain of a range of n samples in callbacks of B (Processing.cpp:1262-1274), planned on the host (planEqGain) and put on
+// the device: the table entries that flip to unity or back, and -- only while some stream is moving -- the ramp kernel's segments.
+// pass: streams (or nullptr) that are bypassed for the whole range; their ramp must not move either.
+static int prepareGain(cpq_engine* e, int n, int B, const char* pass, EqGainPlan& g)
+{
+    const int S = e->desc.n_streams, cbs = n / B;
+    // CPQ_CALLS_ANY: the last callback of the call is shorter than the quantum.  Refused before any ramp has moved
+    if (n % B != 0 && anyGainRamp(e->gainRamp.data(), e->agcOnHost.data(), pass, S))
+        return fail(e, CPQ_ERR_UNSUPPORTED, "a total-gain ramp is running: the call must be whole callbacks of %d samples until it ends", B);
+    g = planEqGain(e->gainRamp.data(), e->agcOnHost.data(), pass, S, cbs, B, LinearRamp::stepsFor(e->sampleRate, 0.05));
+    for (const EqGainPlan::Flip& f : g.flips) {
+        for (int ch = 0; ch < 2; ++ch)
+            CPQ_TRY(stageUpload(e, e->eqTab.satGain + (size_t)(2 * f.s + ch) * 2 + 1, &f.gain, sizeof(double)));
+        e->gainRamp[f.s].devUnity = f.unity;
+    }
+    if (!g.anyRamp) return CPQ_OK;
+    const size_t cbMax = (size_t)e->tMax * e->P / B;
+    if (!e->rampOn)
+        CPQ_TRY(allocAll(e, { { e->rampOn, (size_t)S }, { e->rampGains, 2 * S * cbMax } }, "gain ramp buffers could not be allocated"));
+    CPQ_TRY(stageUpload(e, e->rampOn, g.rampOn.data(), sizeof(int) * S));
+    return stageUpload(e, e->rampGains, g.segments.data(), sizeof(double) * g.segments.size());
+}
+
+// EQ over n samples of rows `stride` apart, in callbacks of B samples (AGC and gain ramp are block-rate), with the total gain as
+// prepareGain left it on the device.
+static int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int n, int B, const EqGainPlan& g)
 {
     bool tp = (e->eqMode == CPQ_EQ_MODE_AUTO);
     for (char s : e->eqTpSafe) tp = tp && s;
-    const int cbs = n / e->B;            // callback blocks in this range (AGC is block-rate)
-    const bool raggedTail = n % e->B != 0;     // CPQ_CALLS_ANY: the last callback of the call is shorter than the quantum
-    // total-gain ramp (Processing.cpp:1262-1274): per callback setTargetValue / skip on a LinearRamp (50 ms);
-    // evaluated on the host (scalar per-stream state), applied by the ramp kernel only while some stream is moving
-    std::vector<int> rampOnHost;
-    std::vector<double> rampHost;
-    bool anyRamp = false;
-    {
-        const int S = e->desc.n_streams;
-        const int total = LinearRamp::stepsFor(e->sampleRate, 0.05);
-        for (int s = 0; s < S; ++s) {
-            auto& r = e->gainRamp[s];
-            if (e->agcOnHost[s] || (pass && pass[s]) || !r.moving()) continue;
-            if (raggedTail)
-                return fail(e, CPQ_ERR_UNSUPPORTED, "a total-gain ramp is running: the call must be whole callbacks of %d samples until it ends", e->B);
-            if (!anyRamp) { rampOnHost.assign(S, 0); rampHost.assign((size_t)S * cbs * 2, 0.0); anyRamp = true; }
-            rampOnHost[s] = 1;
-            for (int t = 0; t < cbs; ++t) {
-                const GainRamp::Segment g = r.callback(e->B, total);
-                rampHost[((size_t)s * cbs + t) * 2] = g.start;
-                rampHost[((size_t)s * cbs + t) * 2 + 1] = g.increment;
-            }
-        }
-        // streams whose gain is applied by the ramp kernel need unity gain in the cascade kernel, and back again
-        for (int s = 0; s < S; ++s) {
-            auto& r = e->gainRamp[s];
-            if (e->agcOnHost[s] || (pass && pass[s])) continue;
-            const bool needUnity = anyRamp && rampOnHost[s];
-            if (needUnity != r.devUnity) {
-                const double g = needUnity ? 1.0 : r.wanted;
-                for (int ch = 0; ch < 2; ++ch)
-                    CPQ_TRY(stageUpload(e, e->svfSatGain + (size_t)(2 * s + ch) * 2 + 1, &g, sizeof(double)));
-                r.devUnity = needUnity;
-            }
-        }
-        if (anyRamp) {
-            const size_t cbMax = (size_t)e->tMax * e->P / e->B;
-            if (!e->rampOn)
-                CPQ_TRY(allocAll(e, { { e->rampOn, (size_t)S }, { e->rampGains, 2 * S * cbMax } }, "gain ramp buffers could not be allocated"));
-            CPQ_TRY(stageUpload(e, e->rampOn, rampOnHost.data(), sizeof(int) * S));
-            CPQ_TRY(stageUpload(e, e->rampGains, rampHost.data(), sizeof(double) * rampHost.size()));
-        }
-    }
+    const int cbs = n / B;
     e->eqProcessed = true;
-    if (e->anyAgc && raggedTail) return fail(e, CPQ_ERR_UNSUPPORTED, "the block-rate AGC needs calls of whole callbacks of %d samples", e->B);
+    if (e->anyAgc && n % B != 0) return fail(e, CPQ_ERR_UNSUPPORTED, "the block-rate AGC needs calls of whole callbacks of %d samples", B);
     if (e->anyAgc) {
         ProfScope p(e, CPQ_K_MIX);
-        cpq::launch_agc_block_rms(e->stream, dIn, stride, e->nCh, e->B, cbs, e->agcRmsIn);     // cachedInputRMS (:1116-1127)
+        cpq::launch_agc_block_rms(e->stream, dIn, stride, e->nCh, B, cbs, e->agcRmsIn);     // cachedInputRMS (:1116-1127)
     }
     bool midSide = false;
     for (char m : e->eqMidSide) midSide = midSide || m;
-    CPQ_TRY(enqueueCascade(e, dIn, dOut, stride, n, tp, CPQ_K_SVF_TP, CPQ_K_SVF, e->svfCoef, e->svfFlags, e->svfSatGain,
-                           e->svfState, e->svfTp, midSide));
-    if (anyRamp) {
+    CPQ_TRY(enqueueCascade(e, dIn, dOut, stride, n, tp, CPQ_K_SVF_TP, CPQ_K_SVF, e->eqTab, midSide));
+    if (g.anyRamp) {
         ProfScope p(e, CPQ_K_MIX);
-        cpq::launch_gain_ramp(e->stream, dOut, stride, e->desc.n_streams, e->B, cbs, e->rampGains, e->rampOn);
+        cpq::launch_gain_ramp(e->stream, dOut, stride, e->desc.n_streams, B, cbs, e->rampGains, e->rampOn);
         CPQ_HIP(e, hipGetLastError());
     }
     if (!e->anyAgc) return CPQ_OK;
     {
         ProfScope p(e, CPQ_K_MIX);
         // block coefficients of the tables prepareToPlay builds (src/eqprocessor/EQProcessor.Core.cpp:776-784)
-        const double nn = (double)e->B, sr = e->sampleRate;
+        const double nn = (double)B, sr = e->sampleRate;
         const double bAtt = 1.0 - std::exp(-nn / (sr * 0.2)), bRel = 1.0 - std::exp(-nn / (sr * 2.0)),
                      bSm = 1.0 - std::exp(-nn / (sr * 0.2));
-        cpq::launch_agc_block_rms(e->stream, dOut, stride, e->nCh, e->B, cbs, e->agcRmsOut);
-        cpq::launch_agc_apply(e->stream, dOut, stride, e->desc.n_streams, e->B, cbs, e->agcRmsIn, e->agcRmsOut,
+        cpq::launch_agc_block_rms(e->stream, dOut, stride, e->nCh, B, cbs, e->agcRmsOut);
+        cpq::launch_agc_apply(e->stream, dOut, stride, e->desc.n_streams, B, cbs, e->agcRmsIn, e->agcRmsOut,
                               e->agcState, e->agcOn, e->agcGains, bAtt, bRel, bSm);
     }
     CPQ_HIP(e, hipGetLastError());
+    return CPQ_OK;
+}
+
+// rtAgcCurrentGainShadow = 1, envelopes = 0 (Processing.cpp:586-593, 1070-1077)
+static int agcReset(cpq_engine* e, int s)
+{
+    if (e->agcState) CPQ_TRY(agcStateReset(e, s, 1));
+    e->agcResetPending[s] = 0;
+    return CPQ_OK;
+}
+
+// Silence is only known on the device: one small kernel, one read-back and ONE stream synchronisation per call while a band
+// reset waits on a stream that is playing.  Leaves silent[stream][callback] in e->silentHost
+static int readSilence(cpq_engine* e, const double* dIn, int64_t stride, int B, int cbs)
+{
+    const int S = e->desc.n_streams;
+    const size_t cbMax = (size_t)e->tMax * e->P / B;
+    if (!e->silentDev)
+        CPQ_TRY(allocAll(e, { { e->silentDev, S * cbMax }, { e->silentHost, S * cbMax } }, "silence flags could not be allocated"));
+    cpq::launch_block_silence(e->stream, dIn, stride, B, cbs, S, e->silentDev);
+    CPQ_HIP(e, hipMemcpyAsync(e->silentHost, e->silentDev, sizeof(int) * (size_t)S * cbs, hipMemcpyDeviceToHost, e->stream));
+    CPQ_HIP(e, hipStreamSynchronize(e->stream));
+    return CPQ_OK;
+}
+
+// one stream in front of a piece: the band states its reset mask names cleared, its tables switched to its class, a pending AGC
+// reset carried out (a bypassed block returns before it)
+static int applyPiece(cpq_engine* e, int s, const EqPiece::Stream& ps, int& rc)
+{
+    using T = cpq::CascadeTables;
+    if (ps.reset == 0xFFFFFFFFu) {             // every band of the stream, Mid / Side states included
+        CPQ_HIP(e, hipMemsetAsync(e->eqTab.state + T::stateAt(s, 0, 0), 0, sizeof(double) * T::stateDoubles(2), e->stream));
+    } else if (ps.reset) {
+        for (int b = 0; b < kBands; ++b)
+            if (ps.reset & (1u << b))
+                for (int ch = 0; ch < 2; ++ch)
+                    CPQ_HIP(e, hipMemsetAsync(e->eqTab.state + T::stateAt(s, ch, b), 0, sizeof(double) * 2, e->stream));
+    }
+    rc = setEqStreamMode(e, s, ps.cls == EqBypass::kPass ? 2 : ps.cls == EqBypass::kFade ? 1 : 0);
+    if (rc == CPQ_OK && e->agcResetPending[s] && ps.cls != EqBypass::kPass) rc = agcReset(e, s);
+    return CPQ_OK;
+}
+
+// the cross-fade tables of a piece in which some stream fades: per stream on / length / end value and its fade values
+static int uploadBlend(cpq_engine* e, const EqCallPlan& plan, const EqPiece& pc)
+{
+    const int S = e->desc.n_streams;
+    std::vector<int> on(S), len(S);
+    std::vector<double> end(S);
+    int cap = 1;
+    for (int s = 0; s < S; ++s) {
+        on[s] = pc.streams[s].cls == EqBypass::kFade;
+        len[s] = pc.streams[s].fadeLen;
+        end[s] = pc.streams[s].fadeEnd;
+        cap = std::max(cap, len[s]);
+    }
+    if (!e->eqDry)
+        CPQ_TRY(allocAll(e, { { e->eqDry, (size_t)e->nCh * e->tMax * e->P }, { e->blendOn, (size_t)S }, { e->blendLen, (size_t)S },
+                              { e->blendEnd, (size_t)S } }, "EQ bypass cross-fade buffers could not be allocated"));
+    CPQ_TRY(grow(e, e->blendGains, e->blendCap, cap, (size_t)S, "EQ bypass cross-fade buffers could not be allocated"));
+    std::vector<double> gains((size_t)S * e->blendCap, 0.0);
+    for (int s = 0; s < S; ++s)
+        if (len[s] > 0) std::memcpy(&gains[(size_t)s * e->blendCap], plan.fade[s].data() + pc.streams[s].fadeStart, sizeof(double) * (size_t)len[s]);
+    CPQ_TRY(stageUpload(e, e->blendOn, on.data(), sizeof(int) * S));
+    CPQ_TRY(stageUpload(e, e->blendLen, len.data(), sizeof(int) * S));
+    CPQ_TRY(stageUpload(e, e->blendEnd, end.data(), sizeof(double) * S));
+    return stageUpload(e, e->blendGains, gains.data(), sizeof(double) * gains.size());
+}
+
+// One piece of a call: the streams' states and tables, then the ordinary kernels, cross-faded with the dry block where a stream
+// fades.  A status of the table switch, the AGC reset or the kernels comes back in rc and ends the call in order (the caller
+// still settles anyEqBypass); every other failure returns at once, as a device error does anywhere.
+static int runPiece(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int B, const EqCallPlan& plan, const EqPiece& pc,
+                    int& rc)
+{
+    const int S = e->desc.n_streams;
+    const int64_t off = (int64_t)pc.c0 * B;
+    const int nSeg = (pc.c1 - pc.c0) * B;
+    std::vector<char> pass(S);
+    bool anyFade = false;
+    for (int s = 0; s < S && rc == CPQ_OK; ++s) {
+        CPQ_TRY(applyPiece(e, s, pc.streams[s], rc));
+        pass[s] = pc.streams[s].cls == EqBypass::kPass;
+        anyFade = anyFade || pc.streams[s].cls == EqBypass::kFade;
+    }
+    if (rc != CPQ_OK) return CPQ_OK;
+    if (anyFade) {
+        CPQ_TRY(uploadBlend(e, plan, pc));
+        ProfScope p(e, CPQ_K_MIX);
+        cpq::launch_rows_copy(e->stream, dIn, stride, off, e->eqDry, (int64_t)nSeg, 0, nSeg, e->nCh);
+    }
+    EqGainPlan g;
+    rc = prepareGain(e, nSeg, B, pass.data(), g);
+    if (rc == CPQ_OK) rc = enqueueEqCore(e, dIn + off, dOut + off, stride, nSeg, B, g);
+    if (rc == CPQ_OK && anyFade) {
+        ProfScope p(e, CPQ_K_MIX);
+        cpq::launch_bypass_blend(e->stream, dOut + off, stride, e->eqDry, (int64_t)nSeg, nSeg, e->nCh, e->blendOn,
+                                 e->blendLen, e->blendEnd, e->blendGains, e->blendCap);
+        CPQ_HIP(e, hipGetLastError());
+    }
     return CPQ_OK;
 }
 
@@ -219,147 +352,36 @@ int enqueueEqCore(cpq_engine* e, const double* dIn, double* dOut, int64_t stride
 // (band nodes) and cross-faded with the dry block sample by sample; once the fade-out is complete the EQ returns early
 // (states, gain ramp and AGC frozen); releasing the bypass clears every filter state and fades back in.  The call is cut
 // where some stream changes class, each piece runs the ordinary kernels with the streams' tables switched accordingly.
-// n samples of rows `stride` apart: whole callbacks of e->B samples, or (no per-callback state in play) any n
-static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int n)
+// The plan is host_replay.hpp's (planEqCall, needsSilence, assignResets, cutPieces); here it is carried out.
+// n samples of rows `stride` apart: whole callbacks of B samples, or (no per-callback state in play) any n
+static int enqueueEqRange(cpq_engine* e, const double* dIn, double* dOut, int64_t stride, int n, int B)
 {
     if (!e->eqSet) return fail(e, CPQ_ERR_NOT_READY, "cpq_eq_set_params has not been called");
     const int S = e->desc.n_streams;
-    auto agcReset = [e](int s) -> int {        // rtAgcCurrentGainShadow = 1, envelopes = 0 (Processing.cpp:586-593, 1070-1077)
-        if (e->agcState) CPQ_TRY(agcStateReset(e, s, 1));
-        e->agcResetPending[s] = 0;
-        return CPQ_OK;
-    };
     if (!e->anyEqBypass && !e->anyEqReset) {
         for (int s = 0; s < S; ++s)
-            if (e->agcResetPending[s]) CPQ_TRY(agcReset(s));
+            if (e->agcResetPending[s]) CPQ_TRY(agcReset(e, s));
         e->eqProcessed = true;
-        return enqueueEqCore(e, dIn, dOut, stride, n, nullptr);
+        EqGainPlan g;
+        CPQ_TRY(prepareGain(e, n, B, nullptr, g));
+        return enqueueEqCore(e, dIn, dOut, stride, n, B, g);
     }
-    if (n % e->B != 0)
-        return fail(e, CPQ_ERR_UNSUPPORTED, "an EQ bypass transition or band reset is pending: the call must be whole callbacks of %d samples", e->B);
-    const int cbs = n / e->B;
-    const int total = LinearRamp::stepsFor(e->sampleRate, 0.005);            // BYPASS_FADE_TIME_SEC (EQProcessor.h:564)
-    using enum EqBypass::Class;         // kNormal, kFade, kPass
-    std::vector<char> cls((size_t)S * cbs, kNormal);
-    std::vector<uint32_t> reset((size_t)S * cbs, 0u);           // bands cleared at the start of the callback
-    std::vector<char> released((size_t)S * cbs, 0);             // the bypass is released here: every band is to be cleared
-    std::vector<std::vector<double>> gains(S);          // fade values of a stream's kFade callbacks, in order
-    bool stillActive = false;
-    for (int s = 0; s < S; ++s)
-        for (int t = 0; t < cbs; ++t) {
-            const EqBypass::Step st = e->eqBypass[s].callback(e->B, total, gains[s]);
-            cls[(size_t)s * cbs + t] = st.cls;
-            released[(size_t)s * cbs + t] = st.released ? 1 : 0;
-        }
-    // pending band resets: at the first callback that is fading (canSafelyResetState, :565-568) or whose input block is
-    // silent; a fully bypassed callback returns before it gets there.  Silence is only known on the device: one small
-    // kernel, one read-back and ONE stream synchronisation per call while a reset waits on a stream that is playing.
-    {
-        bool needSilence = false;
-        for (int s = 0; s < S && !needSilence; ++s) {
-            if (!e->eqResetPending[s]) continue;
-            for (int t = 0; t < cbs; ++t) {
-                if (cls[(size_t)s * cbs + t] == kFade) break;
-                if (cls[(size_t)s * cbs + t] == kNormal) { needSilence = true; break; }
-            }
-        }
-        if (needSilence) {
-            const size_t cbMax = (size_t)e->tMax * e->P / e->B;
-            if (!e->silentDev)
-                CPQ_TRY(allocAll(e, { { e->silentDev, S * cbMax }, { e->silentHost, S * cbMax } }, "silence flags could not be allocated"));
-            cpq::launch_block_silence(e->stream, dIn, stride, e->B, cbs, S, e->silentDev);
-            CPQ_HIP(e, hipMemcpyAsync(e->silentHost, e->silentDev, sizeof(int) * (size_t)S * cbs, hipMemcpyDeviceToHost, e->stream));
-            CPQ_HIP(e, hipStreamSynchronize(e->stream));
-        }
-        e->anyEqReset = false;
-        for (int s = 0; s < S; ++s) {
-            uint32_t pending = e->eqResetPending[s];
-            for (int t = 0; t < cbs; ++t) {
-                if (released[(size_t)s * cbs + t]) pending = 0xFFFFFFFFu;
-                if (!pending) continue;
-                const char k = cls[(size_t)s * cbs + t];
-                if (k == kFade || (k == kNormal && needSilence && e->silentHost[(size_t)s * cbs + t])) {
-                    reset[(size_t)s * cbs + t] = pending;
-                    pending = 0u;
-                }
-            }
-            e->eqResetPending[s] = pending;
-            e->anyEqReset = e->anyEqReset || pending != 0u;
-        }
-    }
+    if (n % B != 0)
+        return fail(e, CPQ_ERR_UNSUPPORTED, "an EQ bypass transition or band reset is pending: the call must be whole callbacks of %d samples", B);
+    const int cbs = n / B;
+    EqCallPlan plan = planEqCall(e->eqBypass.data(), S, cbs, B, LinearRamp::stepsFor(e->sampleRate, 0.005));    // BYPASS_FADE_TIME_SEC (EQProcessor.h:564)
+    const bool silence = needsSilence(plan, e->eqResetPending.data());
+    if (silence) CPQ_TRY(readSilence(e, dIn, stride, B, cbs));
+    e->anyEqReset = assignResets(plan, e->eqResetPending.data(), silence ? e->silentHost.get() : nullptr);
     e->eqProcessed = true;
-    std::vector<char> pass(S);
-    std::vector<int> onHost(S), lenHost(S);
-    std::vector<double> endHost(S), gainsHost;
-    std::vector<size_t> used(S, 0);                     // fade values of the stream consumed by earlier pieces
     int rc = CPQ_OK;
-    for (int c0 = 0; c0 < cbs && rc == CPQ_OK;) {
-        int c1 = c0 + 1;
-        auto sameClass = [&](int t) {
-            for (int s = 0; s < S; ++s)
-                if (cls[(size_t)s * cbs + t] != cls[(size_t)s * cbs + c0] || reset[(size_t)s * cbs + t]) return false;
-            return true;
-        };
-        while (c1 < cbs && sameClass(c1)) ++c1;
-        const int64_t off = (int64_t)c0 * e->B;
-        const int nSeg = (c1 - c0) * e->B;
-        bool anyFade = false;
-        int cap = 1;
-        for (int s = 0; s < S && rc == CPQ_OK; ++s) {
-            const char k = cls[(size_t)s * cbs + c0];
-            const uint32_t mask = reset[(size_t)s * cbs + c0];
-            if (mask == 0xFFFFFFFFu) {             // every band of the stream, Mid / Side states included
-                CPQ_HIP(e, hipMemsetAsync(e->svfState + (size_t)s * 2 * kBands * 2, 0, sizeof(double) * 2 * kBands * 2, e->stream));
-            } else if (mask) {
-                for (int b = 0; b < kBands; ++b)
-                    if (mask & (1u << b))
-                        for (int ch = 0; ch < 2; ++ch)
-                            CPQ_HIP(e, hipMemsetAsync(e->svfState + ((size_t)(2 * s + ch) * kBands + b) * 2, 0, sizeof(double) * 2, e->stream));
-            }
-            rc = setEqStreamMode(e, s, k == kPass ? 2 : k == kFade ? 1 : 0);
-            if (rc == CPQ_OK && e->agcResetPending[s] && k != kPass) rc = agcReset(s);      // a bypassed block returns before it
-            pass[s] = k == kPass;
-            onHost[s] = k == kFade;
-            lenHost[s] = 0;
-            endHost[s] = 1.0;
-            if (k == kFade) {
-                anyFade = true;
-                lenHost[s] = (int)std::min<size_t>(gains[s].size() - used[s], (size_t)nSeg);
-                // past the end of the ramp getNextValue keeps returning its final value
-                endHost[s] = gains[s].empty() ? e->eqBypass[s].fade.current : gains[s][std::min(gains[s].size(), used[s] + (size_t)nSeg) - 1];
-                cap = std::max(cap, lenHost[s]);
-            }
-        }
+    for (const EqPiece& pc : cutPieces(plan)) {
+        CPQ_TRY(runPiece(e, dIn, dOut, stride, B, plan, pc, rc));
         if (rc != CPQ_OK) break;
-        if (anyFade) {
-            if (!e->eqDry)
-                CPQ_TRY(allocAll(e, { { e->eqDry, (size_t)e->nCh * e->tMax * e->P }, { e->blendOn, (size_t)S }, { e->blendLen, (size_t)S },
-                                              { e->blendEnd, (size_t)S } }, "EQ bypass cross-fade buffers could not be allocated"));
-            CPQ_TRY(grow(e, e->blendGains, e->blendCap, cap, (size_t)S, "EQ bypass cross-fade buffers could not be allocated"));
-            gainsHost.assign((size_t)S * e->blendCap, 0.0);
-            for (int s = 0; s < S; ++s) {
-                if (!onHost[s]) continue;
-                std::memcpy(&gainsHost[(size_t)s * e->blendCap], gains[s].data() + used[s], sizeof(double) * (size_t)lenHost[s]);
-                used[s] += (size_t)lenHost[s];
-            }
-            CPQ_TRY(stageUpload(e, e->blendOn, onHost.data(), sizeof(int) * S));
-            CPQ_TRY(stageUpload(e, e->blendLen, lenHost.data(), sizeof(int) * S));
-            CPQ_TRY(stageUpload(e, e->blendEnd, endHost.data(), sizeof(double) * S));
-            CPQ_TRY(stageUpload(e, e->blendGains, gainsHost.data(), sizeof(double) * gainsHost.size()));
-            ProfScope p(e, CPQ_K_MIX);
-            cpq::launch_rows_copy(e->stream, dIn, stride, off, e->eqDry, (int64_t)nSeg, 0, nSeg, e->nCh);
-        }
-        rc = enqueueEqCore(e, dIn + off, dOut + off, stride, nSeg, pass.data());
-        if (rc == CPQ_OK && anyFade) {
-            ProfScope p(e, CPQ_K_MIX);
-            cpq::launch_bypass_blend(e->stream, dOut + off, stride, e->eqDry, (int64_t)nSeg, nSeg, e->nCh, e->blendOn,
-                                     e->blendLen, e->blendEnd, e->blendGains, e->blendCap);
-            CPQ_HIP(e, hipGetLastError());
-        }
-        c0 = c1;
     }
     // after the pieces ran: a stream whose tables were left on the basic path's band nodes (its fade ended inside this call)
     // still needs the next call to come through here, which puts the parameter tables back
+    bool stillActive = false;
     for (const auto& b : e->eqBypass) stillActive = stillActive || b.active();
     e->anyEqBypass = stillActive;
     return rc;
@@ -375,22 +397,16 @@ int enqueueEq(cpq_engine* e, const double* dIn, double* dOut, int n)
     const int r = n % e->B;
     bool perCallback = e->anyAgc || e->anyEqBypass || e->anyEqReset;
     for (size_t s = 0; s < e->gainRamp.size() && !perCallback; ++s) perCallback = !e->agcOnHost[s] && e->gainRamp[s].moving();
-    if (r == 0 || !perCallback) return enqueueEqRange(e, dIn, dOut, (int64_t)n, n);
-    if (n - r > 0) CPQ_TRY(enqueueEqRange(e, dIn, dOut, (int64_t)n, n - r));
-    struct QuantumOf {            // the short callback is a callback of r samples to everything below
-        cpq_engine* e; int saved;
-        QuantumOf(cpq_engine* e_, int b) : e(e_), saved(e_->B) { e->B = b; }
-        ~QuantumOf() { e->B = saved; }
-    } tail(e, r);
-    return enqueueEqRange(e, dIn + (n - r), dOut + (n - r), (int64_t)n, r);
+    if (r == 0 || !perCallback) return enqueueEqRange(e, dIn, dOut, (int64_t)n, n, e->B);
+    if (n - r > 0) CPQ_TRY(enqueueEqRange(e, dIn, dOut, (int64_t)n, n - r, e->B));
+    return enqueueEqRange(e, dIn + (n - r), dOut + (n - r), (int64_t)n, r, r);     // the short callback: a callback of r samples
 }
 
 int enqueueOutFilter(cpq_engine* e, const double* dIn, double* dOut, int n)
 {
     if (!e->ofSet) return fail(e, CPQ_ERR_NOT_READY, "cpq_outfilter_set_params has not been called");
     const bool tp = (e->eqMode == CPQ_EQ_MODE_AUTO) && e->ofTpSafe;
-    return enqueueCascade(e, dIn, dOut, (int64_t)n, n, tp, CPQ_K_OUTFILT, CPQ_K_OUTFILT, e->ofCoef, e->ofFlags,
-                          e->ofSatGain, e->ofState, e->ofTp);
+    return enqueueCascade(e, dIn, dOut, (int64_t)n, n, tp, CPQ_K_OUTFILT, CPQ_K_OUTFILT, e->ofTab);
 }
 
 
@@ -409,35 +425,12 @@ int32_t cpq_eq_set_params(cpq_engine* e, int32_t stream, const cpq_eq_params* p)
         if (p->bands[b].enabled && (p->bands[b].channel_mode < 0 || p->bands[b].channel_mode > 4))
             return fail(e, CPQ_ERR_INVALID_ARG, "band %d: channel_mode must be 0..4 (Stereo, Left, Right, Mid, Side)", b);
 
-    EqDesign d;
+    CascadeImage d;
     designEqStream(e, *p, false, d);
-    const auto& coef = d.coef;
-    const auto& flags = d.flags;
-    const std::vector<double>& tp = d.tp;
-    bool tpSafe = d.tpSafe;
-    const bool midSide = d.midSide;
-    const double satGain[2] = { d.satGain[0], d.satGain[1] };
-
     CPQ_HIP(e, hipSetDevice(e->device));
-    std::vector<double> hc((size_t)(s1 - s0) * 2 * kBands * 6), hs((size_t)(s1 - s0) * 2 * 2);
-    std::vector<int> hf((size_t)(s1 - s0) * 2 * kBands);
-    std::vector<double> ht((size_t)(s1 - s0) * tp.size());
-    for (int s = s0; s < s1; ++s)
-        for (int ch = 0; ch < 2; ++ch) {
-            const size_t ci = (size_t)(s - s0) * 2 + ch;
-            std::memcpy(&hc[ci * kBands * 6], coef[ch], sizeof(coef[ch]));
-            std::memcpy(&hf[ci * kBands], flags[ch], sizeof(flags[ch]));
-            hs[ci * 2] = satGain[0];
-            hs[ci * 2 + 1] = satGain[1];
-        }
-    for (int s = s0; s < s1; ++s) std::memcpy(&ht[(size_t)(s - s0) * tp.size()], tp.data(), tp.size() * sizeof(double));
-    for (int s = s0; s < s1; ++s) { e->eqTpSafe[s] = tpSafe ? 1 : 0; e->eqMidSide[s] = midSide ? 1 : 0; }
-    const size_t c0 = (size_t)s0 * 2;
+    for (int s = s0; s < s1; ++s) { e->eqTpSafe[s] = d.tpSafe ? 1 : 0; e->eqMidSide[s] = d.midSide ? 1 : 0; }
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    CPQ_HIP(e, hipMemcpy(e->svfCoef + c0 * kBands * 6, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice));
-    CPQ_HIP(e, hipMemcpy(e->svfFlags + c0 * kBands, hf.data(), hf.size() * sizeof(int), hipMemcpyHostToDevice));
-    CPQ_HIP(e, hipMemcpy(e->svfSatGain + c0 * 2, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
-    CPQ_HIP(e, hipMemcpy(e->svfTp + (size_t)s0 * tp.size(), ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_TRY(uploadCascade(e, e->eqTab, d, s0, s1, Upload::kBlocking));
     e->eqSet = true;   // streams never given parameters keep all bands inactive (pass-through)
     for (int s = s0; s < s1; ++s) { e->eqParamsHost[s] = *p; e->eqParamsSet[s] = 1; e->eqBypass[s].mode = 0; }
     for (int s = s0; s < s1; ++s) {
@@ -550,29 +543,13 @@ int32_t cpq_outfilter_set_params(cpq_engine* e, int32_t stream, int32_t convIsLa
     cpq_biquad_coeffs q[3];
     const int rc = cpq_outfilter_design(convIsLast, hcMode, lcMode, lpMode, e->sampleRate, q);
     if (rc != CPQ_OK) return fail(e, rc, "bad output filter mode");
-    std::vector<double> coef((size_t)kBands * 6, 0.0), tp((size_t)kBands * cpq::kSvfTpTableDoubles, 0.0);
-    std::vector<int> flags(kBands, 0);
-    bool safe = true;
-    for (int b = 0; b < 3; ++b) {
-        const double v[6] = { q[b].b0, q[b].b1, q[b].b2, q[b].a1, q[b].a2, 0.0 };
-        std::memcpy(&coef[(size_t)b * 6], v, sizeof(v));
-        flags[b] = 1 | 4;       // active, DF-II-T section (an identity section is run like the reference runs it)
-        safe = cpq::buildBiquadTpTables(q[b], &tp[(size_t)b * cpq::kSvfTpTableDoubles]) && safe;
-    }
+    CascadeImage d;
+    outFilterImage(q, d);
     CPQ_HIP(e, hipSetDevice(e->device));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
-    const double sg[2] = { 0.0, 1.0 };
     for (int s = s0; s < s1; ++s) { e->ofModesHost[s] = cpq_engine::OfModes{ convIsLast, hcMode, lcMode, lpMode }; e->ofModesSet[s] = 1; }
-    for (int s = s0; s < s1; ++s) {
-        for (int ch = 0; ch < 2; ++ch) {
-            const size_t c = (size_t)2 * s + ch;
-            CPQ_HIP(e, hipMemcpy(e->ofCoef + c * kBands * 6, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
-            CPQ_HIP(e, hipMemcpy(e->ofFlags + c * kBands, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice));
-            CPQ_HIP(e, hipMemcpy(e->ofSatGain + c * 2, sg, sizeof(sg), hipMemcpyHostToDevice));
-        }
-        CPQ_HIP(e, hipMemcpy(e->ofTp + (size_t)s * tp.size(), tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    e->ofTpSafe = e->ofTpSafe && safe;
+    CPQ_TRY(uploadCascade(e, e->ofTab, d, s0, s1, Upload::kBlocking));      // active flags, whatever ofPass says of the stream
+    e->ofTpSafe = e->ofTpSafe && d.tpSafe;      // one flag for every stream: once false it stays false
     e->ofSet = true;
     return CPQ_OK;
 }
@@ -588,7 +565,7 @@ int32_t cpq_outfilter_reset(cpq_engine* e)
 {
     if (!e) return CPQ_ERR_INVALID_ARG;
     CPQ_HIP(e, hipSetDevice(e->device));
-    CPQ_HIP(e, hipMemsetAsync(e->ofState, 0, (size_t)e->nCh * kBands * 2 * sizeof(double), e->stream));
+    CPQ_HIP(e, hipMemsetAsync(e->ofTab.state, 0, e->ofTab.stateDoubles(e->nCh) * sizeof(double), e->stream));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     return CPQ_OK;
 }

@@ -4,7 +4,8 @@
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
 //   engine_native.cpp  plan groups: streams whose convolver runs on the reference's own layer plan, replayed per chunk
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
-//   engine_eq.cpp    EQ and output filter: design, device tables, bypass / band-reset state machine
+//   engine_eq.cpp    EQ and output filter: design into one host image of a stream's tables, the one routine that uploads it,
+//                    and the EQ call carried out piece by piece as host_replay.hpp plans it
 //   engine_os.cpp    half-band oversampler around the routing: stage buffers, per-stream state machine
 //   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
 //   engine_out.cpp   output stage: DC blocker, headroom, limiter and clamp on the delivered rows
@@ -16,7 +17,8 @@
 //   engine_resample.cpp  cpq_ir_resample / _batch: the device side of the IR sample-rate conversion, no engine (uses only fail and
 //                    the device buffers of this header; design, checks, host path and tail trim are resample_design.cpp's)
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
-// host_replay.hpp: HIP-free steppers that return plain data; the engine files allocate, upload and launch.
+// host_replay.hpp, and so is the EQ's plan of a call (gain segments, bypass classes, band resets, pieces): HIP-free steppers
+// and planners that return plain data; the engine files allocate, upload and launch.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
 // feature allocated on first use, all of it freed with the engine.
 #pragma once
@@ -168,17 +170,8 @@ struct cpq_engine {
     double2* tw512 = nullptr;
     double2* tw1024 = nullptr;
     int* irSlot = nullptr;      // [nCh] device
-    double* svfCoef = nullptr;  // [nCh][20][6]
-    int* svfFlags = nullptr;    // [nCh][20]
-    double* svfSatGain = nullptr;   // [nCh][2]
-    double* svfState = nullptr; // [nCh][20][2]
-    double* svfTp = nullptr;    // [streams][20][kSvfTpTableDoubles]  time-parallel kernel tables
-    // output filter (N2): the same cascade kernels running DF-II-T sections in band slots 0..2
-    double* ofCoef = nullptr;   // [nCh][20][6]  b0 b1 b2 a1 a2 -
-    int* ofFlags = nullptr;     // [nCh][20]
-    double* ofSatGain = nullptr;
-    double* ofState = nullptr;  // [nCh][20][2]  w1 w2
-    double* ofTp = nullptr;     // [streams][20][kSvfTpTableDoubles]
+    cpq::CascadeTables eqTab;   // the EQ's 20 SVF bands (layouts: kernels.hpp)
+    cpq::CascadeTables ofTab;   // output filter (N2): the same cascade kernels running DF-II-T sections in band slots 0..2
     void* svfChain = nullptr;   // scheduling words of the time-parallel cascade: header, arrival counters of the CUs, and (chained spans
                                 // only: svfChainSpans > 0) the [channels][svfChainSpans][20][4] hand-over granules
     int svfChainSpans = 0;
@@ -503,6 +496,8 @@ int checkBlockCall(cpq_engine* e, const void* in, const void* out, int nSamples)
 void syncEqBypass(cpq_engine* e);
 int enqueueEq(cpq_engine* e, const double* dIn, double* dOut, int n);
 int enqueueOutFilter(cpq_engine* e, const double* dIn, double* dOut, int n);
+// output filter tables of stream s to pass-through flags (nothing active) or back to its three sections, on the engine's stream
+int setOutFilterPass(cpq_engine* e, int s, bool pass);
 
 // Host-pointer entry points: H2D, the kernel sequence and D2H.  Long calls are cut into four time chunks (each a complete
 // engine call: the state carries over on the engine's stream) so that the upload of chunk i+1 and the download of chunk

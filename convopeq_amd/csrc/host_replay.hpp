@@ -1,9 +1,12 @@
 // host_replay.hpp -- the reference's per-stream ramps and fades, replayed on the host once per callback before any kernel
 // is launched.  All four are its LinearRamp (src/DspNumericPolicy.h:319-421) with a little policy on top:
-//   GainRamp     smoothTotalGain, 50 ms: setTargetValue + skip(B) per callback         (engine_eq.cpp::enqueueEqCore)
-//   EqBypass     bypassFadeGain, 5 ms: requested / effective / released per callback   (engine_eq.cpp::enqueueEqRange)
+//   GainRamp     smoothTotalGain, 50 ms: setTargetValue + skip(B) per callback         (planEqGain)
+//   EqBypass     bypassFadeGain, 5 ms: requested / effective / released per callback   (planEqCall)
 //   MixRamp      mixSmoother: getNextValue per sample over a prefix of the call        (engine_proc.cpp::enqueueConvProc)
 //   LatencyFade  crossfadeGain, 20 ms, between the delay in use and the new one        (engine_proc.cpp::enqueueConvProc)
+// and, built on the first two, the EQ's plan of a whole call, which engine_eq.cpp only carries out: planEqGain (which streams
+// ramp, their segments, whose device gain flips) and planEqCall / needsSilence / assignResets / cutPieces (classes, band resets
+// and the pieces of equal class the call is cut into).
 // Plain integer and double arithmetic, operation for operation the reference's; no HIP, no engine: a stepper returns plain
 // data and the caller turns it into uploads and launches.  Whatever has to be known BEFORE state may move (which convolvers
 // rest in a call, where latency fades start) is found by running the same steppers on a copy.
@@ -13,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace cpqi {
@@ -113,6 +117,161 @@ struct EqBypass {
         return st;
     }
 };
+
+// ---- the EQ's plan of one range of cbs callbacks of B samples over S streams (engine_eq.cpp carries it out)
+
+// Total gain (Processing.cpp:1262-1274): evaluated per callback on the host, applied by the ramp kernel only while some stream
+// is moving.  A stream's ramp rests in the range while its AGC is on (agcOn[s]) or it is bypassed for the whole range (pass, or
+// null: none is).
+inline bool gainSkipped(const int* agcOn, const char* pass, int s) { return agcOn[s] || (pass && pass[s]); }
+// does planEqGain find a ramp to move?  Nothing moves here: the engine refuses a ragged range on this answer
+inline bool anyGainRamp(const GainRamp* ramps, const int* agcOn, const char* pass, int S)
+{
+    for (int s = 0; s < S; ++s)
+        if (!gainSkipped(agcOn, pass, s) && ramps[s].moving()) return true;
+    return false;
+}
+struct EqGainPlan {
+    bool anyRamp = false;
+    std::vector<int> rampOn;            // [S] the ramp kernel applies this stream's gain; empty while nothing ramps
+    std::vector<double> segments;       // [S][cbs][2] start, increment per callback; empty while nothing ramps
+    // streams whose gain the ramp kernel applies need unity gain in the cascade kernel's table, and `wanted` back afterwards:
+    // the table entries to rewrite.  The caller uploads them and sets GainRamp::devUnity.
+    struct Flip { int s; bool unity; double gain; };
+    std::vector<Flip> flips;
+};
+// steps every moving ramp through the range; a range in which nothing moves and nothing flips allocates nothing
+inline EqGainPlan planEqGain(GainRamp* ramps, const int* agcOn, const char* pass, int S, int cbs, int B, int totalSteps)
+{
+    EqGainPlan g;
+    for (int s = 0; s < S; ++s) {
+        GainRamp& r = ramps[s];
+        if (gainSkipped(agcOn, pass, s) || !r.moving()) continue;
+        if (!g.anyRamp) { g.rampOn.assign((size_t)S, 0); g.segments.assign((size_t)S * cbs * 2, 0.0); g.anyRamp = true; }
+        g.rampOn[(size_t)s] = 1;
+        for (int t = 0; t < cbs; ++t) {
+            const GainRamp::Segment seg = r.callback(B, totalSteps);
+            g.segments[((size_t)s * cbs + t) * 2] = seg.start;
+            g.segments[((size_t)s * cbs + t) * 2 + 1] = seg.increment;
+        }
+    }
+    for (int s = 0; s < S; ++s) {
+        if (gainSkipped(agcOn, pass, s)) continue;
+        const bool needUnity = g.anyRamp && g.rampOn[(size_t)s];
+        if (needUnity != ramps[s].devUnity) g.flips.push_back({ s, needUnity, needUnity ? 1.0 : ramps[s].wanted });
+    }
+    return g;
+}
+
+// Bypass (DSPCore's setBypassFromRT + process per callback): class, release and fade values of every (stream, callback), then
+// the band resets, then the pieces.  Indexed [s * cbs + t].
+struct EqCallPlan {
+    int S = 0, cbs = 0, B = 0;
+    std::vector<char> cls;                      // EqBypass::Class
+    std::vector<char> released;                 // the bypass is released here: every band is to be cleared
+    std::vector<uint32_t> reset;                // bands cleared at the start of the callback (assignResets)
+    std::vector<std::vector<double>> fade;      // per stream: the fade values of its kFade callbacks, in order
+    std::vector<double> fadeRest;               // per stream: where the fade stands behind the range
+    size_t at(int s, int t) const { return (size_t)s * cbs + t; }
+};
+inline EqCallPlan planEqCall(EqBypass* bypass, int S, int cbs, int B, int totalSteps)
+{
+    EqCallPlan p;
+    p.S = S; p.cbs = cbs; p.B = B;
+    p.cls.assign((size_t)S * cbs, EqBypass::kNormal);
+    p.released.assign((size_t)S * cbs, 0);
+    p.reset.assign((size_t)S * cbs, 0u);
+    p.fade.resize((size_t)S);
+    p.fadeRest.resize((size_t)S);
+    for (int s = 0; s < S; ++s) {
+        for (int t = 0; t < cbs; ++t) {
+            const EqBypass::Step st = bypass[s].callback(B, totalSteps, p.fade[(size_t)s]);
+            p.cls[p.at(s, t)] = st.cls;
+            p.released[p.at(s, t)] = st.released ? 1 : 0;
+        }
+        p.fadeRest[(size_t)s] = bypass[s].fade.current;
+    }
+    return p;
+}
+// A pending band reset is taken by the first callback that is fading (canSafelyResetState, Processing.cpp:565-568) or whose
+// input block is silent; a fully bypassed callback returns before it gets there.  Silence is only known on the device: does some
+// stream with a pending reset meet a kNormal callback before a kFade one?
+inline bool needsSilence(const EqCallPlan& p, const uint32_t* pending)
+{
+    for (int s = 0; s < p.S; ++s) {
+        if (!pending[s]) continue;
+        for (int t = 0; t < p.cbs; ++t) {
+            if (p.cls[p.at(s, t)] == EqBypass::kFade) break;
+            if (p.cls[p.at(s, t)] == EqBypass::kNormal) return true;
+        }
+    }
+    return false;
+}
+// silent: [s * cbs + t] != 0 where the stream's input block is silent, or null (nothing was asked: needsSilence was false).
+// Fills p.reset, leaves in pending[] what no callback took; true: some stream still has a reset pending
+inline bool assignResets(EqCallPlan& p, uint32_t* pending, const int* silent)
+{
+    bool anyLeft = false;
+    for (int s = 0; s < p.S; ++s) {
+        uint32_t m = pending[s];
+        for (int t = 0; t < p.cbs; ++t) {
+            if (p.released[p.at(s, t)]) m = 0xFFFFFFFFu;
+            if (!m) continue;
+            const char k = p.cls[p.at(s, t)];
+            if (k == EqBypass::kFade || (k == EqBypass::kNormal && silent && silent[p.at(s, t)])) {
+                p.reset[p.at(s, t)] = m;
+                m = 0u;
+            }
+        }
+        pending[s] = m;
+        anyLeft = anyLeft || m != 0u;
+    }
+    return anyLeft;
+}
+// A piece: a maximal run of callbacks [c0, c1) in which no stream changes class and no callback after the first carries a reset;
+// it runs the ordinary kernels with the streams' tables switched to their class.
+struct EqPiece {
+    int c0 = 0, c1 = 0;
+    struct Stream {
+        char cls;               // EqBypass::Class throughout the piece
+        uint32_t reset;         // bands cleared in front of the piece
+        size_t fadeStart;       // kFade: the piece's samples take fade[fadeStart ... fadeStart + fadeLen), then fadeEnd
+        int fadeLen;
+        double fadeEnd;
+    };
+    std::vector<Stream> streams;
+};
+inline std::vector<EqPiece> cutPieces(const EqCallPlan& p)
+{
+    std::vector<EqPiece> pieces;
+    std::vector<size_t> used((size_t)p.S, 0);           // fade values of the stream consumed by earlier pieces
+    for (int c0 = 0; c0 < p.cbs;) {
+        auto sameClass = [&](int t) {
+            for (int s = 0; s < p.S; ++s)
+                if (p.cls[p.at(s, t)] != p.cls[p.at(s, c0)] || p.reset[p.at(s, t)]) return false;
+            return true;
+        };
+        int c1 = c0 + 1;
+        while (c1 < p.cbs && sameClass(c1)) ++c1;
+        EqPiece pc;
+        pc.c0 = c0; pc.c1 = c1;
+        const size_t n = (size_t)(c1 - c0) * p.B;
+        for (int s = 0; s < p.S; ++s) {
+            const std::vector<double>& f = p.fade[(size_t)s];
+            EqPiece::Stream ps{ p.cls[p.at(s, c0)], p.reset[p.at(s, c0)], used[(size_t)s], 0, 1.0 };
+            if (ps.cls == EqBypass::kFade) {
+                ps.fadeLen = (int)std::min(f.size() - ps.fadeStart, n);
+                // past the end of the ramp getNextValue keeps returning its final value; a ramp that drew nothing rests
+                ps.fadeEnd = f.empty() ? p.fadeRest[(size_t)s] : f[std::min(f.size(), ps.fadeStart + n) - 1];
+                used[(size_t)s] += (size_t)ps.fadeLen;
+            }
+            pc.streams.push_back(ps);
+        }
+        pieces.push_back(std::move(pc));
+        c0 = c1;
+    }
+    return pieces;
+}
 
 // processor-level mix smoother (src/ConvolverProcessor.h:945; Runtime.cpp:340-375, 591-607); ramp.totalSteps is the
 // smoothing time of the stream's parameters

@@ -104,17 +104,28 @@ void launch_rfft_inv_ols(hipStream_t stream, const double2* Y, double* out, int6
 void launch_rfft_inv_ols_ring(hipStream_t stream, const double2* Y, double* ring, int ringSize, const long long* pos,
                               long long pos0, FftTables tw, int P, int nCh, int T, double2* scratch = nullptr);
 
-// 20-band TPT-SVF cascade, lane = (channel, band), bands skewed in time across lanes.  streamPairs: one wave per
-// stream (its L and R channel) instead of 3 channels per wave -- required when a band has flag bits 4/5
-// (Mid / Side component band).
+// Device tables of one cascade -- the EQ's 20 TPT-SVF bands, or the output filter's DF-II-T sections in band slots 0 .. 2 --
+// for every stream s and its channels ch = 0, 1.  The one place that states their layout:
+struct CascadeTables {
+    double* coef = nullptr;      // [2 s + ch][kBands][6]   a1 a2 a3 m0 m1 m2; DF-II-T section: b0 b1 b2 a1 a2 -
+    int* flags = nullptr;        // [2 s + ch][kBands]      bit 0 active, 1 not a Stereo band, 2 DF-II-T, 3 parallel, 4 / 5 Mid / Side
+    double* satGain = nullptr;   // [2 s + ch][2]           saturation, total gain
+    double* state = nullptr;     // [2 s + ch][kBands][2]   carried across calls
+    double* tp = nullptr;        // [s][kBands * kSvfTpTableDoubles]   tables of the time-parallel kernels (below)
+    static constexpr size_t stateDoubles(int nCh) { return (size_t)nCh * kBands * 2; }
+    static constexpr size_t stateAt(int s, int ch, int band) { return ((size_t)(2 * s + ch) * kBands + band) * 2; }
+};
+
+// 20-band TPT-SVF cascade over the tables t (t.tp is not read), lane = (channel, band), bands skewed in time across lanes.
+// streamPairs: one wave per stream (its L and R channel) instead of 3 channels per wave -- required when a band has flag
+// bits 4/5 (Mid / Side component band).
 void launch_svf_cascade(hipStream_t stream, const double* in, double* out, int64_t chStride, int nCh,
-                        int nSamples, const double* coef, const int* flags, const double* satGain,
-                        double* state, bool streamPairs);
+                        int nSamples, CascadeTables t, bool streamPairs);
 
 // Time-parallel SVF cascade (svf_kernels.hip): whole 8192-sample spans on k_svf_cascade_tpv<8> (one workgroup per channel, or
 // chained spans, below), what is left from 1024 samples up as one span of 1 ... 7 waves x 1024 samples whose tail may be
 // padding, the rest (and calls below 1024 samples) on k_svf_cascade_short.  nSamples: any number.
-// tables: kSvfTpTableDoubles doubles per (stream, band): for each chunk length LC in kSvfTpLc ({16, 8}): Mk[6][4] = A^(LC 2^k),
+// t.tp: kSvfTpTableDoubles doubles per (stream, band): for each chunk length LC in kSvfTpLc ({16, 8}): Mk[6][4] = A^(LC 2^k),
 // Mw[4] = A^(64 LC), P[64][4] = A^(LC (c+1)), G[16][2] = C A^i; then the chunk's end-state map e[2][16] = A^(15-k) B.
 // geometry constants kSvfTpLc / kSvfTpTableDoubles: host_design.hpp (shared with the table builder)
 // chain / chainSpans / chainGrid: chained spans for engines whose channels do not fill whole rounds of the workgroups the chip
@@ -124,8 +135,7 @@ void launch_svf_cascade(hipStream_t stream, const double* in, double* out, int64
 // `chain` (svf_chain_bytes(channels, 0) bytes, zero-initialised once; may be nullptr) then only holds the arrival counters by
 // which the two workgroups of a CU take turns at raised priority.
 void launch_svf_cascade_tp(hipStream_t stream, const double* in, double* out, int64_t chStride, int nCh,
-                           int nSamples, const double* coef, const int* flags, const double* satGain,
-                           double* state, const void* tables, void* chain = nullptr, int chainSpans = 0,
+                           int nSamples, CascadeTables t, void* chain = nullptr, int chainSpans = 0,
                            int chainGrid = 0);
 size_t svf_chain_bytes(int nCh, int maxSamples);
 int svf_chain_spans(int maxSamples);

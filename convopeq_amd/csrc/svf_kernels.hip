@@ -1548,14 +1548,14 @@ __global__ __launch_bounds__(256, 1) void k_svf_cascade_short(const double* in, 
 }  // namespace
 
 void launch_svf_cascade(hipStream_t stream, const double* in, double* out, int64_t chStride, int nCh, int nSamples,
-                        const double* coef, const int* flags, const double* satGain, double* state, bool streamPairs)
+                        CascadeTables t, bool streamPairs)
 {
     if (streamPairs)
         hipLaunchKernelGGL(k_svf_cascade<2>, dim3((nCh + 1) / 2), dim3(64), 0, stream, in, out, chStride, nCh, nSamples,
-                           coef, flags, satGain, state);
+                           t.coef, t.flags, t.satGain, t.state);
     else
         hipLaunchKernelGGL(k_svf_cascade<3>, dim3((nCh + 2) / 3), dim3(64), 0, stream, in, out, chStride, nCh, nSamples,
-                           coef, flags, satGain, state);
+                           t.coef, t.flags, t.satGain, t.state);
 }
 
 int svf_chain_spans(int maxSamples) { return maxSamples / kTpvSpan + 1; }
@@ -1567,13 +1567,12 @@ size_t svf_chain_bytes(int nCh, int maxSamples)
 }
 
 void launch_svf_cascade_tp(hipStream_t stream, const double* in, double* out, int64_t chStride, int nCh, int nSamples,
-                           const double* coef, const int* flags, const double* satGain, double* state,
-                           const void* tables, void* chain, int chainSpans, int chainGrid)
+                           CascadeTables t, void* chain, int chainSpans, int chainGrid)
 {
     static_assert(sizeof(TpBandTables) == kSvfTpTableDoubles * sizeof(double), "host/device table layout");
     // whole 8192-sample spans on the eight-wave kernel, what is left as one span of 1 ... 7 waves x 1024 samples, and a
     // last block of 512 on the chunk-length-2 path of the four-wave kernel
-    const TpBandTables* tb = reinterpret_cast<const TpBandTables*>(tables);
+    const TpBandTables* tb = reinterpret_cast<const TpBandTables*>(t.tp);
     constexpr unsigned kAllBands = 0xFFFFFu | kTpvApplyGain;
     int done = 0;
     const int nSpans8 = nSamples / kTpvSpan;
@@ -1583,11 +1582,11 @@ void launch_svf_cascade_tp(hipStream_t stream, const double* in, double* out, in
         if (chain && chainSpans > 0 && nSpans8 >= 2 && nSpans8 <= chainSpans) {
             const int nTasks = nSpans8 * nCh;
             hipLaunchKernelGGL((k_svf_cascade_tpv<kTpvWaves, true>), dim3(nTasks < chainGrid ? nTasks : chainGrid), dim3(kTpvWaves * 64), 0, stream,
-                               in, out, chStride, nSpans8, nCh, coef, flags, satGain, state, tb, reinterpret_cast<unsigned long long*>(chain),
+                               in, out, chStride, nSpans8, nCh, t.coef, t.flags, t.satGain, t.state, tb, reinterpret_cast<unsigned long long*>(chain),
                                chainSpans, kAllBands, 0);
         } else {
             hipLaunchKernelGGL((k_svf_cascade_tpv<kTpvWaves, false>), dim3(nCh), dim3(kTpvWaves * 64), 0, stream, in, out, chStride, nSpans8, nCh,
-                               coef, flags, satGain, state, tb, reinterpret_cast<unsigned long long*>(chain), 0, kAllBands, 0);
+                               t.coef, t.flags, t.satGain, t.state, tb, reinterpret_cast<unsigned long long*>(chain), 0, kAllBands, 0);
         }
         done = nSpans8 * kTpvSpan;
     }
@@ -1602,10 +1601,10 @@ void launch_svf_cascade_tp(hipStream_t stream, const double* in, double* out, in
         const dim3 block(((cnt + 1023) / 1024) * 64);
         if (cnt % 1024 == 0)
             hipLaunchKernelGGL((k_svf_cascade_tpv<0, false, false>), dim3(nCh), block, 0, stream, in + done, out + done, chStride, 1, nCh,
-                               coef, flags, satGain, state, tb, (unsigned long long*)nullptr, 0, kAllBands, cnt);
+                               t.coef, t.flags, t.satGain, t.state, tb, (unsigned long long*)nullptr, 0, kAllBands, cnt);
         else
             hipLaunchKernelGGL((k_svf_cascade_tpv<0, false, true>), dim3(nCh), block, 0, stream, in + done, out + done, chStride, 1, nCh,
-                               coef, flags, satGain, state, tb, (unsigned long long*)nullptr, 0, kAllBands, cnt);
+                               t.coef, t.flags, t.satGain, t.state, tb, (unsigned long long*)nullptr, 0, kAllBands, cnt);
         done += cnt;
     }
     if (nSamples > done) {
@@ -1613,7 +1612,7 @@ void launch_svf_cascade_tp(hipStream_t stream, const double* in, double* out, in
         // one or two: profiles/r04f_eq_short_calls.txt)
         const int cnt = nSamples - done;
         hipLaunchKernelGGL(k_svf_cascade_short<8>, dim3(nCh), dim3(((cnt + 511) / 512) * 64), 0, stream, in + done, out + done, chStride, cnt,
-                           coef, flags, satGain, state, tb);
+                           t.coef, t.flags, t.satGain, t.state, tb);
     }
 }
 }  // namespace cpq

@@ -5,7 +5,10 @@
 //      leave the same state (the reference only ever sees callbacks, so it has this by construction)
 //   3. what is predicted on a copy (which convolver rests, where latency fades start) is what the replay then does, and the
 //      original is untouched by the prediction
-// The per-call drivers below are the loops of enqueueEqCore / enqueueEqRange / enqueueConvProc without their uploads.
+//   4. the EQ's plan of a call (planEqGain, planEqCall, needsSilence, assignResets, cutPieces -- the planners engine_eq.cpp
+//      itself calls): invariant under the cut into calls for several streams at once, its pieces tile the call, and the fade end
+//      value of a piece in hand-written cases
+// The mix and latency drivers below are the loops of enqueueConvProc without their uploads.
 #include "host_replay.hpp"
 
 #include <cstdio>
@@ -45,15 +48,21 @@ static bool same(const LatencyFade& a, const LatencyFade& b)
 struct Shape { int B; double rate; };
 
 struct GainOut { double start, increment; bool operator==(const GainOut&) const = default; };
-// enqueueEqCore: a stream that is not moving at the start of the call draws nothing (the cascade kernel applies `wanted`)
+// planEqGain: a stream that is not moving at the start of the call draws nothing (the cascade kernel applies `wanted`)
 static void gainCall(GainRamp& r, const Shape& sh, int cbs, std::vector<GainOut>& out)
 {
-    const int total = LinearRamp::stepsFor(sh.rate, 0.05);
-    if (!r.moving()) { out.insert(out.end(), (size_t)cbs, GainOut{ r.wanted, 0.0 }); return; }
-    for (int t = 0; t < cbs; ++t) {
-        const GainRamp::Segment g = r.callback(sh.B, total);
-        out.push_back({ g.start, g.increment });
-    }
+    const int agcOff = 0;
+    const GainRamp before = r;
+    const bool predicted = anyGainRamp(&r, &agcOff, nullptr, 1);
+    CHECK(same(before, r));                                     // the prediction moved nothing
+    const EqGainPlan g = planEqGain(&r, &agcOff, nullptr, 1, cbs, sh.B, LinearRamp::stepsFor(sh.rate, 0.05));
+    CHECK(predicted == g.anyRamp);
+    // the device gain flips exactly when it has to (devUnity is the engine's to set: it stays false here)
+    CHECK(g.flips.size() == (g.anyRamp ? 1u : 0u));
+    if (g.anyRamp) CHECK(g.flips[0].s == 0 && g.flips[0].unity && g.flips[0].gain == 1.0 && g.rampOn[0] == 1);
+    if (!g.anyRamp) { CHECK(g.segments.empty() && g.rampOn.empty()); out.insert(out.end(), (size_t)cbs, GainOut{ r.wanted, 0.0 }); return; }
+    CHECK(g.segments.size() == (size_t)cbs * 2);
+    for (int t = 0; t < cbs; ++t) out.push_back({ g.segments[(size_t)t * 2], g.segments[(size_t)t * 2 + 1] });
 }
 
 struct BypassOut {
@@ -63,12 +72,110 @@ struct BypassOut {
 };
 static void bypassCall(EqBypass& b, const Shape& sh, int cbs, BypassOut& out)
 {
-    const int total = LinearRamp::stepsFor(sh.rate, 0.005);
-    for (int t = 0; t < cbs; ++t) {
-        const EqBypass::Step st = b.callback(sh.B, total, out.vals);
-        out.cls.push_back(st.cls);
-        out.released.push_back(st.released ? 1 : 0);
+    const EqCallPlan p = planEqCall(&b, 1, cbs, sh.B, LinearRamp::stepsFor(sh.rate, 0.005));
+    out.cls.insert(out.cls.end(), p.cls.begin(), p.cls.end());
+    out.released.insert(out.released.end(), p.released.begin(), p.released.end());
+    out.vals.insert(out.vals.end(), p.fade[0].begin(), p.fade[0].end());
+    CHECK(p.fadeRest[0] == b.fade.current);
+}
+
+// The whole EQ plan of a call over several streams, as enqueueEqRange runs the planners.  silent: the script's flag per
+// (stream, callback of the stretch), the same however the stretch is cut; pos: callbacks of the stretch already played.
+struct EqState { std::vector<EqBypass> byp; std::vector<uint32_t> pending; int pos; };
+static bool same(const EqState& a, const EqState& b)
+{
+    if (a.byp.size() != b.byp.size() || a.pending != b.pending || a.pos != b.pos) return false;
+    for (size_t s = 0; s < a.byp.size(); ++s)
+        if (!same(a.byp[s], b.byp[s])) return false;
+    return true;
+}
+struct EqOut {
+    std::vector<char> cls;              // per (callback, stream)
+    std::vector<uint32_t> reset;        // per (callback, stream)
+    std::vector<double> gain;           // per (callback, stream, sample): the cross-fade gain, 1 = EQ alone, kPass: 0
+    std::vector<uint32_t> left;         // masks still pending behind the last call
+    bool operator==(const EqOut&) const = default;
+};
+struct EqSaw {
+    bool resetByFade = false, resetBySilence = false, pendingLeft = false, releaseClears = false, noSilenceAsked = false,
+         cutByResetAlone = false, cutByOneStream = false;
+};
+static void checkPieces(const EqCallPlan& p, const std::vector<EqPiece>& pieces, EqSaw& saw)
+{
+    int at = 0;
+    for (const EqPiece& pc : pieces) {
+        CHECK(pc.c0 == at && pc.c1 > pc.c0 && pc.c1 <= p.cbs && (int)pc.streams.size() == p.S);     // contiguous, not empty
+        for (int s = 0; s < p.S; ++s) {
+            const EqPiece::Stream& ps = pc.streams[(size_t)s];
+            CHECK(ps.reset == p.reset[p.at(s, pc.c0)]);
+            for (int t = pc.c0; t < pc.c1; ++t) {
+                CHECK(p.cls[p.at(s, t)] == ps.cls);                         // one class per stream
+                CHECK(t == pc.c0 || p.reset[p.at(s, t)] == 0u);             // a reset only in front
+            }
+            CHECK(ps.fadeLen >= 0 && ps.fadeLen <= (pc.c1 - pc.c0) * p.B && ps.fadeStart + (size_t)ps.fadeLen <= p.fade[(size_t)s].size());
+            CHECK(ps.cls == EqBypass::kFade || (ps.fadeLen == 0 && ps.fadeEnd == 1.0));
+        }
+        if (pc.c1 < p.cbs) {            // maximal: the cut has a reason, in some stream
+            int byClass = 0, byReset = 0, streams = 0;
+            for (int s = 0; s < p.S; ++s) {
+                const bool c = p.cls[p.at(s, pc.c1)] != p.cls[p.at(s, pc.c0)], r = p.reset[p.at(s, pc.c1)] != 0u;
+                byClass += c; byReset += r; streams += c || r;
+            }
+            CHECK(streams > 0);
+            saw.cutByResetAlone = saw.cutByResetAlone || (byClass == 0 && byReset > 0);
+            saw.cutByOneStream = saw.cutByOneStream || (streams == 1 && p.S > 1);
+        }
+        at = pc.c1;
     }
+    CHECK(at == p.cbs);                 // ... and they cover the call
+}
+static void eqCall(EqState& st, const Shape& sh, int cbs, const std::vector<std::vector<int>>& silent, EqOut& out, EqSaw& saw)
+{
+    const int S = (int)st.byp.size();
+    const std::vector<uint32_t> before = st.pending;
+    EqCallPlan p = planEqCall(st.byp.data(), S, cbs, sh.B, LinearRamp::stepsFor(sh.rate, 0.005));
+    const bool ask = needsSilence(p, st.pending.data());
+    std::vector<int> flags((size_t)S * cbs);
+    for (int s = 0; s < S; ++s)
+        for (int t = 0; t < cbs; ++t) flags[p.at(s, t)] = silent[(size_t)s][(size_t)(st.pos + t)];
+    const bool left = assignResets(p, st.pending.data(), ask ? flags.data() : nullptr);     // no flags unless asked for, as in the engine
+    bool anyLeft = false;
+    for (uint32_t m : st.pending) anyLeft = anyLeft || m != 0u;
+    CHECK(left == anyLeft);
+    saw.pendingLeft = saw.pendingLeft || left;
+    const std::vector<EqPiece> pieces = cutPieces(p);
+    checkPieces(p, pieces, saw);
+    std::vector<double> gain((size_t)S * cbs * sh.B, 0.0);
+    for (const EqPiece& pc : pieces)
+        for (int s = 0; s < S; ++s) {
+            const EqPiece::Stream& ps = pc.streams[(size_t)s];
+            for (int i = 0; i < (pc.c1 - pc.c0) * sh.B; ++i) {
+                double g = ps.cls == EqBypass::kNormal ? 1.0 : 0.0;
+                if (ps.cls == EqBypass::kFade) g = i < ps.fadeLen ? p.fade[(size_t)s][ps.fadeStart + (size_t)i] : ps.fadeEnd;
+                gain[((size_t)s * cbs + pc.c0) * sh.B + (size_t)i] = g;
+            }
+        }
+    for (int s = 0; s < S; ++s) {
+        bool fadeFirst = false;
+        for (int t = 0; t < cbs && !fadeFirst && p.cls[p.at(s, t)] != EqBypass::kNormal; ++t) fadeFirst = p.cls[p.at(s, t)] == EqBypass::kFade;
+        saw.noSilenceAsked = saw.noSilenceAsked || (!ask && before[(size_t)s] != 0u && fadeFirst);
+        for (int t = 0; t < cbs; ++t) {
+            const uint32_t m = p.reset[p.at(s, t)];
+            const char k = p.cls[p.at(s, t)];
+            CHECK(m == 0u || k != EqBypass::kPass);
+            saw.resetByFade = saw.resetByFade || (m != 0u && k == EqBypass::kFade && !p.released[p.at(s, t)]);
+            saw.resetBySilence = saw.resetBySilence || (m != 0u && k == EqBypass::kNormal);
+            if (p.released[p.at(s, t)]) { CHECK(m == 0xFFFFFFFFu && k == EqBypass::kFade); saw.releaseClears = true; }
+        }
+    }
+    for (int t = 0; t < cbs; ++t)
+        for (int s = 0; s < S; ++s) {
+            out.cls.push_back(p.cls[p.at(s, t)]);
+            out.reset.push_back(p.reset[p.at(s, t)]);
+            out.gain.insert(out.gain.end(), gain.begin() + (long)(p.at(s, t) * sh.B), gain.begin() + (long)((p.at(s, t) + 1) * sh.B));
+        }
+    out.left = st.pending;
+    st.pos += cbs;
 }
 
 // enqueueConvProc, mix: per-sample values over the smoothed prefix, the value the ramp rests at behind it
@@ -254,6 +361,86 @@ static void splitScripts()
         }
 }
 
+// 2 or 3 streams whose bypass requests and band resets change between stretches, each stream on its own; the silence flags are
+// scripted per (stream, callback) of the stretch
+static void eqPlanScripts()
+{
+    const Shape shapes[3] = { { 64, 48000.0 }, { 441, 44100.0 }, { 512, 48000.0 } };
+    for (const Shape& sh : shapes) {
+        EqSaw saw;
+        for (uint64_t seed = 1; seed <= 6; ++seed) {
+            Rng rng{ seed * 104729u + (uint64_t)sh.B };
+            const int S = 2 + (int)(seed % 2);
+            EqState st{ std::vector<EqBypass>((size_t)S), std::vector<uint32_t>((size_t)S, 0u), 0 };
+            for (int seg = 0; seg < 120; ++seg) {
+                for (int s = 0; s < S; ++s) {
+                    if (rng.below(5) == 0) st.byp[(size_t)s].requested = !st.byp[(size_t)s].requested;
+                    if (rng.below(4) == 0) st.pending[(size_t)s] |= rng.below(8) ? (1u << rng.below(20)) | (1u << rng.below(20)) : 0xFFFFFFFFu;
+                }
+                const std::vector<int> lens = callbacks(rng, sh.B, false);
+                std::vector<std::vector<int>> silent((size_t)S, std::vector<int>(lens.size(), 0));
+                for (auto& row : silent)
+                    for (int& f : row) f = rng.below(4) == 0;
+                st.pos = 0;
+                EqOut eo;
+                st = splitInvariant(st, lens, false, [&](EqState& q, int cbs, EqOut& o) { eqCall(q, sh, cbs, silent, o, saw); }, eo);
+                CHECK(eo.cls.size() == lens.size() * (size_t)S && eo.gain.size() == eo.cls.size() * (size_t)sh.B && st.pos == (int)lens.size());
+            }
+        }
+        CHECK(saw.resetByFade && saw.resetBySilence && saw.pendingLeft && saw.releaseClears && saw.noSilenceAsked);
+        CHECK(saw.cutByResetAlone && saw.cutByOneStream);           // the scripts reach every way a reset is taken and a call is cut
+    }
+}
+
+// the fade end value of a piece, by hand
+static void fadeEndValues()
+{
+    {   // 48 kHz, B = 64: the fade-out of 240 steps ends inside its piece of 4 callbacks; the pass-through piece follows
+        EqBypass b;
+        b.requested = true;
+        const EqCallPlan p = planEqCall(&b, 1, 6, 64, LinearRamp::stepsFor(48000.0, 0.005));
+        const std::vector<EqPiece> pieces = cutPieces(p);
+        CHECK(pieces.size() == 2 && pieces[0].c0 == 0 && pieces[0].c1 == 4 && pieces[1].c1 == 6 && p.fade[0].size() == 240);
+        const EqPiece::Stream& f = pieces[0].streams[0];
+        CHECK(f.cls == EqBypass::kFade && f.fadeStart == 0 && f.fadeLen == 240 && f.fadeEnd == 0.0 && f.fadeEnd == p.fade[0][239]);
+        CHECK(pieces[1].streams[0].cls == EqBypass::kPass && pieces[1].streams[0].fadeLen == 0 && pieces[1].streams[0].fadeEnd == 1.0);
+    }
+    {   // 51.2 kHz: 256 steps end exactly with the piece's fourth callback
+        EqBypass b;
+        b.requested = true;
+        CHECK(LinearRamp::stepsFor(51200.0, 0.005) == 256);
+        const EqCallPlan p = planEqCall(&b, 1, 5, 64, 256);
+        const std::vector<EqPiece> pieces = cutPieces(p);
+        CHECK(pieces.size() == 2 && pieces[0].c1 == 4 && p.fade[0].size() == 256);
+        const EqPiece::Stream& f = pieces[0].streams[0];
+        CHECK(f.fadeLen == 256 && f.fadeEnd == 0.0 && p.fade[0][254] != 0.0 && p.fade[0][255] == 0.0);
+    }
+    {   // a second stream cuts the fade in two pieces: the first ends at the value of its last sample, the second starts behind it
+        EqBypass b[2];
+        b[0].requested = true;
+        b[1].requested = true; b[1].sync();                     // stream 1 passes through; its class is changed by hand
+        EqCallPlan p = planEqCall(b, 2, 2, 64, 240);
+        p.cls[p.at(1, 1)] = EqBypass::kNormal;
+        const std::vector<EqPiece> pieces = cutPieces(p);
+        CHECK(pieces.size() == 2 && pieces[0].c1 == 1 && p.fade[0].size() == 128);
+        CHECK(pieces[0].streams[0].fadeLen == 64 && pieces[0].streams[0].fadeEnd == p.fade[0][63]);
+        CHECK(pieces[1].streams[0].fadeStart == 64 && pieces[1].streams[0].fadeLen == 64 && pieces[1].streams[0].fadeEnd == p.fade[0][127]);
+        CHECK(p.fade[0][127] != 0.0 && p.fadeRest[0] == p.fade[0][127]);
+    }
+    {   // a kFade piece whose ramp drew nothing ends where the fade rests
+        EqCallPlan p;
+        p.S = 1; p.cbs = 2; p.B = 64;
+        p.cls.assign(2, EqBypass::kFade);
+        p.released.assign(2, 0);
+        p.reset.assign(2, 0u);
+        p.fade.resize(1);
+        p.fadeRest.assign(1, 0.25);
+        const std::vector<EqPiece> pieces = cutPieces(p);
+        CHECK(pieces.size() == 1 && pieces[0].c0 == 0 && pieces[0].c1 == 2);
+        CHECK(pieces[0].streams[0].fadeLen == 0 && pieces[0].streams[0].fadeStart == 0 && pieces[0].streams[0].fadeEnd == 0.25);
+    }
+}
+
 // test_latency_cross_fade_starting_in_a_one_sample_call: quantum 96, the latency moves just before a call of ONE sample
 static void oneSampleFadeStart()
 {
@@ -361,6 +548,8 @@ int main()
     oneSampleFadeStart();
     unequalRamps();
     splitScripts();
+    eqPlanScripts();
+    fadeEndValues();
     std::printf("%d checks, %d failed checks\n", g_checks, g_failed);
     return g_failed ? 1 : 0;
 }
