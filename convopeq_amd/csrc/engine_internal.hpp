@@ -2,7 +2,9 @@
 //   engine_core.cpp  create / destroy / prepare, status and profiling entry points, DSPCore routing (whole path); what the stage
 //                    files below share: checkCall, checkBaseRows, hostRoundTrip, refreshBaseRateStages
 //   engine_conv.cpp  kernel-level convolver: set_impulse, FilterSpec tail layers, the per-call kernel sequence
-//   engine_native.cpp  plan groups: streams whose convolver runs on the reference's own layer plan, replayed per chunk
+//   engine_native.cpp  plan groups: streams whose convolver runs on the reference's own layer plan; a call is carried out as
+//                    nuc_replay.hpp plans it
+//   engine_upload.cpp  the pinned staging ring behind every small host -> device upload of a call
 //   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
 //   engine_eq.cpp    EQ and output filter: design into one host image of a stream's tables, the one routine that uploads it,
 //                    and the EQ call carried out piece by piece as host_replay.hpp plans it
@@ -18,7 +20,8 @@
 //                    the device buffers of this header; design, checks, host path and tail trim are resample_design.cpp's)
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp, and so is the EQ's plan of a call (gain segments, bypass classes, band resets, pieces): HIP-free steppers
-// and planners that return plain data; the engine files allocate, upload and launch.
+// and planners that return plain data; the engine files allocate, upload and launch.  The plan groups' integer state (the
+// reference's Add / Get bookkeeping per layer) and the plan of one of their calls are nuc_replay.hpp's, in the same way.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
 // feature allocated on first use, all of it freed with the engine.
 #pragma once
@@ -42,6 +45,7 @@
 #include "device_buffers.hpp"
 #include "host_design.hpp"
 #include "host_replay.hpp"
+#include "nuc_replay.hpp"
 #include "resample_design.hpp"
 #include "kernels.hpp"
 
@@ -59,18 +63,9 @@ struct ProfileSlot {
 // air-absorption damping) multiply every partition spectrum of a layer at that layer's FFT size, which folds time-aliased
 // energy into the frame (src/MKLNonUniformConvolver.cpp:336-443) -- only reproducible with the same partitioning; and the
 // reference's Add / Get bookkeeping (input fill, distributed tail MAC, delay-line reader) runs per layer.
-// What a layer carries over when its group is resized or a member is moved to a group of its own: plain host state.
-struct LayerState {
-    int head = 0, histSel = 0, accSel = 0, fill = 0;     // FDL ring head, ping-pong selectors, input fill (inputPos)
-    int fftAhead = 0;           // blocks of this call already transformed straight from the call's input (groupsAppend), 0 = none
-    // host replay of the reference's integer state: layer 0 -- samples written to / read from the output ring
-    // (m_ringAvail = wPos - rPos); tail layers -- delayWriteCursor / delayReadCursor, the distributed MAC's progress
-    bool distributing = false;
-    int nextPart = 0;
-    long long wPos = 0, rPos = 0;
-};
-
-struct NativeLayer : LayerState {
+// What a layer carries over when its group is resized or a member is moved to a group of its own is its LayerState
+// (nuc_replay.hpp): plain host state.
+struct NativeLayer : cpqi::LayerState {
     int P = 0, K = 0, kPad = 0, hRows = 0, ringSlots = 0, nbMax = 0, accCap = 0, outRing = 0;
     double gain = 1.0;          // tail-layer gain applied by the delay-line reader
     int ppc = 1, outputDelay = 0;       // partsPerCallback (:988-994), outputDelaySamples (:1005-1024)
@@ -95,20 +90,14 @@ struct PlanGroup {
     cpqi::DeviceBuffer<int> irSlotDev;               // [capCh] local channel -> IR slot
     cpqi::DeviceBuffer<long long> tabDev;            // the call's chunk tables
     int tabCap = 0;
-    std::vector<long long> tabHost;
-    std::vector<size_t> tabOffs;
-    std::vector<int> nbOf;
-    long long callW0 = 0, callR0 = 0;           // layer 0's write / read positions before the call in flight was replayed
-    bool tabOnDevice = false;                   // the call's tables went out with its first launch (kernel arguments)
-    bool tailsDone = false;                     // the call's tail layers ran ahead of layer 0, whose transform adds their blocks
-    bool getDeferred = false;                   // layer 0's chunk-wise ring read waits for the tails' read-add: one pass does both
+    cpqi::NucCallPlan call;                     // the call in flight: built by groupsAppend, carried out by groupsRunLayer0 / groupsRunTails
     long long samplesSinceReset = 0;
     int lastGot = 0, lastCall = 0;              // Get()'s return value summed over the chunks of the last call
-    // tail layer l's delay line as Get() reads it in the call in flight (its schedule: tabOffs[2 l]); empty when the plan has no layer l
+    // tail layer l's delay line as Get() reads it in the call in flight (its schedule: call.offs[2 l]); empty when the plan has no layer l
     cpq::RingTap tap(size_t l) const
     {
         if (l >= layers.size()) return cpq::RingTap{};
-        return cpq::RingTap{ layers[l].ring, layers[l].outRing, tabDev + tabOffs[2 * l], layers[l].gain };
+        return cpq::RingTap{ layers[l].ring, layers[l].outRing, tabDev + call.offs[2 * l], layers[l].gain };
     }
 };
 
@@ -434,9 +423,10 @@ int hostRoundTrip(cpq_engine* e, const double* in, size_t inLen, double* out, si
 void hostTwiddles(int P, std::vector<double2>& w1, std::vector<double2>& w2);
 int zeroRuntimeState(cpq_engine* e, bool conv, bool eq);
 
-// engine_native.cpp
+// engine_upload.cpp
 int stageUpload(cpq_engine* e, void* dst, const void* src, size_t bytes);
 void freePinnedRing(cpq_engine* e);
+// engine_native.cpp
 int resetGroups(cpq_engine* e);
 int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double* irR, int irLen, double scale, int headTaps,
                      const cpq_filter_spec* spec, const cpq_nuc_plan& pl);

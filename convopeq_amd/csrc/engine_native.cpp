@@ -107,12 +107,7 @@ void layerGeometry(const cpq_engine* e, const cpq_nuc_plan& pl, int l, NativeLay
 
 void resetGroupHost(PlanGroup& g)
 {
-    for (NativeLayer& t : g.layers) {
-        t.head = t.histSel = t.accSel = t.fill = 0;
-        t.distributing = false;
-        t.nextPart = 0;
-        t.wPos = t.rPos = 0;
-    }
+    for (NativeLayer& t : g.layers) static_cast<LayerState&>(t) = LayerState{};
     g.samplesSinceReset = 0;
 }
 
@@ -134,14 +129,6 @@ int uploadGroupMaps(cpq_engine* e, PlanGroup& g)
     CPQ_HIP(e, hipMemcpy(g.chMapDev, chMap.data(), sizeof(int) * chMap.size(), hipMemcpyHostToDevice));
     CPQ_HIP(e, hipMemcpy(g.irSlotDev, irSlot.data(), sizeof(int) * irSlot.size(), hipMemcpyHostToDevice));
     return CPQ_OK;
-}
-
-int tabEntries(const cpq_engine* e, const std::vector<NativeLayer>& layers)
-{
-    const int chunks = (e->maxCall + e->B - 1) / e->B + 1;
-    int n = 2 * chunks;                                             // layer 0: pos, cnt per chunk
-    for (size_t l = 1; l < layers.size(); ++l) n += chunks + layers[l].nbMax + 1;     // sched per chunk, put position per block
-    return n;
 }
 
 // a group with room for capPairs streams: allocates every layer (the old buffers' row prefixes are kept when growing).
@@ -178,7 +165,7 @@ int sizeGroup(cpq_engine* e, PlanGroup& g, int capPairs)
         }
     }
     if (hipStreamSynchronize(e->stream) != hipSuccess) return undo(fail(e, CPQ_ERR_DEVICE, "plan group resize: stream error"));
-    const int tabCap = tabEntries(e, fresh);  // table size of the new geometry
+    const int tabCap = nucTabEntries(fresh.data(), fresh.size(), e->maxCall, e->B);  // table size of the new geometry
     {
         const int rc = allocAll(e, { { chMapNew, (size_t)newCapCh }, { irSlotNew, (size_t)newCapCh }, { tabNew, (size_t)tabCap } },
                                 "plan group tables could not be allocated");
@@ -209,67 +196,6 @@ int zeroPairState(cpq_engine* e, PlanGroup& g, int pair)
 }
 
 }  // namespace
-
-// Small host -> device uploads on the processing path (chunk schedules, per-stream gains / flags / fade tables): staged
-// through a ring of pinned memory so that the copy is truly stream-ordered, never blocks the host, and never reads host
-// storage that has gone out of scope (a pageable hipMemcpyAsync is only safe because the runtime happens to stage it
-// synchronously).  Uploads larger than a quarter of the ring take the plain copy and wait for it.
-int stageUpload(cpq_engine* e, void* dst, const void* src, size_t bytes)
-{
-    if (bytes == 0) return CPQ_OK;
-    ++e->uploadSeq;
-    PinnedRing& r = e->pinned;
-    if (!r.host) {
-        r.cap = (size_t)8 << 20;
-        CPQ_TRY(allocAll(e, { { r.host, r.cap } }, "pinned staging ring could not be allocated"));
-    }
-    const size_t need = (bytes + 255) & ~(size_t)255;
-    if (need > r.cap / 4) {
-        CPQ_HIP(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->stream));
-        CPQ_HIP(e, hipStreamSynchronize(e->stream));
-        return CPQ_OK;
-    }
-    if (r.head + need > r.cap) r.head = 0;
-    const size_t begin = r.head, end = r.head + need;
-    // uploads still in flight that own bytes of [begin, end) must have run; they retire in issue order
-    size_t done = 0;
-    for (; done < r.pending.size(); ++done) {
-        const PinnedRing::Pending& p = r.pending[done];
-        bool overlapsLater = false;
-        for (size_t k = done; k < r.pending.size() && !overlapsLater; ++k)
-            overlapsLater = r.pending[k].begin < end && begin < r.pending[k].end;
-        if (!overlapsLater) break;
-        CPQ_HIP(e, hipEventSynchronize(p.ev));
-        r.freeEvents.push_back(p.ev);
-    }
-    if (done) r.pending.erase(r.pending.begin(), r.pending.begin() + (long)done);
-    // retire whatever has completed anyway (keeps the list short)
-    while (!r.pending.empty() && hipEventQuery(r.pending.front().ev) == hipSuccess) {
-        r.freeEvents.push_back(r.pending.front().ev);
-        r.pending.erase(r.pending.begin());
-    }
-    (void)hipGetLastError();            // hipEventQuery reports "not ready" as an error code
-    std::memcpy(r.host + begin, src, bytes);
-    CPQ_HIP(e, hipMemcpyAsync(dst, r.host + begin, bytes, hipMemcpyHostToDevice, e->stream));
-    hipEvent_t ev;
-    if (!r.freeEvents.empty()) { ev = r.freeEvents.back(); r.freeEvents.pop_back(); }
-    else CPQ_HIP(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    CPQ_HIP(e, hipEventRecord(ev, e->stream));
-    r.pending.push_back(PinnedRing::Pending{ begin, end, ev });
-    r.head = end;
-    return CPQ_OK;
-}
-
-void freePinnedRing(cpq_engine* e)
-{
-    PinnedRing& r = e->pinned;
-    if (!r.host) return;
-    for (auto& p : r.pending) (void)hipEventDestroy(p.ev);
-    for (auto& ev : r.freeEvents) (void)hipEventDestroy(ev);
-    r.pending.clear();
-    r.freeEvents.clear();
-    r.host.reset();
-}
 
 int resetGroups(cpq_engine* e)
 {
@@ -346,7 +272,6 @@ static int isolateStream(cpq_engine* e, int stream)
             }
         }
         static_cast<LayerState&>(dst) = src;
-        dst.fftAhead = 0;               // (belongs to a call in flight)
     }
     n->streamOfPair[0] = stream;
     // the stream is the new group's from here on, whatever happens below: the engine stays consistent
@@ -449,161 +374,88 @@ int nativeSetImpulse(cpq_engine* e, int stream, const double* irL, const double*
 }
 
 // ---------------------------------------------------------------------------------------------------- per call
-// Replays Add() / Get() of the reference for the chunks of one call (integers only) and fills the call's tables:
-// layer 0 read position and count per chunk; per tail layer the delay-line read position per chunk (-1 = skip) and the
-// delay-line position of every block whose partition fills in this call.
-static void replayCall(const cpq_engine* e, PlanGroup& g, int n, std::vector<long long>& tab, std::vector<size_t>& offs,
-                       std::vector<int>& nbOf)
-{
-    const int q = e->B;
-    const int chunks = (n + q - 1) / q;
-    const size_t L = g.layers.size();
-    offs.assign(2 * L + 1, 0);
-    nbOf.assign(L, 0);
-    size_t at = 0;
-    for (size_t l = 0; l < L; ++l) {
-        offs[2 * l] = at; at += (size_t)chunks;                     // layer 0: pos / tails: sched
-        offs[2 * l + 1] = at;                                       // layer 0: cnt   / tails: put positions
-        at += (l == 0) ? (size_t)chunks : (size_t)((g.layers[l].fill + n) / g.layers[l].P);
-    }
-    offs[2 * L] = at;
-    tab.assign(at, -1);
-    std::vector<int> fillOf(L), pendingIdx(L, -1);      // pendingIdx: this call's block whose MAC is still being distributed
-    for (size_t l = 0; l < L; ++l) fillOf[l] = g.layers[l].fill;
-    for (int c = 0; c < chunks; ++c) {
-        const int len = std::min(q, n - c * q);
-        for (size_t l = 0; l < L; ++l) {
-            NativeLayer& t = g.layers[l];
-            // Add(): input accumulation; a partition that fills is transformed at once (:1448-1494)
-            fillOf[l] += len;
-            while (fillOf[l] >= t.P) {
-                fillOf[l] -= t.P;
-                if (l == 0) t.wPos += t.P;                          // processLayerBlock -> ringWrite
-                else {
-                    // a block still distributing is abandoned (:1487-1490): it never reaches the delay line (one of an
-                    // earlier call already sits at wPos and is overwritten by this one)
-                    if (t.distributing && pendingIdx[l] >= 0) tab[offs[2 * l + 1] + (size_t)pendingIdx[l]] = -1;
-                    tab[offs[2 * l + 1] + (size_t)nbOf[l]] = t.wPos;        // where delayLineWrite will put it -- if its MAC completes
-                    pendingIdx[l] = nbOf[l];
-                    t.distributing = true;
-                    t.nextPart = 0;
-                }
-                ++nbOf[l];
-            }
-            if (l > 0 && t.distributing) {                          // distributed MAC, once per Add() (:1497-1545)
-                t.nextPart = std::min(t.nextPart + t.ppc, t.K);
-                if (t.nextPart >= t.K) { t.wPos += t.P; t.distributing = false; t.nextPart = 0; }
-            }
-            // Get()
-            if (l == 0) {
-                const long long avail = t.wPos - t.rPos;
-                const long long toRead = std::min<long long>(len, avail);
-                tab[offs[0] + (size_t)c] = t.rPos;
-                tab[offs[1] + (size_t)c] = toRead;
-                t.rPos += toRead;
-            } else {
-                const long long maxRead = t.wPos >= t.outputDelay ? t.wPos - t.outputDelay : 0;
-                const long long start = std::max(t.rPos, maxRead);
-                if (start + len <= t.wPos) { tab[offs[2 * l] + (size_t)c] = start; t.rPos = start + len; }
-            }
-        }
-    }
-}
+// nuc_replay.hpp plans a call: planNucCall, run once per group in groupsAppend, replays the reference's Add / Get bookkeeping and
+// makes every decision.  The three functions enqueueConv calls at three points of a call -- groupsAppend, groupsRunLayer0,
+// groupsRunTails -- carry that plan out and decide nothing; what is left to them are the launchers' own limits
+// (rfft_fwd_can_carry_side, kGatherTabMax).
 
 // the group sits this call out: only the processor-level call rests a stream (ConvolverProcessor does not call its NUC then); a
 // NUC-level call runs every stream
 static bool resting(const cpq_engine* e, const PlanGroup& g) { return g.frozen && e->honourFrozen; }
 
-// layer 0 had no input waiting and nothing in its output ring before this call (w0 = its write position then)
-static bool layer0WasEmpty(const PlanGroup& g, long long w0, long long r0)
+// the call is whole partitions of layer t and its accumulator is empty: its forward transforms run straight from the call's input
+static void fftFromInput(cpq_engine* e, const PlanGroup& g, const NativeLayer& t, const double* dIn, int n)
 {
-    return g.layers[0].fill == 0 && r0 == w0;
+    ProfScope p(e, CPQ_K_RFFT_FWD);
+    cpq::launch_rfft_fwd_ols(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
+                             t.tables(), t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
+}
+
+static int appendGroup(cpq_engine* e, PlanGroup& g, const double* dIn, int n)
+{
+    NucCallPlan& c = g.call;
+    planNucCall(c, g.layers.data(), g.layers.size(), n, NucCallFacts{ e->B, e->nCh, g.usedCh, g.identityMap, e->anyDirect, cpq::kP });
+    if ((int)c.tab.size() > g.tabCap) return fail(e, CPQ_ERR_INVALID_ARG, "call of %d samples exceeds the engine's call capacity", n);
+    // the straight layers' transforms run right here (before anything can write dOut, which may alias dIn) and runLayerBlocks
+    // continues behind them; a held-back layer 0 follows below
+    for (size_t l = c.hold0 ? 1 : 0; l < c.L; ++l)
+        if (c.layer[l].straight) fftFromInput(e, g, g.layers[l], dIn, n);
+    // every other layer accumulates the same input (Add(), :1431-1446): one pass over it
+    double* dst[kNucMaxLayers];
+    int64_t stride[kNucMaxLayers], off[kNucMaxLayers];
+    for (int a = 0; a < c.nAcc; ++a) {
+        const NativeLayer& t = g.layers[(size_t)c.accLayer[a]];
+        dst[a] = t.acc[t.accSel];
+        stride[a] = t.accCap;
+        off[a] = t.fill;
+    }
+    // a small table leaves with the launch below (kernel arguments) instead of a host -> device copy of its own in front of layer 0
+    const bool ride = (int)c.tab.size() <= cpq::kGatherTabMax && g.usedCh > 0 && n > 0;
+    const int nTab = ride ? (int)c.tab.size() : 0;
+    bool gathered = c.nAcc == 0, rode = false;
+    if (c.hold0 && cpq::rfft_fwd_can_carry_side(g.layers[0].P, c.nAcc, stride, off, nTab)) {
+        const NativeLayer& t = g.layers[0];
+        ProfScope p(e, CPQ_K_RFFT_FWD);
+        cpq::launch_rfft_fwd_ols_side(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
+                                      t.tables(), g.usedCh, n / t.P, t.head, t.ringSlots, c.nAcc, dst,
+                                      stride, off, ride ? g.tabDev : nullptr, c.tab.data(), nTab);
+        gathered = true;
+        rode = ride;
+    } else if (c.hold0) {
+        fftFromInput(e, g, g.layers[0], dIn, n);
+    }
+    if (!gathered) {
+        ProfScope p(e, CPQ_K_MIX);
+        cpq::launch_rows_gather_multi(e->stream, dIn, n, g.chMapDev, c.nAcc, dst, stride, off, n, g.usedCh,
+                                      ride ? g.tabDev : nullptr, c.tab.data(), nTab);
+        rode = ride;
+    }
+    c.tabOnDevice = rode;       // the one launch outcome on the plan: from here on it is read-only
+    return CPQ_OK;
 }
 
 int groupsAppend(cpq_engine* e, const double* dIn, int n)
 {
-    for (const auto& gp : e->groups) {
-        PlanGroup& g = *gp;
-        if (resting(e, g)) continue;
-        // every layer accumulates the same input (Add(), :1431-1446): one pass over it.  A layer whose accumulator is
-        // empty and for which the call is whole partitions needs no accumulation at all when the group's rows are the
-        // call's rows: its forward transforms run right here, straight from the call's input (before anything can write
-        // dOut, which may alias dIn), and runLayerBlocks continues behind them.
-        const bool rowsAreCallRows = g.identityMap && g.usedCh == e->nCh;
-        // the reference's Add / Get bookkeeping of this call, replayed here so that a small table can leave with the gather
-        // launch below (kernel arguments) instead of a host -> device copy of its own in front of layer 0
-        g.callW0 = g.layers[0].wPos;
-        g.callR0 = g.layers[0].rPos;
-        replayCall(e, g, n, g.tabHost, g.tabOffs, g.nbOf);
-        g.tabOnDevice = false;
-        if ((int)g.tabHost.size() > g.tabCap) return fail(e, CPQ_ERR_INVALID_ARG, "call of %d samples exceeds the engine's call capacity", n);
-        double* dst[3];
-        int64_t stride[3], off[3];
-        int nl = 0, li = 0;
-        auto straight = [&](const NativeLayer& t) { return rowsAreCallRows && t.fill == 0 && n % t.P == 0 && n / t.P <= t.nbMax; };
-        // layer 0 at 512 samples, transformed straight from the input, is held back: its launch can carry the other layers'
-        // accumulation and the call's tables (one launch instead of two and a copy)
-        const bool hold0 = straight(g.layers[0]) && g.layers[0].P == cpq::kP;
-        for (NativeLayer& t : g.layers) {
-            if (li++ == 3) break;
-            t.fftAhead = 0;
-            if (straight(t)) {
-                t.fftAhead = n / t.P;
-                if (hold0 && &t == &g.layers[0]) continue;
-                ProfScope p(e, CPQ_K_RFFT_FWD);
-                cpq::launch_rfft_fwd_ols(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
-                                         t.tables(), t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
-                continue;
-            }
-            dst[nl] = t.acc[t.accSel];
-            stride[nl] = t.accCap;
-            off[nl] = t.fill;
-            ++nl;
-        }
-        const bool ride = (int)g.tabHost.size() <= cpq::kGatherTabMax && g.usedCh > 0 && n > 0;
-        bool gathered = nl == 0;
-        if (hold0) {
-            NativeLayer& t = g.layers[0];
-            ProfScope p(e, CPQ_K_RFFT_FWD);
-            if (cpq::rfft_fwd_can_carry_side(t.P, nl, stride, off, ride ? (int)g.tabHost.size() : 0)) {
-                cpq::launch_rfft_fwd_ols_side(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
-                                              t.tables(), g.usedCh, n / t.P, t.head, t.ringSlots, nl, dst,
-                                              stride, off, ride ? g.tabDev : nullptr, g.tabHost.data(), ride ? (int)g.tabHost.size() : 0);
-                gathered = true;
-                g.tabOnDevice = ride;
-            } else {
-                cpq::launch_rfft_fwd_ols(e->stream, dIn, (int64_t)n, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN,
-                                         t.tables(), t.P, g.usedCh, n / t.P, t.head, t.ringSlots, t.scratch);
-            }
-        }
-        if (!gathered) {
-            ProfScope p(e, CPQ_K_MIX);
-            cpq::launch_rows_gather_multi(e->stream, dIn, n, g.chMapDev, nl, dst, stride, off, n, g.usedCh,
-                                          ride ? g.tabDev : nullptr, g.tabHost.data(), ride ? (int)g.tabHost.size() : 0);
-            g.tabOnDevice = ride;
-        }
-    }
+    for (const auto& gp : e->groups)
+        if (!resting(e, *gp)) CPQ_TRY(appendGroup(e, *gp, dIn, n));
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;
 }
 
-// one layer: every partition that filled up in this call is convolved (FFT, FDL push, MAC over the layer's partitions,
-// IFFT; NUC.cpp:1245-1336 / :1456-1544) and stored in the layer's output ring / delay line
-// directOut != nullptr (layer 0 only): the inverse transform writes the members' output rows themselves and the output ring is
-// passed by -- the caller has checked that this call's Get() reads exactly what this call's blocks produce
-// addTails (with directOut, layer 0 at 512 samples): the transform also adds the delay-line blocks of the tail layers, which
-// the caller has run ahead of layer 0 (groupsRunLayer0)
-static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, const long long* putPos, long long ringPos0,
-                          double* directOut = nullptr, bool addTails = false)
+// layer l: every partition that filled up in this call is convolved (FFT, FDL push, MAC over the layer's partitions,
+// IFFT; NUC.cpp:1245-1336 / :1456-1544) and stored in the layer's output ring / delay line at the replayed positions
+// directOut != nullptr (layer 0 only, the plan's `direct`): the inverse transform writes the members' output rows themselves and
+// the output ring is passed by; with the plan's addTails it also adds the delay-line blocks of the tail layers, which have run
+// ahead of layer 0 then
+static int runLayerBlocks(cpq_engine* e, PlanGroup& g, const NucCallPlan& c, size_t l, double* directOut = nullptr)
 {
-    const int total = t.fill + n;
-    const int nb = total / t.P;
-    const int rem = total - nb * t.P;
+    NativeLayer& t = g.layers[l];
+    const int nb = c.layer[l].nb, rem = c.layer[l].rem;
     const int nCh = g.usedCh;
     if (nb > 0) {
         const cpq::FftTables tw = t.tables();
         bool remMoved = false;
-        if (t.fftAhead != nb) {        // (else: transformed straight from the call's input in groupsAppend)
+        if (!c.layer[l].straight) {        // (else: transformed straight from the call's input in groupsAppend)
             ProfScope p(e, CPQ_K_RFFT_FWD);
             if (t.P == cpq::kP) {      // the 512-sample transform also moves the accumulator's remainder (no copy launch behind it)
                 cpq::launch_rfft_fwd_ols_side(e->stream, t.acc[t.accSel], t.accCap, t.hist[t.histSel], t.hist[t.histSel ^ 1], t.X, t.XDN, tw, nCh, nb,
@@ -614,7 +466,6 @@ static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, co
                                          t.P, nCh, nb, t.head, t.ringSlots, t.scratch);
             }
         }
-        t.fftAhead = 0;
         {
             ProfScope p(e, CPQ_K_FDL_MAC);
             cpq::launch_fdl_mac(e->stream, e->macTile, t.X, t.H, g.irSlotDev, t.Y, t.P, nCh, t.K, t.ringSlots, t.head, nb,
@@ -626,12 +477,13 @@ static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, co
         }
         {
             // the finished blocks go where the reference puts them: layer 0 straight to the members' output rows (directOut:
-            // the output ring is passed by -- read and write positions advanced together on the host), otherwise into the
-            // layer's output ring / delay line at the replayed positions, written by the transform itself
+            // read and write positions advanced together by the replay), otherwise into the layer's output ring (layer 0: from
+            // its write position before the call) / delay line (the table's put positions), written by the transform itself
             ProfScope p(e, CPQ_K_RFFT_INV);
-            if (directOut && addTails) cpq::launch_rfft_inv_ols_add(e->stream, t.Y, directOut, (int64_t)n, tw, nCh, nb, g.tap(1), g.tap(2));
-            else if (directOut) cpq::launch_rfft_inv_ols(e->stream, t.Y, directOut, (int64_t)n, tw, t.P, nCh, nb, t.scratch);
-            else           cpq::launch_rfft_inv_ols_ring(e->stream, t.Y, t.ring, t.outRing, putPos, ringPos0, tw, t.P, nCh, nb, t.scratch);
+            if (directOut && c.addTails) cpq::launch_rfft_inv_ols_add(e->stream, t.Y, directOut, (int64_t)c.n, tw, nCh, nb, g.tap(1), g.tap(2));
+            else if (directOut) cpq::launch_rfft_inv_ols(e->stream, t.Y, directOut, (int64_t)c.n, tw, t.P, nCh, nb, t.scratch);
+            else cpq::launch_rfft_inv_ols_ring(e->stream, t.Y, t.ring, t.outRing, l == 0 ? nullptr : g.tabDev + c.offs[2 * l + 1],
+                                               l == 0 ? c.w0 : 0, tw, t.P, nCh, nb, t.scratch);
         }
         if (!remMoved && rem > 0) {
             ProfScope p(e, CPQ_K_MIX);
@@ -646,49 +498,30 @@ static int runLayerBlocks(cpq_engine* e, PlanGroup& g, NativeLayer& t, int n, co
     return CPQ_OK;
 }
 
+static int runTailBlocks(cpq_engine* e, PlanGroup& g, const NucCallPlan& c)
+{
+    for (size_t l = 1; l < c.L; ++l) CPQ_TRY(runLayerBlocks(e, g, c, l));
+    return CPQ_OK;
+}
+
 // layer 0 of every group: blocks, then the chunk-wise ring read into the members' output rows (which it overwrites)
 int groupsRunLayer0(cpq_engine* e, double* dOut, int n)
 {
     for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
         if (resting(e, g)) continue;
-        const long long w0 = g.callW0, r0 = g.callR0;        // (replayed in groupsAppend)
-        if (!g.tabOnDevice) CPQ_TRY(stageUpload(e, g.tabDev, g.tabHost.data(), g.tabHost.size() * sizeof(long long)));
-        // Whole-block call on an empty ring, every chunk's Get() taking exactly the chunk this call's blocks produce, members =
-        // all channels in order: the inverse FFT writes the output rows directly, no ring put / get (two passes and two
-        // launches less; the ring stays empty, its positions advanced on the host by the replay above)
-        bool direct = g.identityMap && g.usedCh == e->nCh && layer0WasEmpty(g, w0, r0) && n % g.layers[0].P == 0;
-        if (direct) {
-            const size_t chunks = (size_t)((n + e->B - 1) / e->B);
-            for (size_t c = 0; c < chunks && direct; ++c) {
-                const long long want = std::min<long long>(e->B, n - (long long)c * e->B);
-                direct = g.tabHost[g.tabOffs[0] + c] == w0 + (long long)c * e->B && g.tabHost[g.tabOffs[1] + c] == want;
-            }
-        }
-        // Layer 0's transform can add the tail layers' delay-line blocks as it stores the output rows (no read-modify-write pass
-        // over the output behind it) when every 512-sample block is one chunk of the call and nothing sits between layer 0 and
-        // the tails in Get() (no direct head): the tail layers then run FIRST.  Same additions in the same order: bit-identical.
-        g.tailsDone = false;
-        const bool addTails = direct && g.layers.size() >= 2 && g.layers.size() <= 3 && g.layers[0].P == cpq::kP && e->B == cpq::kP && !e->anyDirect;
-        if (addTails) {
-            for (size_t l = 1; l < g.layers.size(); ++l) {
-                CPQ_TRY(runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0));
-            }
-            g.tailsDone = true;
-        }
-        CPQ_TRY(runLayerBlocks(e, g, g.layers[0], n, nullptr, w0, direct ? dOut : nullptr, addTails));
-        // Get() reads layer 0's ring chunk by chunk and then adds the tail layers' delay-line blocks: with nothing in between (no
-        // direct head) the read waits for groupsRunTails, whose pass over the output does both
-        g.getDeferred = !direct && !e->anyDirect && g.layers.size() >= 2 && g.layers.size() <= 3;
-        if (!direct && !g.getDeferred) {
+        const NucCallPlan& c = g.call;
+        if (!c.tabOnDevice) CPQ_TRY(stageUpload(e, g.tabDev, c.tab.data(), c.tab.size() * sizeof(long long)));
+        if (c.addTails) CPQ_TRY(runTailBlocks(e, g, c));        // ahead of layer 0, whose transform adds their blocks
+        CPQ_TRY(runLayerBlocks(e, g, c, 0, c.direct ? dOut : nullptr));
+        if (!c.direct && !c.getDeferred) {
             ProfScope p(e, CPQ_K_MIX);
             cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, g.layers[0].ring, g.layers[0].outRing,
-                                    g.tabDev + g.tabOffs[0], g.tabDev + g.tabOffs[1], cpq::RingTap{}, cpq::RingTap{}, g.usedCh);
+                                    g.tabDev + c.offs[0], g.tabDev + c.offs[1], cpq::RingTap{}, cpq::RingTap{}, g.usedCh);
         }
         g.samplesSinceReset += n;
         g.lastCall = n;
-        g.lastGot = 0;
-        for (size_t c = 0; c < g.tabOffs[2] - g.tabOffs[1] && g.tabOffs[1] + c < g.tabHost.size(); ++c) g.lastGot += (int)g.tabHost[g.tabOffs[1] + c];
+        g.lastGot = c.lastGot;
     }
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;
@@ -700,20 +533,18 @@ int groupsRunTails(cpq_engine* e, double* dOut, int n)
     for (const auto& gp : e->groups) {
         PlanGroup& g = *gp;
         if (resting(e, g)) continue;
-        if (g.tailsDone) { g.tailsDone = false; continue; }     // (ran ahead of layer 0, whose transform added their blocks: groupsRunLayer0)
-        for (size_t l = 1; l < g.layers.size(); ++l) {
-            CPQ_TRY(runLayerBlocks(e, g, g.layers[l], n, g.tabDev + g.tabOffs[2 * l + 1], 0));
-        }
+        const NucCallPlan& c = g.call;
+        if (c.addTails) continue;       // (ran ahead of layer 0, whose transform added their blocks: groupsRunLayer0)
+        CPQ_TRY(runTailBlocks(e, g, c));
         // one pass over the output: layer 0's chunk-wise ring read where it was deferred, then the delay lines (layer 1 first, as
         // Get() adds them)
         ProfScope p(e, CPQ_K_MIX);
         const NativeLayer& z = g.layers[0];
-        if (g.getDeferred)
-            cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, z.ring, z.outRing, g.tabDev + g.tabOffs[0], g.tabDev + g.tabOffs[1],
+        if (c.getDeferred)
+            cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, z.ring, z.outRing, g.tabDev + c.offs[0], g.tabDev + c.offs[1],
                                     g.tap(1), g.tap(2), g.usedCh);
-        else if (g.layers.size() == 2 || g.layers.size() == 3)
+        else if (c.L >= 2)
             cpq::launch_ring_chunks(e->stream, dOut, n, g.chMapDev, n, e->B, nullptr, 0, nullptr, nullptr, g.tap(1), g.tap(2), g.usedCh);
-        g.getDeferred = false;
     }
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;
