@@ -5,7 +5,8 @@
 //   engine_native.cpp  plan groups: streams whose convolver runs on the reference's own layer plan; a call is carried out as
 //                    nuc_replay.hpp plans it
 //   engine_upload.cpp  the pinned staging ring behind every small host -> device upload of a call
-//   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade
+//   engine_proc.cpp  processor-level stage: dry delay ring, mix ramp, latency cross-fade; a call is carried out step by step as
+//                    host_replay.hpp plans it
 //   engine_eq.cpp    EQ and output filter: design into one host image of a stream's tables, the one routine that uploads it,
 //                    and the EQ call carried out piece by piece as host_replay.hpp plans it
 //   engine_os.cpp    half-band oversampler around the routing: stage buffers, per-stream state machine
@@ -19,8 +20,9 @@
 //   engine_resample.cpp  cpq_ir_resample / _batch: the device side of the IR sample-rate conversion, no engine (uses only fail and
 //                    the device buffers of this header; design, checks, host path and tail trim are resample_design.cpp's)
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
-// host_replay.hpp, and so is the EQ's plan of a call (gain segments, bypass classes, band resets, pieces): HIP-free steppers
-// and planners that return plain data; the engine files allocate, upload and launch.  The plan groups' integer state (the
+// host_replay.hpp, and so are the EQ's plan of a call (gain segments, bypass classes, band resets, pieces) and the processor-level
+// stage's (who rests, mix prefixes, latency ranges): HIP-free steppers and planners that return plain data; the engine files
+// allocate, upload and launch.  The plan groups' integer state (the
 // reference's Add / Get bookkeeping per layer) and the plan of one of their calls are nuc_replay.hpp's, in the same way.
 // Device memory is owned (device_buffers.hpp): the arena for what every engine needs, one buffer or group of buffers per
 // feature allocated on first use, all of it freed with the engine.

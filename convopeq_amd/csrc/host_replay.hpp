@@ -2,19 +2,23 @@
 // is launched.  All four are its LinearRamp (src/DspNumericPolicy.h:319-421) with a little policy on top:
 //   GainRamp     smoothTotalGain, 50 ms: setTargetValue + skip(B) per callback         (planEqGain)
 //   EqBypass     bypassFadeGain, 5 ms: requested / effective / released per callback   (planEqCall)
-//   MixRamp      mixSmoother: getNextValue per sample over a prefix of the call        (engine_proc.cpp::enqueueConvProc)
-//   LatencyFade  crossfadeGain, 20 ms, between the delay in use and the new one        (engine_proc.cpp::enqueueConvProc)
+//   MixRamp      mixSmoother: getNextValue per sample over a prefix of the call        (planProcRest, planProcMix)
+//   LatencyFade  crossfadeGain, 20 ms, between the delay in use and the new one        (planProcLatency)
 // and, built on the first two, the EQ's plan of a whole call, which engine_eq.cpp only carries out: planEqGain (which streams
 // ramp, their segments, whose device gain flips) and planEqCall / needsSilence / assignResets / cutPieces (classes, band resets
-// and the pieces of equal class the call is cut into).
+// and the pieces of equal class the call is cut into); built on the last two, the processor-level stage's plan of a call, which
+// engine_proc.cpp only carries out: planProcRest (whose convolver rests), planProcMix (the smoothed prefixes and their gain
+// pairs) and planProcLatency (the ranges between fade starts, their delays and fade values), with the stage's pure arithmetic
+// (equalPowerSin, staticMixGains, procDelay).
 // Plain integer and double arithmetic, operation for operation the reference's; no HIP, no engine: a stepper returns plain
-// data and the caller turns it into uploads and launches.  Whatever has to be known BEFORE state may move (which convolvers
-// rest in a call, where latency fades start) is found by running the same steppers on a copy.
+// data and the caller turns it into uploads and launches.  What has to be known BEFORE state may move (which convolvers rest
+// in a call) is asked of a copy of the ramp, once, in planProcRest.
 // tests/sanitize/host_replay_check.cpp drives this header alone, on the CPU.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <utility>
 #include <vector>
@@ -333,5 +337,150 @@ struct LatencyFade {
         if (!fade.isSmoothing()) { latCurrent = latTarget; oldDelay = latCurrent; }
     }
 };
+
+// ---- the processor-level stage's plan of one call of n samples, callbacks of B (the last one may be shorter), over S streams
+// (engine_proc.cpp carries it out).  Per stream: bypass[s], dryOnly[s] (mix <= 0.001), mix[s] and irPeak[s] as last set.
+
+// equalPowerSin, src/convolver/ConvolverProcessor.Runtime.cpp:26-31 (9th-order Taylor of sin(pi x / 2))
+inline double equalPowerSin(double x)
+{
+    const double t = x * (3.141592653589793238462643383279502884 * 0.5);
+    const double t2 = t * t;
+    return t * (1.0 + t2 * (-1.0 / 6.0 + t2 * (1.0 / 120.0 + t2 * (-1.0 / 5040.0 + t2 * (1.0 / 362880.0)))));
+}
+// the gains of a mix at rest (targetMixValue, the float widened, :366)
+struct MixGains { double wet, dry; };
+inline MixGains staticMixGains(double mix)
+{
+    // !needsConvolution (:374, :573-585): the delayed dry signal is copied as it is -- matters when the convolver still runs
+    // because a mix ramp is finishing in the same call
+    if (!(mix > 0.001)) return { 0.0, 1.0 };
+    return { equalPowerSin(mix) * 1.0,                              // * CONVOLUTION_HEADROOM_GAIN
+             (mix < 0.999) ? equalPowerSin(1.0 - mix) : 0.0 };      // needsDrySignal, :375, :676
+}
+// the dry signal's delay: algorithmLatency = conv->latency = the layer-0 partition P0, 0 with the direct head (:266), plus
+// irPeakLatency, clamped like :266-277 (MAX_BLOCK_SIZE 524288, MAX_IR_LATENCY 2^21)
+inline int procDelay(bool directHead, int P0, int irPeakLatency)
+{
+    const int alg = directHead ? 0 : std::min(P0, 524288);
+    const int peak = std::min(std::max(0, irPeakLatency), 2097152);
+    return alg + peak;
+}
+
+// Whose convolver rests in this call: needsConvolution = isSmoothing || mix > 0.001 (:374); bypassed: the convolver is not called
+// (:123-186).  A dry-only stream keeps convolving while its mix ramp runs, so streams set dry-only together can still differ for
+// a call or two when their ramps have different lengths left.  Nothing moves here: the answer is what planProcMix will decide.
+struct ProcRest {
+    std::vector<char> rest;             // [S]
+    bool allRest = true, anyRest = false;
+};
+inline ProcRest planProcRest(const MixRamp* ramps, const char* bypass, const char* dryOnly, const double* mix, int S, int n, int B)
+{
+    ProcRest r;
+    r.rest.assign((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        r.rest[(size_t)s] = bypass[s] || (dryOnly[s] && !ramps[s].wouldSmooth(mix[s], n, B));
+        r.allRest = r.allRest && r.rest[(size_t)s];
+        r.anyRest = r.anyRest || r.rest[(size_t)s];
+    }
+    return r;
+}
+
+// Mix smoothing: per callback the reference moves the ramp's target to the current mix (:366-371) and, while the ramp is running
+// at the START of a callback, mixes that whole callback with per-sample gains equalPowerSin(getNextValue()) (:591-607).
+// Parameters only change between calls, so the smoothed region is a prefix of the call.
+struct ProcMixPlan {
+    bool anyRamp = false;
+    int rampStride = 0;                 // samples per stream in gains: the longest smoothed prefix
+    std::vector<int> len;               // [S] smoothed prefix per stream; empty while nothing ramps
+    std::vector<double> gains;          // [S][rampStride][2] wet, dry per sample; zero behind a stream's prefix
+};
+// steps the ramps of the streams that are not bypassed (the bypass path does not touch the smoother, :123-186); a call in which
+// nothing ramps allocates nothing
+inline ProcMixPlan planProcMix(MixRamp* ramps, const char* bypass, const double* mix, int S, int n, int B)
+{
+    ProcMixPlan p;
+    for (int s = 0; s < S; ++s) {
+        if (bypass[s]) continue;
+        const int len = ramps[s].beginCall(mix[s], n, B);
+        if (len <= 0) continue;
+        if (!p.anyRamp) { p.len.assign((size_t)S, 0); p.anyRamp = true; }
+        p.len[(size_t)s] = len;
+        p.rampStride = std::max(p.rampStride, len);
+    }
+    if (p.anyRamp) p.gains.assign((size_t)S * p.rampStride * 2, 0.0);
+    for (int s = 0; s < S && p.anyRamp; ++s)
+        for (int i = 0; i < p.len[(size_t)s]; ++i) {
+            const double m = ramps[s].next();
+            p.gains[((size_t)s * p.rampStride + i) * 2] = equalPowerSin(m) * 1.0;
+            p.gains[((size_t)s * p.rampStride + i) * 2 + 1] = equalPowerSin(1.0 - m);
+        }
+    return p;
+}
+
+// Latency compensation per callback and stream (:263-290): a total latency that moved by >= 2 samples starts, unless one is
+// running, a 20 ms cross-fade of the dry read from the delay in use to the new one; the callbacks that start while it runs blend
+// sample by sample until the ramp ends (:394-540).  The bypass reads at the present latency (:141-145) and leaves the fade alone.
+// The call is cut into ranges of callbacks [c0, c1) at the callbacks t > 0 where some stream starts a fade: one launch each.
+struct ProcLatRange {
+    int c0 = 0, c1 = 0;
+    std::vector<int> dNew, dOld, xLen;  // [S] delay read, delay faded out, leading samples of the range with a gain of their own
+    std::vector<double> gains;          // [S][xStride], zero behind xLen[s]; empty while no stream fades in the range
+    bool fade() const { return !gains.empty(); }
+};
+struct ProcLatPlan {
+    int xStride = 0;                    // xTotal + B: no range draws more (a fade ends inside a callback at the latest)
+    std::vector<ProcLatRange> ranges;
+    bool anyFade = false;               // a fade of ONE value (a one-sample call) counts
+};
+// steps the fades of the streams that are not bypassed, each (stream, callback) once: what the callback's start showed and how
+// many values it drew are kept per stream, and the ranges are cut from that record.  reprime: the first call since prepare
+// primes every fade anew.
+inline ProcLatPlan planProcLatency(LatencyFade* fades, const char* bypass, const int* irPeak, int S, bool directHead, int P0,
+                                   bool reprime, int n, int B, int xTotal)
+{
+    const int cbs = (n + B - 1) / B;
+    struct Seen { int dNew, dOld; size_t drawn; };      // at the callback's start; values of the stream drawn in front of it
+    std::vector<Seen> seen((size_t)S * cbs);
+    std::vector<std::vector<double>> vals((size_t)S);
+    std::vector<char> starts((size_t)cbs, 0);
+    for (int s = 0; s < S; ++s) {
+        const int total = procDelay(directHead, P0, irPeak[s]);
+        if (bypass[s]) {
+            for (int t = 0; t < cbs; ++t) seen[(size_t)s * cbs + t] = { total, total, 0 };
+            continue;
+        }
+        LatencyFade& f = fades[s];
+        if (!f.primed || reprime) f.prime(P0, irPeak[s]);
+        for (int t = 0; t < cbs; ++t) {
+            if (f.beginCallback((double)total, xTotal) && t > 0) starts[(size_t)t] = 1;
+            seen[(size_t)s * cbs + t] = { f.newDelay(), (int)f.oldDelay, vals[(size_t)s].size() };
+            f.advance(std::min(B, n - t * B), &vals[(size_t)s]);
+        }
+    }
+    ProcLatPlan p;
+    p.xStride = xTotal + B;
+    for (int c0 = 0, t = 1; t <= cbs; ++t) {
+        if (t != cbs && !starts[(size_t)t]) continue;
+        ProcLatRange r;
+        r.c0 = c0; r.c1 = t;
+        r.dNew.resize((size_t)S); r.dOld.resize((size_t)S); r.xLen.resize((size_t)S);
+        for (int s = 0; s < S; ++s) {
+            const Seen& at = seen[(size_t)s * cbs + c0];
+            const size_t end = t < cbs ? seen[(size_t)s * cbs + t].drawn : vals[(size_t)s].size();
+            r.dNew[(size_t)s] = at.dNew;
+            r.dOld[(size_t)s] = at.dOld;
+            r.xLen[(size_t)s] = (int)(end - at.drawn);
+            if (end == at.drawn) continue;
+            if (r.gains.empty()) r.gains.assign((size_t)S * p.xStride, 0.0);
+            std::copy(vals[(size_t)s].begin() + (std::ptrdiff_t)at.drawn, vals[(size_t)s].begin() + (std::ptrdiff_t)end,
+                      r.gains.begin() + (std::ptrdiff_t)((size_t)s * p.xStride));
+        }
+        p.anyFade = p.anyFade || r.fade();
+        p.ranges.push_back(std::move(r));
+        c0 = t;
+    }
+    return p;
+}
 
 }  // namespace cpqi

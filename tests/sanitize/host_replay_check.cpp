@@ -3,12 +3,14 @@
 //   1. LinearRamp semantics
 //   2. call-split invariance: N callbacks as one call, as every split into two calls and as N calls give the same outputs and
 //      leave the same state (the reference only ever sees callbacks, so it has this by construction)
-//   3. what is predicted on a copy (which convolver rests, where latency fades start) is what the replay then does, and the
-//      original is untouched by the prediction
+//   3. what is predicted before state may move (which convolver rests) is what the plan then decides, and the prediction moved
+//      nothing
 //   4. the EQ's plan of a call (planEqGain, planEqCall, needsSilence, assignResets, cutPieces -- the planners engine_eq.cpp
 //      itself calls): invariant under the cut into calls for several streams at once, its pieces tile the call, and the fade end
 //      value of a piece in hand-written cases
-// The mix and latency drivers below are the loops of enqueueConvProc without their uploads.
+//   5. the processor-level stage's plan of a call (planProcRest, planProcMix, planProcLatency -- the planners engine_proc.cpp
+//      itself calls) and its arithmetic (equalPowerSin, staticMixGains, procDelay): the same properties, the shape of the gain
+//      tables and of the latency ranges in hand-written cases
 #include "host_replay.hpp"
 
 #include <cstdio>
@@ -178,62 +180,76 @@ static void eqCall(EqState& st, const Shape& sh, int cbs, const std::vector<std:
     st.pos += cbs;
 }
 
-// enqueueConvProc, mix: per-sample values over the smoothed prefix, the value the ramp rests at behind it
+// planProcRest + planProcMix of one stream: the gain pair of every sample -- the plan's over the smoothed prefix, behind it the
+// pair of the value the ramp rests at
 struct MixState { MixRamp r; double mix; };
 static bool same(const MixState& a, const MixState& b) { return same(a.r, b.r) && a.mix == b.mix; }
 static void mixCall(MixState& m, const Shape& sh, int n, std::vector<double>& out)
 {
+    const char bypass = 0, dryOnly = !(m.mix > 0.001);
     const MixRamp before = m.r;
-    const bool predicted = m.r.wouldSmooth(m.mix, n, sh.B);
+    const ProcRest rest = planProcRest(&m.r, &bypass, &dryOnly, &m.mix, 1, n, sh.B);
     CHECK(same(before, m.r));                                   // the prediction moved nothing
-    const int len = m.r.beginCall(m.mix, n, sh.B);
-    CHECK(predicted == (len > 0));                              // ... and is what the replay decides
+    const ProcMixPlan p = planProcMix(&m.r, &bypass, &m.mix, 1, n, sh.B);
+    CHECK((rest.rest[0] != 0) == (dryOnly && !p.anyRamp));      // ... and is what the ramps decide once they have moved
+    CHECK(rest.allRest == (rest.rest[0] != 0) && rest.anyRest == rest.allRest);
+    const int len = p.anyRamp ? p.len[0] : 0;
+    CHECK(p.anyRamp == (len > 0) && p.rampStride == len && p.gains.size() == (size_t)len * 2 && (p.anyRamp || p.len.empty()));
     CHECK(len <= n && (len == n || len % sh.B == 0));
-    for (int i = 0; i < len; ++i) out.push_back(m.r.next());
+    out.insert(out.end(), p.gains.begin(), p.gains.end());
     if (len < n) CHECK(!m.r.ramp.isSmoothing());                // the prefix covers the whole ramp or the whole call
-    for (int i = len; i < n; ++i) out.push_back(m.r.ramp.current);
+    for (int i = len; i < n; ++i) { out.push_back(equalPowerSin(m.r.ramp.current) * 1.0); out.push_back(equalPowerSin(1.0 - m.r.ramp.current)); }
 }
 
-// enqueueConvProc, latency: pass 1 on a copy finds the callbacks where a fade starts, pass 2 replays range by range
-struct LatState { LatencyFade f; bool processed; int total, irPeak; };
-static bool same(const LatState& a, const LatState& b) { return same(a.f, b.f) && a.processed == b.processed && a.total == b.total; }
+// planProcLatency of one stream: per sample the delay read, the delay faded out (-1: none) and the fade gain
+struct LatState { LatencyFade f; bool processed; int irPeak; };
+static bool same(const LatState& a, const LatState& b) { return same(a.f, b.f) && a.processed == b.processed && a.irPeak == b.irPeak; }
 struct LatSample { int dNew, dOld; double g; bool operator==(const LatSample&) const = default; };
 constexpr int kP0 = 64;
+// what every plan shows: the ranges tile the call, a range behind the first begins where some stream starts a fade (its first
+// value is one step of xTotal) and no fade starts inside a range (the values of a row only rise)
+static void checkRanges(const ProcLatPlan& p, int S, int n, int B, int xTotal)
+{
+    const int cbs = (n + B - 1) / B;
+    int at = 0;
+    bool any = false;
+    CHECK(p.xStride == xTotal + B && !p.ranges.empty());
+    for (size_t r = 0; r < p.ranges.size(); ++r) {
+        const ProcLatRange& g = p.ranges[r];
+        const int len = std::min(g.c1 * B, n) - g.c0 * B;
+        CHECK(g.c0 == at && g.c1 > g.c0 && g.c1 <= cbs && (int)g.dNew.size() == S && (int)g.dOld.size() == S && (int)g.xLen.size() == S);
+        CHECK(g.gains.empty() || g.gains.size() == (size_t)S * p.xStride);
+        bool starts = false, draws = false;
+        for (int s = 0; s < S; ++s) {
+            const int x = g.xLen[(size_t)s];
+            CHECK(x >= 0 && x <= len && x <= xTotal);
+            CHECK(x == 0 || g.fade());
+            draws = draws || x > 0;
+            if (!g.fade()) continue;
+            const double* row = &g.gains[(size_t)s * p.xStride];
+            starts = starts || (x > 0 && row[0] == 1.0 / (double)xTotal);
+            for (int i = 1; i < x; ++i) CHECK(row[i] > row[i - 1]);
+            for (int i = x; i < p.xStride; ++i) CHECK(row[i] == 0.0);
+        }
+        CHECK(draws == g.fade());
+        CHECK(r == 0 || starts);
+        any = any || g.fade();
+        at = g.c1;
+    }
+    CHECK(at == cbs && any == p.anyFade);
+}
 static void latCall(LatState& st, const Shape& sh, int n, std::vector<LatSample>& out)
 {
-    const int B = sh.B, cbs = (n + B - 1) / B, xTotal = LinearRamp::stepsFor(sh.rate, 0.02);
-    auto lenOf = [&](int t) { return std::min(B, n - t * B); };
+    const int xTotal = LinearRamp::stepsFor(sh.rate, 0.02);
     const bool firstCall = !st.processed;
     st.processed = true;
-    std::vector<char> starts((size_t)cbs, 0);
-    {
-        const LatencyFade before = st.f;
-        LatencyFade f = st.f;
-        if (!f.primed || firstCall) f.prime(kP0, st.irPeak);
-        for (int t = 0; t < cbs; ++t) {
-            if (f.beginCallback((double)st.total, xTotal) && t > 0) starts[(size_t)t] = 1;
-            f.advance(lenOf(t), nullptr);
-        }
-        CHECK(same(before, st.f));
-    }
-    LatencyFade& f = st.f;
-    if (!f.primed || firstCall) f.prime(kP0, st.irPeak);
-    for (int c0 = 0, t1 = 1; t1 <= cbs; ++t1) {
-        if (t1 != cbs && !starts[(size_t)t1]) continue;
-        std::vector<double> vals;
-        int dNew = 0, dOld = 0, len = 0;
-        for (int t = c0; t < t1; ++t) {
-            const bool started = f.beginCallback((double)st.total, xTotal);
-            CHECK(t == 0 || started == (starts[(size_t)t] != 0));        // pass 1 found exactly the starts of pass 2
-            CHECK(!started || t == c0);
-            if (t == c0) { dNew = f.newDelay(); dOld = (int)f.oldDelay; }
-            f.advance(lenOf(t), &vals);
-            len += lenOf(t);
-        }
-        CHECK((int)vals.size() <= len && (int)vals.size() <= xTotal);
+    const char bypass = 0;
+    const ProcLatPlan p = planProcLatency(&st.f, &bypass, &st.irPeak, 1, false, kP0, firstCall, n, sh.B, xTotal);
+    checkRanges(p, 1, n, sh.B, xTotal);
+    for (const ProcLatRange& r : p.ranges) {
+        const int len = std::min(r.c1 * sh.B, n) - r.c0 * sh.B;
         for (int i = 0; i < len; ++i)
-            out.push_back(i < (int)vals.size() ? LatSample{ dNew, dOld, vals[(size_t)i] } : LatSample{ dNew, -1, 1.0 });
-        c0 = t1;
+            out.push_back(i < r.xLen[0] ? LatSample{ r.dNew[0], r.dOld[0], r.gains[(size_t)i] } : LatSample{ r.dNew[0], -1, 1.0 });
     }
 }
 
@@ -332,14 +348,14 @@ static void splitScripts()
             EqBypass byp;
             MixState mix{ MixRamp{}, 1.0 };
             mix.r.ramp.totalSteps = LinearRamp::stepsFor(sh.rate, seed % 2 ? 0.1 : 0.01);
-            LatState lat{ LatencyFade{}, false, kP0, 0 };
+            LatState lat{ LatencyFade{}, false, 0 };
             bool sawFade = false, sawPass = false, sawRelease = false, sawLatFade = false, sawMixRamp = false, sawGainRamp = false;
             for (int seg = 0; seg < 60; ++seg) {
                 // parameters change between calls only
                 if (rng.below(3) == 0) gain.wanted = rng.below(4) ? gainsOf[rng.below(6)] : 0.1 + rng.unit();
                 if (rng.below(4) == 0) byp.requested = !byp.requested;
                 if (rng.below(3) == 0) mix.mix = rng.below(3) ? (double)(float)rng.unit() : (rng.below(2) ? 0.0 : mix.mix + 5.0e-6);
-                if (rng.below(3) == 0) { lat.irPeak = peaks[rng.below(5)]; lat.total = kP0 + lat.irPeak; }
+                if (rng.below(3) == 0) lat.irPeak = peaks[rng.below(5)];
                 const std::vector<int> whole = callbacks(rng, sh.B, false), ragged = callbacks(rng, sh.B, true);
 
                 std::vector<GainOut> go;
@@ -352,7 +368,7 @@ static void splitScripts()
                 CHECK(byp.active() == (byp.requested || byp.effective || byp.fade.isSmoothing()));
                 std::vector<double> mo;
                 mix = splitInvariant(mix, ragged, true, [&](MixState& m, int n, std::vector<double>& o) { mixCall(m, sh, n, o); }, mo);
-                for (double v : mo) sawMixRamp = sawMixRamp || v != mo.back();
+                for (size_t i = 0; i < mo.size(); i += 2) sawMixRamp = sawMixRamp || mo[i] != mo[mo.size() - 2];
                 std::vector<LatSample> lo;
                 lat = splitInvariant(lat, ragged, true, [&](LatState& l, int n, std::vector<LatSample>& o) { latCall(l, sh, n, o); }, lo);
                 for (const auto& v : lo) sawLatFade = sawLatFade || v.dOld >= 0;
@@ -445,22 +461,120 @@ static void fadeEndValues()
 static void oneSampleFadeStart()
 {
     const Shape sh{ 96, 48000.0 };
-    LatState st{ LatencyFade{}, false, kP0 + 700, 700 };
+    LatState st{ LatencyFade{}, false, 700 };
     std::vector<LatSample> o;
     latCall(st, sh, 96 * 2, o);
     CHECK(o.size() == 192 && o[0] == (LatSample{ kP0 + 700, -1, 1.0 }) && !st.f.fading());
-    st.irPeak = 150; st.total = kP0 + 150;
+    st.irPeak = 150;
     o.clear();
     latCall(st, sh, 1, o);
     CHECK(o.size() == 1 && o[0] == (LatSample{ kP0 + 150, kP0 + 700, 1.0 / 960.0 }) && st.f.fade.remaining == 959);
     // ... and the same stretch in any cut: 1 + 288 + 2 samples as three calls or as callbacks of the quantum
-    LatState a{ LatencyFade{}, false, kP0 + 700, 700 }, b = a;
+    LatState a{ LatencyFade{}, false, 700 }, b = a;
     std::vector<LatSample> oa, ob;
     latCall(a, sh, 192, oa); latCall(b, sh, 192, ob);
-    a.irPeak = b.irPeak = 150; a.total = b.total = kP0 + 150;
+    a.irPeak = b.irPeak = 150;
     for (int n : { 1, 288, 2 }) latCall(a, sh, n, oa);
     for (int n : { 96, 96, 96, 3 }) latCall(b, sh, n, ob);
     CHECK(oa == ob && same(a, b));
+    {   // B = 64: the plan of such a call is one range of one faded sample, and the gain buffer is wanted for it
+        LatencyFade f;
+        const char bypass = 0;
+        int peak = 700;
+        planProcLatency(&f, &bypass, &peak, 1, false, kP0, true, 128, 64, 960);
+        peak = 150;
+        const ProcLatPlan p = planProcLatency(&f, &bypass, &peak, 1, false, kP0, false, 1, 64, 960);
+        CHECK(p.ranges.size() == 1 && p.ranges[0].c0 == 0 && p.ranges[0].c1 == 1 && p.ranges[0].xLen[0] == 1 && p.anyFade);
+        CHECK(p.ranges[0].fade() && p.ranges[0].gains[0] == 1.0 / 960.0 && p.ranges[0].dNew[0] == kP0 + 150 && p.ranges[0].dOld[0] == kP0 + 700);
+    }
+}
+
+// the shape of a latency plan, by hand: 48 kHz, B = 64, the fade of 960 samples is 15 callbacks
+static void latencyRanges()
+{
+    const int B = 64, xTotal = 960, S = 2;
+    LatencyFade f[2];
+    char bypass[2] = { 0, 0 };
+    int peak[2] = { 0, 300 };
+    ProcLatPlan p = planProcLatency(f, bypass, peak, S, false, kP0, true, 4 * B, B, xTotal);       // the first call primes: nothing fades
+    CHECK(p.ranges.size() == 1 && !p.anyFade && !p.ranges[0].fade() && p.ranges[0].dNew == p.ranges[0].dOld);
+    CHECK(p.ranges[0].dNew[0] == kP0 && p.ranges[0].dNew[1] == kP0 + 300 && f[0].primed && f[1].primed);
+    peak[0] = 700;
+    p = planProcLatency(f, bypass, peak, S, false, kP0, false, 4 * B, B, xTotal);                  // a fade starts at callback 0: one range
+    checkRanges(p, S, 4 * B, B, xTotal);
+    CHECK(p.ranges.size() == 1 && p.ranges[0].xLen[0] == 4 * B && p.ranges[0].xLen[1] == 0 && f[0].fade.remaining == xTotal - 4 * B);
+    CHECK(p.ranges[0].dNew[0] == kP0 + 700 && p.ranges[0].dOld[0] == kP0);
+    // the latency moves again while the fade runs, and stream 1 is bypassed with a move of its own waiting: the running fade
+    // ends with callback 11 of the next call and the new one starts there, in mid-call -- two ranges, the second fading out the
+    // delay the first faded in; the bypassed stream reads at its present latency in both and its fade is not touched
+    peak[0] = 150; peak[1] = 20; bypass[1] = 1;
+    const LatencyFade was = f[1];
+    p = planProcLatency(f, bypass, peak, S, false, kP0, false, 32 * B, B, xTotal);
+    checkRanges(p, S, 32 * B, B, xTotal);
+    CHECK(p.ranges.size() == 2 && p.ranges[0].c1 == 11 && p.ranges[1].c0 == 11 && p.ranges[1].c1 == 32);
+    CHECK(p.ranges[0].xLen[0] == 11 * B && p.ranges[1].xLen[0] == xTotal);
+    CHECK(p.ranges[0].dNew[0] == kP0 + 700 && p.ranges[0].dOld[0] == kP0);
+    CHECK(p.ranges[1].dNew[0] == kP0 + 150 && p.ranges[1].dOld[0] == p.ranges[0].dNew[0]);
+    for (const ProcLatRange& r : p.ranges) CHECK(r.dNew[1] == kP0 + 20 && r.dOld[1] == r.dNew[1] && r.xLen[1] == 0);
+    CHECK(same(was, f[1]) && !f[0].fading() && f[0].latCurrent == (double)(kP0 + 150));
+    // with the direct head the algorithm's share of the delay is 0 while the priming still starts from P0 + irPeakLatency: the
+    // first call fades from there
+    LatencyFade d;
+    const char on = 0;
+    const int pk = 77;
+    p = planProcLatency(&d, &on, &pk, 1, true, kP0, true, 2 * B, B, xTotal);
+    CHECK(p.ranges.size() == 1 && p.ranges[0].dNew[0] == 77 && p.ranges[0].dOld[0] == kP0 + 77 && p.ranges[0].xLen[0] == 2 * B);
+}
+
+// the shape of a mix plan, by hand: B = 64, four streams -- a long ramp, a short one, one at rest, one bypassed with a new mix
+static void mixPlanShape()
+{
+    const int B = 64, n = 10 * B, S = 4;
+    MixRamp r[4];
+    r[0].ramp.totalSteps = 480; r[1].ramp.totalSteps = 100; r[2].ramp.totalSteps = 480; r[3].ramp.totalSteps = 480;
+    const char bypass[4] = { 0, 0, 0, 1 }, dryOnly[4] = { 0, 1, 0, 0 };
+    const double mix[4] = { 0.25, 0.0, 1.0, 0.5 };
+    const MixRamp was[4] = { r[0], r[1], r[2], r[3] };
+    const ProcRest rest = planProcRest(r, bypass, dryOnly, mix, S, n, B);
+    for (int s = 0; s < S; ++s) CHECK(same(was[s], r[s]));
+    CHECK(!rest.rest[0] && !rest.rest[1] && !rest.rest[2] && rest.rest[3] && rest.anyRest && !rest.allRest);     // 1 is dry-only but ramps
+    const ProcMixPlan p = planProcMix(r, bypass, mix, S, n, B);
+    CHECK(p.anyRamp && p.len.size() == 4 && p.len[0] == 512 && p.len[1] == 128 && p.len[2] == 0 && p.len[3] == 0);
+    CHECK(p.rampStride == 512 && p.gains.size() == (size_t)S * 512 * 2);       // the longest prefix
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < p.rampStride; ++i) {
+            const double wet = p.gains[((size_t)s * p.rampStride + i) * 2], dry = p.gains[((size_t)s * p.rampStride + i) * 2 + 1];
+            if (i >= p.len[(size_t)s]) CHECK(wet == 0.0 && dry == 0.0);        // rows of streams that do not ramp, and behind a prefix
+            else CHECK(wet > 0.0 || dry > 0.0);
+        }
+    CHECK(p.gains[(size_t)(479 * 2)] == equalPowerSin(0.25) * 1.0 && p.gains[(size_t)(479 * 2 + 1)] == equalPowerSin(1.0 - 0.25));
+    CHECK(p.gains[(size_t)(480 * 2)] == p.gains[(size_t)(479 * 2)]);           // behind the ramp's end the prefix holds the target
+    CHECK(same(was[2], r[2]) && same(was[3], r[3]) && !r[0].ramp.isSmoothing() && !r[1].ramp.isSmoothing());
+    const ProcMixPlan none = planProcMix(r, bypass, mix, S, n, B);              // nothing ramps: nothing allocated
+    CHECK(!none.anyRamp && none.rampStride == 0 && none.len.empty() && none.gains.empty());
+}
+
+// the stage's arithmetic against the expressions of the engine in front of the move, written out
+static void procArithmetic()
+{
+    const double pi = 3.141592653589793238462643383279502884;
+    for (double x : { 0.0, 0.25, 0.5, 1.0 }) {
+        const double t = x * (pi * 0.5), t2 = t * t;
+        CHECK(equalPowerSin(x) == t * (1.0 + t2 * (-1.0 / 6.0 + t2 * (1.0 / 120.0 + t2 * (-1.0 / 5040.0 + t2 * (1.0 / 362880.0))))));
+    }
+    CHECK(equalPowerSin(0.0) == 0.0 && equalPowerSin(1.0) > 1.0000035 && equalPowerSin(1.0) < 1.0000036);
+    for (double value : { 0.0, 0.001, 0.0011, 0.5, 0.999, 1.0 })
+        for (double mix : { value, (double)(float)value }) {        // the engine hands over the float it was given, widened
+            double g0 = equalPowerSin(mix) * 1.0;
+            double g1 = (mix < 0.999) ? equalPowerSin(1.0 - mix) : 0.0;
+            if (!(mix > 0.001)) { g0 = 0.0; g1 = 1.0; }
+            const MixGains g = staticMixGains(mix);
+            CHECK(g.wet == g0 && g.dry == g1);
+        }
+    CHECK(staticMixGains(0.001).wet == 0.0 && staticMixGains(0.001).dry == 1.0 && staticMixGains(0.0011).wet > 0.0);
+    CHECK(staticMixGains(0.999).dry == 0.0 && staticMixGains(1.0).dry == 0.0 && staticMixGains(0.5).dry == staticMixGains(0.5).wet);
+    CHECK(procDelay(false, 64, 40) == 104 && procDelay(true, 64, 40) == 40 && procDelay(false, 64, -5) == 64);
+    CHECK(procDelay(false, 1 << 20, 0) == 524288 && procDelay(false, 64, 1 << 30) == 64 + 2097152 && procDelay(true, 1 << 20, 1 << 30) == 2097152);
 }
 
 // test_processor_level_dry_only_with_unequal_ramps_fails_before_any_state_moves: B = 512, calls of 4 callbacks; stream 0 is in
@@ -482,12 +596,17 @@ static void unequalRamps()
     CHECK(m[0].r.ramp.remaining == 704 && m[1].r.ramp.remaining == 2752);
     for (auto& s : m) mixCall(s, sh, n, o);
     CHECK(!m[0].r.ramp.isSmoothing() && m[1].r.ramp.remaining == 704);
-    const MixState was[2] = { m[0], m[1] };
+    MixRamp r[2] = { m[0].r, m[1].r };
+    const double mix[2] = { m[0].mix, m[1].mix };
+    const char bypass[2] = { 0, 0 }, dryOnly[2] = { 1, 1 };
     for (int attempt = 0; attempt < 2; ++attempt) {
-        CHECK(!m[0].r.wouldSmooth(m[0].mix, n, sh.B) && m[1].r.wouldSmooth(m[1].mix, n, sh.B));    // dry-only: 0 rests, 1 does not
-        CHECK(same(was[0], m[0]) && same(was[1], m[1]));
+        const ProcRest rest = planProcRest(r, bypass, dryOnly, mix, 2, n, sh.B);
+        CHECK(rest.rest[0] && !rest.rest[1] && rest.anyRest && !rest.allRest);                      // dry-only: 0 rests, 1 does not
+        CHECK(same(m[0].r, r[0]) && same(m[1].r, r[1]));
     }
-    CHECK(m[0].r.beginCall(m[0].mix, n, sh.B) == 0 && m[1].r.beginCall(m[1].mix, n, sh.B) == 1024);
+    const ProcMixPlan p = planProcMix(r, bypass, mix, 2, n, sh.B);
+    CHECK(p.anyRamp && p.len[0] == 0 && p.len[1] == 1024 && p.rampStride == 1024 && p.gains.size() == (size_t)2 * 1024 * 2);
+    for (size_t i = 0; i < (size_t)1024 * 2; ++i) CHECK(p.gains[i] == 0.0);                         // the row of the stream at rest
 }
 
 static void policies()
@@ -545,8 +664,11 @@ int main()
 {
     rampSemantics();
     policies();
+    procArithmetic();
     oneSampleFadeStart();
+    latencyRanges();
     unequalRamps();
+    mixPlanShape();
     splitScripts();
     eqPlanScripts();
     fadeEndValues();

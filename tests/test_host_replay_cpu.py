@@ -3,9 +3,10 @@ reference's LinearRamp, the total-gain ramp, the EQ bypass fade, the mix smoothe
 and double arithmetic, so they are tested here without a GPU: a small host program includes that header alone -- no HIP, not
 the library -- and checks, exactly (== on doubles), the ramp's semantics, that N callbacks give the same outputs and leave the
 same state however they are cut into calls, and that what the engine predicts on a copy of a ramp (which convolver rests in a
-call, where a latency fade starts) is what the replay then decides, with the original untouched.  The EQ's plan of a call
+call) is what the replay then decides, with the original untouched.  The EQ's plan of a call
 (gain segments, bypass classes, band resets, pieces) is the same header's and is checked the same way, for several streams
-at once.  Built with the address and
+at once.  The processor-level stage's plan of a call (who rests, mix prefixes and gain pairs, latency ranges) and its arithmetic
+are driven through the planners engine_proc.cpp itself calls.  Built with the address and
 undefined-behaviour sanitizers and run as a program of its own."""
 import os
 import shutil
