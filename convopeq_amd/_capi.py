@@ -292,6 +292,11 @@ SYMBOLS = {
     "cpq_ir_resample_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
     "cpq_ir_resample_host": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
     "cpq_ir_resample_last_kernel_ms": (C.c_double, []),
+    "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
+    "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
+    "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),
+    "cpq_ir_prepare_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_double, C.c_float, C.c_int32,
+                                         C.POINTER(C.POINTER(IrBuffer)), c_double_p, C.POINTER(IrPrepared)]),
     "cpq_profile_enable": (C.c_int32, [_E, C.c_int32]),
     "cpq_profile_reset": (C.c_int32, [_E]),
     "cpq_profile_read": (C.c_int32, [_E, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -320,6 +325,7 @@ SYMBOLS = {
                                                                                c_double_p, C.c_int32]),
     "cpq_diag_rows": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int64, C.c_int64, c_double_p, C.c_int64, C.c_int64,
                                   c_double_p, _i32p, _i32p, c_double_p, c_double_p, C.c_int32]),
+    "cpq_diag_cfft": (C.c_int32, [c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
     "cpq_diag_eq_chain_status": (C.c_int32, [_E, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "cpq_kernel_name": (C.c_char_p, [C.c_int32]),
     "cpq_scorer_create": (C.c_int32, [C.POINTER(ScorerDesc), C.POINTER(C.c_void_p)]),

@@ -770,6 +770,62 @@ int32_t cpq_diag_score_reduce(int32_t nLearners, int32_t nCand, const int32_t* c
     return d.rc;
 }
 
+// ---------------------------------------------------------------- the complex transforms of minphase_kernels.hip (tests/test_gpu_ir_minphase.py)
+// `rows` transforms of 2^log2n points, natural order in and out, on the path minphase_plan.hpp gives the size: up to the LDS bound
+// the row pass alone (kRowsFwd; kRowsInv with the 1 / N scale), above it columns then rows (forward) or rows then columns
+// (inverse).  The four-step forward leaves X[k1 + N1 k2] at [k1][k2] and the inverse reads that layout; the reordering between it
+// and natural order is done here, on the host.
+int32_t cpq_diag_cfft(const double* re_im, int32_t log2n, int32_t rows, int32_t inverse, double* out)
+{
+    if (!re_im || !out || log2n < 1 || log2n > 23 || rows < 1 || !fits(rows, 2LL << log2n)) return CPQ_ERR_INVALID_ARG;
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    int lg1 = 0, lg2 = 0;
+    cpq::minphaseFactor(log2n, lg1, lg2);
+    const size_t N = (size_t)1 << log2n, N1 = (size_t)1 << lg1, N2 = (size_t)1 << lg2, total = (size_t)rows * N;
+    std::vector<double> hi, lo, host;
+    const std::vector<double> roots = cpq::minphaseStageRoots();
+    cpq::minphaseSplitRoots(log2n, hi, lo);
+    const double* src = re_im;
+    if (lg1 > 0 && inverse) {       // natural order -> [k1][k2]
+        host.resize(2 * total);
+        for (size_t r = 0; r < (size_t)rows; ++r)
+            for (size_t k = 0; k < N; ++k) {
+                const size_t at = r * N + (k & (N1 - 1)) * N2 + (k >> lg1);
+                host[2 * at] = re_im[2 * (r * N + k)];
+                host[2 * at + 1] = re_im[2 * (r * N + k) + 1];
+            }
+        src = host.data();
+    }
+
+    Scope d;
+    const cpq::MinphaseTables t{ c2(d.put(roots.data(), roots.size())), c2(d.put(hi.data(), hi.size())), c2(d.put(lo.data(), lo.size())) };
+    double2* z = c2(d.put(src, 2 * total));
+    if (d.rc == CPQ_OK) {
+        if (lg1 == 0) cpq::launch_cfft_rows(nullptr, inverse ? cpq::kRowsInv : cpq::kRowsFwd, z, nullptr, t, 0, lg2, rows, 1.0 / (double)N);
+        else if (inverse) {
+            cpq::launch_cfft_rows(nullptr, cpq::kRowsInv, z, nullptr, t, lg1, lg2, rows, 1.0);
+            cpq::launch_cfft_cols(nullptr, cpq::kColsInvComplex, z, nullptr, nullptr, nullptr, nullptr, t, lg1, lg2, rows);
+        } else {
+            cpq::launch_cfft_cols(nullptr, cpq::kColsFwdComplex, z, nullptr, nullptr, nullptr, nullptr, t, lg1, lg2, rows);
+            cpq::launch_cfft_rows(nullptr, cpq::kRowsFwd, z, nullptr, t, lg1, lg2, rows, 1.0);
+        }
+        d.launched();
+    }
+    if (lg1 > 0 && !inverse) {      // [k1][k2] -> natural order
+        host.resize(2 * total);
+        d.get(host.data(), reinterpret_cast<const double*>(z), 2 * total);
+        if (d.rc == CPQ_OK)
+            for (size_t r = 0; r < (size_t)rows; ++r)
+                for (size_t k = 0; k < N; ++k) {
+                    const size_t at = r * N + (k & (N1 - 1)) * N2 + (k >> lg1);
+                    out[2 * (r * N + k)] = host[2 * at];
+                    out[2 * (r * N + k) + 1] = host[2 * at + 1];
+                }
+    } else d.get(out, reinterpret_cast<const double*>(z), 2 * total);
+    return d.rc;
+}
+
 // needs the engine: the header of its chained-span launches
 int32_t cpq_diag_eq_chain_status(cpq_engine* e, uint32_t* launches, uint32_t* gaveUp)
 {

@@ -16,6 +16,8 @@
 // Not here: sample-rate conversion, a call of its own (cpq_ir_resample, resample_design.cpp / engine_resample.cpp) -- cpq_ir_prepare
 // refuses an IR at another rate with CPQ_ERR_UNSUPPORTED -- and the mixed phase transform (PhaseMode::AsIs and Minimum only).
 //   * minimum phase                          src/convolver/ConvolverProcessor.ResampleAndFallback.cpp:333-469
+// cpq_ir_prepare is three steps (ir_ingest.hpp) around that transform; cpq_ir_prepare_batch (engine_minphase.cpp) runs the same
+// steps around the device's batched transform.
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "convopeq_mi355x.h"
+#include "ir_ingest.hpp"
 
 namespace {
 
@@ -430,6 +433,96 @@ std::vector<const double*> planes(const cpq_ir_buffer* b)
 
 }  // namespace
 
+namespace cpq {
+
+int irPrepareTrim(const cpq_ir_buffer* loaded, double sample_rate, float target_ir_length_sec, int phase_mode, const cpq_ir_buffer* current_ir,
+                  cpq_ir_prepared* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    out->scale.scale_factor = 1.0;
+    out->scale.frequency_peak_gain = 1.0;
+    if (!validBuffer(loaded) || !(sample_rate > 0.0) || !std::isfinite(sample_rate) || !(target_ir_length_sec > 0.0f))
+        return CPQ_ERR_INVALID_ARG;
+    if (current_ir && !validBuffer(current_ir)) return CPQ_ERR_INVALID_ARG;
+    if (phase_mode != CPQ_PHASE_AS_IS && phase_mode != CPQ_PHASE_MINIMUM)
+        return phase_mode == CPQ_PHASE_MIXED ? CPQ_ERR_UNSUPPORTED : CPQ_ERR_INVALID_ARG;
+    if (loaded->sample_rate > 0.0 && std::fabs(loaded->sample_rate - sample_rate) > 1e-6)
+        return CPQ_ERR_UNSUPPORTED;                               // cpq_ir_resample first
+    const double rate = loaded->sample_rate > 0.0 ? loaded->sample_rate : 0.0;
+
+    // trailing silence, DC blocker, window: on a working copy of the kept part
+    const int kept = trimmedLength(loaded);
+    const int channels = loaded->n_channels;
+    std::vector<double> work;
+    try { work.resize((size_t)channels * (size_t)kept); } catch (const std::bad_alloc&) { return CPQ_ERR_OOM; }
+    for (int ch = 0; ch < channels; ++ch) {
+        double* w = work.data() + (size_t)ch * (size_t)kept;
+        std::memcpy(w, plane(loaded, ch), sizeof(double) * (size_t)kept);
+        if (rate > 0.0) dcBlock(w, kept, rate, 1.0);
+        asymmetricTukey(w, kept);
+    }
+
+    // target length (seconds of the engine rate, capped at 2^21) and the fade-out of the copied part
+    int target = (int)(rate * (double)target_ir_length_sec);
+    target = std::max(1, std::min(target, 2097152));
+    if (!allocBuffer(&out->ir, channels, target, rate)) return CPQ_ERR_OOM;
+    const int copy = std::min(target, kept);
+    const int maxFade = std::max(256, (int)std::round(sample_rate * 0.080));
+    int fade = (int)std::round((double)copy * 0.02);
+    fade = std::max(256, std::min(maxFade, fade));
+    fade = std::max(0, std::min(fade, copy - 1));
+    for (int ch = 0; ch < channels; ++ch) {
+        double* d = plane(&out->ir, ch);
+        std::memcpy(d, work.data() + (size_t)ch * (size_t)kept, sizeof(double) * (size_t)copy);
+        if (fade > 0) {
+            double g = 1.0;
+            const double inc = (0.0 - 1.0) / (float)fade;
+            for (int i = copy - fade; i < copy; ++i) { d[i] *= g; g += inc; }
+        }
+    }
+    return CPQ_OK;
+}
+
+bool irPrepareAccept(const cpq_ir_buffer* converted, cpq_ir_buffer* ir)
+{
+    const size_t count = (size_t)ir->n_channels * (size_t)ir->n_samples;
+    double peak = 0.0;
+    bool finite = true;
+    for (size_t i = 0; i < count; ++i) {
+        finite = finite && std::isfinite(converted->data[i]);
+        peak = std::max(peak, std::fabs(converted->data[i]));
+    }
+    if (!(finite && peak > 1.0e-12)) return false;
+    std::memcpy(ir->data, converted->data, sizeof(double) * count);
+    return true;
+}
+
+int irPrepareFinish(const cpq_ir_buffer* current_ir, double current_scale, cpq_ir_prepared* out)
+{
+    const int channels = out->ir.n_channels, target = out->ir.n_samples;
+    const auto p = planes(&out->ir);
+    const auto cur = current_ir ? planes(current_ir) : std::vector<const double*>();
+    const int32_t rc = cpq_ir_compute_scale_factor(p.data(), channels, target, current_ir ? cur.data() : nullptr,
+                                                   current_ir ? current_ir->n_channels : 0,
+                                                   current_ir ? current_ir->n_samples : 0, current_scale, &out->scale);
+    if (rc != CPQ_OK) { cpq_ir_buffer_free(&out->ir); return rc; }
+    if (!out->scale.has_scale_factor) out->scale.scale_factor = 1.0;
+    out->ir_peak_latency = peakLatency(p.data(), channels, target);
+    return CPQ_OK;
+}
+
+const char* irPrepareWhy(int rc)
+{
+    switch (rc) {
+    case CPQ_ERR_INVALID_ARG: return "an invalid buffer, rate, length or phase mode";
+    case CPQ_ERR_UNSUPPORTED: return "the mixed phase mode, or an IR at another rate (cpq_ir_resample first)";
+    case CPQ_ERR_OOM: return "host allocation failed";
+    default: return "failed";
+    }
+}
+
+}  // namespace cpq
+
 extern "C" {
 
 void cpq_ir_buffer_free(cpq_ir_buffer* b)
@@ -579,76 +672,19 @@ int32_t cpq_ir_prepare(const cpq_ir_buffer* loaded, double sample_rate, float ta
                        const cpq_ir_buffer* current_ir, double current_scale, cpq_ir_prepared* out)
 {
     if (!out) return CPQ_ERR_INVALID_ARG;
-    std::memset(out, 0, sizeof(*out));
-    out->scale.scale_factor = 1.0;
-    out->scale.frequency_peak_gain = 1.0;
-    if (!validBuffer(loaded) || !(sample_rate > 0.0) || !std::isfinite(sample_rate) || !(target_ir_length_sec > 0.0f))
-        return CPQ_ERR_INVALID_ARG;
-    if (current_ir && !validBuffer(current_ir)) return CPQ_ERR_INVALID_ARG;
-    if (phase_mode != CPQ_PHASE_AS_IS && phase_mode != CPQ_PHASE_MINIMUM)
-        return phase_mode == CPQ_PHASE_MIXED ? CPQ_ERR_UNSUPPORTED : CPQ_ERR_INVALID_ARG;
-    if (loaded->sample_rate > 0.0 && std::fabs(loaded->sample_rate - sample_rate) > 1e-6)
-        return CPQ_ERR_UNSUPPORTED;                               // cpq_ir_resample first
-    const double rate = loaded->sample_rate > 0.0 ? loaded->sample_rate : 0.0;
-
-    // trailing silence, DC blocker, window: on a working copy of the kept part
-    const int kept = trimmedLength(loaded);
-    const int channels = loaded->n_channels;
-    std::vector<double> work;
-    try { work.resize((size_t)channels * (size_t)kept); } catch (const std::bad_alloc&) { return CPQ_ERR_OOM; }
-    for (int ch = 0; ch < channels; ++ch) {
-        double* w = work.data() + (size_t)ch * (size_t)kept;
-        std::memcpy(w, plane(loaded, ch), sizeof(double) * (size_t)kept);
-        if (rate > 0.0) dcBlock(w, kept, rate, 1.0);
-        asymmetricTukey(w, kept);
-    }
-
-    // target length (seconds of the engine rate, capped at 2^21) and the fade-out of the copied part
-    int target = (int)(rate * (double)target_ir_length_sec);
-    target = std::max(1, std::min(target, 2097152));
-    if (!allocBuffer(&out->ir, channels, target, rate)) return CPQ_ERR_OOM;
-    const int copy = std::min(target, kept);
-    const int maxFade = std::max(256, (int)std::round(sample_rate * 0.080));
-    int fade = (int)std::round((double)copy * 0.02);
-    fade = std::max(256, std::min(maxFade, fade));
-    fade = std::max(0, std::min(fade, copy - 1));
-    for (int ch = 0; ch < channels; ++ch) {
-        double* d = plane(&out->ir, ch);
-        std::memcpy(d, work.data() + (size_t)ch * (size_t)kept, sizeof(double) * (size_t)copy);
-        if (fade > 0) {
-            double g = 1.0;
-            const double inc = (0.0 - 1.0) / (float)fade;
-            for (int i = copy - fade; i < copy; ++i) { d[i] *= g; g += inc; }
-        }
-    }
-
+    const int32_t rc = cpq::irPrepareTrim(loaded, sample_rate, target_ir_length_sec, phase_mode, current_ir, out);
+    if (rc != CPQ_OK) return rc;
     if (phase_mode == CPQ_PHASE_MINIMUM) {
-        // doTransformStep: the converted IR replaces the trimmed one only when it validates -- finite, peak above 1e-12
-        // (LoaderThread.cpp:652-680); a conversion the reference gives up on leaves the IR as it is
+        // doTransformStep: a conversion the reference gives up on leaves the IR as it is
         cpq_ir_buffer mp;
         const int32_t rcMp = cpq_ir_convert_to_minimum_phase(&out->ir, &mp);
         if (rcMp == CPQ_ERR_OOM) { cpq_ir_buffer_free(&out->ir); return rcMp; }
         if (rcMp == CPQ_OK) {
-            double peak = 0.0;
-            bool finite = true;
-            for (size_t i = 0; i < (size_t)channels * (size_t)target; ++i) {
-                finite = finite && std::isfinite(mp.data[i]);
-                peak = std::max(peak, std::fabs(mp.data[i]));
-            }
-            if (finite && peak > 1.0e-12) std::memcpy(out->ir.data, mp.data, sizeof(double) * (size_t)channels * (size_t)target);
+            cpq::irPrepareAccept(&mp, &out->ir);
             cpq_ir_buffer_free(&mp);
         }
     }
-
-    const auto p = planes(&out->ir);
-    const auto cur = current_ir ? planes(current_ir) : std::vector<const double*>();
-    const int32_t rc = cpq_ir_compute_scale_factor(p.data(), channels, target, current_ir ? cur.data() : nullptr,
-                                                   current_ir ? current_ir->n_channels : 0,
-                                                   current_ir ? current_ir->n_samples : 0, current_scale, &out->scale);
-    if (rc != CPQ_OK) { cpq_ir_buffer_free(&out->ir); return rc; }
-    if (!out->scale.has_scale_factor) out->scale.scale_factor = 1.0;
-    out->ir_peak_latency = peakLatency(p.data(), channels, target);
-    return CPQ_OK;
+    return cpq::irPrepareFinish(current_ir, current_scale, out);
 }
 
 void cpq_ir_prepared_free(cpq_ir_prepared* p)

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "host_design.hpp"
+#include "minphase_plan.hpp"
 
 namespace cpq {
 
@@ -344,5 +345,20 @@ int resampleTile(int L, int M);
 int resampleSpan(int L, int M, int tile);   // input samples the first taps of a tile's outputs spread over
 void launch_ir_resample(hipStream_t stream, const double* taps, int L, int M, int T, const double* x, double* y, const ResampleRow* rows,
                         const ResampleTile* tiles, int nTiles);
+
+// ---- minimum-phase conversion of IR rows (minphase_kernels.hip), launched as minphase_plan.hpp lists.  x and y hold the rows of a
+// chunk back to back: row r reads x[off ... off + n) and writes y[off ... off + n); z is its complex scratch [rows][N] (four-step
+// path only); flags[r] becomes non-zero where the row holds a non-finite value after the exponential or in its output.  Tables:
+// roots = the 4096th roots (minphaseStageRoots), hi / lo = the two levels of the N-th roots (minphaseSplitRoots).  Nothing here
+// checks an index: the tables and grids are engine_minphase.cpp's and engine_diag.cpp's, built from validated lengths.
+struct MinphaseRow { long long off; int n, pad; };
+struct MinphaseTables { const double2 *roots, *hi, *lo; };
+void launch_minphase_small(hipStream_t stream, const double* x, double* y, const MinphaseRow* rows, int* flags, MinphaseTables t,
+                           int log2n, long long nRows);
+void launch_cfft_cols(hipStream_t stream, int op, double2* z, const double* x, double* y, const MinphaseRow* rows, int* flags,
+                      MinphaseTables t, int log2n1, int log2n2, long long nRows);
+// scale multiplies what kRowsInv stores (1 / N when the row pass is the whole transform, log2n1 == 0)
+void launch_cfft_rows(hipStream_t stream, int op, double2* z, int* flags, MinphaseTables t, int log2n1, int log2n2, long long nRows,
+                      double scale);
 
 }  // namespace cpq

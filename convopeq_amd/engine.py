@@ -258,6 +258,65 @@ def ir_resample_batch(irs, target_rate, phase=K.CPQ_RESAMPLE_LINEAR_PHASE):
     return [_take_ir(outs[i]) for i in range(len(pairs))]
 
 
+def _ir_buffer_list(irs, rate=48000.0):
+    """irs: arrays [channels][samples], or (array, rate) pairs.  (what must stay alive, the pointer array)"""
+    pairs = [_ir_buffer(*(ir if isinstance(ir, tuple) else (ir, rate))) for ir in irs]
+    bufs = (K.IrBuffer * len(pairs))(*[b for _, b in pairs])
+    ptrs = (C.POINTER(K.IrBuffer) * len(pairs))(*[C.pointer(bufs[i]) for i in range(len(pairs))])
+    return (pairs, bufs), ptrs
+
+
+def ir_minimum_phase_batch(irs, workspace_bytes=0):
+    """cpq_ir_minimum_phase_batch on the device: irs a list of arrays [channels][samples].  (list of arrays, None where the IR was
+    refused; list of statuses)."""
+    lib = K.load()
+    keep, ptrs = _ir_buffer_list(irs)
+    n = len(irs)
+    outs = (K.IrBuffer * n)()
+    status = (C.c_int32 * n)()
+    rc = lib.cpq_ir_minimum_phase_batch(ptrs, n, int(workspace_bytes), outs, status)
+    if rc != 0:
+        raise CpqError(rc, lib.cpq_last_error(None).decode())
+    return [_take_ir(outs[i]) if status[i] == 0 else None for i in range(n)], [int(v) for v in status]
+
+
+def ir_minimum_phase(ir, rate=48000.0):
+    """cpq_ir_minimum_phase: one IR [channels][samples] on the device; CpqError(CPQ_ERR_UNSUPPORTED) where the reference gives up."""
+    lib = K.load()
+    keep, b = _ir_buffer(ir, rate)
+    out = K.IrBuffer()
+    rc = lib.cpq_ir_minimum_phase(C.byref(b), C.byref(out))
+    if rc != 0:
+        raise CpqError(rc, lib.cpq_last_error(None).decode())
+    return _take_ir(out)
+
+
+def ir_prepare_batch(irs, sample_rate, target_ir_length_sec=1.0, current_irs=None, current_scales=None, phase_mode=0):
+    """cpq_ir_prepare_batch: irs a list of (ir [channels][samples], rate); current_irs None or a list with None entries;
+    current_scales None or a list.  A list of ir_prepare's dicts."""
+    lib = K.load()
+    n = len(irs)
+    keep, ptrs = _ir_buffer_list(irs)
+    cur_ptrs = None
+    if current_irs is not None:
+        cur = [None if c is None else _ir_buffer(c, sample_rate) for c in current_irs]
+        cur_ptrs = (C.POINTER(K.IrBuffer) * n)(*[C.POINTER(K.IrBuffer)() if c is None else C.pointer(c[1]) for c in cur])
+    scales = None if current_scales is None else (C.c_double * n)(*[float(v) for v in current_scales])
+    outs = (K.IrPrepared * n)()
+    rc = lib.cpq_ir_prepare_batch(ptrs, n, float(sample_rate), float(target_ir_length_sec), int(phase_mode), cur_ptrs, scales, outs)
+    if rc != 0:
+        raise CpqError(rc, lib.cpq_last_error(None).decode())
+    res = []
+    for i in range(n):
+        o = outs[i]
+        try:
+            data = np.ctypeslib.as_array(o.ir.data, shape=(o.ir.n_channels, o.ir.n_samples)).copy()
+            res.append({"ir": data, "sample_rate": o.ir.sample_rate, "scale": _scale_dict(o.scale), "ir_peak_latency": o.ir_peak_latency})
+        finally:
+            lib.cpq_ir_prepared_free(C.byref(o))
+    return res
+
+
 def ir_compute_scale_factor(ir, current_ir=None, current_scale=1.0):
     a, pa = _planes(ir)
     cur_ptrs, cc, cn = None, 0, 0

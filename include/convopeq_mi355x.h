@@ -560,6 +560,44 @@ double  cpq_ir_resample_last_kernel_ms(void);
 /* the same table in the same summation order on the host's threads (at most 16): what the device is checked against; no GPU */
 int32_t cpq_ir_resample_host(const cpq_ir_buffer* in, double target_rate, int32_t phase, cpq_ir_buffer* out);
 
+/* ---------------------------------------------------------------- minimum-phase conversion on the device */
+/* cpq_ir_convert_to_minimum_phase for a whole IR library: convertToMinimumPhase (ResampleAndFallback.cpp:333-469) per row (a row
+ * is one channel of one IR of n samples), rows of one FFT size N = nextPow2(4 n) batched into one sequence of launches:
+ *     zero-pad to N -> FFT -> ln max(|X|, 1e-300) -> IFFT / N -> fold (bin 0 and N / 2 real, 1 ... N / 2 - 1 real * 2, rest 0)
+ *     -> FFT -> clamp re and im to +-50, exp(re) (cos im, sin im) -> IFFT / N -> real part of the first n, |v| < 1e-18 -> 0
+ * in fp64.  N <= 4096 stays in LDS from the samples in to the samples out; above, N = N1 N2 runs as column and row passes over a
+ * complex scratch row.  The FFTs are not the host path's, so the result agrees with
+ * cpq_ir_convert_to_minimum_phase to rounding, not bit for bit; an IR's result does not depend on what else is in the batch or
+ * on workspace_bytes, bit for bit.
+ *
+ * Refused before anything is allocated (CPQ_ERR_INVALID_ARG): a null argument, n < 0, a buffer without channels, samples or data,
+ * workspace_bytes < 0, workspace_bytes below what one row needs (cpq_last_error(NULL) names the need).  Per IR, in status[i]:
+ * CPQ_ERR_UNSUPPORTED where the reference gives up -- 4 n above 8388608 (decided on the host; the other IRs still run), or a
+ * value that is not finite after the exponential or in the output of one of its rows -- and out[i] is zeroed; else CPQ_OK and
+ * out[i] is the library's (cpq_ir_buffer_free).  The call returns CPQ_OK when it ran, CPQ_ERR_NO_DEVICE without a gfx950 device
+ * when a row needs one (no quiet fall-back: the host path is a call of its own), CPQ_ERR_OOM / CPQ_ERR_DEVICE otherwise; on an
+ * error every out[i] is zeroed.
+ *
+ * workspace_bytes caps the device scratch of the call: per row 16 n + 32 bytes, plus 16 N above N = 4096; the rows of one FFT size
+ * run in as many chunks as the cap needs.  0: 2 GiB.  The twiddle tables (at most 160 KB) are not counted. */
+#define CPQ_HAS_IR_MINPHASE_DEVICE 1
+int32_t cpq_ir_minimum_phase_batch(const cpq_ir_buffer* const* in, int32_t n, int64_t workspace_bytes, cpq_ir_buffer* out /* [n] */,
+                                   int32_t* status /* [n] */);
+/* a batch of one with the default workspace; returns status[0] */
+int32_t cpq_ir_minimum_phase(const cpq_ir_buffer* in, cpq_ir_buffer* out);
+/* milliseconds the kernel launches of this thread's last cpq_ir_minimum_phase* call took, from device events; negative when that
+ * call launched nothing */
+double  cpq_ir_minimum_phase_last_kernel_ms(void);
+/* cpq_ir_prepare for n IRs: trim, DC blocker, window, target length per IR on the host, then with CPQ_PHASE_MINIMUM one
+ * cpq_ir_minimum_phase_batch over all of them (a conversion that is refused or does not validate leaves that IR as trimmed, as
+ * the reference does), then scale factor and peak latency per IR.  current_ir: NULL or [n] with NULL entries allowed;
+ * current_scale: NULL (1.0) or [n].  With CPQ_PHASE_AS_IS no device is needed and out[i] is cpq_ir_prepare's result bit for bit.
+ * CPQ_PHASE_MIXED is CPQ_ERR_UNSUPPORTED.  All or nothing: on an error every out[i] is zeroed and cpq_last_error(NULL) names the
+ * IR ("IR i"). */
+int32_t cpq_ir_prepare_batch(const cpq_ir_buffer* const* loaded, int32_t n, double sample_rate, float target_ir_length_sec,
+                             int32_t phase_mode, const cpq_ir_buffer* const* current_ir /* NULL or [n], entries may be NULL */,
+                             const double* current_scale /* NULL or [n] */, cpq_ir_prepared* out /* [n] */);
+
 /* ---------------------------------------------------------------- metering */
 /* The two meters DSPCore runs on the final block of every callback (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:
  * 695-701): LoudnessMeter::processBlock (src/LoudnessMeter.{h,cpp}; ITU-R BS.1770 K-weighting, mean square and peak per
@@ -1103,6 +1141,13 @@ int32_t cpq_diag_score_lattice(int32_t bit_depth, int32_t n_src, const double* s
                                const uint64_t* rng);
 int32_t cpq_diag_score_reduce(int32_t n_learners, int32_t n_cand, const int32_t* counts, const int32_t* state,
                               const double* blended, const double* weights, double* scores);
+
+/* The complex fp64 transforms of the minimum-phase conversion alone (minphase_kernels.hip): `rows` transforms of 2^log2n points,
+ * re_im and out [rows][2^log2n][2], natural order in and out, on the path the size selects (up to 4096 points the LDS transform,
+ * above it the column and row passes); inverse != 0: the inverse transform with its 1 / N.  The four-step path keeps its spectra
+ * as [k1][k2] on the device; the reordering to and from natural order is host work of this entry.
+ * Refused unless: 1 <= log2n <= 23, rows >= 1, rows * 2^(log2n + 1) <= 2^28. */
+int32_t cpq_diag_cfft(const double* re_im, int32_t log2n, int32_t rows, int32_t inverse, double* out);
 
 #ifdef __cplusplus
 }
