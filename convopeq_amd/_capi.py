@@ -42,6 +42,7 @@ CPQ_PHASE_MINIMUM = 2
 CPQ_RESAMPLE_LINEAR_PHASE = 0
 CPQ_RESAMPLE_MINIMUM_PHASE = 1
 CPQ_RESAMPLE_MAX_FACTOR = 1280
+CPQ_SRC_HOST = 1
 CPQ_OS_IIR = 0
 CPQ_OS_LINEAR_PHASE = 1
 CPQ_METER_LOUDNESS = 1
@@ -140,6 +141,11 @@ class IrPrepared(C.Structure):
 class ResampleInfo(C.Structure):
     _fields_ = [("l", C.c_int32), ("m", C.c_int32), ("taps", C.c_int32), ("reserved", C.c_int32), ("group_delay", C.c_double),
                 ("cutoff", C.c_double), ("attenuation_db", C.c_double)]
+
+
+class SrcDesc(C.Structure):
+    _fields_ = [("n_channels", C.c_int32), ("in_rate", C.c_double), ("out_rate", C.c_double), ("max_in", C.c_int32), ("phase", C.c_int32),
+                ("flags", C.c_uint32), ("start_period", C.c_int64)]
 
 
 class OsStageInfo(C.Structure):
@@ -292,6 +298,14 @@ SYMBOLS = {
     "cpq_ir_resample_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
     "cpq_ir_resample_host": (C.c_int32, [C.POINTER(IrBuffer), C.c_double, C.c_int32, C.POINTER(IrBuffer)]),
     "cpq_ir_resample_last_kernel_ms": (C.c_double, []),
+    "cpq_src_create": (C.c_int32, [C.POINTER(SrcDesc), C.POINTER(C.c_void_p)]),
+    "cpq_src_destroy": (None, [C.c_void_p]),
+    "cpq_src_last_error": (C.c_char_p, [C.c_void_p]),
+    "cpq_src_reset": (C.c_int32, [C.c_void_p]),
+    "cpq_src_latency": (C.c_int32, [C.c_void_p]),
+    "cpq_src_out_count": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "cpq_src_max_out": (C.c_int32, [C.c_void_p]),
+    "cpq_src_process": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _i32p]),
     "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
     "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
     "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),

@@ -560,6 +560,58 @@ double  cpq_ir_resample_last_kernel_ms(void);
 /* the same table in the same summation order on the host's threads (at most 16): what the device is checked against; no GPU */
 int32_t cpq_ir_resample_host(const cpq_ir_buffer* in, double target_rate, int32_t phase, cpq_ir_buffer* out);
 
+/* ---------------------------------------------------------------- streaming sample-rate conversion of audio */
+/* cpq_src: the filter of cpq_resample_design applied to audio, call by call, for n_channels planar fp64 rows at once; an object of
+ * its own beside cpq_engine (an engine runs at one rate: sources at another rate pass through a cpq_src in front of it).  The
+ * object keeps the history between calls.  Built: the object that computes on the host (flags & CPQ_SRC_HOST), the counterpart of
+ * cpq_ir_resample_host.  Not built: the object that computes on the device; cpq_src_create without CPQ_SRC_HOST is
+ * CPQ_ERR_UNSUPPORTED, never the host in its place.
+ *
+ * Let x be everything a stream received since creation, cpq_src_reset or the last flush, zero before index 0 and, after a flush,
+ * zero from its end on.  Output j is the sum stated above for cpq_ir_resample, in that order and with that fma.  A call emits
+ * every j, in order, whose newest input floor(j M / L) + T / 2 has been received; with flush != 0 it also emits the rest, up to
+ * ceil(n_total L / M) outputs in all, and leaves the object as new.  So the concatenated output of a stream equals the one-shot
+ * conversion of the concatenated input bit for bit, for every split into calls and every channel count; the latency is T / 2
+ * input samples.  Rates no more than 1e-6 apart: a copy, latency 0.
+ *
+ * start_period = p >= 0 starts the stream at output p L and input p M, as if p whole periods of silence had passed (for
+ * resuming); by the filter's periodicity the outputs are those of p = 0 bit for bit.
+ *
+ * Rows are [channel][stride] doubles; n_in may be 0 and *n_out may come back 0.  Refused before any state changes,
+ * CPQ_ERR_INVALID_ARG: a null pointer (in may be NULL when n_in == 0, out when nothing is written), n_channels outside 1 ... 65535,
+ * max_in < 1, start_period outside 0 ... 2^50, an unknown phase or flag, n_in < 0 or above max_in, a stride shorter than its row,
+ * out_capacity below cpq_src_out_count, rows of in and out that overlap; CPQ_ERR_UNSUPPORTED: what cpq_resample_design refuses,
+ * CPQ_RESAMPLE_MINIMUM_PHASE, a max_in whose cpq_src_max_out exceeds 2^30, and a device object.  The reason is in
+ * cpq_src_last_error (with NULL: of a failed create). */
+/* The host object only.  CPQ_HAS_STREAM_RESAMPLING is not defined: that name is kept for a library that also has the device object
+ * and its cpq_src_process_device, cpq_src_set_stream and cpq_src_last_kernel_ms. */
+#define CPQ_HAS_STREAM_RESAMPLING_HOST 1
+#define CPQ_SRC_HOST 1u
+typedef struct cpq_src cpq_src;
+typedef struct {
+    int32_t  n_channels;
+    double   in_rate, out_rate;
+    int32_t  max_in;                /* most samples per channel of one call */
+    int32_t  phase;                 /* cpq_resample_phase */
+    uint32_t flags;                 /* CPQ_SRC_* */
+    int64_t  start_period;
+} cpq_src_desc;
+int32_t cpq_src_create(const cpq_src_desc* desc, cpq_src** out);
+void    cpq_src_destroy(cpq_src* s);
+const char* cpq_src_last_error(const cpq_src* s);
+/* forgets the stream: the object is as new */
+int32_t cpq_src_reset(cpq_src* s);
+/* T / 2 in input samples; 0 for a copy; negative: s is NULL */
+int32_t cpq_src_latency(const cpq_src* s);
+/* samples per channel the next call of n_in samples will write: host arithmetic only.  CPQ_ERR_INVALID_ARG (negative) for a
+ * NULL object or n_in outside 0 ... max_in. */
+int32_t cpq_src_out_count(const cpq_src* s, int32_t n_in, int32_t flush);
+/* the bound of cpq_src_out_count for any call: a call of max_in samples with flush */
+int32_t cpq_src_max_out(const cpq_src* s);
+/* host rows in and out */
+int32_t cpq_src_process(cpq_src* s, const double* in, int64_t in_stride, int32_t n_in, double* out, int64_t out_stride,
+                        int32_t out_capacity, int32_t flush, int32_t* n_out);
+
 /* ---------------------------------------------------------------- minimum-phase conversion on the device */
 /* cpq_ir_convert_to_minimum_phase for a whole IR library: convertToMinimumPhase (ResampleAndFallback.cpp:333-469) per row (a row
  * is one channel of one IR of n samples), rows of one FFT size N = nextPow2(4 n) batched into one sequence of launches:

@@ -452,4 +452,40 @@ private:
     int status_ = CPQ_OK;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// Streaming sample-rate conversion of nChannels planar rows (cpq_src): one object per source rate in front of an Engine.  Only the
+// object that computes on the host is built (CPQ_SRC_HOST).
+class StreamResampler {
+public:
+    explicit StreamResampler(const cpq_src_desc& desc) { status_ = cpq_src_create(&desc, &s_); }
+    // flags: CPQ_SRC_HOST for the object that computes on the host; 0 asks for the device object (CPQ_ERR_UNSUPPORTED: not built)
+    StreamResampler(int nChannels, double inRate, double outRate, int maxIn, uint32_t flags)
+    {
+        const cpq_src_desc d{ nChannels, inRate, outRate, maxIn, CPQ_RESAMPLE_LINEAR_PHASE, flags, 0 };
+        status_ = cpq_src_create(&d, &s_);
+    }
+    ~StreamResampler() { cpq_src_destroy(s_); }
+    StreamResampler(const StreamResampler&) = delete;
+    StreamResampler& operator=(const StreamResampler&) = delete;
+    bool valid() const noexcept { return s_ != nullptr; }
+    int latency() const noexcept { return cpq_src_latency(s_); }
+    int outCount(int numSamples, bool flush = false) const noexcept { return cpq_src_out_count(s_, numSamples, flush ? 1 : 0); }
+    int maxOut() const noexcept { return cpq_src_max_out(s_); }
+    bool reset() { return (status_ = cpq_src_reset(s_)) == CPQ_OK; }
+    // rows [channel][stride]; returns the samples written per channel, or -1 with lastStatus() set
+    int process(const double* in, int64_t inStride, int numSamples, double* out, int64_t outStride, int outCapacity, bool flush = false)
+    {
+        int32_t n = 0;
+        status_ = cpq_src_process(s_, in, inStride, numSamples, out, outStride, outCapacity, flush ? 1 : 0, &n);
+        return status_ == CPQ_OK ? n : -1;
+    }
+    cpq_src* get() const noexcept { return s_; }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return cpq_src_last_error(s_); }
+
+private:
+    cpq_src* s_ = nullptr;
+    int status_ = CPQ_OK;
+};
+
 }  // namespace cpq
