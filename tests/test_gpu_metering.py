@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import meter_model as M
+from meter_edge_inputs import check_loudness, check_true_peak, signals
 
 pytestmark = pytest.mark.gpu
 
@@ -26,58 +27,6 @@ LOUD, PEAK = 1, 2
 def amd():
     import convopeq_amd
     return convopeq_amd
-
-
-def signals(n, seed=11):
-    """four stereo streams: noise, a multi-sine, noise with silent stretches, noise at -120 dB"""
-    rng = np.random.default_rng(seed)
-    t = np.arange(n)
-    x = np.empty((8, n))
-    x[0:2] = 0.25 * rng.standard_normal((2, n))
-    for ch in range(2):
-        x[2 + ch] = sum(a * np.sin(2 * np.pi * f * t + p + ch) for a, f, p in ((0.4, 0.0021, 0.3), (0.3, 0.0517, 1.1), (0.2, 0.2203, 2.0)))
-    x[4:6] = 0.5 * rng.standard_normal((2, n))
-    gate = (np.arange(n) // 700) % 3 == 1
-    x[4:6, gate] = 0.0
-    x[6:8] = 1.0e-6 * rng.standard_normal((2, n))
-    return x
-
-
-def loud_model(x, cb, rate, calls=None):
-    """records of the model in long double and in fp64: (ms [K, S], pk [K, S]) each; calls = the call lengths (ragged ends)"""
-    S = x.shape[0] // 2
-    out = []
-    for dt in (np.longdouble, np.float64):
-        m = M.LoudnessMeter(rate, S, dt)
-        recs, o = [], 0
-        for n in (calls or [x.shape[1]]):
-            recs += m.process(x[:, o:o + n], cb)
-            o += n
-        out.append((np.stack([r[0] for r in recs]), np.stack([r[1] for r in recs])))
-        assert [r[2] for r in recs] == list(range(len(recs)))
-    return out
-
-
-def check_loudness(rec, x, cb, rate, calls=None, label="", tail=None):
-    """rec against the model on x; tail: rec holds only the last `tail` records of the run.  Returns the distances the bars are
-    made of: {field: [per stream] largest |fp64 model - long-double model|}."""
-    (ms_l, pk_l), (ms_d, pk_d) = loud_model(x, cb, rate, calls)
-    if tail is not None:
-        ms_l, pk_l, ms_d, pk_d = ms_l[-tail:], pk_l[-tail:], ms_d[-tail:], pk_d[-tail:]
-    K = ms_l.shape[0]
-    assert rec.shape[1] == K, (rec.shape, K)
-    dists = {"mean_square": [], "peak_linear": []}
-    for s in range(rec.shape[0]):
-        for name, ref, f64 in (("mean_square", ms_l[:, s], ms_d[:, s]), ("peak_linear", pk_l[:, s], pk_d[:, s])):
-            dist = float(np.max(np.abs(f64.astype(np.longdouble) - ref)))
-            err = float(np.max(np.abs(rec[name][s].astype(np.longdouble) - ref)))
-            scale = float(np.max(np.abs(ref)))
-            print(f"{label} stream {s} {name}: fp64 model vs long double {dist:.3e}, kernel vs long double {err:.3e} "
-                  f"(bar {8 * dist:.3e}, largest value {scale:.3e})")
-            assert err <= 8 * dist, (s, name, err, dist)
-            dists[name].append(dist)
-    assert np.array_equal(rec["block_index"][0], np.arange(K, dtype=np.uint64) + rec["block_index"][0][0])
-    return dists
 
 
 def meter_engine(amd, S, B, T, rate=48000.0, flags=LOUD | PEAK, any_calls=False, factor=1):
@@ -169,22 +118,6 @@ def tp_signals(n, cb, seed=21):
             x[4, (k + 1) * cb - back:(k + 1) * cb + (40 if k % 2 else 0)] = 0.8
     x[5] = 0.1 * x[4]
     return x
-
-
-def check_true_peak(rec, x, cb, label=""):
-    K = x.shape[1] // cb
-    assert rec.shape[1] == K
-    worst = 0.0
-    for s in range(rec.shape[0]):
-        det = M.TruePeakDetector()
-        for k in range(K):
-            tp, _, bound = det.process_block(x[2 * s:2 * s + 2, k * cb:(k + 1) * cb])
-            err = abs(float(rec["true_peak"][s, k]) - tp)
-            assert err <= bound, (s, k, err, bound, tp)
-            worst = max(worst, err / bound if bound else 0.0)
-        # the hold is the replay of the peaks the engine returned, to the bit
-        assert np.array_equal(rec["true_peak_hold"][s], np.array(M.hold_replay(rec["true_peak"][s].tolist()))), s
-    print(f"{label}: worst |true_peak - model| / bound = {worst:.3f}")
 
 
 @pytest.mark.parametrize("B,T", ((512, 4), (64, 8), (2048, 2)))
