@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import out_model as M
+from out_edge_inputs import scan_dc, scan_section, scan_tables  # noqa: F401  (the kernel's fast path, lane by lane)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -114,63 +115,6 @@ def test_splitting_the_signal_changes_nothing(flags):
 
 
 # --------------------------------------------------------------------------------------------------------- the DC scan
-def scan_tables(alpha):
-    """outSectionTable: a = 1 - alpha and its powers in long double, rounded once"""
-    a = LD(1) - LD(alpha)
-    ac = LD(1)
-    for _ in range(8):
-        ac = ac * a
-    pow2, p = [], ac
-    for _ in range(7):
-        pow2.append(float(p))
-        p = p * p
-    lane, q = [], LD(1)
-    for _ in range(64):
-        lane.append(float(q))
-        q = q * ac
-    return pow2, np.array(lane)
-
-
-def scan_section(u, alpha, carry, tab):
-    """one section over a span: u [256, 8]; returns (u - lowpass, the state after every sample) as the lanes compute them"""
-    pow2, lane_pow = tab
-    z = np.zeros(256)
-    for i in range(8):
-        z = z + alpha * (u[:, i] - z)
-    ln, wv = np.arange(256) & 63, np.arange(256) >> 6
-    for k in range(6):
-        d = 1 << k
-        z = np.where(ln >= d, z + pow2[k] * np.roll(z, d), z)
-    inc = [carry]
-    for w in range(3):
-        inc.append(pow2[6] * inc[-1] + z[64 * w + 63])
-    e = np.where(ln == 0, 0.0, np.roll(z, 1))
-    s = e + lane_pow[ln] * np.array([inc[w] for w in wv])
-    y, states = np.empty_like(u), np.empty_like(u)
-    for i in range(8):
-        s = s + alpha * (u[:, i] - s)
-        y[:, i] = u[:, i] - s
-        states[:, i] = s
-    return y, states
-
-
-def scan_dc(x, alpha, state=(0.0, 0.0)):
-    """k_out_pre's fast path on one channel: spans of 2048 samples (the last one padded with zeros), the states after a span's
-    last sample carried to the next span and out of the call"""
-    t0, t1 = scan_tables(alpha[0]), scan_tables(alpha[1])
-    c0, c1 = state
-    out = []
-    for s0 in range(0, len(x), 2048):
-        seg = x[s0:s0 + 2048]
-        flat = np.zeros(2048)
-        flat[:len(seg)] = seg
-        y, st0 = scan_section(flat.reshape(256, 8), alpha[0], c0, t0)
-        y, st1 = scan_section(y, alpha[1], c1, t1)
-        out.append(y.reshape(-1)[:len(seg)])
-        c0, c1 = st0.reshape(-1)[len(seg) - 1], st1.reshape(-1)[len(seg) - 1]
-    return np.concatenate(out), (c0, c1)
-
-
 def dc_signals(n, seed=3):
     rng = np.random.default_rng(seed)
     t = np.arange(n)
