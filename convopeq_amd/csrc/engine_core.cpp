@@ -318,7 +318,7 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
                     "partition_size %d must be a power of two in [block_size, 4096] dividing block_size*max_blocks_per_call", p);
     }
     e->tMax = (int)(((int64_t)e->maxCall + e->P - 1) / e->P);     // partitions per call (rounded up for ragged calls)
-    e->macTile = d->mac_tile;     // 0 = automatic (workgroup-cooperative kernel for calls of >= 32 blocks)
+    e->macTile = d->mac_tile;     // 0 = automatic (the rule: fdl_mac_variant, mac_kernels.hip)
 
     // partition capacity from the longest h_eff the plan can produce for max_ir_len
     cpq_nuc_plan pl;

@@ -144,7 +144,8 @@ int32_t cpq_diag_fdl_mac(int32_t P, int32_t nCh, int32_t K, int32_t T, int32_t t
 {
     if (!x || !h || !irSlot || !y || !variantUsed) return CPQ_ERR_INVALID_ARG;
     if (!partition(P) || P > 4096 || nCh < 1 || K < 1 || T < 1 || nIrSlots < 1) return CPQ_ERR_INVALID_ARG;
-    if (tile != 0 && tile != 4 && tile != 8 && tile != 16 && tile != 32 && tile != cpq::kMacTileCoop) return CPQ_ERR_INVALID_ARG;
+    if (tile != 0 && tile != 4 && tile != 8 && tile != 16 && tile != 32 && tile != cpq::kMacTileCoop && tile != cpq::kMacTileRows128)
+        return CPQ_ERR_INVALID_ARG;
     // the engines' own sizing rules (engine_core.cpp: ringSlots; engine_native.cpp layerGeometry: hRows, the smaller of the two)
     const int64_t kPad32 = cpqi::alignUp(K, cpq::kMacMaxTile);
     int64_t ringMin = 1;

@@ -67,26 +67,32 @@ void launch_spectrum_gain(hipStream_t stream, double2* H, double2* HDN, const do
 // >= 64); slot(s) = s & (ringSlots - 1).  Element 0 packs (DC, Nyquist), two independent real MACs: the 4- and 8-row tiles and the
 // cooperative kernel produce it themselves, the 16- and 32-row tiles store a complex product there that launch_fdl_mac_dcnyq
 // (fdl_mac_needs_dcnyq) must overwrite.
-// tile: 0 = automatic (fdl_mac_variant), 4 / 8 / 16 / 32 = that register tile, kMacTileCoop = the cooperative kernel at any T
-// (engines only pass 0 / 4 / 8 / 16 / 32: cpq_engine_create).
+// tile: 0 = automatic (fdl_mac_variant), 4 / 8 / 16 / 32 = that register tile, kMacTileCoop / kMacTileRows128 = the cooperative
+// kernel's 64- / 128-row workgroup at any T (engines only pass 0 / 4 / 8 / 16 / 32: cpq_engine_create).
 // What a call consumes: IR rows 0 .. K - 1 of the slots irSlot[] names and ring slots head + t - k (t < T, k < K); every
 // accumulation is guarded by k < K, so neither the zero padding behind row K nor the rest of the ring enters a result.
 // What it may LOAD (and discard) beyond that, TT = the variant's tile:
 //   IR rows     0 .. max(K, kMacPrefetch) - 1 (register tiles: the prologue fetches kMacPrefetch rows whatever K is),
 //               0 .. max(K, 8) - 1 (cooperative kernel: the prologue stages one chunk of 8 rows)
 //   ring slots  head - max(K - 1, kMacPrefetch) .. head + alignUp(T, TT) - 1 (register tiles),
-//               head - alignUp(K, 8) .. head + alignUp(T, 64) - 1 (cooperative kernel), every index masked by ringSlots - 1
+//               head - alignUp(K, 8) .. head + alignUp(T, 64) - 1 (cooperative kernel; alignUp(T, 128) with 128-row workgroups),
+//               every index masked by ringSlots - 1
 // So a slot needs max(K, 8) allocated rows -- both engine rules (alignUp(K, 32) + 16 rows and more per slot, alignUp(K, 32) + 32
 // rows per layer of a layered slot) allocate at least 48 -- and the ring any power of two >= K + T - 1 slots, so that the
 // consumed slots are distinct (the engines allocate nextPow2(alignUp(K, 32) + 32 + T)).
 // hPrivate: every channel has its own IR rows (no CPQ_ALL_STREAMS sharing): single-tile calls may then stream them past the cache
 constexpr int kMacTileCoop = -1;
+constexpr int kMacTileRows128 = -2;      // the cooperative kernel's 128-row workgroup at any T
+// what fdl_mac_variant returns for the two cooperative geometries (a register tile returns its size)
+constexpr int kMacVariantCoop = 0;
+constexpr int kMacVariantRows128 = 128;
 void launch_fdl_mac(hipStream_t stream, int tile, const double2* X, const double2* H, const int* irSlot,
                     double2* Y, int P, int nCh, int K, int ringSlots, int head, int T, int64_t hSlotStride,
                     bool hPrivate = false);      // K = partitions in use (walked in steps of the variant's tile)
 
 // packed bin 0: DC and Nyquist are two independent real MACs.
-// kernel variant launch_fdl_mac uses for (tile, T) (0 = workgroup-cooperative) and the multiple kPad must be padded to
+// kernel variant launch_fdl_mac uses for (tile, T) (kMacVariantCoop / kMacVariantRows128 = workgroup-cooperative) and the
+// multiple kPad must be padded to
 int fdl_mac_variant(int tile, int T);
 int fdl_mac_kpad_align(int tile, int T);
 bool fdl_mac_needs_dcnyq(int tile, int T);    // only the 16- and 32-row register tiles leave packed bin 0 to launch_fdl_mac_dcnyq

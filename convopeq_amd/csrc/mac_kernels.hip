@@ -119,8 +119,11 @@ __global__ __launch_bounds__(256, (TT >= 32 || (TT == 16 && PF >= 16)) ? 1 : 2) 
 // ---------------------------------------------------------------------------------------------------------
 // Workgroup-cooperative variant for calls of >= 48 blocks.
 //
-// At that batching the kernel is bound by the fp64 FMA rate, not by HBM (8 K T flop per 16 (2K + T) bytes), so the
-// complex MAC is done with THREE real FMAs (Gauss): M1 += a c, M2 += b d, M3 += (a + b)(c + d), Re = M1 - M2,
+// Arithmetic intensity: 8 K T flop per 16 (2K + T) bytes per (channel, bin) -- K + T - 1 FDL rows, K IR rows, T output rows.
+// At K = 33 (131072 taps at P = 4096) and T = 128 that is 4.9 flop/B, half the fp64 ridge of 9.8 flop/B (78.6 TFLOP/s over
+// 8 TB/s): the kernel is HBM-bound there.  At K = 259 (the same taps at P = 512) and T = 128 it is 25.7 flop/B and the fp64
+// FMA rate binds.  For that regime the complex MAC is done with THREE real FMAs (Gauss): M1 += a c, M2 += b d,
+// M3 += (a + b)(c + d), Re = M1 - M2,
 // Im = M3 - M1 - M2 at the end.  The X-side sum a + b is formed once when a row enters the register window, the
 // H-side sum c + d once per IR row for the lane's 8 outputs: 26 VALU operations per partition step instead of 32.
 // Rounding differs from the 4-multiply form by the usual Gauss bound (normwise the same order; measured RMS error
@@ -128,28 +131,45 @@ __global__ __launch_bounds__(256, (TT >= 32 || (TT == 16 && PF >= 16)) ? 1 : 2) 
 //
 // fp64 FMA needs >= 4 waves per SIMD to approach its issue rate on gfx950 (measured: 1 wave 25-45, 2 waves
 // ~50, 4 waves ~60 TFLOP/s), i.e. <= 128 VGPRs per lane, which caps the register tile at 8 outputs per lane;
-// a tile that small re-reads every FDL and IR row 8x more often than a 64-output tile.  So eight waves of one
-// workgroup take the eight consecutive 8-block tiles of the SAME (channel, 64-bin column) and share the FDL rows
+// a tile that small re-reads every FDL and IR row 8x more often than a 64-output tile.  So the NW waves of one
+// workgroup take NW consecutive 8-block tiles of the SAME (channel, 64-bin column) and share the FDL rows
 // through LDS: wave w needs FDL row (t0 + 8w - k - 1) at partition step k, which wave w-1 needs eight steps
-// later, so each row is fetched from HBM once, parked in a 9-block LDS ring (72 KB, lane-linear rows: every
-// ds_read/ds_write_b128 is conflict-free) and read by the eight waves at eight different times.  One barrier per
-// 8 steps (plus one for the IR rows, which are staged the same way: each wave fetches one IR row of the next chunk).
+// later, so each row is fetched from HBM once, parked in an (NW + 1)-block LDS ring (lane-linear rows: every
+// ds_read/ds_write_b128 is conflict-free) and read by the NW waves at NW different times.  The IR rows of a chunk of 8
+// steps are staged through LDS the same way, one chunk ahead.
 // HBM traffic per launch = every needed FDL row, IR row and output row exactly once.
-constexpr int kWgWaves = 8;
-constexpr int kWgTile = 8;                       // outputs per lane
-constexpr int kWgRingBlocks = kWgWaves + 1;      // blocks of 8 rows
-static_assert(kWgWaves == kWgTile, "k_fdl_mac_wg fetches block -1 one row per wave: waves per workgroup == rows per block");
+//
+// Two geometries, NW = waves per workgroup:
+//   <8>    64 output rows per workgroup: 9-block ring (72 KB) + the IR stage (8 KB), 512 threads, two workgroups per CU.
+//          Every wave fetches one FDL row AND one IR row of the next chunk.  A 128-row call runs two workgroups per column,
+//          each fetching the 33 IR rows and its own history rows: the CUs take in 2 (64 + 25 + 33) = 244 row segments per
+//          column where 186 are unique (HBM still sees each once: the second fetch hits the XCD's L2).
+//          This is what every engine runs (fdl_mac_variant).
+//   <16>   128 output rows per workgroup: 17-block ring (136 KB) + the IR stage (8 KB) = 144 KB of the CU's 160 KB, 1024
+//          threads (4 waves per SIMD), one workgroup per CU.  A chunk still needs 8 FDL rows and 8 IR rows and there are 16
+//          waves: waves 0-7 fetch FDL row w of block -j-2, waves 8-15 fetch IR row w - 8 of chunk j + 1, one 1 KB load per
+//          wave and chunk (in the prologue: waves 0-7 row w of block -1, waves 8-15 IR row w - 8 of chunk 0).
+//          Every row enters a CU once -- and the kernel is 19 % SLOWER at the bench shape (2.37 against 1.99 ms, RESULTS.md):
+//          a CU now has 16 KB of loads in flight per chunk where two 64-row workgroups have 32 KB, and no second workgroup
+//          that computes while this one waits at its barriers.  Reachable through cpq_diag_fdl_mac only (kMacTileRows128).
+// The inner loop -- and so every operation per output and their order -- is the same in both: the results are bit-identical.
+constexpr int kWgTile = 8;                       // outputs per lane = rows per ring block = rows per chunk
 
 // The IR rows of a chunk are staged through LDS one chunk ahead (one row per wave, like the FDL rows): a prefetch distance
 // of 8+ partition steps without holding them in registers (a 4-deep register prefetch measured 7 % slower, 2-deep 35 %).
-__global__ __launch_bounds__(64 * kWgWaves, 4) void k_fdl_mac_wg(const double2* __restrict__ X,
-                                                                  const double2* __restrict__ H,
-                                                                  const int* __restrict__ irSlot,
-                                                                  double2* __restrict__ Y, int kPad, int ringMask,
-                                                                  int head, int T, int nGroups, int64_t hSlotStride,
-                                                                  int P, int nCols, int nWork, int K)
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 4) void k_fdl_mac_wg(const double2* __restrict__ X,
+                                                            const double2* __restrict__ H,
+                                                            const int* __restrict__ irSlot,
+                                                            double2* __restrict__ Y, int kPad, int ringMask,
+                                                            int head, int T, int nGroups, int64_t hSlotStride,
+                                                            int P, int nCols, int nWork, int K)
 {
-    __shared__ double2 ring[kWgRingBlocks * kWgTile * 64];
+    static_assert(NW == kWgTile || NW == 2 * kWgTile,
+                  "a chunk stages 8 FDL rows and 8 IR rows, one row per wave: 8 waves fetch one of each, 16 waves one of either");
+    constexpr int kRingBlocks = NW + 1;           // blocks of 8 rows
+    constexpr bool kSplitRoles = NW == 2 * kWgTile;
+    __shared__ double2 ring[kRingBlocks * kWgTile * 64];
     __shared__ double2 hst[kWgTile * 64];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform: the loop below branches on it
@@ -162,13 +182,16 @@ __global__ __launch_bounds__(64 * kWgWaves, 4) void k_fdl_mac_wg(const double2* 
     const int cg = logical / nGroups;
     const int c = cg / nCols;
     const int bin = (cg - c * nCols) * 64 + lane;
-    const int base = head + grp * (kWgWaves * kWgTile);          // FDL slot of the group's first output block
-    const int t0w = grp * (kWgWaves * kWgTile) + w * kWgTile;    // this wave's first output block
+    const int base = head + grp * (NW * kWgTile);          // FDL slot of the group's first output block
+    const int t0w = grp * (NW * kWgTile) + w * kWgTile;    // this wave's first output block
+    // which row of a chunk this wave stages, and from where (kernel comment above)
+    const int rr = kSplitRoles ? (w & (kWgTile - 1)) : w;
+    const bool fdlRole = !kSplitRoles || w < kWgTile, irRole = !kSplitRoles || w >= kWgTile;
 
     // uniform row bases (SGPR) + per-lane bin offset: the loads use the scalar-base addressing form
     const double2* __restrict__ Xu = X + (int64_t)c * (ringMask + 1) * P;
     const double2* __restrict__ Hu = H + (int64_t)irSlot[c] * hSlotStride;
-    auto slotOf = [](int b) { return ((b % kWgRingBlocks) + kWgRingBlocks) % kWgRingBlocks; };
+    auto slotOf = [](int b) { return ((b % kRingBlocks) + kRingBlocks) % kRingBlocks; };
     auto xrow = [&](int slot) { return Xu + (int64_t)(slot & ringMask) * P; };
     auto hrow = [&](int k) { return Hu + (int64_t)k * P; };
 
@@ -183,17 +206,17 @@ __global__ __launch_bounds__(64 * kWgWaves, 4) void k_fdl_mac_wg(const double2* 
         xw[u] = xrow(base + kWgTile * w + u)[bin];
         xsum[u] = xw[u].x + xw[u].y;
     }
-    // ring prologue: block b (rows base+8b .. base+8b+7) for b = 0..6 is the register window of wave b;
+    // ring prologue: block b (rows base+8b .. base+8b+7) for b = 0..NW-2 is the register window of wave b;
     // block -1 is fetched one row per wave
-    if (w < kWgWaves - 1) {
+    if (w < NW - 1) {
 #pragma unroll
         for (int u = 0; u < kWgTile; ++u) ring[(slotOf(w) * kWgTile + u) * 64 + lane] = xw[u];
     }
-    {
-        const double2 xs = xrow(base - kWgTile + w)[bin];
-        ring[(slotOf(-1) * kWgTile + w) * 64 + lane] = xs;
+    if (fdlRole) {
+        const double2 xs = xrow(base - kWgTile + rr)[bin];
+        ring[(slotOf(-1) * kWgTile + rr) * 64 + lane] = xs;
     }
-    hst[w * 64 + lane] = hrow(w)[bin];            // IR rows of chunk 0
+    if (irRole) hst[rr * 64 + lane] = hrow(rr)[bin];            // IR rows of chunk 0
     __syncthreads();
 
     // The last chunk holds rem = K - 8 (nChunks - 1) partition steps (1 ... 8): the steps past K are skipped, and so
@@ -210,14 +233,14 @@ __global__ __launch_bounds__(64 * kWgWaves, 4) void k_fdl_mac_wg(const double2* 
         // the FDL rows of a channel are read by this workgroup alone (one group at T <= 64): streaming hint; the IR rows
         // may be shared by every channel (CPQ_ALL_STREAMS) and stay cacheable
         double2 xs = make_double2(0.0, 0.0), hsn = make_double2(0.0, 0.0);
-        if (!lastChunk && (!nextIsLast || w > kWgTile - rem)) {
-            const double* xp = reinterpret_cast<const double*>(xrow(base + kWgTile * (-j - 2) + w) + bin);
+        if (fdlRole && !lastChunk && (!nextIsLast || rr > kWgTile - rem)) {
+            const double* xp = reinterpret_cast<const double*>(xrow(base + kWgTile * (-j - 2) + rr) + bin);
             xs = make_double2(__builtin_nontemporal_load(xp), __builtin_nontemporal_load(xp + 1));
         }
-        if (!lastChunk && (!nextIsLast || w < rem))
-            hsn = hrow((j + 1) * kWgTile + w)[bin];               // IR row w of the next chunk
+        if (irRole && !lastChunk && (!nextIsLast || rr < rem))
+            hsn = hrow((j + 1) * kWgTile + rr)[bin];              // IR row rr of the next chunk
         const double2* blk = ring + slotOf(w - j - 1) * kWgTile * 64 + lane;
-        // a wave whose 8 outputs lie beyond T only feeds the ring (partial last group: T mod 64 != 0)
+        // a wave whose 8 outputs lie beyond T only feeds the ring (partial last group)
         if (active)
 #pragma unroll
         for (int r = 0; r < kWgTile; ++r) {
@@ -248,13 +271,13 @@ __global__ __launch_bounds__(64 * kWgWaves, 4) void k_fdl_mac_wg(const double2* 
             }
         }
         if (lastChunk) break;
-        // slot of block (-j-2) == slot of block (7-j), last read by wave 7 in chunk j-1: free since the barrier
+        // slot of block (-j-2) == slot of block (NW-1-j), last read by wave NW-1 in chunk j-1: free since the barrier
         // that ended that chunk
-        ring[(slotOf(-j - 2) * kWgTile + w) * 64 + lane] = xs;
+        if (fdlRole) ring[(slotOf(-j - 2) * kWgTile + rr) * 64 + lane] = xs;
         // slot 0 was refilled in the last step of this chunk
         xsum[0] = xw[0].x + xw[0].y;
         __syncthreads();                      // every wave is done with this chunk's IR rows
-        hst[w * 64 + lane] = hsn;
+        if (irRole) hst[rr * 64 + lane] = hsn;
         __syncthreads();
     }
 #pragma unroll
@@ -325,28 +348,49 @@ void launch_mac_t(hipStream_t stream, const double2* X, const double2* H, const 
                        ringSlots - 1, head, T, nTiles, hSlotStride, P, segShift, K);
 }
 
+// one workgroup per (channel, 64-bin column, group of NW * 8 output rows); the grid is padded to a multiple of 8 (XCD remap)
+template <int NW>
+void launch_mac_wg(hipStream_t stream, const double2* X, const double2* H, const int* irSlot, double2* Y, int P, int nCh,
+                   int kPad, int K, int ringSlots, int head, int T, int64_t hSlotStride)
+{
+    const int nGroups = (T + NW * kWgTile - 1) / (NW * kWgTile);
+    const int nCols = P / 64;
+    const int nWork = nCh * nCols * nGroups;
+    hipLaunchKernelGGL((k_fdl_mac_wg<NW>), dim3((nWork + 7) / 8 * 8), dim3(64 * NW), 0, stream, X, H, irSlot, Y, kPad,
+                       ringSlots - 1, head, T, nGroups, hSlotStride, P, nCols, nWork, K);
+}
+
 }  // namespace
 
-// Variant for `tile` (0 = automatic) and T output rows per channel: 0 = the workgroup-cooperative kernel (64 outputs
-// per workgroup: waves past the last row only feed the LDS ring; worth it from ~48 rows on (below, the register tiles measured faster)), else the register tile -- sized so that short calls do not spend most
-// of their FMAs on rows that are not there (T = 1, the reference's own call pattern, is HBM-bound at any tile).
+// Variant for `tile` (0 = automatic) and T output rows per channel: kMacVariantCoop / kMacVariantRows128 = the
+// workgroup-cooperative kernel with 64 / 128 outputs per workgroup (waves past the last row only feed the LDS ring), else the
+// register tile -- sized so that short calls do not spend most of their FMAs on rows that are not there (T = 1, the
+// reference's own call pattern, is HBM-bound at any tile).
+// The automatic rule, all of it:
+//   T >= 48   cooperative, 64-row workgroups (below, the register tiles measured faster).  The 128-row workgroup is never
+//             chosen: at T = 128 it measured 0.39 ms per launch slower than two 64-row workgroups (RESULTS.md).
 int fdl_mac_variant(int tile, int T)
 {
-    if (tile == kMacTileCoop) return 0;      // the cooperative kernel at any T (cpq_diag_fdl_mac; no engine passes it)
+    if (tile == kMacTileCoop) return kMacVariantCoop;          // at any T (cpq_diag_fdl_mac; no engine passes these two)
+    if (tile == kMacTileRows128) return kMacVariantRows128;
     if (tile) return tile;
-    if (T >= 48) return 0;
+    if (T >= 48) return kMacVariantCoop;
     if (T >= 12) return 16;
     if (T >= 6) return 8;
     return 4;
 }
 
 // the variants that leave packed bin 0 to launch_fdl_mac_dcnyq
-bool fdl_mac_needs_dcnyq(int tile, int T) { return fdl_mac_variant(tile, T) > 8; }
+bool fdl_mac_needs_dcnyq(int tile, int T)
+{
+    const int v = fdl_mac_variant(tile, T);
+    return v == 16 || v == 32;
+}
 
 int fdl_mac_kpad_align(int tile, int T)
 {
     const int v = fdl_mac_variant(tile, T);
-    return v == 0 ? kWgTile : v;
+    return (v == kMacVariantCoop || v == kMacVariantRows128) ? kWgTile : v;
 }
 
 void launch_fdl_mac(hipStream_t stream, int tile, const double2* X, const double2* H, const int* irSlot, double2* Y,
@@ -356,12 +400,12 @@ void launch_fdl_mac(hipStream_t stream, int tile, const double2* X, const double
     const int kAlign = fdl_mac_kpad_align(tile, T);
     const int kPad = (K + kAlign - 1) / kAlign * kAlign;
     tile = fdl_mac_variant(tile, T);
-    if (tile == 0) {      // long calls: workgroup-cooperative kernel
-        const int nGroups = (T + kWgWaves * kWgTile - 1) / (kWgWaves * kWgTile);
-        const int nCols = P / 64;
-        const int nWork = nCh * nCols * nGroups;
-        hipLaunchKernelGGL(k_fdl_mac_wg, dim3((nWork + 7) / 8 * 8), dim3(64 * kWgWaves), 0, stream, X, H,
-                           irSlot, Y, kPad, ringSlots - 1, head, T, nGroups, hSlotStride, P, nCols, nWork, K);
+    if (tile == kMacVariantCoop) {      // long calls: workgroup-cooperative kernel
+        launch_mac_wg<8>(stream, X, H, irSlot, Y, P, nCh, kPad, K, ringSlots, head, T, hSlotStride);
+        return;
+    }
+    if (tile == kMacVariantRows128) {
+        launch_mac_wg<16>(stream, X, H, irSlot, Y, P, nCh, kPad, K, ringSlots, head, T, hSlotStride);
         return;
     }
     const int pf = 4;     // prefetch depth in partition steps (deeper measured slower: register pressure)

@@ -895,8 +895,9 @@ int32_t     cpq_diag_partition_fft_split(int32_t partition, int32_t n_channels, 
  * ir_slot: [n_channels]; y: [n_channels][n_blocks][partition][2]; all host memory.  The compact DC/Nyquist rows the 16- and
  * 32-row tiles read are formed from element 0 of x and h.
  * tile: 0 = automatic (by n_blocks), 4 / 8 / 16 / 32 = that register tile, -1 = the workgroup-cooperative kernel at any
- * n_blocks (no engine selects it below 48 blocks).  *variant_used = the kernel that ran: 4 / 8 / 16 / 32, or 0 for the
- * cooperative kernel.  h_private != 0: no two channels share an IR slot (one-tile calls may then stream the IR rows).
+ * n_blocks (no engine selects it below 48 blocks), -2 = the same kernel with 128-row workgroups at any n_blocks (no engine
+ * selects it).  *variant_used = the kernel that ran: 4 / 8 / 16 / 32, 0 for the cooperative kernel, 128 for its 128-row
+ * workgroups.  h_private != 0: no two channels share an IR slot (one-tile calls may then stream the IR rows).
  * Rows k_parts ... h_rows - 1 of a slot, IR slots no channel names and ring slots outside {head + t - k} may hold anything
  * finite: they may be loaded, never consumed.
  * CPQ_ERR_INVALID_ARG, before anything is launched, unless: partition is a power of two in 64 ... 4096; n_channels, k_parts,
