@@ -261,7 +261,7 @@ double totalGainLinear(float db)
 //   A = [[2 a1 - 1, -2 a2], [2 a2, 1 - 2 a3]],  Bv = [2 a2, 2 a3],  C = [m1 a1 + m2 a2, -m1 a2 + m2 (1 - a3)]
 namespace {
 typedef long double ld;
-bool buildTpTablesFromStateSpace(const ld* A, const ld* C, const ld* Bv, ld D, double* out);
+bool buildTpTablesFromStateSpace(const ld* A, const ld* C, const ld* Bv, double* out);
 }  // namespace
 
 bool buildSvfTpTables(const cpq_svf_coeffs& c, double* out)
@@ -270,8 +270,7 @@ bool buildSvfTpTables(const cpq_svf_coeffs& c, double* out)
     const ld A[4] = { 2 * a1 - 1, -2 * a2, 2 * a2, 1 - 2 * a3 };
     const ld C[2] = { m1 * a1 + m2 * a2, -m1 * a2 + m2 * (1 - a3) };
     const ld Bv[2] = { 2 * a2, 2 * a3 };
-    const ld D = (ld)c.m0 + m1 * a2 + m2 * a3;          // coefficient of v0 in y = m0 v0 + m1 v1 + m2 v2
-    return buildTpTablesFromStateSpace(A, C, Bv, D, out);
+    return buildTpTablesFromStateSpace(A, C, Bv, out);
 }
 
 // DF-II-T biquad (src/OutputFilter.h:33-68): y = b0 x + w1; w1' = b1 x - a1 y + w2; w2' = b2 x - a2 y
@@ -281,11 +280,11 @@ bool buildBiquadTpTables(const cpq_biquad_coeffs& q, double* out)
     const ld A[4] = { -(ld)q.a1, 1, -(ld)q.a2, 0 };
     const ld C[2] = { 1, 0 };
     const ld Bv[2] = { (ld)q.b1 - (ld)q.a1 * q.b0, (ld)q.b2 - (ld)q.a2 * q.b0 };
-    return buildTpTablesFromStateSpace(A, C, Bv, (ld)q.b0, out);
+    return buildTpTablesFromStateSpace(A, C, Bv, out);
 }
 
 namespace {
-bool buildTpTablesFromStateSpace(const ld* A, const ld* C, const ld* Bv, ld D, double* out)
+bool buildTpTablesFromStateSpace(const ld* A, const ld* C, const ld* Bv, double* out)
 {
     auto mul = [](const ld* x, const ld* y, ld* z) {
         const ld r[4] = { x[0] * y[0] + x[1] * y[2], x[0] * y[1] + x[1] * y[3],
@@ -301,46 +300,31 @@ bool buildTpTablesFromStateSpace(const ld* A, const ld* C, const ld* Bv, ld D, d
         }
         for (int q = 0; q < 4; ++q) r[q] = acc[q];
     };
-    // layout: struct TpLcTables { Mk[6][4]; Mw[4]; P[64][4]; G[16][2]; } for LC = 16 then LC = 2 (svf_kernels.hip)
-    const int* lcs = kSvfTpLc;
-    constexpr int kPerLc = 6 * 4 + 4 + 64 * 4 + 16 * 2;
+    TpBandTables& tb = *reinterpret_cast<TpBandTables*>(out);
     for (int li = 0; li < kSvfTpLcCount; ++li) {
-        double* o = out + li * kPerLc;
-        const int lc = lcs[li];
+        TpLcTables& t = tb.t[li];
+        const int lc = kSvfTpLc[li];
         ld M[4];
         for (int k = 0; k < 6; ++k) {
             power((long)lc << k, M);
-            for (int q = 0; q < 4; ++q) o[k * 4 + q] = (double)M[q];
+            for (int q = 0; q < 4; ++q) t.Mk[k][q] = (double)M[q];
         }
         power((long)lc * 64, M);
-        for (int q = 0; q < 4; ++q) o[24 + q] = (double)M[q];
+        for (int q = 0; q < 4; ++q) t.Mw[q] = (double)M[q];
         for (int c = 0; c < 64; ++c) {
             power((long)lc * (c + 1), M);
-            for (int q = 0; q < 4; ++q) o[28 + c * 4 + q] = (double)M[q];
-        }
-        ld P[4] = { 1, 0, 0, 1 };
-        for (int i = 0; i < 16; ++i) {
-            o[28 + 256 + 2 * i] = (double)(C[0] * P[0] + C[1] * P[2]);
-            o[28 + 256 + 2 * i + 1] = (double)(C[0] * P[1] + C[1] * P[3]);
-            mul(A, P, P);
+            for (int q = 0; q < 4; ++q) t.P[c][q] = (double)M[q];
         }
     }
-    // matrix form of a 16-sample chunk (MFMA path of the time-parallel kernel): zero-state impulse response
-    // h[0] = D, h[n] = C A^(n-1) B behind 15 zeros, and the chunk's end-state map e[:, k] = A^(15-k) B
+    // the end-state map of a 16-sample chunk: e[:, k] = A^(15-k) B
     {
-        double* o = out + kSvfTpLcCount * kPerLc;
-        for (int i = 0; i < kSvfTpMfmaDoubles; ++i) o[i] = 0.0;
         ld v[2] = { Bv[0], Bv[1] };                     // A^n B
-        o[15] = (double)D;
-        for (int n = 1; n < 16; ++n) {
-            o[15 + n] = (double)(C[0] * v[0] + C[1] * v[1]);
-            o[32 + (16 - n)] = (double)v[0];            // e[0][15 - (n-1)] = (A^(n-1) B)_0
-            o[48 + (16 - n)] = (double)v[1];
+        for (int n = 0; n < 16; ++n) {
+            tb.e[0][15 - n] = (double)v[0];
+            tb.e[1][15 - n] = (double)v[1];
             const ld t0 = A[0] * v[0] + A[1] * v[1], t1 = A[2] * v[0] + A[3] * v[1];
             v[0] = t0; v[1] = t1;
         }
-        o[32 + 0] = (double)v[0];                       // A^15 B
-        o[48 + 0] = (double)v[1];
     }
     for (int i = 0; i < kSvfTpTableDoubles; ++i) if (!std::isfinite(out[i])) return false;
 

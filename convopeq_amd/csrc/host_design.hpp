@@ -12,11 +12,17 @@ namespace cpq {
 // samples on one or two waves: k_svf_cascade_short)
 constexpr int kSvfTpLcCount = 2;
 constexpr int kSvfTpLc[kSvfTpLcCount] = { 16, 8 };
-constexpr int kSvfTpLcDoubles = 6 * 4 + 4 + 64 * 4 + 16 * 2;
-// after the two per-chunk-length blocks: the matrix form of one 16-sample chunk for the MFMA path (chunk length 16 only):
-// ht[32] = 15 zeros, h[0..15], 0 (zero-state impulse response; T[m][k] = ht[15 + m - k]),  e[2][16] = A^(15-k) B
-constexpr int kSvfTpMfmaDoubles = 32 + 2 * 16;
-constexpr int kSvfTpTableDoubles = kSvfTpLcCount * kSvfTpLcDoubles + kSvfTpMfmaDoubles;
+// the tables of one (stream, band), as the builder fills them and the kernels read them; A = the band's 2x2 state matrix
+struct TpLcTables {         // one per chunk length LC
+    double Mk[6][4];        // A^(LC 2^k), row-major 2x2: in-wave scan steps
+    double Mw[4];           // A^(LC 64): one whole wave of chunks
+    double P[64][4];        // A^(LC (c+1)): carries the wave's start state to the end of chunk c
+};
+struct TpBandTables {
+    TpLcTables t[kSvfTpLcCount];
+    double e[2][16];        // e[:, k] = A^(15-k) B: end state of a 16-sample chunk's zero-state run (its last LC columns serve a chunk of LC)
+};
+constexpr int kSvfTpTableDoubles = (int)(sizeof(TpBandTables) / sizeof(double));
 
 int    computeNucPlan(int irLen, int blockSize, bool enableDirectHead, const cpq_filter_spec* spec,
                       cpq_nuc_plan* out);
@@ -27,8 +33,8 @@ bool   airAbsorptionGains(const cpq_filter_spec& spec, int layer, int complexSiz
 void   designSvf(int type, float freq, float gainDb, float q, double sr, cpq_svf_coeffs* c);
 void   defaultEqParams(cpq_eq_params* p);
 double totalGainLinear(float db);
-// Tables of the time-parallel SVF kernel for one band (kSvfTpTableDoubles doubles, layout TpBandTables in
-// svf_kernels.hip: 2x2 powers of the state matrix and the state-to-output response).  Returns false when the state guards of the reference could
+// Tables of the time-parallel SVF kernels for one band (out: one TpBandTables, kSvfTpTableDoubles doubles).
+// Returns false when the state guards of the reference could
 // trip for inputs / carried states below 1e9 (or the filter does not decay), i.e. the kernel must not be used.
 bool   buildSvfTpTables(const cpq_svf_coeffs& c, double* out);
 bool   buildBiquadTpTables(const cpq_biquad_coeffs& q, double* out);

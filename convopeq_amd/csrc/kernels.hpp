@@ -132,9 +132,9 @@ void launch_svf_cascade(hipStream_t stream, const double* in, double* out, int64
 // Time-parallel SVF cascade (svf_kernels.hip): whole 8192-sample spans on k_svf_cascade_tpv<8> (one workgroup per channel, or
 // chained spans, below), what is left from 1024 samples up as one span of 1 ... 7 waves x 1024 samples whose tail may be
 // padding, the rest (and calls below 1024 samples) on k_svf_cascade_short.  nSamples: any number.
-// t.tp: kSvfTpTableDoubles doubles per (stream, band): for each chunk length LC in kSvfTpLc ({16, 8}): Mk[6][4] = A^(LC 2^k),
-// Mw[4] = A^(64 LC), P[64][4] = A^(LC (c+1)), G[16][2] = C A^i; then the chunk's end-state map e[2][16] = A^(15-k) B.
-// geometry constants kSvfTpLc / kSvfTpTableDoubles: host_design.hpp (shared with the table builder)
+// t.tp: one TpBandTables (host_design.hpp, kSvfTpTableDoubles = 600 doubles) per (stream, band): for each chunk length LC in
+// kSvfTpLc ({16, 8}): Mk[6][4] = A^(LC 2^k), Mw[4] = A^(64 LC), P[64][4] = A^(LC (c+1)); then the 16-sample chunk's end-state
+// map e[2][16] = A^(15-k) B.
 // chain / chainSpans / chainGrid: chained spans for engines whose channels do not fill whole rounds of the workgroups the chip
 // holds of the span kernel (chainGrid = 2 per CU): the (span, channel) pairs of a call are dealt to chainGrid workgroups, a band's state is
 // handed from span to span through `chain` (svf_chain_bytes(channels, largest call) bytes, zero-initialised once,

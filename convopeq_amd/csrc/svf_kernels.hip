@@ -215,25 +215,9 @@ __global__ __launch_bounds__(64) void k_svf_cascade(const double* in, double* ou
 // Result differs from the sequential recurrence by rounding only (measured <= 3e-15 abs over 20 bands).
 
 constexpr double kTpInputBound = 1.0e9;
-constexpr int kTpChunks = 256;               // (default thread count of tp_scan)
 constexpr int kTpLcMain = kSvfTpLc[0];       // samples per chunk of the span kernels
 constexpr int kTpStride = kTpLcMain + 2;     // LDS row stride in doubles: rows 16-byte aligned for b128 access, 36 dwords
                                              // apart so that 16 consecutive rows cover all 64 banks
-
-// per (stream, band); one block per chunk length (host_design.hpp: kSvfTpLc = {16, 8}); must match host buildSvfTpTables()
-struct TpLcTables {
-    double Mk[6][4];     // A^(LC*2^k), row-major 2x2: in-wave scan steps
-    double Mw[4];        // A^(LC*64): one whole wave of chunks
-    double P[64][4];     // A^(LC*(c+1)): carries the wave's start state to the end of chunk c
-    double G[16][2];     // C*A^i, i < LC (state-to-output response; not read by the kernels of this file any more)
-};
-// e[:, k] = A^(15-k) B: end state of a 16-sample chunk's zero-state run (its last LC columns serve a chunk of LC);
-// ht: the chunk's zero-state impulse response in matrix form (round 2's MFMA path, tools/variants/; not read here)
-struct TpMfmaTables {
-    double ht[32];
-    double e[2][16];
-};
-struct TpBandTables { TpLcTables t[kSvfTpLcCount]; TpMfmaTables mm; };
 
 // num / den for the fastTanh Pade: den in [27, 209.25], |num| <= 212.7, so the range scaling and special-case
 // fix-up of the generic fp64 division (v_div_scale / v_div_fmas / v_div_fixup, which serialise on VCC) are
@@ -254,7 +238,7 @@ __device__ __forceinline__ double pade_div(double num, double den)
 
 // Output stage of one band for N independent samples (blend with fastTanh, output guard, clamp), written
 // stage by stage so that independent operations are adjacent in program order.
-template <bool MONO, bool SAT, int N, bool GUARD = true>
+template <bool MONO, bool SAT, int N, bool GUARD>
 __device__ __forceinline__ void tp_nonlinear(double (&y)[N], double sat, double oneMinusSat)
 {
     if (SAT) {
@@ -299,12 +283,10 @@ __device__ __forceinline__ void tp_nonlinear(double (&y)[N], double sat, double 
 // the scalar path's hard +-1, nor the +-100 clamp can act (|out| <= |y| for 0 <= sat <= 1), and the blend folds into
 // one rational function:  y (1 - s) + s y (27 + y^2) / (27 + 9 y^2)  =  y (27 + c1 y^2) / (27 + 9 y^2),  c1 = 9 - 8 s,
 // which in partial fractions is  y (c1 / 9 + (3 - c1 / 3) / (3 + y^2)):  one reciprocal of den in [3, 23.25] and a
-// multiply-add instead of a full division.  The reciprocal is refined with one third-order step (r (1 + e + e^2), e = 1 -
-// den r: v_rcp_f64 is good to 4.6e-8 here, e^3 ~ 1e-22), so r is the correctly rounded reciprocal up to 1 ulp and the
-// result is within ~1 ulp of the reference expression (rounding-level, like the rest of the time-parallel evaluation;
-// 7 operations per sample instead of 10).  Both band kinds share it.
-// ORDER 2: one second-order step instead (r (1 + e): relative error e^2 <= 2.2e-15 in r, <= 0.4 ... 2 e-15 in the result
-// for sat = 0.2 ... 1 -- the size of the other rounding errors of a band; one operation less).
+// multiply-add instead of a full division.  The reciprocal is refined with one second-order step (r (1 + e), e = 1 - den r:
+// v_rcp_f64 is good to 4.6e-8 here, so the relative error e^2 <= 2.2e-15 in r, <= 0.4 ... 2 e-15 in the result for
+// sat = 0.2 ... 1 -- the size of the other rounding errors of a band; rounding-level, like the rest of the time-parallel
+// evaluation).  Both band kinds share it.
 // (the callers form the two constants once per channel and say that they are wave-uniform: computed here they sat in vector
 // registers across the band loop, at the 128-register limit of the span kernel)
 struct TpSmallConsts { double ca, cb; };
@@ -313,18 +295,19 @@ __device__ __forceinline__ TpSmallConsts tp_small_consts(double sat)
     const double c1 = 9.0 - 8.0 * sat;
     return { c1 * (1.0 / 9.0), 3.0 - c1 * (1.0 / 3.0) };
 }
-template <int N, int ORDER = 3>
+template <int N>
 __device__ __forceinline__ void tp_nonlinear_small(double (&y)[N], const TpSmallConsts& k)
 {
+    static_assert(N == 4 || N == 2, "a group of four (span kernels) or a pair (short kernel)");
     const double ca = k.ca, cb = k.cb;
-    double den[N], r[N];
+    double den[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) den[j] = fma(y[j], y[j], 3.0);
-    if (N == 4 && ORDER == 2) {
+    if constexpr (N == 4) {
         // one reciprocal for the four denominators (v_rcp_f64 issues at a quarter of the FMA rate): 1 / (d0 d1 d2 d3),
         // refined once, then multiplied back apart -- 27 issue slots for four samples instead of 36.  The denominators
         // lie in [3, 3 + bound^2]: no over- or underflow in the products.
-        const double p01 = den[0] * den[1], p23 = den[2 % N] * den[3 % N];
+        const double p01 = den[0] * den[1], p23 = den[2] * den[3];
         const double pp = p01 * p23;
         double q = __builtin_amdgcn_rcp(pp);
         q = fma(fma(-pp, q, 1.0), q, q);
@@ -332,28 +315,16 @@ __device__ __forceinline__ void tp_nonlinear_small(double (&y)[N], const TpSmall
         const double q01 = q * p23, q23 = q * p01;
         y[0] *= fma(q01, den[1], ca);
         y[1] *= fma(q01, den[0], ca);
-        y[2 % N] *= fma(q23, den[3 % N], ca);
-        y[3 % N] *= fma(q23, den[2 % N], ca);
-        return;
-    }
-    if (N == 2 && ORDER == 2) {          // the same for a pair: 14 slots for two samples instead of 18
-        const double pp = den[0] * den[1 % N];
+        y[2] *= fma(q23, den[3], ca);
+        y[3] *= fma(q23, den[2], ca);
+    } else {                             // the same for a pair: 14 slots for two samples instead of 18
+        const double pp = den[0] * den[1];
         double q = __builtin_amdgcn_rcp(pp);
         q = fma(fma(-pp, q, 1.0), q, q);
         q *= cb;                         // cb / (den0 den1): one product for the pair, and ONE scalar operand per instruction
-        y[0] *= fma(q, den[1 % N], ca);
-        y[1 % N] *= fma(q, den[0], ca);
-        return;
+        y[0] *= fma(q, den[1], ca);
+        y[1] *= fma(q, den[0], ca);
     }
-#pragma unroll
-    for (int j = 0; j < N; ++j) r[j] = __builtin_amdgcn_rcp(den[j]);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const double e = fma(-den[j], r[j], 1.0);
-        r[j] = (ORDER == 2) ? fma(e, r[j], r[j]) : fma(fma(e, e, e), r[j], r[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) y[j] *= fma(cb, r[j], ca);
 }
 
 // a * b + c with a in scalar registers, as the three-address instruction: for the output of a peaking band (m1 v1 + v0, v0 the
@@ -370,7 +341,7 @@ __device__ __forceinline__ double fma_sgpr(double a, double b, double c)
 // of the OutputFilter (coefficients b0 b1 b2 a1 a2 in a1 a2 a3 m0 m1; state w1 w2 in ic1 ic2)
 // CAP: the state behind sample capAt is copied to (c1, c2) -- the end state of a span whose last chunk is partly padding
 // UNI: the coefficients are wave-uniform (scalar registers)
-template <int KIND, int N, bool CAP = false, bool UNI = false>
+template <int KIND, int N, bool CAP, bool UNI>
 __device__ __forceinline__ void tp_recur(double (&v)[N], double& ic1, double& ic2, double a1, double a2, double a3,
                                          double m0, double m1, double m2, int capAt = -1, double* c1 = nullptr, double* c2 = nullptr)
 {
@@ -478,7 +449,7 @@ struct TpvLink {
     int* flag;                        // LDS: != 0 once a start state outside the proven range has arrived (1 + band)
     unsigned* error;                  // header word: a poll gave up
     int slice;                        // 0 / 1: the time slices in which this workgroup runs at raised priority; -1: none
-    const struct TpBandTables* tb;    // the stream's tables in device memory (the pass reads the next band's E rows through the scalar cache)
+    const TpBandTables* tb;           // the stream's tables in device memory (the pass reads the next band's E rows through the scalar cache)
 };
 
 // Two workgroups of the span kernel share a CU, and the instruction arbiter serves the older wave first: left alone, the
@@ -547,14 +518,15 @@ __device__ __forceinline__ void tpv_publish_state(unsigned long long* g, unsigne
 // wave that is already in the next band writes the other half while slow waves still read this one) and the span's
 // end state goes to sNext while every wave reads the start state from sCur (the caller swaps the two per span).
 // Plate != nullptr: the per-lane powers are loaded from there right where they are used (register-tight callers: the
-// loads then wait on L2 behind the other waves of the SIMD) and pw is ignored.
-// CHAINED (link != nullptr): the span's start state of band b arrives from the workgroup that has the span before (four
+// loads then wait on LDS behind the other waves of the SIMD) and pw is ignored.
+// NTHREADS: the workgroup's thread count, 0: blockDim.x.
+// CHAINED: the span's start state of band b arrives from the workgroup that has the span before (four
 // lanes of wave 0 poll for it in front of the barrier), the end state is published to the workgroup that has the span behind.
 // FLUSH (DF-II-T sections of the OutputFilter): the span's end state gets the reference's denormal flush before it is handed on.
-template <int NTHREADS = kTpChunks, bool CHAINED = false, bool FLUSH = false>
+template <int NTHREADS, bool CHAINED, bool FLUSH>
 __device__ __forceinline__ void tp_scan(double ic1, double ic2, double& s0x, double& s0y, const double* Mall, int b,
                                         const TpLanePowers& pw, double* wtot, double* sCur, double* sNext, int tid,
-                                        const double* __restrict__ Plate = nullptr, int endTid = -1, const TpvLink* link = nullptr)
+                                        const double* __restrict__ Plate, int endTid, const TpvLink* link)
 {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: the chain below branches on it
@@ -564,7 +536,7 @@ __device__ __forceinline__ void tp_scan(double ic1, double ic2, double& s0x, dou
     uint32_t mOff = (uint32_t)b * (uint32_t)(28 * sizeof(double));      // Mall = [band][28]
     asm volatile("" : "+v"(mOff));
     const double* Mb = reinterpret_cast<const double*>(reinterpret_cast<const char*>(Mall) + mOff);
-    const double2* Mb2 = reinterpret_cast<const double2*>(Mb);          // rows of 28 doubles: 16-byte aligned (TpLds / TpLdsM)
+    const double2* Mb2 = reinterpret_cast<const double2*>(Mb);          // rows of 28 doubles: 16-byte aligned (TpvShared::M)
     double sx = ic1, sy = ic2;
 #define CPQ_ROW_STEP(k)                                                                                       \
     {                                                                                                         \
@@ -655,10 +627,10 @@ __device__ void tp_band_guarded(double* buf, int lc, const double* cf, double sa
     for (int c = 0; c * lc < nSamples; ++c)
         for (int i = 0; i < lc && c * lc + i < nSamples; ++i) {
             double y[1] = { buf[c * kTpStride + i] };
-            tp_recur<KIND, 1>(y, ic1, ic2, a1, a2, a3, m0, m1, m2);
+            tp_recur<KIND, 1, false, false>(y, ic1, ic2, a1, a2, a3, m0, m1, m2);
             if (KIND != 2) {          // (OutputFilter: no output stage; tp_recur flushes its states like OutputFilter.cpp:154-162)
-                if (sat > 0.0) tp_nonlinear<KIND == 1, true, 1>(y, sat, oneMinusSat);
-                else           tp_nonlinear<KIND == 1, false, 1>(y, sat, oneMinusSat);
+                if (sat > 0.0) tp_nonlinear<KIND == 1, true, 1, true>(y, sat, oneMinusSat);
+                else           tp_nonlinear<KIND == 1, false, 1, true>(y, sat, oneMinusSat);
                 ic1 = sanitize(ic1);
                 ic2 = sanitize(ic2);
             }
@@ -751,7 +723,7 @@ __device__ __forceinline__ float tpv_max3_hi(float m, double b, double c)      /
 // independent evaluations behind ONE wave-uniform test for the small-signal form.  En = the NEXT band's E rows in LDS.
 // CAP (spans whose last chunk is partly padding): the lane with capAt >= 0 also returns the band's state behind its sample
 // capAt in (c1, c2).
-template <int KIND, bool SAT, bool CAP = false>
+template <int KIND, bool SAT, bool CAP>
 __device__ __forceinline__ void tpv_pass(double (&x)[16], double ic1, double ic2, const double* __restrict__ cfb, bool mono,
                                          const double* En, const double* Eglob, double& e0o, double& e1o,
                                          double sat, bool smallOk, const TpSmallConsts& smallK,
@@ -762,7 +734,7 @@ __device__ __forceinline__ void tpv_pass(double (&x)[16], double ic1, double ic2
         if (KIND == 3)          // m0 == 1 and m2 == 0 (peaking bands)
             tp_recur<3, 16, CAP, true>(x, ic1, ic2, 2.0 * a2, 2.0 * a3, 0.0, a2, m1, a1, capAt, c1, c2);
         else
-        tp_recur<KIND, 16, CAP>(x, ic1, ic2, a1, a2, a3, m0, m1, m2, capAt, c1, c2);
+            tp_recur<KIND, 16, CAP, false>(x, ic1, ic2, a1, a2, a3, m0, m1, m2, capAt, c1, c2);
     }
     double e0 = 0.0, e1 = 0.0;
     bool done = false;
@@ -793,7 +765,7 @@ __device__ __forceinline__ void tpv_pass(double (&x)[16], double ic1, double ic2
                 double v[kTpvU];
 #pragma unroll
                 for (int j = 0; j < kTpvU; ++j) v[j] = x[kTpvU * h + j];
-                if (SAT) tp_nonlinear_small<kTpvU, 2>(v, smallK);
+                if (SAT) tp_nonlinear_small<kTpvU>(v, smallK);
 #pragma unroll
                 for (int j = 0; j < kTpvU; ++j) {
                     e0 = fma(ea[j], v[j], e0);
@@ -989,7 +961,7 @@ __device__ __forceinline__ int tpv_lane_id()
 template <int CLS, bool SAT, int NT, bool CHAINED, bool PARTIAL, class SH>
 __device__ __forceinline__ void tpv_band_run(double (&x)[16], double& e0, double& e1, int& par, unsigned run, unsigned rest,
                                              unsigned monoMask, SH& sh, double* sState, double* sNext, const double* __restrict__ cf,
-                                             double sat, int waveU, int nThreads, const TpvLink& link, int endTid = -1, int capAt = 15)
+                                             double sat, int waveU, int nThreads, const TpvLink& link, int endTid, int capAt)
 {
     const bool smallOk = (sat >= 0.0) && (sat <= 1.0);
     TpSmallConsts smallK = tp_small_consts(sat);
@@ -1015,16 +987,16 @@ __device__ __forceinline__ void tpv_band_run(double (&x)[16], double& e0, double
             // the band's end state is the one behind the span's last valid sample, which the pass meets inside chunk endTid
             // (the scan above left there the state behind that chunk's padding)
             double c1 = 0.0, c2 = 0.0;
-            tpv_pass<CLS, SAT, true>(x, s0x, s0y, cf + b * 6, (monoMask >> b) & 1, &sh.E[nb][0][0], &link.tb[nb].mm.e[0][0], e0, e1, sat, smallOk, smallK,
+            tpv_pass<CLS, SAT, true>(x, s0x, s0y, cf + b * 6, (monoMask >> b) & 1, &sh.E[nb][0][0], &link.tb[nb].e[0][0], e0, e1, sat, smallOk, smallK,
                                      tidL == endTid ? capAt : -1, &c1, &c2);
             if (tidL == endTid) { sNext[2 * b] = c1; sNext[2 * b + 1] = c2; }
         } else {
-            tpv_pass<CLS, SAT>(x, s0x, s0y, cf + b * 6, (monoMask >> b) & 1, &sh.E[nb][0][0], &link.tb[nb].mm.e[0][0], e0, e1, sat, smallOk, smallK);
+            tpv_pass<CLS, SAT, false>(x, s0x, s0y, cf + b * 6, (monoMask >> b) & 1, &sh.E[nb][0][0], &link.tb[nb].e[0][0], e0, e1, sat, smallOk, smallK);
         }
     }
 }
 
-// band masks of one channel: active bands of this launch; DF-II-T sections; SVF bands with the scalar fastTanh; SVF bands
+// band masks of one channel: active bands; DF-II-T sections; SVF bands with the scalar fastTanh; SVF bands
 // whose output is v0 + m1 v1 (every peaking band).  Wave-uniform by construction; said so, they live in scalar registers
 // (left in vector registers they were spilled and reloaded inside the band loop).
 struct TpvBands { unsigned active, df, mono, peak; unsigned long long kinds; };
@@ -1057,7 +1029,7 @@ __device__ __forceinline__ TpvBands tpv_band_masks(const int* __restrict__ flags
     return m;
 }
 // the tables of one stream into LDS: 16-byte pieces (Mk and Mw are contiguous in TpLcTables: 14 pieces per band; the E rows are
-// paired up from the two rows of the host's e[2][16]), every load independent of the others
+// paired up from the two rows of e[2][16]), every load independent of the others
 template <class SH>
 __device__ __forceinline__ void tpv_load_tables(SH& sh, const TpBandTables* __restrict__ tb, int tid, int nThreads)
 {
@@ -1067,7 +1039,7 @@ __device__ __forceinline__ void tpv_load_tables(SH& sh, const TpBandTables* __re
     }
     for (int i = tid; i < kBands * 16; i += nThreads) {
         const int b = i >> 4, k = i & 15;
-        *reinterpret_cast<double2*>(&sh.E[b][k][0]) = make_double2(tb[b].mm.e[0][k], tb[b].mm.e[1][k]);
+        *reinterpret_cast<double2*>(&sh.E[b][k][0]) = make_double2(tb[b].e[0][k], tb[b].e[1][k]);
     }
     for (int i = tid; i < kBands * 128; i += nThreads) {       // 16-byte pieces of P[64][4]
         const int b = i >> 7, q = i & 127;
@@ -1201,7 +1173,7 @@ __global__ __launch_bounds__((WAVES ? WAVES : 7) * 64, PARTIAL ? 2 : 4) void k_s
             tpv_guarded_span(sh, kPartial ? nValid : spanLen, inCh + (int64_t)sp * spanLen, outCh + (int64_t)sp * spanLen, sState, cf, bm.active, bm.kinds,
                              sat, gain, tidE, nThreads);
         __syncthreads();
-        // the call's end states (only this launch's bands are written)
+        // the call's end states (of the active bands)
         if (nSpans > 0 && tidE < kBands * 2 && ((bm.active >> (tidE >> 1)) & 1)) state[(int64_t)c * kBands * 2 + tidE] = sState[tidE];
     } else {
         TpvChainHeader* hdr = reinterpret_cast<TpvChainHeader*>(chain);
@@ -1385,8 +1357,8 @@ __device__ __forceinline__ void short_pass(double (&x)[LC], double ic1, double i
                                            double& e0, double& e1, double sat, int capAt, double& c1, double& c2)
 {
     const double a1 = k.cf[0].x, a2 = k.cf[0].y, a3 = k.cf[1].x, m0 = k.cf[1].y, m1 = k.cf[2].x, m2 = k.cf[2].y;
-    if (CLS == 3) tp_recur<3, LC, true>(x, ic1, ic2, 2.0 * a2, 2.0 * a3, 0.0, a2, m1, a1, capAt, &c1, &c2);
-    else          tp_recur<CLS, LC, true>(x, ic1, ic2, a1, a2, a3, m0, m1, m2, capAt, &c1, &c2);
+    if (CLS == 3) tp_recur<3, LC, true, false>(x, ic1, ic2, 2.0 * a2, 2.0 * a3, 0.0, a2, m1, a1, capAt, &c1, &c2);
+    else          tp_recur<CLS, LC, true, false>(x, ic1, ic2, a1, a2, a3, m0, m1, m2, capAt, &c1, &c2);
     if (CLS != 2) {           // class 2: linear section (OutputFilter), no output stage
         int small = 1;
 #pragma unroll
@@ -1397,7 +1369,7 @@ __device__ __forceinline__ void short_pass(double (&x)[LC], double ic1, double i
 #pragma unroll
                 for (int h = 0; h < LC / 2; ++h) {
                     double v[2] = { x[2 * h], x[2 * h + 1] };
-                    tp_nonlinear_small<2, 2>(v, ks);
+                    tp_nonlinear_small<2>(v, ks);
                     x[2 * h] = v[0];
                     x[2 * h + 1] = v[1];
                 }
@@ -1454,7 +1426,7 @@ __global__ __launch_bounds__(256, 1) void k_svf_cascade_short(const double* in, 
     }
     for (int i = tid; i < kBands * LC * 2; i += nThreads) {
         const int b = i / (LC * 2), k = (i % (LC * 2)) >> 1, r = i & 1;
-        sh.E[b][k][r] = tb[b].mm.e[r][16 - LC + k];          // A^(LC - 1 - k) B: the last LC columns of the 16-sample map
+        sh.E[b][k][r] = tb[b].e[r][16 - LC + k];          // A^(LC - 1 - k) B: the last LC columns of the 16-sample map
     }
     for (int i = tid; i < kBands * 6; i += nThreads) sh.cf[i / 6][i % 6] = cfg[i];
     if (tid < kBands * 2) { sh.stateA[tid] = state[(int64_t)c * kBands * 2 + tid]; sh.stateB[tid] = sh.stateA[tid]; }
@@ -1569,9 +1541,8 @@ size_t svf_chain_bytes(int nCh, int maxSamples)
 void launch_svf_cascade_tp(hipStream_t stream, const double* in, double* out, int64_t chStride, int nCh, int nSamples,
                            CascadeTables t, void* chain, int chainSpans, int chainGrid)
 {
-    static_assert(sizeof(TpBandTables) == kSvfTpTableDoubles * sizeof(double), "host/device table layout");
-    // whole 8192-sample spans on the eight-wave kernel, what is left as one span of 1 ... 7 waves x 1024 samples, and a
-    // last block of 512 on the chunk-length-2 path of the four-wave kernel
+    // whole 8192-sample spans on the eight-wave kernel, what is left as spans of 1 ... 7 waves x 1024 samples on the same
+    // kernel, and a remainder below 1024 samples on k_svf_cascade_short (chunks of 8, one or two waves)
     const TpBandTables* tb = reinterpret_cast<const TpBandTables*>(t.tp);
     constexpr unsigned kAllBands = 0xFFFFFu | kTpvApplyGain;
     int done = 0;
