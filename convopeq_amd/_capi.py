@@ -43,6 +43,7 @@ CPQ_RESAMPLE_LINEAR_PHASE = 0
 CPQ_RESAMPLE_MINIMUM_PHASE = 1
 CPQ_RESAMPLE_MAX_FACTOR = 1280
 CPQ_SRC_HOST = 1
+CPQ_SRC_DEVICE = 2
 CPQ_OS_IIR = 0
 CPQ_OS_LINEAR_PHASE = 1
 CPQ_METER_LOUDNESS = 1
@@ -306,6 +307,9 @@ SYMBOLS = {
     "cpq_src_out_count": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "cpq_src_max_out": (C.c_int32, [C.c_void_p]),
     "cpq_src_process": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _i32p]),
+    "cpq_src_process_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _i32p]),
+    "cpq_src_set_stream": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "cpq_src_last_kernel_ms": (C.c_double, [C.c_void_p]),
     "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
     "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
     "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),

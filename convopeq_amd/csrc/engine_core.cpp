@@ -41,6 +41,21 @@ int fail(cpq_engine* e, int code, const char* fmt, ...)
     return code;
 }
 
+int checkCurrentDevice()
+{
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) {
+        (void)hipGetLastError();
+        return fail(nullptr, CPQ_ERR_NO_DEVICE, "no HIP device visible: the gfx950 kernels cannot run (no CPU fallback)");
+    }
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return fail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(nullptr, CPQ_ERR_NO_DEVICE, "device %d is %s; this library ships gfx950 code only", device, prop.gcnArchName);
+    return CPQ_OK;
+}
 
 int nextPow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 int64_t alignUp(int64_t v, int64_t a) { return (v + a - 1) / a * a; }

@@ -342,8 +342,11 @@ struct cpq_engine {
 namespace cpqi {
 
 int fail(cpq_engine* e, int code, const char* fmt, ...);
+// what runs without an engine (cpq_ir_resample, cpq_ir_minimum_phase, the device object of cpq_src) asks before its first HIP call:
+// CPQ_OK where the current device is a gfx950, else CPQ_ERR_NO_DEVICE with the reason in cpq_last_error(NULL)
+int checkCurrentDevice();
 
-#define CPQ_HIP(e, call)                                                                             \
+#define CPQ_HIP(e, call)                                                                            \
     do {                                                                                             \
         hipError_t err__ = (call);                                                                   \
         if (err__ != hipSuccess)                                                                     \

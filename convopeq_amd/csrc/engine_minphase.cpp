@@ -23,22 +23,6 @@ thread_local double g_lastKernelMs = -1.0;
             return cpqi::fail(nullptr, CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__)); \
     } while (0)
 
-int checkDevice()
-{
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) {
-        (void)hipGetLastError();
-        return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "no HIP device visible: the gfx950 kernels cannot run (no CPU fallback)");
-    }
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "device %d is %s; this library ships gfx950 code only", device, prop.gcnArchName);
-    return CPQ_OK;
-}
-
 struct Events {
     hipEvent_t ev[2] = {};
     ~Events()
@@ -121,7 +105,7 @@ int minphaseBatch(const cpq_ir_buffer* const* in, int n, long long workspace, cp
                               cpq::minphaseRowNeed(groups[g]), 1LL << groups[g].log2n);
     for (int i = 0; i < n; ++i) status[i] = refused[(size_t)i] ? CPQ_ERR_UNSUPPORTED : CPQ_OK;
     if (groups.empty()) return CPQ_OK;
-    CPQ_TRY(checkDevice());
+    CPQ_TRY(cpqi::checkCurrentDevice());
 
     for (int i = 0; i < n; ++i) {
         if (refused[(size_t)i]) continue;

@@ -20,22 +20,6 @@ thread_local double g_lastKernelMs = -1.0;
             return cpqi::fail(nullptr, CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__)); \
     } while (0)
 
-int checkDevice()
-{
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) {
-        (void)hipGetLastError();
-        return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "no HIP device visible: the gfx950 kernels cannot run (no CPU fallback)");
-    }
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return cpqi::fail(nullptr, CPQ_ERR_NO_DEVICE, "device %d is %s; this library ships gfx950 code only", device, prop.gcnArchName);
-    return CPQ_OK;
-}
-
 struct Events {
     hipEvent_t ev[2] = {};
     ~Events()
@@ -127,7 +111,7 @@ int resampleBatch(const cpq_ir_buffer* const* in, int n, double targetRate, int 
         }
         members[g].push_back(i);
     }
-    if (!rates.empty()) CPQ_TRY(checkDevice());
+    if (!rates.empty()) CPQ_TRY(cpqi::checkCurrentDevice());
     double kernelMs = 0.0;
     for (size_t g = 0; g < rates.size(); ++g) CPQ_TRY(runGroup(in, members[g], designs[g], targetRate, out, kernelMs));
     for (int i = 0; i < n; ++i)

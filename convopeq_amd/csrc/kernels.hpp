@@ -7,6 +7,7 @@
 
 #include "host_design.hpp"
 #include "minphase_plan.hpp"
+#include "src_device_plan.hpp"
 
 namespace cpq {
 
@@ -351,6 +352,14 @@ int resampleTile(int L, int M);
 int resampleSpan(int L, int M, int tile);   // input samples the first taps of a tile's outputs spread over
 void launch_ir_resample(hipStream_t stream, const double* taps, int L, int M, int T, const double* x, double* y, const ResampleRow* rows,
                         const ResampleTile* tiles, int nTiles);
+
+// ---- streaming sample-rate conversion of audio (resample_kernels.hip), the device object of cpq_src: the call src_device_plan.hpp
+// states in `a`, over hist [channels][a.hBound] and the caller's rows.  launch_src_resample writes out[ch][0 ... a.nOut) and launches
+// nothing for a call without outputs; launch_src_keep then moves the kept samples to the front of hist, and launches nothing where
+// srcKeepMoves says nothing moves.  Both go to one stream, in that order.  Nothing here checks an index: `a` is engine_src.cpp's,
+// built from a planned and validated call.
+void launch_src_resample(hipStream_t stream, const double* taps, const double* hist, const double* in, double* out, const SrcLaunch& a);
+void launch_src_keep(hipStream_t stream, double* hist, const double* in, const SrcLaunch& a);
 
 // ---- minimum-phase conversion of IR rows (minphase_kernels.hip), launched as minphase_plan.hpp lists.  x and y hold the rows of a
 // chunk back to back: row r reads x[off ... off + n) and writes y[off ... off + n); z is its complex scratch [rows][N] (four-step

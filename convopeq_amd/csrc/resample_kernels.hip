@@ -12,6 +12,10 @@
 //
 // Arithmetic: acc = 0, then acc = fma(taps[p][k], x[n0 + T / 2 - k], acc) for k = 0 ... T - 1 in that order, n0 = floor(j M / L),
 // x zero outside the row.  The order does not depend on the tile, the chunk or the batch, and it is the host path's order.
+//
+// k_src_resample, k_src_keep: the device object of cpq_src (engine_src.cpp), the same mapping over the channels of a stream, call
+// by call.  Every index, offset, count and stride of theirs is src_device_plan.hpp's arithmetic on SrcLaunch, which arrives by
+// value: there is no table in device memory.  They read taps, hist and the caller's in, and write out and hist.
 #include "kernels.hpp"
 
 namespace cpq {
@@ -56,6 +60,51 @@ __global__ void __launch_bounds__(kResampleTileMax) k_ir_resample(const double* 
     if (live) y[row.outOff + j] = acc;
 }
 
+static_assert(kSrcTileMax == kResampleTileMax && kSrcChunk == kResampleChunk, "cpq_src launches with k_ir_resample's geometry");
+
+// grid (tilesPerRow, channels), a.tile lanes: lane `tid` of tile blockIdx.x computes output srcLaneOutput of channel blockIdx.y
+__global__ void __launch_bounds__(kSrcTileMax) k_src_resample(const double* __restrict__ taps, const double* __restrict__ hist,
+                                                              const double* __restrict__ in, double* __restrict__ out, SrcLaunch a)
+{
+    extern __shared__ double stage[];
+    const int tid = (int)threadIdx.x, nThreads = (int)blockDim.x;
+    const int tileIndex = (int)blockIdx.x, ch = (int)blockIdx.y;
+    const int o = tileIndex * a.tile + tid;
+    const SrcOutput at = srcOutput(a, srcLaneOutput(a, tileIndex, tid));
+    const int cBase = srcTileBase(a, tileIndex);
+    const int d = at.c - cBase;                                         // 0 ... span - 1
+    const int kEnd = srcTapEnd(a, at.c);
+    const double* __restrict__ h = taps + (size_t)at.row * (size_t)a.T;
+
+    double acc = 0.0;
+    for (int kc = 0; kc < a.T; kc += kSrcChunk) {
+        const int kn = srcChunkLen(a, kc);
+        const int lo = srcStageLo(cBase, kc, kn);
+        for (int s = tid; s < srcStageLen(a.span, kn); s += nThreads) stage[s] = srcVirt(a, hist, in, ch, lo + s);
+        __syncthreads();
+        const double* __restrict__ hk = h + kc;
+        const double* xs = stage + srcStageAt(d, kn, 0);
+        const int mine = min(kn, kEnd - kc);                            // below kn only where the row starts inside the filter
+#pragma unroll 8
+        for (int kk = 0; kk < mine; ++kk) acc = fma(hk[kk], xs[-kk], acc);
+        __syncthreads();
+    }
+    if (o < a.nOut) out[(long long)ch * a.outStride + o] = acc;
+}
+
+// one workgroup of kSrcKeepBlock lanes per channel: ascending chunks, each loaded whole before it is stored
+__global__ void __launch_bounds__(kSrcKeepBlock) k_src_keep(double* hist, const double* __restrict__ in, SrcLaunch a)
+{
+    const int tid = (int)threadIdx.x, ch = (int)blockIdx.x;
+    for (int chunk = 0; chunk < srcKeepChunks(a); ++chunk) {
+        const int i = chunk * kSrcKeepBlock + tid;
+        const double v = i < a.keepLen ? srcVirt(a, hist, in, ch, a.keepShift + i) : 0.0;
+        __syncthreads();
+        if (i < a.keepLen) hist[(long long)ch * a.hBound + i] = v;
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 int resampleTile(int L, int M) { return (long long)M <= 8LL * L ? kResampleTileMax : 64; }
@@ -69,6 +118,19 @@ void launch_ir_resample(hipStream_t stream, const double* taps, int L, int M, in
     const int tile = resampleTile(L, M), span = resampleSpan(L, M, tile);
     const size_t lds = (size_t)(span + kResampleChunk - 1) * sizeof(double);
     hipLaunchKernelGGL(k_ir_resample, dim3((unsigned)nTiles), dim3((unsigned)tile), lds, stream, taps, L, M, T, x, y, rows, tiles, span);
+}
+
+void launch_src_resample(hipStream_t stream, const double* taps, const double* hist, const double* in, double* out, const SrcLaunch& a)
+{
+    if (a.tilesPerRow <= 0 || a.channels <= 0) return;
+    hipLaunchKernelGGL(k_src_resample, dim3((unsigned)a.tilesPerRow, (unsigned)a.channels), dim3((unsigned)a.tile), (size_t)srcLdsBytes(a.span),
+                       stream, taps, hist, in, out, a);
+}
+
+void launch_src_keep(hipStream_t stream, double* hist, const double* in, const SrcLaunch& a)
+{
+    if (!srcKeepMoves(a) || a.channels <= 0) return;
+    hipLaunchKernelGGL(k_src_keep, dim3((unsigned)a.channels), dim3(kSrcKeepBlock), 0, stream, hist, in, a);
 }
 
 }  // namespace cpq

@@ -563,9 +563,10 @@ int32_t cpq_ir_resample_host(const cpq_ir_buffer* in, double target_rate, int32_
 /* ---------------------------------------------------------------- streaming sample-rate conversion of audio */
 /* cpq_src: the filter of cpq_resample_design applied to audio, call by call, for n_channels planar fp64 rows at once; an object of
  * its own beside cpq_engine (an engine runs at one rate: sources at another rate pass through a cpq_src in front of it).  The
- * object keeps the history between calls.  Built: the object that computes on the host (flags & CPQ_SRC_HOST), the counterpart of
- * cpq_ir_resample_host.  Not built: the object that computes on the device; cpq_src_create without CPQ_SRC_HOST is
- * CPQ_ERR_UNSUPPORTED, never the host in its place.
+ * object keeps the history between calls.  Two objects, one definition, equal bits: the one that computes on the host
+ * (flags = CPQ_SRC_HOST, the counterpart of cpq_ir_resample_host, no GPU) and the one that computes on the device (flags =
+ * CPQ_SRC_DEVICE, gfx950 kernels, CPQ_ERR_NO_DEVICE without one).  The caller says which: flags = 0 is CPQ_ERR_UNSUPPORTED, and
+ * neither object ever stands in for the other.
  *
  * Let x be everything a stream received since creation, cpq_src_reset or the last flush, zero before index 0 and, after a flush,
  * zero from its end on.  Output j is the sum stated above for cpq_ir_resample, in that order and with that fma.  A call emits
@@ -581,12 +582,15 @@ int32_t cpq_ir_resample_host(const cpq_ir_buffer* in, double target_rate, int32_
  * CPQ_ERR_INVALID_ARG: a null pointer (in may be NULL when n_in == 0, out when nothing is written), n_channels outside 1 ... 65535,
  * max_in < 1, start_period outside 0 ... 2^50, an unknown phase or flag, n_in < 0 or above max_in, a stride shorter than its row,
  * out_capacity below cpq_src_out_count, rows of in and out that overlap; CPQ_ERR_UNSUPPORTED: what cpq_resample_design refuses,
- * CPQ_RESAMPLE_MINIMUM_PHASE, a max_in whose cpq_src_max_out exceeds 2^30, and a device object.  The reason is in
+ * CPQ_RESAMPLE_MINIMUM_PHASE, a max_in whose cpq_src_max_out exceeds 2^30, and flags = 0.  The reason is in
  * cpq_src_last_error (with NULL: of a failed create). */
-/* The host object only.  CPQ_HAS_STREAM_RESAMPLING is not defined: that name is kept for a library that also has the device object
- * and its cpq_src_process_device, cpq_src_set_stream and cpq_src_last_kernel_ms. */
+/* CPQ_HAS_STREAM_RESAMPLING_HOST announces the host object, CPQ_HAS_STREAM_RESAMPLING the device object with
+ * cpq_src_process_device, cpq_src_set_stream and cpq_src_last_kernel_ms.  Both flags at once, or an unknown bit, are
+ * CPQ_ERR_INVALID_ARG. */
 #define CPQ_HAS_STREAM_RESAMPLING_HOST 1
+#define CPQ_HAS_STREAM_RESAMPLING 1
 #define CPQ_SRC_HOST 1u
+#define CPQ_SRC_DEVICE 2u
 typedef struct cpq_src cpq_src;
 typedef struct {
     int32_t  n_channels;
@@ -608,9 +612,22 @@ int32_t cpq_src_latency(const cpq_src* s);
 int32_t cpq_src_out_count(const cpq_src* s, int32_t n_in, int32_t flush);
 /* the bound of cpq_src_out_count for any call: a call of max_in samples with flush */
 int32_t cpq_src_max_out(const cpq_src* s);
-/* host rows in and out */
+/* host rows in and out.  On a device object the rows pass through buffers the object owns ([n_channels][max_in] and
+ * [n_channels][cpq_src_max_out]): upload, the device call, download, and the object's stream is synchronised before the return. */
 int32_t cpq_src_process(cpq_src* s, const double* in, int64_t in_stride, int32_t n_in, double* out, int64_t out_stride,
                         int32_t out_capacity, int32_t flush, int32_t* n_out);
+/* Device object only (a host object: CPQ_ERR_INVALID_ARG): device rows in and out, the same refusals in the same order, all
+ * before any state changes.  Asynchronous: the call enqueues its work on the object's stream and returns; d_in and d_out must stay
+ * valid, and d_in unchanged, until the stream has reached the call.  d_out is written at [channel][0 ... *n_out) and nowhere else.
+ * CPQ_ERR_DEVICE: a launch failed; the state is as before the call. */
+int32_t cpq_src_process_device(cpq_src* s, const double* d_in, int64_t in_stride, int32_t n_in, double* d_out, int64_t out_stride,
+                               int32_t out_capacity, int32_t flush, int32_t* n_out);
+/* Device object only: the stream (a hipStream_t; NULL, the default, is the null stream) every later call enqueues on.  The stream
+ * used so far is synchronised first, so the history a call reads has been written. */
+int32_t cpq_src_set_stream(cpq_src* s, void* stream);
+/* milliseconds between device events around the launches of the last cpq_src_process on a device object (transfers excluded);
+ * -1 on a host object, for NULL, and before such a call.  cpq_src_process_device records no events. */
+double  cpq_src_last_kernel_ms(const cpq_src* s);
 
 /* ---------------------------------------------------------------- minimum-phase conversion on the device */
 /* cpq_ir_convert_to_minimum_phase for a whole IR library: convertToMinimumPhase (ResampleAndFallback.cpp:333-469) per row (a row

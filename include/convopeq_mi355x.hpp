@@ -453,12 +453,12 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// Streaming sample-rate conversion of nChannels planar rows (cpq_src): one object per source rate in front of an Engine.  Only the
-// object that computes on the host is built (CPQ_SRC_HOST).
+// Streaming sample-rate conversion of nChannels planar rows (cpq_src): one object per source rate in front of an Engine, computing
+// on the host (CPQ_SRC_HOST) or on the device (CPQ_SRC_DEVICE), with equal bits.
 class StreamResampler {
 public:
     explicit StreamResampler(const cpq_src_desc& desc) { status_ = cpq_src_create(&desc, &s_); }
-    // flags: CPQ_SRC_HOST for the object that computes on the host; 0 asks for the device object (CPQ_ERR_UNSUPPORTED: not built)
+    // flags: CPQ_SRC_HOST or CPQ_SRC_DEVICE; 0 is CPQ_ERR_UNSUPPORTED, both CPQ_ERR_INVALID_ARG
     StreamResampler(int nChannels, double inRate, double outRate, int maxIn, uint32_t flags)
     {
         const cpq_src_desc d{ nChannels, inRate, outRate, maxIn, CPQ_RESAMPLE_LINEAR_PHASE, flags, 0 };
@@ -479,6 +479,17 @@ public:
         status_ = cpq_src_process(s_, in, inStride, numSamples, out, outStride, outCapacity, flush ? 1 : 0, &n);
         return status_ == CPQ_OK ? n : -1;
     }
+    // device object: device rows, asynchronous on the object's stream; dIn and dOut stay valid until the stream has reached the call
+    int processDevice(const double* dIn, int64_t inStride, int numSamples, double* dOut, int64_t outStride, int outCapacity, bool flush = false)
+    {
+        int32_t n = 0;
+        status_ = cpq_src_process_device(s_, dIn, inStride, numSamples, dOut, outStride, outCapacity, flush ? 1 : 0, &n);
+        return status_ == CPQ_OK ? n : -1;
+    }
+    // device object: a hipStream_t (nullptr: the null stream); the stream used so far is synchronised first
+    bool setStream(void* stream) { return (status_ = cpq_src_set_stream(s_, stream)) == CPQ_OK; }
+    // device time of the launches of the last process() on a device object; -1 otherwise
+    double lastKernelMs() const noexcept { return cpq_src_last_kernel_ms(s_); }
     cpq_src* get() const noexcept { return s_; }
     int lastStatus() const noexcept { return status_; }
     const char* lastError() const noexcept { return cpq_src_last_error(s_); }
