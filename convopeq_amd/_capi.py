@@ -149,6 +149,16 @@ class SrcDesc(C.Structure):
                 ("flags", C.c_uint32), ("start_period", C.c_int64)]
 
 
+class LoudnessDesc(C.Structure):
+    _fields_ = [("n_streams", C.c_int32), ("sample_rate", C.c_double), ("max_seconds", C.c_double), ("flags", C.c_int32)]
+
+
+class LoudnessResult(C.Structure):
+    _fields_ = [("integrated", C.c_double), ("range", C.c_double), ("momentary_max", C.c_double), ("short_term_max", C.c_double),
+                ("relative_gate", C.c_double), ("n_hops", C.c_int64), ("n_blocks", C.c_int32), ("n_abs", C.c_int32),
+                ("n_rel", C.c_int32), ("n_short_kept", C.c_int32)]
+
+
 class OsStageInfo(C.Structure):
     _fields_ = [("taps", C.c_int32), ("center_tap", C.c_int32), ("center_parity", C.c_int32), ("conv_parity", C.c_int32),
                 ("conv_count", C.c_int32), ("center_delay_input", C.c_int32), ("history_up_keep", C.c_int32),
@@ -310,6 +320,17 @@ SYMBOLS = {
     "cpq_src_process_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _i32p]),
     "cpq_src_set_stream": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "cpq_src_last_kernel_ms": (C.c_double, [C.c_void_p]),
+    "cpq_loudness_create": (C.c_int32, [C.POINTER(LoudnessDesc), C.POINTER(C.c_void_p)]),
+    "cpq_loudness_destroy": (None, [C.c_void_p]),
+    "cpq_loudness_last_error": (C.c_char_p, [C.c_void_p]),
+    "cpq_loudness_reset": (C.c_int32, [C.c_void_p]),
+    "cpq_loudness_set_stream": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "cpq_loudness_process_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "cpq_loudness_process": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "cpq_loudness_finish": (C.c_int32, [C.c_void_p, C.POINTER(LoudnessResult)]),
+    "cpq_loudness_read_hops": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, _i64p]),
+    "cpq_loudness_finish_host": (C.c_int32, [c_double_p, C.c_int64, C.c_double, C.POINTER(LoudnessResult)]),
+    "cpq_loudness_gain": (C.c_int32, [C.POINTER(LoudnessResult), C.c_double, c_double_p]),
     "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
     "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
     "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),

@@ -1,0 +1,223 @@
+// engine_prog.cpp -- cpq_loudness: gated programme loudness (EBU R 128) per stream, an object of its own beside cpq_engine.  The
+// definition and the plan of a call are prog_plan.hpp's, the kernels prog_kernels.hip's: this file checks, allocates, launches and
+// copies, and holds no arithmetic of its own.  The rules are the device object of cpq_src's.  No device-side
+// tables of the call: what the kernels index with arrives by value.  Zeroed at create: hop sums, partial hops and filter states
+// are cleared synchronously before create returns.  One stream: everything is enqueued on the object's stream, and the position
+// advances only after the launch was enqueued without an error.
+#include "engine_internal.hpp"
+
+struct cpq_loudness {
+    cpq_loudness_desc desc{};
+    int H = 0, maxHops = 0;
+    long long pos = 0;                              // samples every programme has taken
+    std::string lastError;
+    hipStream_t stream = nullptr;
+    cpqi::DeviceBuffer<double> tab, state, part, hops;      // section tables; [2 S][8]; [2 S]; [S][maxHops]
+    cpqi::DeviceBuffer<cpq::ProgRecord> rec;                // [S]
+    cpqi::DeviceBuffer<double> rows;                        // [2 S][rowsCap]: the host rows of cpq_loudness_process
+    int rowsCap = 0;
+};
+
+namespace {
+
+int pfail(cpq_loudness* p, int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (p) p->lastError = buf;
+    else return cpqi::fail(nullptr, code, "%s", buf);       // before an object exists: cpq_last_error(NULL) has it
+    return code;
+}
+
+#define CPQ_PROG_HIP(p, call)                                                                         \
+    do {                                                                                              \
+        hipError_t err__ = (call);                                                                    \
+        if (err__ != hipSuccess) {                                                                    \
+            (void)hipGetLastError();                                                                  \
+            return pfail((p), CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__));      \
+        }                                                                                             \
+    } while (0)
+
+constexpr size_t kTabDoubles = 2 * (size_t)cpq::kMeterSectionDoubles;
+
+// the refusals of a call, host rows or device rows alike, all before any state moves; c: the plan of the call
+int checkCall(cpq_loudness* p, const double* rows, int64_t stride, int32_t n, cpq::ProgCall& c)
+{
+    if (!rows) return pfail(p, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (n < 1 || n > cpq::kProgMaxCall) return pfail(p, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, cpq::kProgMaxCall);
+    if (stride < n) return pfail(p, CPQ_ERR_INVALID_ARG, "row stride %lld shorter than its row of %d", (long long)stride, n);
+    if (reinterpret_cast<uintptr_t>(rows) & 15u) return pfail(p, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    if (!cpq::progPlan(p->pos, n, p->H, p->maxHops, p->desc.n_streams, stride, c))
+        return pfail(p, CPQ_ERR_UNSUPPORTED, "%d samples after %lld pass the %d hops of max_seconds=%g", n, p->pos, p->maxHops, p->desc.max_seconds);
+    return CPQ_OK;
+}
+
+int runDevice(cpq_loudness* p, const double* dRows, const cpq::ProgCall& c)
+{
+    cpq::launch_prog_hops(p->stream, dRows, c, p->tab, p->state, p->part, p->hops);
+    CPQ_PROG_HIP(p, hipGetLastError());
+    p->pos += c.n;
+    return CPQ_OK;
+}
+
+int clearState(cpq_loudness* p)
+{
+    CPQ_PROG_HIP(p, hipMemsetAsync(p->state, 0, p->state.count() * sizeof(double), p->stream));
+    CPQ_PROG_HIP(p, hipMemsetAsync(p->part, 0, p->part.count() * sizeof(double), p->stream));
+    CPQ_PROG_HIP(p, hipMemsetAsync(p->hops, 0, p->hops.count() * sizeof(double), p->stream));
+    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    p->pos = 0;
+    return CPQ_OK;
+}
+
+int createDevice(cpq_loudness* p)
+{
+    const size_t S = (size_t)p->desc.n_streams;
+    CPQ_TRY(cpqi::allocAll(nullptr, { { p->tab, kTabDoubles }, { p->state, 16 * S, true }, { p->part, 2 * S, true },
+                                      { p->hops, S * (size_t)p->maxHops, true }, { p->rec, S } },
+                           "hop sums of %d streams and %d hops could not be allocated", p->desc.n_streams, p->maxHops));
+    std::vector<double> tab(kTabDoubles, 0.0);
+    double pre[5], rlb[5];
+    cpq::meterKWeighting(p->desc.sample_rate, pre, rlb);
+    cpq::meterSectionTables(pre, tab.data());
+    cpq::meterSectionTables(rlb, tab.data() + cpq::kMeterSectionDoubles);
+    CPQ_PROG_HIP(nullptr, hipMemcpy(p->tab, tab.data(), kTabDoubles * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_PROG_HIP(nullptr, hipDeviceSynchronize());      // the clears have run before the first call, whatever its stream
+    return CPQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t cpq_loudness_create(const cpq_loudness_desc* d, cpq_loudness** out)
+{
+    if (!d || !out) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (d->n_streams < 1 || d->n_streams > 32767) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "n_streams %d outside 1..32767", d->n_streams);
+    if (d->flags) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "unknown flags");
+    if (!(d->sample_rate > 0.0) || !std::isfinite(d->sample_rate)) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "sample_rate must be finite and > 0");
+    const long long maxHops = cpq::progMaxHops(d->max_seconds);
+    if (!maxHops) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "max_seconds must be finite and > 0");
+    const int H = cpq::progHop(d->sample_rate);
+    if (!H) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", d->sample_rate);
+    if (cpq::progShortCount(maxHops) > cpq::kProgSortMax)
+        return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "max_seconds=%g holds more than %d short-term blocks at the 1 s step", d->max_seconds, cpq::kProgSortMax);
+    try {
+        std::unique_ptr<cpq_loudness, void (*)(cpq_loudness*)> p(new cpq_loudness(), cpq_loudness_destroy);
+        p->desc = *d;
+        p->H = H;
+        p->maxHops = (int)maxHops;
+        CPQ_TRY(cpqi::checkCurrentDevice());
+        CPQ_TRY(createDevice(p.get()));
+        *out = p.release();
+        return CPQ_OK;
+    } catch (const std::exception&) {
+        return pfail(nullptr, CPQ_ERR_OOM, "host allocation failed");
+    }
+}
+
+void cpq_loudness_destroy(cpq_loudness* p) { delete p; }
+
+const char* cpq_loudness_last_error(const cpq_loudness* p) { return p ? p->lastError.c_str() : cpq_last_error(nullptr); }
+
+int32_t cpq_loudness_reset(cpq_loudness* p)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    return clearState(p);
+}
+
+int32_t cpq_loudness_set_stream(cpq_loudness* p, void* stream)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));       // what was enqueued has run before a call on the new stream touches the state
+    p->stream = (hipStream_t)stream;
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_process_device(cpq_loudness* p, const double* d_rows, int64_t row_stride, int32_t n_samples)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    cpq::ProgCall c;
+    CPQ_TRY(checkCall(p, d_rows, row_stride, n_samples, c));
+    return runDevice(p, d_rows, c);
+}
+
+int32_t cpq_loudness_process(cpq_loudness* p, const double* rows, int64_t row_stride, int32_t n_samples)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    cpq::ProgCall c;
+    CPQ_TRY(checkCall(p, rows, row_stride, n_samples, c));
+    const size_t nRows = 2 * (size_t)p->desc.n_streams;
+    if (n_samples > p->rowsCap) CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));       // no call in flight reads the buffer that goes
+    if (cpqi::grow(nullptr, p->rows, p->rowsCap, n_samples, nRows, "row buffer") != CPQ_OK)
+        return pfail(p, CPQ_ERR_OOM, "row buffer of %d samples could not be allocated", n_samples);
+    c.stride = p->rowsCap;
+    CPQ_PROG_HIP(p, hipMemcpy2DAsync(p->rows, (size_t)p->rowsCap * sizeof(double), rows, (size_t)row_stride * sizeof(double),
+                                     (size_t)n_samples * sizeof(double), nRows, hipMemcpyHostToDevice, p->stream));
+    CPQ_TRY(runDevice(p, p->rows, c));
+    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_finish(cpq_loudness* p, cpq_loudness_result* out)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    if (!out) return pfail(p, CPQ_ERR_INVALID_ARG, "null result");
+    try {
+        const int S = p->desc.n_streams;
+        cpq::ProgFinish f;
+        f.nHops = (int)(p->pos / p->H); f.H = p->H; f.maxHops = p->maxHops; f.zAbs = cpq::progAbsGate();
+        std::vector<cpq::ProgRecord> rec((size_t)S);
+        cpq::launch_prog_finish(p->stream, p->hops, f, S, p->rec);
+        CPQ_PROG_HIP(p, hipGetLastError());
+        CPQ_PROG_HIP(p, hipMemcpyAsync(rec.data(), p->rec, rec.size() * sizeof(cpq::ProgRecord), hipMemcpyDeviceToHost, p->stream));
+        CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+        for (int s = 0; s < S; ++s) out[s] = cpq::progResult(rec[(size_t)s], f.nHops);
+        return CPQ_OK;
+    } catch (const std::exception&) {
+        return pfail(p, CPQ_ERR_OOM, "host allocation failed");
+    }
+}
+
+int32_t cpq_loudness_read_hops(cpq_loudness* p, int32_t stream, double* out, int64_t capacity, int64_t* n)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    if (stream < 0 || stream >= p->desc.n_streams) return pfail(p, CPQ_ERR_INVALID_ARG, "stream %d outside 0..%d", stream, p->desc.n_streams - 1);
+    if (!n || capacity < 0 || (capacity > 0 && !out)) return pfail(p, CPQ_ERR_INVALID_ARG, "bad hop buffer");
+    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    const int64_t have = p->pos / p->H, cnt = std::min(have, capacity);
+    if (cnt > 0)
+        CPQ_PROG_HIP(p, hipMemcpy(out, p->hops.get() + (size_t)stream * (size_t)p->maxHops, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
+    *n = have;
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_finish_host(const double* hops, int64_t n_hops, double sample_rate, cpq_loudness_result* out)
+{
+    if (!out || n_hops < 0 || (n_hops > 0 && !hops)) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    cpq::ProgFinish f;
+    f.H = cpq::progHop(sample_rate);
+    if (!f.H) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
+    if (cpq::progShortCount(n_hops) > cpq::kProgSortMax) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "more than %d short-term blocks at the 1 s step", cpq::kProgSortMax);
+    f.nHops = (int)n_hops; f.maxHops = (int)n_hops; f.zAbs = cpq::progAbsGate();
+    try {
+        *out = cpq::progResult(cpq::progFinishHost(hops, f), n_hops);
+        return CPQ_OK;
+    } catch (const std::exception&) {
+        return pfail(nullptr, CPQ_ERR_OOM, "host allocation failed");
+    }
+}
+
+int32_t cpq_loudness_gain(const cpq_loudness_result* r, double target_lufs, double* gain)
+{
+    if (!r || !gain || !std::isfinite(target_lufs)) return CPQ_ERR_INVALID_ARG;
+    if (!std::isfinite(r->integrated)) return pfail(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
+    *gain = std::pow(10.0, (target_lufs - r->integrated) / 20.0);
+    return CPQ_OK;
+}
+
+}  // extern "C"

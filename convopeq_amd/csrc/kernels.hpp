@@ -8,6 +8,7 @@
 #include "host_design.hpp"
 #include "minphase_plan.hpp"
 #include "src_device_plan.hpp"
+#include "prog_plan.hpp"
 
 namespace cpq {
 
@@ -375,5 +376,12 @@ void launch_cfft_cols(hipStream_t stream, int op, double2* z, const double* x, d
 // scale multiplies what kRowsInv stores (1 / N when the row pass is the whole transform, log2n1 == 0)
 void launch_cfft_rows(hipStream_t stream, int op, double2* z, int* flags, MinphaseTables t, int log2n1, int log2n2, long long nRows,
                       double scale);
+
+// ---- programme loudness (prog_kernels.hip), the object cpq_loudness: the call prog_plan.hpp states in `c`, over rows [2 streams] of
+// c.stride doubles.  tab = the meters' two section tables; state [2 streams][8] and part [2 streams] (the partial hop sum of a
+// channel) are carried across calls; hops [streams][c.maxHops].  launch_prog_finish writes one ProgRecord per stream from the
+// first f.nHops hop sums.  Nothing here checks an index: `c` and `f` are engine_prog.cpp's, built from a planned and validated call.
+void launch_prog_hops(hipStream_t stream, const double* in, const ProgCall& c, const double* tab, double* state, double* part, double* hops);
+void launch_prog_finish(hipStream_t stream, const double* hops, const ProgFinish& f, int nStreams, ProgRecord* out);
 
 }  // namespace cpq

@@ -629,6 +629,71 @@ int32_t cpq_src_set_stream(cpq_src* s, void* stream);
  * -1 on a host object, for NULL, and before such a call.  cpq_src_process_device records no events. */
 double  cpq_src_last_kernel_ms(const cpq_src* s);
 
+/* ---------------------------------------------------------------- gated programme loudness (EBU R 128) per stream */
+/* cpq_loudness: integrated loudness (BS.1770-4 gating), loudness range (EBU Tech 3342), the momentary and short-term maxima of
+ * n_streams stereo programmes at once, computed on the device; an object of its own beside cpq_engine.  Rows are planar fp64,
+ * [2 n_streams] of them, L0 R0 L1 R1 ... as cpq_engine_process_block_device writes them, so that an engine's output rows are
+ * metered where they lie.  The K-weighting is cpq_meter_kweighting(sample_rate), the filter of the per-callback records
+ * (cpq_engine_set_metering), its state carried over calls; samples are scrubbed as the meters scrub them (not finite or
+ * |v| >= 1e300 reads as 0).  The K-weighted squares of both channels are added up on a grid of hops of sample_rate / 10
+ * samples that belongs to the stream, not to a call: calls may have any length and a hop may straddle them.  The definition,
+ * with the order of every sum and the rounding rule of the range's percentiles, is convopeq_amd/csrc/prog_plan.hpp's.
+ *
+ * sample_rate: a whole number of Hz in 8000 ... 768000 that is divisible by 10, else CPQ_ERR_UNSUPPORTED.  max_seconds: the
+ * longest programme (hops are kept for all of it: 80 bytes per stream and second); more than 8192 short-term blocks at the 1 s
+ * step (2 1/4 hours) is CPQ_ERR_UNSUPPORTED.  flags: 0.  CPQ_ERR_INVALID_ARG: a null argument, n_streams outside 1 ... 32767,
+ * max_seconds not positive and finite, flags not 0.  CPQ_ERR_NO_DEVICE without a gfx950 device: there is no host object.
+ * Everything the object keeps on the device is cleared before create returns.  The reason of a refusal is in
+ * cpq_loudness_last_error (with NULL: of a failed create). */
+#define CPQ_HAS_PROGRAMME_LOUDNESS 1
+typedef struct cpq_loudness cpq_loudness;
+typedef struct {
+    int32_t n_streams;
+    double  sample_rate;
+    double  max_seconds;
+    int32_t flags;
+} cpq_loudness_desc;
+/* Loudnesses in LUFS, range in LU.  An empty set gives -HUGE_VAL for its loudness and 0 for the range; the counts tell "silent"
+ * (n_blocks > 0, n_abs == 0) from "too short" (n_blocks == 0). */
+typedef struct {
+    double  integrated;             /* mean of the momentary blocks past both gates */
+    double  range;                  /* LRA */
+    double  momentary_max;          /* over every 400 ms block */
+    double  short_term_max;         /* over every 3 s block, at every hop */
+    double  relative_gate;          /* the gate of `integrated`: 10 LU below the mean of the blocks above -70 LUFS */
+    int64_t n_hops;                 /* complete hops so far */
+    int32_t n_blocks;               /* momentary blocks: n_hops - 3 */
+    int32_t n_abs;                  /* of those above -70 LUFS */
+    int32_t n_rel;                  /* of those also above the relative gate */
+    int32_t n_short_kept;           /* short-term blocks at the 1 s step past both gates of the range */
+} cpq_loudness_result;
+int32_t cpq_loudness_create(const cpq_loudness_desc* desc, cpq_loudness** out);
+void    cpq_loudness_destroy(cpq_loudness* p);
+const char* cpq_loudness_last_error(const cpq_loudness* p);
+/* the programmes start again: hop sums, partial hops and filter states cleared; the object's stream is synchronised */
+int32_t cpq_loudness_reset(cpq_loudness* p);
+/* the stream (a hipStream_t; NULL, the default, is the null stream) every later call enqueues on; the stream used so far is
+ * synchronised first */
+int32_t cpq_loudness_set_stream(cpq_loudness* p, void* stream);
+/* n_samples more samples of every programme from device rows d_rows[(2 s + channel) * row_stride + i].  Asynchronous: enqueued on
+ * the object's stream; the rows must stay as they are until the stream has reached the call.  Refused before any state moves, in
+ * this order: a null object (no message) or buffer, n_samples outside 1 ... 2^30, row_stride below n_samples, a buffer that is not
+ * 16-byte aligned (all CPQ_ERR_INVALID_ARG), a call that would pass max_seconds (CPQ_ERR_UNSUPPORTED: no part of it is taken). */
+int32_t cpq_loudness_process_device(cpq_loudness* p, const double* d_rows, int64_t row_stride, int32_t n_samples);
+/* the same from host rows, through a buffer the object owns; the object's stream is synchronised before the return */
+int32_t cpq_loudness_process(cpq_loudness* p, const double* rows, int64_t row_stride, int32_t n_samples);
+/* out[n_streams]: the figures of everything taken so far.  Synchronises the object's stream.  May be called at any time and
+ * repeatedly; the programmes go on. */
+int32_t cpq_loudness_finish(cpq_loudness* p, cpq_loudness_result* out);
+/* diagnostic and test hook: *n = the complete hops so far, out[0 ... min(*n, capacity)) = their sums E[h] of one stream.
+ * Synchronises the object's stream. */
+int32_t cpq_loudness_read_hops(cpq_loudness* p, int32_t stream, double* out, int64_t capacity, int64_t* n);
+/* host only: the same figures from hop sums on the host (hops[n_hops] of one stream), in the device's order of operations */
+int32_t cpq_loudness_finish_host(const double* hops, int64_t n_hops, double sample_rate, cpq_loudness_result* out);
+/* host only: the linear gain 10^((target_lufs - integrated) / 20) that brings the programme to target_lufs.  Applying it is the
+ * caller's.  CPQ_ERR_NOT_READY where nothing passed the gates (integrated is -HUGE_VAL); *gain is left alone. */
+int32_t cpq_loudness_gain(const cpq_loudness_result* r, double target_lufs, double* gain);
+
 /* ---------------------------------------------------------------- minimum-phase conversion on the device */
 /* cpq_ir_convert_to_minimum_phase for a whole IR library: convertToMinimumPhase (ResampleAndFallback.cpp:333-469) per row (a row
  * is one channel of one IR of n samples), rows of one FFT size N = nextPow2(4 n) batched into one sequence of launches:

@@ -499,4 +499,42 @@ private:
     int status_ = CPQ_OK;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// Gated programme loudness (EBU R 128) of nStreams stereo programmes on the device (cpq_loudness): rows L0 R0 L1 R1 ... as an
+// Engine delivers them, calls of any length, the figures readable at any time.
+class ProgrammeLoudness {
+public:
+    ProgrammeLoudness(int nStreams, double sampleRate, double maxSeconds)
+    {
+        const cpq_loudness_desc d{ nStreams, sampleRate, maxSeconds, 0 };
+        status_ = cpq_loudness_create(&d, &p_);
+    }
+    ~ProgrammeLoudness() { cpq_loudness_destroy(p_); }
+    ProgrammeLoudness(const ProgrammeLoudness&) = delete;
+    ProgrammeLoudness& operator=(const ProgrammeLoudness&) = delete;
+    bool valid() const noexcept { return p_ != nullptr; }
+    bool reset() { return (status_ = cpq_loudness_reset(p_)) == CPQ_OK; }
+    // a hipStream_t (nullptr: the null stream); the stream used so far is synchronised first
+    bool setStream(void* stream) { return (status_ = cpq_loudness_set_stream(p_, stream)) == CPQ_OK; }
+    // host rows [2 nStreams][rowStride], synchronous
+    bool process(const double* rows, int64_t rowStride, int numSamples) { return (status_ = cpq_loudness_process(p_, rows, rowStride, numSamples)) == CPQ_OK; }
+    // device rows, asynchronous on the object's stream
+    bool processDevice(const double* dRows, int64_t rowStride, int numSamples) { return (status_ = cpq_loudness_process_device(p_, dRows, rowStride, numSamples)) == CPQ_OK; }
+    // out[nStreams]; may be called repeatedly, the programmes go on
+    bool finish(cpq_loudness_result* out) { return (status_ = cpq_loudness_finish(p_, out)) == CPQ_OK; }
+    // the linear gain to targetLufs, or 0 where nothing passed the gates
+    static double gain(const cpq_loudness_result& r, double targetLufs)
+    {
+        double g = 0.0;
+        return cpq_loudness_gain(&r, targetLufs, &g) == CPQ_OK ? g : 0.0;
+    }
+    cpq_loudness* get() const noexcept { return p_; }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return cpq_loudness_last_error(p_); }
+
+private:
+    cpq_loudness* p_ = nullptr;
+    int status_ = CPQ_OK;
+};
+
 }  // namespace cpq
