@@ -159,6 +159,10 @@ class LoudnessResult(C.Structure):
                 ("n_rel", C.c_int32), ("n_short_kept", C.c_int32)]
 
 
+class LoudnessPeaks(C.Structure):
+    _fields_ = [("true_peak", C.c_double * 2), ("sample_peak", C.c_double * 2)]
+
+
 class OsStageInfo(C.Structure):
     _fields_ = [("taps", C.c_int32), ("center_tap", C.c_int32), ("center_parity", C.c_int32), ("conv_parity", C.c_int32),
                 ("conv_count", C.c_int32), ("center_delay_input", C.c_int32), ("history_up_keep", C.c_int32),
@@ -331,6 +335,12 @@ SYMBOLS = {
     "cpq_loudness_read_hops": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int64, _i64p]),
     "cpq_loudness_finish_host": (C.c_int32, [c_double_p, C.c_int64, C.c_double, C.POINTER(LoudnessResult)]),
     "cpq_loudness_gain": (C.c_int32, [C.POINTER(LoudnessResult), C.c_double, c_double_p]),
+    "cpq_loudness_set_true_peak": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "cpq_loudness_read_peaks": (C.c_int32, [C.c_void_p, C.POINTER(LoudnessPeaks)]),
+    "cpq_loudness_peaks_host": (C.c_int32, [c_double_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, c_double_p, c_double_p]),
+    "cpq_loudness_gain_limited": (C.c_int32, [C.POINTER(LoudnessResult), C.POINTER(LoudnessPeaks), C.c_double, C.c_double, c_double_p,
+                                              C.POINTER(C.c_int32)]),
+    "cpq_loudness_apply_device": (C.c_int32, [C.c_void_p, c_double_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
     "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
     "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
     "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),

@@ -3,7 +3,8 @@
 // copies, and holds no arithmetic of its own.  The rules are the device object of cpq_src's.  No device-side
 // tables of the call: what the kernels index with arrives by value.  Zeroed at create: hop sums, partial hops and filter states
 // are cleared synchronously before create returns.  One stream: everything is enqueued on the object's stream, and the position
-// advances only after the launch was enqueued without an error.
+// advances only after the launch was enqueued without an error.  With cpq_loudness_set_true_peak a call also enqueues k_prog_peak
+// behind k_prog_hops (the position advances after both); cpq_loudness_apply_device touches no programme state.
 #include "engine_internal.hpp"
 
 struct cpq_loudness {
@@ -16,6 +17,9 @@ struct cpq_loudness {
     cpqi::DeviceBuffer<cpq::ProgRecord> rec;                // [S]
     cpqi::DeviceBuffer<double> rows;                        // [2 S][rowsCap]: the host rows of cpq_loudness_process
     int rowsCap = 0;
+    cpqi::DeviceBuffer<double> pk;                          // [2 S][kPeakState]: true peak per programme, allocated by its switch
+    bool peakOn = false;
+    cpqi::DeviceBuffer<double> gains;                       // [S]: the gains of cpq_loudness_apply_device
 };
 
 namespace {
@@ -59,6 +63,12 @@ int runDevice(cpq_loudness* p, const double* dRows, const cpq::ProgCall& c)
 {
     cpq::launch_prog_hops(p->stream, dRows, c, p->tab, p->state, p->part, p->hops);
     CPQ_PROG_HIP(p, hipGetLastError());
+    if (p->peakOn) {
+        cpq::PeakCall k;
+        k.n = c.n; k.mask = cpq::progPeakMask(p->desc.sample_rate); k.rows = 2 * c.streams; k.stride = c.stride;
+        cpq::launch_prog_peak(p->stream, dRows, k, p->pk);
+        CPQ_PROG_HIP(p, hipGetLastError());
+    }
     p->pos += c.n;
     return CPQ_OK;
 }
@@ -68,6 +78,7 @@ int clearState(cpq_loudness* p)
     CPQ_PROG_HIP(p, hipMemsetAsync(p->state, 0, p->state.count() * sizeof(double), p->stream));
     CPQ_PROG_HIP(p, hipMemsetAsync(p->part, 0, p->part.count() * sizeof(double), p->stream));
     CPQ_PROG_HIP(p, hipMemsetAsync(p->hops, 0, p->hops.count() * sizeof(double), p->stream));
+    if (p->pk) CPQ_PROG_HIP(p, hipMemsetAsync(p->pk, 0, p->pk.count() * sizeof(double), p->stream));
     CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
     p->pos = 0;
     return CPQ_OK;
@@ -77,7 +88,7 @@ int createDevice(cpq_loudness* p)
 {
     const size_t S = (size_t)p->desc.n_streams;
     CPQ_TRY(cpqi::allocAll(nullptr, { { p->tab, kTabDoubles }, { p->state, 16 * S, true }, { p->part, 2 * S, true },
-                                      { p->hops, S * (size_t)p->maxHops, true }, { p->rec, S } },
+                                      { p->hops, S * (size_t)p->maxHops, true }, { p->rec, S }, { p->gains, S } },
                            "hop sums of %d streams and %d hops could not be allocated", p->desc.n_streams, p->maxHops));
     std::vector<double> tab(kTabDoubles, 0.0);
     double pre[5], rlb[5];
@@ -217,6 +228,106 @@ int32_t cpq_loudness_gain(const cpq_loudness_result* r, double target_lufs, doub
     if (!r || !gain || !std::isfinite(target_lufs)) return CPQ_ERR_INVALID_ARG;
     if (!std::isfinite(r->integrated)) return pfail(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
     *gain = std::pow(10.0, (target_lufs - r->integrated) / 20.0);
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_set_true_peak(cpq_loudness* p, int32_t on)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    if (on != 0 && on != 1) return pfail(p, CPQ_ERR_INVALID_ARG, "on must be 0 or 1");
+    if (p->pos) return pfail(p, CPQ_ERR_NOT_READY, "true peak is switched at the start of a programme: %lld samples were taken; reset first", p->pos);
+    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    if (!on) {
+        p->peakOn = false;
+        p->pk.reset();
+        return CPQ_OK;
+    }
+    if (!p->pk) {
+        const int rc = cpqi::allocAll(nullptr, { { p->pk, 2 * (size_t)p->desc.n_streams * cpq::kPeakState, true } }, "peak state");
+        if (rc != CPQ_OK) return pfail(p, rc, "the peak state of %d streams could not be allocated", p->desc.n_streams);
+    } else {
+        CPQ_PROG_HIP(p, hipMemset(p->pk, 0, p->pk.count() * sizeof(double)));
+    }
+    CPQ_PROG_HIP(p, hipDeviceSynchronize());        // cleared before the first call, whatever its stream
+    p->peakOn = true;
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_read_peaks(cpq_loudness* p, cpq_loudness_peaks* out)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    if (!out) return pfail(p, CPQ_ERR_INVALID_ARG, "null result");
+    if (!p->peakOn) return pfail(p, CPQ_ERR_NOT_READY, "true peak is not switched on (cpq_loudness_set_true_peak)");
+    try {
+        const int S = p->desc.n_streams;
+        std::vector<double> st(p->pk.count());
+        CPQ_PROG_HIP(p, hipMemcpyAsync(st.data(), p->pk, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+        for (int s = 0; s < S; ++s)
+            for (int ch = 0; ch < 2; ++ch) {
+                const double* r = st.data() + (size_t)(2 * s + ch) * cpq::kPeakState;
+                out[s].true_peak[ch] = r[cpq::kPeakTp];
+                out[s].sample_peak[ch] = r[cpq::kPeakSp];
+            }
+        return CPQ_OK;
+    } catch (const std::exception&) {
+        return pfail(p, CPQ_ERR_OOM, "host allocation failed");
+    }
+}
+
+int32_t cpq_loudness_peaks_host(const double* rows, int64_t row_stride, int32_t n_rows, int64_t n_samples, double sample_rate,
+                                double* true_peak, double* sample_peak)
+{
+    if (!rows || !true_peak || !sample_peak) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    if (n_rows < 1 || n_samples < 0 || row_stride < n_samples) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "bad rows");
+    if (!cpq::progHop(sample_rate)) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
+    const int mask = cpq::progPeakMask(sample_rate);
+    for (int32_t r = 0; r < n_rows; ++r) {
+        double st[cpq::kPeakState] = {};
+        cpq::progPeakRowHost(rows + (size_t)r * (size_t)row_stride, n_samples, mask, st);
+        true_peak[r] = st[cpq::kPeakTp];
+        sample_peak[r] = st[cpq::kPeakSp];
+    }
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_gain_limited(const cpq_loudness_result* r, const cpq_loudness_peaks* pk, double target_lufs, double max_true_peak_dbtp,
+                                  double* gain, int32_t* limited)
+{
+    if (!r || !pk || !gain || !limited || !std::isfinite(target_lufs) || !std::isfinite(max_true_peak_dbtp)) return CPQ_ERR_INVALID_ARG;
+    double peak = 0.0;
+    for (double v : { pk->true_peak[0], pk->true_peak[1], pk->sample_peak[0], pk->sample_peak[1] }) {
+        if (!std::isfinite(v) || v < 0.0) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "a peak is not a finite linear value >= 0");
+        peak = v > peak ? v : peak;
+    }
+    if (!std::isfinite(r->integrated)) return pfail(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
+    bool lim = false;
+    *gain = cpq::progGainLimited(r->integrated, peak, target_lufs, max_true_peak_dbtp, lim);
+    *limited = lim ? 1 : 0;
+    return CPQ_OK;
+}
+
+int32_t cpq_loudness_apply_device(cpq_loudness* p, const double* gains, const double* d_in, int64_t in_stride, double* d_out, int64_t out_stride,
+                                  int32_t n_samples)
+{
+    if (!p) return CPQ_ERR_INVALID_ARG;
+    if (!gains || !d_in || !d_out) return pfail(p, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (n_samples < 1 || n_samples > cpq::kProgMaxCall) return pfail(p, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n_samples, cpq::kProgMaxCall);
+    if (in_stride < n_samples || out_stride < n_samples)
+        return pfail(p, CPQ_ERR_INVALID_ARG, "row strides %lld and %lld, rows of %d", (long long)in_stride, (long long)out_stride, n_samples);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    if ((a | b) & 15u) return pfail(p, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    const int S = p->desc.n_streams;
+    for (int s = 0; s < S; ++s)
+        if (!std::isfinite(gains[s])) return pfail(p, CPQ_ERR_INVALID_ARG, "the gain of stream %d is not finite", s);
+    if (cpq::progApplyOverlap(a / 8, in_stride, b / 8, out_stride, 2 * S, n_samples))
+        return pfail(p, CPQ_ERR_INVALID_ARG, "input and output rows overlap in part: in place takes the same pointer and stride");
+    cpq::ApplyCall c;
+    c.n = n_samples; c.rows = 2 * S; c.inStride = in_stride; c.outStride = out_stride;
+    c.wide = in_stride % 2 == 0 && out_stride % 2 == 0;
+    CPQ_PROG_HIP(p, hipMemcpyAsync(p->gains, gains, (size_t)S * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    cpq::launch_prog_apply(p->stream, d_in, c, p->gains, d_out);
+    CPQ_PROG_HIP(p, hipGetLastError());
     return CPQ_OK;
 }
 

@@ -383,5 +383,9 @@ void launch_cfft_rows(hipStream_t stream, int op, double2* z, int* flags, Minpha
 // first f.nHops hop sums.  Nothing here checks an index: `c` and `f` are engine_prog.cpp's, built from a planned and validated call.
 void launch_prog_hops(hipStream_t stream, const double* in, const ProgCall& c, const double* tab, double* state, double* part, double* hops);
 void launch_prog_finish(hipStream_t stream, const double* hops, const ProgFinish& f, int nStreams, ProgRecord* out);
+// true peak per programme: c.rows rows of c.n samples; pk [c.rows][kPeakState] (history and the two running maxima) is read and
+// written.  launch_prog_apply: out = in * gain[row / 2] over c.rows rows, gain [c.rows / 2] on the device; in may be out.
+void launch_prog_peak(hipStream_t stream, const double* in, const PeakCall& c, double* pk);
+void launch_prog_apply(hipStream_t stream, const double* in, const ApplyCall& c, const double* gain, double* out);
 
 }  // namespace cpq

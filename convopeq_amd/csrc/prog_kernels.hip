@@ -2,6 +2,8 @@
 // call are prog_plan.hpp's.
 //   k_prog_hops    K-weights a call's rows and adds them up on the stream's 100 ms hop grid: hops[stream][h]
 //   k_prog_finish  gating, means, maxima and the sort for the loudness range over a stream's hop sums: one ProgRecord per stream
+//   k_prog_peak    true peak (BS.1770-4 Annex 2) and sample peak per row, carried over calls; described where it stands
+//   k_prog_apply   out = in * gain[stream]
 //
 // k_prog_hops.  A workgroup is a stream: waves 0-3 take its left row, waves 4-7 its right row, both through the time-parallel
 // K-weighting of k_meter_kweight (meter_kernels.hip: the (y, d) scan over spans of 2048 samples, 8 per lane, with the host's
@@ -216,7 +218,91 @@ k_prog_finish(const double* __restrict__ hops, ProgFinish f, ProgRecord* __restr
     }
 }
 
+// k_prog_peak.  A workgroup of kPeakThreads lanes is a row.  It walks the row in tiles of kPeakTile samples, scrubbed into LDS
+// behind a halo of kPeakHist samples: the row's history in the call's first tile, the previous tile's tail afterwards.  A lane holds
+// kPeakPer outputs and their kPeakWindow inputs in registers (progPeakLane), all phases of c.mask.  The lane maxima meet in a wave
+// butterfly and then in LDS; lane 0 folds them into the row's running maxima, lanes 0 ... 10 write the new history, which is the
+// last tile's buffer at [len, len + 11): [old history | call] where the call is shorter than the history.  One writer per row.
+__global__ void __launch_bounds__(kPeakThreads)
+k_prog_peak(const double* __restrict__ in, PeakCall c, double* __restrict__ pk)
+{
+    __shared__ double buf[kPeakBufDoubles];
+    __shared__ double shMax[kPeakThreads / 64][2];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const double* x = in + (long long)row * c.stride;
+    double* st = pk + (long long)row * kPeakState;
+    if (t < kPeakHist) buf[progPeakPad(t)] = st[t];
+    double tp = 0.0, sp = 0.0;
+    int len = 0;
+    for (int s0 = 0; s0 < c.n; s0 += kPeakTile) {
+        len = progPeakTileLen(c, s0);
+        __syncthreads();                            // the halo is written, the tile before it has been read
+        for (int i = t; i < kPeakTile; i += kPeakThreads) buf[progPeakPad(kPeakHist + i)] = i < len ? progPeakScrub(x[s0 + i]) : 0.0;
+        __syncthreads();
+        double w[kPeakWindow];
+#pragma unroll
+        for (int m = 0; m < kPeakWindow; ++m) w[m] = buf[progPeakPad(kPeakPer * t + m)];
+        progPeakLane(w, len - kPeakPer * t, c.mask, tp, sp);
+        if (s0 + kPeakTile < c.n) {                 // a full tile with another behind it: its tail is that one's halo
+            const double h = t < kPeakHist ? buf[progPeakPad(kPeakTile + t)] : 0.0;
+            __syncthreads();                        // every window has been read
+            if (t < kPeakHist) buf[progPeakPad(t)] = h;
+        }
+    }
+    if (!c.mask) tp = sp;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double a = __shfl_xor(tp, d), b = __shfl_xor(sp, d);
+        tp = a > tp ? a : tp;
+        sp = b > sp ? b : sp;
+    }
+    if ((t & 63) == 0) { shMax[t >> 6][0] = tp; shMax[t >> 6][1] = sp; }
+    __syncthreads();
+    if (t < kPeakHist) st[t] = buf[progPeakPad(len + t)];
+    if (t == 0) {
+        double a = st[kPeakTp], b = st[kPeakSp];
+        for (int wv = 0; wv < kPeakThreads / 64; ++wv) {
+            a = shMax[wv][0] > a ? shMax[wv][0] : a;
+            b = shMax[wv][1] > b ? shMax[wv][1] : b;
+        }
+        st[kPeakTp] = a;
+        st[kPeakSp] = b;
+    }
+}
+
+// out = in * gain[row / 2]: one rounding, nothing scrubbed.  in and out may be the same rows, so neither is __restrict__: every
+// element is read and written by the same lane.  c.wide: two samples per access, the odd last one alone
+__global__ void __launch_bounds__(kApplyThreads)
+k_prog_apply(const double* in, ApplyCall c, const double* __restrict__ gain, double* out)
+{
+    const int row = blockIdx.y;
+    const double g = gain[row >> 1];
+    const double* x = in + (long long)row * c.inStride;
+    double* y = out + (long long)row * c.outStride;
+    const int step = gridDim.x * kApplyThreads, first = blockIdx.x * kApplyThreads + threadIdx.x;
+    if (c.wide) {
+        const int pairs = c.n >> 1;
+        for (int i = first; i < pairs; i += step) {
+            const double2 v = reinterpret_cast<const double2*>(x)[i];
+            reinterpret_cast<double2*>(y)[i] = double2{ v.x * g, v.y * g };
+        }
+        if ((c.n & 1) && first == 0) y[c.n - 1] = x[c.n - 1] * g;
+    } else {
+        for (int i = first; i < c.n; i += step) y[i] = x[i] * g;
+    }
+}
+
 }  // namespace
+
+void launch_prog_peak(hipStream_t stream, const double* in, const PeakCall& c, double* pk)
+{
+    hipLaunchKernelGGL(k_prog_peak, dim3(c.rows), dim3(kPeakThreads), 0, stream, in, c, pk);
+}
+
+void launch_prog_apply(hipStream_t stream, const double* in, const ApplyCall& c, const double* gain, double* out)
+{
+    hipLaunchKernelGGL(k_prog_apply, dim3(progApplyBlocks(c), c.rows), dim3(kApplyThreads), 0, stream, in, c, gain, out);
+}
 
 void launch_prog_hops(hipStream_t stream, const double* in, const ProgCall& c, const double* tab, double* state, double* part, double* hops)
 {

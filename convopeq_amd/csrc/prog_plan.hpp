@@ -1,7 +1,9 @@
 // prog_plan.hpp -- the definition of cpq_loudness (gated programme loudness, EBU R 128) and every piece of integer arithmetic of
 // its calls, stated once for the kernels (prog_kernels.hip: k_prog_hops, k_prog_finish), for engine_prog.cpp, which plans a call
 // on the host and passes the plan by value, and for tests/sanitize/prog_plan_check.cpp, which restates both kernels as host loops
-// over grid, waves and lanes on exactly sized heap blocks.  No HIP include: what both sides call is CPQ_HD.
+// over grid, waves and lanes on exactly sized heap blocks.  No HIP include: what both sides call is CPQ_HD.  The true peak per
+// programme, the gain under a ceiling and its application (k_prog_peak, k_prog_apply; tests/sanitize/prog_peak_check.cpp) are
+// defined at the end of the file.
 //
 // Definition.  A stream is a stereo pair of rows.  Every sample is scrubbed as the meters scrub it (not finite or |v| >= 1e300
 // reads as 0) and K-weighted with cpq_meter_kweighting(rate): two Direct-Form-I biquads per channel, state carried over calls.
@@ -224,6 +226,125 @@ inline ProgRecord progFinishHost(const double* E, const ProgFinish& f)
     r.zHi = kept ? v[progPick95(kept)] : 0.0;
     delete[] v;
     return r;
+}
+
+// ------------------------------------------------------------------------------------------------- true peak per programme
+// ITU-R BS.1770-4 Annex 2: the 48-tap, 4-phase interpolator, every coefficient an integer over 8192 (exact in binary).  Phases 2
+// and 3 are phases 1 and 0 reversed.  Per channel, for sample i of the programme (counted from create / reset) and phase p:
+//     y = c[p][0] x[i];  y = y + c[p][k] x[i - k]  for k = 1 ... 11 in that order, the multiply and the add rounding separately
+// with x scrubbed as above and x[j] = 0 for j < 0.  true_peak = max |y| over i and the phases in use, sample_peak = max |x|: both
+// linear.  A maximum does not depend on order, so the result is defined to the bit.  Phases by rate: all four below 88200 Hz;
+// 0 and 2 (the same low-pass at offsets 0 and 1 / 2) from 88200 Hz to below 176400 Hz; none from 176400 Hz, where true_peak is
+// sample_peak.  State per channel (kPeakState doubles): the last 11 scrubbed samples, oldest first, then the two maxima.
+constexpr int kPeakTaps = 12;
+constexpr int kPeakHist = kPeakTaps - 1;
+constexpr int kPeakThreads = 512;                   // a workgroup is a row
+constexpr int kPeakPer = 8;                         // outputs a lane holds
+constexpr int kPeakTile = kPeakThreads * kPeakPer;  // samples of a row staged in LDS at a time, behind a halo of kPeakHist
+constexpr int kPeakWindow = kPeakPer + kPeakHist;   // inputs of a lane's outputs
+constexpr int kPeakState = 16;                      // doubles per row: [0, 11) history, [11] true peak, [12] sample peak
+constexpr int kPeakTp = kPeakHist, kPeakSp = kPeakHist + 1;
+CPQ_HD inline int progPeakPad(int j) { return j + (j >> 3); }       // a lane's window begins 9 doubles behind its neighbour's
+constexpr int kPeakBufDoubles = kPeakHist + kPeakTile + (kPeakHist + kPeakTile - 1) / 8;
+
+CPQ_HD inline double progPeakCoef(int p, int k)
+{
+    constexpr double c[2][kPeakTaps] = {
+        { 14.0 / 8192.0, 90.0 / 8192.0, -161.0 / 8192.0, 272.0 / 8192.0, -487.0 / 8192.0, 1125.0 / 8192.0,
+          7964.0 / 8192.0, -838.0 / 8192.0, 390.0 / 8192.0, -218.0 / 8192.0, 122.0 / 8192.0, -68.0 / 8192.0 },
+        { -239.0 / 8192.0, 240.0 / 8192.0, -424.0 / 8192.0, 730.0 / 8192.0, -1364.0 / 8192.0, 3810.0 / 8192.0,
+          6388.0 / 8192.0, -1641.0 / 8192.0, 832.0 / 8192.0, -477.0 / 8192.0, 271.0 / 8192.0, -155.0 / 8192.0 } };
+    return p < 2 ? c[p][k] : c[3 - p][kPeakTaps - 1 - k];
+}
+// bit p: phase p is in use
+inline int progPeakMask(double rate) { return rate < 88200.0 ? 0xF : rate < 176400.0 ? 0x5 : 0; }
+CPQ_HD inline double progPeakScrub(double v) { return std::fabs(v) < 1.0e300 ? v : 0.0; }
+// |y| of phase p at the sample whose scrubbed value is w[0], w[-1 ... -11] the samples before it
+CPQ_HD inline double progPeakAt(const double* w, int p)
+{
+    double y = progPeakCoef(p, 0) * w[0];
+#pragma GCC unroll 12
+    for (int k = 1; k < kPeakTaps; ++k) y = y + progPeakCoef(p, k) * w[-k];
+    return std::fabs(y);
+}
+
+struct PeakCall {
+    int n = 0;              // samples per row
+    int mask = 0;           // phases in use
+    int rows = 0;           // the grid
+    long long stride = 0;   // doubles between rows
+};
+CPQ_HD inline int progPeakTileLen(const PeakCall& c, int s0) { return c.n - s0 < kPeakTile ? c.n - s0 : kPeakTile; }
+// a lane's share of a tile: w[m] = the tile's buffer at 8 lane + m (the halo in front: output o reads w[o ... o + 11]); the first
+// `valid` of its outputs are samples of the call.  tp and sp: the lane's maxima, carried over tiles
+CPQ_HD inline void progPeakLane(const double w[kPeakWindow], int valid, int mask, double& tp, double& sp)
+{
+#pragma GCC unroll 8
+    for (int o = 0; o < kPeakPer; ++o)
+        if (o < valid) { const double a = std::fabs(w[kPeakHist + o]); sp = a > sp ? a : sp; }
+#pragma GCC unroll 4
+    for (int p = 0; p < 4; ++p) {
+        if (!((mask >> p) & 1)) continue;
+#pragma GCC unroll 8
+        for (int o = 0; o < kPeakPer; ++o) {
+            const double a = progPeakAt(w + kPeakHist + o, p);
+            if (o < valid) tp = a > tp ? a : tp;
+        }
+    }
+}
+// one row of one call in a sequential pass: st is the row's kPeakState doubles
+inline void progPeakRowHost(const double* x, long long n, int mask, double* st)
+{
+    double w[kPeakTaps];                            // w[11] the current sample, w[0 ... 10] the history
+    for (int j = 0; j < kPeakHist; ++j) w[j] = st[j];
+    double tp = 0.0, sp = 0.0;
+    for (long long i = 0; i < n; ++i) {
+        w[kPeakHist] = progPeakScrub(x[i]);
+        const double a = std::fabs(w[kPeakHist]);
+        sp = a > sp ? a : sp;
+        for (int p = 0; p < 4; ++p)
+            if ((mask >> p) & 1) { const double y = progPeakAt(w + kPeakHist, p); tp = y > tp ? y : tp; }
+        for (int j = 0; j < kPeakHist; ++j) w[j] = w[j + 1];
+    }
+    if (!mask) tp = sp;
+    for (int j = 0; j < kPeakHist; ++j) st[j] = w[j];
+    st[kPeakTp] = tp > st[kPeakTp] ? tp : st[kPeakTp];
+    st[kPeakSp] = sp > st[kPeakSp] ? sp : st[kPeakSp];
+}
+
+// gain under a ceiling: the loudness gain of cpq_loudness_gain, or what brings the largest of the four peaks to maxDbtp, whichever
+// is smaller; peak == 0 sets no limit
+inline double progGainLimited(double integrated, double peak, double targetLufs, double maxDbtp, bool& limited)
+{
+    const double gLoud = std::pow(10.0, (targetLufs - integrated) / 20.0);
+    limited = false;
+    if (!(peak > 0.0)) return gLoud;
+    const double gPeak = std::pow(10.0, maxDbtp / 20.0) / peak;
+    limited = gPeak < gLoud;
+    return limited ? gPeak : gLoud;
+}
+
+// ------------------------------------------------------------------------------------------------------- applying a gain
+struct ApplyCall {
+    int n = 0;              // samples per row
+    int rows = 0;
+    int wide = 0;           // both strides even (and both buffers 16-byte aligned): rows are moved two samples at a time
+    long long inStride = 0, outStride = 0;
+};
+constexpr int kApplyThreads = 256;
+constexpr int kApplyMaxBlocks = 1024;               // per row: the lanes stride over what is left
+// rows [rows][n] at stride s from a and from b (addresses in doubles): they overlap in part unless they are the same rows
+inline bool progApplyOverlap(unsigned long long a, long long sa, unsigned long long b, long long sb, int rows, int n)
+{
+    if (a == b && sa == sb) return false;
+    const unsigned long long ea = a + (unsigned long long)(rows - 1) * (unsigned long long)sa + (unsigned long long)n;
+    const unsigned long long eb = b + (unsigned long long)(rows - 1) * (unsigned long long)sb + (unsigned long long)n;
+    return a < eb && b < ea;
+}
+CPQ_HD inline int progApplyBlocks(const ApplyCall& c)
+{
+    const int units = c.wide ? (c.n + 1) / 2 : c.n, b = (units + kApplyThreads - 1) / kApplyThreads;
+    return b < kApplyMaxBlocks ? b : kApplyMaxBlocks;
 }
 
 }  // namespace cpq

@@ -694,6 +694,40 @@ int32_t cpq_loudness_finish_host(const double* hops, int64_t n_hops, double samp
  * caller's.  CPQ_ERR_NOT_READY where nothing passed the gates (integrated is -HUGE_VAL); *gain is left alone. */
 int32_t cpq_loudness_gain(const cpq_loudness_result* r, double target_lufs, double* gain);
 
+/* True peak per programme (ITU-R BS.1770-4 Annex 2: the 48-tap, 4-phase interpolator) and normalisation under a ceiling: the
+ * second number of a delivery specification (-23 LUFS and -1 dBTP for R 128).  Per channel, over the whole programme since create
+ * or reset, on the scrubbed samples: true_peak = max |y| over every sample and the phases in use, sample_peak = max |x|, both
+ * linear.  All four phases below 88200 Hz; phases 0 and 2 from 88200 Hz to below 176400 Hz; from 176400 Hz true_peak is
+ * sample_peak.  The table, the order of the 12-term sum and the state carried over calls (the last 11 samples) are
+ * convopeq_amd/csrc/prog_plan.hpp's; the result is defined to the bit.  This is not the engine's per-callback detector
+ * (cpq_engine_set_metering: the reference's, and not a standard one). */
+#define CPQ_HAS_PROGRAMME_TRUE_PEAK 1
+typedef struct { double true_peak[2]; double sample_peak[2]; } cpq_loudness_peaks;   /* linear; L, R */
+/* on: 1 or 0.  Accepted only at the start of a programme (after create or reset, before a sample was taken), else
+ * CPQ_ERR_NOT_READY.  Switching on allocates and clears the peak state synchronously, all or nothing (CPQ_ERR_OOM); from then on
+ * cpq_loudness_process and cpq_loudness_process_device also take the peaks of what they are given, and cpq_loudness_reset clears
+ * them.  The hop sums do not depend on the switch. */
+int32_t cpq_loudness_set_true_peak(cpq_loudness* p, int32_t on);
+/* out[n_streams]: the peaks of everything taken so far.  Synchronises the object's stream.  CPQ_ERR_NOT_READY without the switch. */
+int32_t cpq_loudness_read_peaks(cpq_loudness* p, cpq_loudness_peaks* out);
+/* host only: the same two figures of n_rows rows of n_samples samples at rows[r * row_stride + i], each row a programme from its
+ * start; true_peak[n_rows], sample_peak[n_rows].  The rate rule is create's. */
+int32_t cpq_loudness_peaks_host(const double* rows, int64_t row_stride, int32_t n_rows, int64_t n_samples, double sample_rate,
+                                double* true_peak, double* sample_peak);
+/* host only: *gain = min(g_loud, g_peak), *limited = 1 where the ceiling won.  g_loud is cpq_loudness_gain's; g_peak =
+ * 10^(max_true_peak_dbtp / 20) / peak with peak the largest of the stream's four values (the sample peaks included: at fs / 4 a
+ * phase of the interpolator reads below the samples); peak == 0 sets no limit.  CPQ_ERR_INVALID_ARG: a null or non-finite
+ * argument, a peak that is negative or not finite.  CPQ_ERR_NOT_READY where nothing passed the gates; *gain is left alone. */
+int32_t cpq_loudness_gain_limited(const cpq_loudness_result* r, const cpq_loudness_peaks* pk, double target_lufs,
+                                  double max_true_peak_dbtp, double* gain, int32_t* limited);
+/* d_out[(2 s + channel) * out_stride + i] = d_in[(2 s + channel) * in_stride + i] * gains[s]: one rounding, nothing scrubbed.
+ * gains[n_streams] on the host, uploaded into a buffer of the object on its stream by the call.  Works on any object, does not
+ * touch the programme, asynchronous on the object's stream.  In place with d_out == d_in and equal strides.  Refused before
+ * anything moves, all CPQ_ERR_INVALID_ARG: a null object (no message) or buffer, n_samples outside 1 ... 2^30, a stride below
+ * n_samples, a device buffer that is not 16-byte aligned, a gain that is not finite, rows of d_in and d_out that overlap in part. */
+int32_t cpq_loudness_apply_device(cpq_loudness* p, const double* gains, const double* d_in, int64_t in_stride, double* d_out,
+                                  int64_t out_stride, int32_t n_samples);
+
 /* ---------------------------------------------------------------- minimum-phase conversion on the device */
 /* cpq_ir_convert_to_minimum_phase for a whole IR library: convertToMinimumPhase (ResampleAndFallback.cpp:333-469) per row (a row
  * is one channel of one IR of n samples), rows of one FFT size N = nextPow2(4 n) batched into one sequence of launches:

@@ -528,6 +528,24 @@ public:
         double g = 0.0;
         return cpq_loudness_gain(&r, targetLufs, &g) == CPQ_OK ? g : 0.0;
     }
+    // true peak per programme (BS.1770-4 Annex 2): switched at the start of a programme only; out[nStreams], linear
+    bool setTruePeak(bool on) { return (status_ = cpq_loudness_set_true_peak(p_, on ? 1 : 0)) == CPQ_OK; }
+    bool readPeaks(cpq_loudness_peaks* out) { return (status_ = cpq_loudness_read_peaks(p_, out)) == CPQ_OK; }
+    // the smaller of the gain to targetLufs and the gain that brings the largest peak to maxDbtp (limited: the ceiling won), or 0
+    // where nothing passed the gates
+    static double gainLimited(const cpq_loudness_result& r, const cpq_loudness_peaks& pk, double targetLufs, double maxDbtp, bool* limited = nullptr)
+    {
+        double g = 0.0;
+        int32_t lim = 0;
+        if (cpq_loudness_gain_limited(&r, &pk, targetLufs, maxDbtp, &g, &lim) != CPQ_OK) return 0.0;
+        if (limited) *limited = lim != 0;
+        return g;
+    }
+    // dOut = dIn * gains[stream] on device rows, asynchronous on the object's stream; in place with the same pointer and stride
+    bool applyDevice(const double* gains, const double* dIn, int64_t inStride, double* dOut, int64_t outStride, int numSamples)
+    {
+        return (status_ = cpq_loudness_apply_device(p_, gains, dIn, inStride, dOut, outStride, numSamples)) == CPQ_OK;
+    }
     cpq_loudness* get() const noexcept { return p_; }
     int lastStatus() const noexcept { return status_; }
     const char* lastError() const noexcept { return cpq_loudness_last_error(p_); }
