@@ -67,6 +67,12 @@ CPQ_SCORE_RECENT = 4096 + 2048 * 15
 CPQ_SCORE_BINS = 2049
 CPQ_SCORE_MAX_CANDIDATES = 1024
 CPQ_SCORE_UNSTABLE = 1e18
+CPQ_LEARN_DIM = 9
+CPQ_LEARN_POPULATION = 18
+CPQ_LEARN_ELITE = 6
+CPQ_LEARN_MAX_GENERATIONS = 4096
+CPQ_LEARN_MAX_TRIES = 32
+CPQ_LEARN_SHORTEST, CPQ_LEARN_SHORT, CPQ_LEARN_MIDDLE, CPQ_LEARN_LONG, CPQ_LEARN_ULTRA, CPQ_LEARN_CONTINUOUS = range(6)
 CPQ_SEGMENT_BROADBAND = 0
 CPQ_SEGMENT_TONAL = 1
 CPQ_SEGMENT_TRANSIENT = 2
@@ -200,6 +206,17 @@ class DiagScoreEval(C.Structure):
 
 class DiagScoreChain(C.Structure):
     _fields_ = [("src", C.c_int32), ("dst", C.c_int32), ("coef", C.c_int32), ("rng", C.c_int32)]
+
+
+class LearnParams(C.Structure):
+    _fields_ = [("sigma_min", C.c_double), ("sigma_max", C.c_double), ("cov_retention_target", C.c_double),
+                ("cov_retention_step", C.c_double), ("level_weights", C.c_double * 4)]
+
+
+class LearnState(C.Structure):
+    _fields_ = [("mean", C.c_double * 9), ("cov_upper", C.c_double * 45), ("sigma", C.c_double), ("cov_retention", C.c_double),
+                ("rng", C.c_uint64 * 4), ("best_score", C.c_double), ("best_raw", C.c_double * 9), ("best_scored", C.c_double * 9),
+                ("generations", C.c_int32), ("rejected_pairs", C.c_int32)]
 
 
 class EngineDesc(C.Structure):
@@ -396,6 +413,25 @@ SYMBOLS = {
     "cpq_diag_score_lattice": (C.c_int32, [C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.POINTER(DiagScoreChain),
                                            C.c_int32, c_double_p, C.c_int32, C.POINTER(C.c_uint64)]),
     "cpq_diag_score_reduce": (C.c_int32, [C.c_int32, C.c_int32, _i32p, _i32p, c_double_p, c_double_p, c_double_p]),
+    "cpq_learner_create": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cpq_learner_destroy": (None, [C.c_void_p]),
+    "cpq_learner_last_error": (C.c_char_p, [C.c_void_p]),
+    "cpq_learner_init": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_uint64]),
+    "cpq_learner_set_params": (C.c_int32, [C.c_void_p, C.POINTER(LearnParams)]),
+    "cpq_learner_run": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "cpq_learner_get_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(LearnState)]),
+    "cpq_learner_set_state": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(LearnState)]),
+    "cpq_learner_read_generation": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, _i32p]),
+    "cpq_learner_read_history": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, _i32p]),
+    "cpq_learner_published": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p]),
+    "cpq_learner_last_timing": (C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
+    "cpq_learn_init_host": (C.c_int32, [c_double_p, C.c_uint64, C.POINTER(LearnParams), C.POINTER(LearnState)]),
+    "cpq_learn_normals_host": (C.c_int32, [C.POINTER(LearnState), c_double_p, _i32p]),
+    "cpq_learn_ask_host": (C.c_int32, [C.POINTER(LearnState), c_double_p, c_double_p]),
+    "cpq_learn_tell_host": (C.c_int32, [C.POINTER(LearnState), C.POINTER(LearnParams), c_double_p, c_double_p, c_double_p, _i32p]),
+    "cpq_learn_phase": (C.c_int32, [C.c_int32, C.c_double]),
+    "cpq_learn_phase_params": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(LearnParams), c_double_p]),
+    "cpq_diag_learn_tell": (C.c_int32, [C.c_int32, C.POINTER(LearnState), C.POINTER(LearnParams), c_double_p, c_double_p, c_double_p]),
 }
 
 _lib = None

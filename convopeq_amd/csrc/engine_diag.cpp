@@ -3,6 +3,7 @@
 //   FFT launch variants, IR spectra  cpq_diag_fft_forward, _fft_inverse_store, _ir_spectra                tests/test_gpu_fft_variants.py
 //   mix_kernels.hip                  cpq_diag_direct_head, _agc, _ring_chunks, _convproc_mix, _tail_reader, _rows    test_gpu_mix_kernels.py
 //   score_kernels.hip                cpq_diag_score_spectrum, _score_lattice, _score_reduce                 tests/test_gpu_score_kernels.py
+//   learn_kernels.hip                cpq_diag_learn_tell                                                    tests/test_gpu_learn_kernels.py
 //   chained EQ spans of an engine    cpq_diag_eq_chain_status                                             tests/test_gpu_eq_chained.py
 // One convention for all but the last: host pointers, own device buffers of exactly the documented sizes (Scope), the null
 // stream, no engine; what a kernel may write is filled with 0xFF bytes (NaN) unless the caller supplies its contents, and comes
@@ -768,6 +769,31 @@ int32_t cpq_diag_score_reduce(int32_t nLearners, int32_t nCand, const int32_t* c
         d.launched();
     }
     d.get(scores, dScores, nPairs);
+    return d.rc;
+}
+
+int32_t cpq_diag_learn_tell(int32_t nLearners, cpq_learn_state* states, const cpq_learn_params* params, const double* candidates,
+                            const double* mapped, const double* fitness)
+{
+    if (!states || !params || !candidates || !mapped || !fitness) return fail(nullptr, CPQ_ERR_INVALID_ARG, "learn_tell: null buffer");
+    if (nLearners < 1 || nLearners > (1 << 20)) return fail(nullptr, CPQ_ERR_INVALID_ARG, "learn_tell: n_learners outside 1..2^20");
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+
+    Scope d;
+    const size_t L = (size_t)nLearners;
+    const std::vector<int> ones(L, 1);
+    cpq_learn_state* dStates = d.put(states, L);
+    const int* dActive = d.put(ones.data(), L);
+    const double* dCand = d.put(candidates, L * cpq::kLearnVars);
+    const double* dMapped = d.put(mapped, L * cpq::kLearnVars);
+    const double* dFitness = d.put(fitness, L * cpq::kLearnPop);
+    int* dOrder = d.put<int>(nullptr, L * cpq::kLearnPop);
+    double* dHistory = d.put<double>(nullptr, L);
+    if (d.rc == CPQ_OK) {
+        cpq::launch_learn_tell(nullptr, dStates, dActive, nLearners, *params, dCand, dMapped, dFitness, dOrder, dHistory, 1, 0);
+        d.launched();
+    }
+    d.get(states, dStates, L);
     return d.rc;
 }
 

@@ -7,41 +7,12 @@
 //   thr   [learner][16][2049]               LeveledSegment::maskingThresholds
 //   err   [learner][max_candidates][16][2][4096]   error rows of the last score call (allocated at the first one)
 // A score call builds its chain and evaluation tables on the host (unstable candidates and empty learners take no lane), uploads
-// them, and runs lattice, spectrum and reduction on the scorer's stream; it carries nothing to the next call.
-#include "engine_internal.hpp"
+// them, and runs lattice, spectrum and reduction on the scorer's stream; it carries nothing to the next call.  The two halves
+// (scoreBuildTables, scoreLaunch; score_internal.hpp) are also cpq_learner's (engine_learn.cpp), which builds the tables once
+// for a run and launches once per generation.
+#include "score_internal.hpp"
 
-#include <array>
 #include <cfloat>
-
-struct cpq_scorer {
-    cpq_scorer_desc desc{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {};
-    std::string lastError;
-
-    cpq::ScoreTables tab;
-    cpqi::ScoreTableBuffers tables;             // tab on the device
-    cpq::DitherParams p{};
-    unsigned long long rngStart[2][4] = {};
-    cpqi::DeviceBuffer<unsigned long long> rng; // [max_candidates * 16][2][4]
-
-    std::vector<int> nSeg;                                                  // per learner
-    std::vector<std::array<int, cpq::kScoreLevels>> counts;
-    std::vector<std::array<cpq::ScoreSegment, cpq::kScoreMaxSegments>> segs;
-    cpqi::DeviceBuffer<double> seg, thr, recent, segGain;
-    cpqi::DeviceBuffer<int> segStart;
-
-    cpqi::DeviceBuffer<double> err, coef, blended, scores;
-    cpqi::DeviceBuffer<cpq::ScoreChain> chains;
-    cpqi::DeviceBuffer<cpq::ScoreEval> evals;
-    cpqi::DeviceBuffer<cpq_score_parts> parts;
-    cpqi::DeviceBuffer<int> countsDev, state;
-    // what the last score call ran: per (learner, max_candidates slot), and the segments each learner held then
-    std::vector<char> lastRan;
-    std::vector<int> lastNSeg;
-    bool scored = false;
-};
 
 namespace cpqi {
 
@@ -200,59 +171,28 @@ int setAudio(cpq_scorer* s, int learner, const double* left, const double* right
 
 int score(cpq_scorer* s, const double* mapped, int nCand, double* scores, cpq_score_parts* parts)
 {
-    const int L = s->desc.n_learners, maxC = s->desc.max_candidates;
+    const int L = s->desc.n_learners;
     CPQ_SHIP(s, hipSetDevice(s->device));
-    if (!s->err && !s->err.alloc((size_t)L * maxC * kScoreMaxSegments * 2 * kScoreLen))
-        return sfail(s, CPQ_ERR_OOM, "the error rows of %d learners x %d candidates could not be allocated", L, maxC);
     const int nPairs = L * nCand;
     std::vector<double> coef((size_t)nPairs * cpq::kLatticeOrder);
-    std::vector<int> state(nPairs), counts((size_t)L * cpq::kScoreLevels);
-    std::vector<cpq::ScoreChain> chains;
-    std::vector<cpq::ScoreEval> evals;
-    std::fill(s->lastRan.begin(), s->lastRan.end(), 0);
-    s->lastNSeg = s->nSeg;
-    for (int l = 0; l < L; ++l) {
-        for (int i = 0; i < cpq::kScoreLevels; ++i) counts[(size_t)l * cpq::kScoreLevels + i] = s->counts[l][i];
-        const int nSeg = s->nSeg[l];
-        int ranBefore = 0;                          // a refused candidate draws no words: the chained stream passes it by
-        for (int c = 0; c < nCand; ++c) {
-            const int pair = l * nCand + c;
-            const double* k = mapped + (size_t)pair * cpq::kLatticeOrder;
-            const bool refused = s->desc.stability_check && !cpq::scoreStable(k, cpq::kLatticeOrder);
-            state[pair] = refused ? 1 : 0;
-            cpq::ditherClampAdaptive(k, cpq::kLatticeOrder, &coef[(size_t)pair * cpq::kLatticeOrder]);     // setCoefficients
-            if (refused || nSeg == 0) continue;
-            s->lastRan[(size_t)l * maxC + c] = 1;
-            for (int sg = 0; sg < nSeg; ++sg) {
-                const int row = (l * maxC + c) * kScoreMaxSegments + sg, src = l * kScoreMaxSegments + sg;
-                const int rng = cpq::scoreRngIndex(s->desc.rng_mode, ranBefore, nSeg, sg);
-                evals.push_back(cpq::ScoreEval{ row, src, pair * kScoreMaxSegments + sg, cpq::scoreAlpha(s->segs[l][sg].level) });
-                for (int ch = 0; ch < 2; ++ch) chains.push_back(cpq::ScoreChain{ 2 * src + ch, 2 * row + ch, pair, 2 * rng + ch });
-            }
-            ++ranBefore;
-        }
+    std::vector<int> state(nPairs);
+    std::vector<char> runs(nPairs);
+    for (int pair = 0; pair < nPairs; ++pair) {
+        const double* k = mapped + (size_t)pair * cpq::kLatticeOrder;
+        const bool refused = s->desc.stability_check && !cpq::scoreStable(k, cpq::kLatticeOrder);
+        state[pair] = refused ? 1 : 0;
+        runs[pair] = refused ? 0 : 1;               // a refused candidate draws no words: the chained stream passes it by
+        cpq::ditherClampAdaptive(k, cpq::kLatticeOrder, &coef[(size_t)pair * cpq::kLatticeOrder]);     // setCoefficients
     }
     hipStream_t st = s->stream;
+    cpqi::ScoreCallTables t;
     CPQ_SHIP(s, hipMemcpyAsync(s->coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, st));
     CPQ_SHIP(s, hipMemcpyAsync(s->state, state.data(), state.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    CPQ_SHIP(s, hipMemcpyAsync(s->countsDev, counts.data(), counts.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    if (!chains.empty()) {
-        CPQ_SHIP(s, hipMemcpyAsync(s->chains, chains.data(), chains.size() * sizeof(cpq::ScoreChain), hipMemcpyHostToDevice, st));
-        CPQ_SHIP(s, hipMemcpyAsync(s->evals, evals.data(), evals.size() * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, st));
-    }
-    CPQ_SHIP(s, hipMemsetAsync(s->parts, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), st));
-    CPQ_SHIP(s, hipMemsetAsync(s->blended, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(double), st));
-    CPQ_SHIP(s, hipEventRecord(s->ev[0], st));
-    cpq::launch_score_lattice(st, s->seg, s->err, s->chains, (int)chains.size(), s->coef, s->rng, s->p);
-    CPQ_SHIP(s, hipEventRecord(s->ev[1], st));
-    cpq::launch_score_spectrum(st, s->err, s->thr, s->evals, (int)evals.size(), s->tables.dev, s->parts, s->blended, false);
-    CPQ_SHIP(s, hipEventRecord(s->ev[2], st));
-    cpq::launch_score_reduce(st, s->blended, s->countsDev, s->state, L, nCand, s->desc.level_weights, s->scores);
-    CPQ_SHIP(s, hipGetLastError());
+    CPQ_TRY(cpqi::scoreBuildTables(s, nCand, runs.data(), t));
+    CPQ_TRY(cpqi::scoreLaunch(s, nCand, s->desc.level_weights));
     CPQ_SHIP(s, hipMemcpyAsync(scores, s->scores, (size_t)nPairs * sizeof(double), hipMemcpyDeviceToHost, st));
     if (parts) CPQ_SHIP(s, hipMemcpyAsync(parts, s->parts, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), hipMemcpyDeviceToHost, st));
     CPQ_SHIP(s, hipStreamSynchronize(st));
-    s->scored = true;
     return CPQ_OK;
 }
 
@@ -270,6 +210,66 @@ void fillSegments(const cpq::ScoreSegment* in, int n, cpq_score_segment* out)
 }
 
 }  // namespace
+
+namespace cpqi {
+
+int scoreBuildTables(cpq_scorer* s, int nCand, const char* runs, ScoreCallTables& t)
+{
+    const int L = s->desc.n_learners, maxC = s->desc.max_candidates;
+    CPQ_SHIP(s, hipSetDevice(s->device));
+    if (!s->err && !s->err.alloc((size_t)L * maxC * kScoreMaxSegments * 2 * kScoreLen))
+        return sfail(s, CPQ_ERR_OOM, "the error rows of %d learners x %d candidates could not be allocated", L, maxC);
+    const int nPairs = L * nCand;
+    t.counts.assign((size_t)L * cpq::kScoreLevels, 0);
+    t.chains.clear();
+    t.evals.clear();
+    std::fill(s->lastRan.begin(), s->lastRan.end(), 0);
+    s->lastNSeg = s->nSeg;
+    for (int l = 0; l < L; ++l) {
+        for (int i = 0; i < cpq::kScoreLevels; ++i) t.counts[(size_t)l * cpq::kScoreLevels + i] = s->counts[l][i];
+        const int nSeg = s->nSeg[l];
+        int ranBefore = 0;
+        for (int c = 0; c < nCand; ++c) {
+            const int pair = l * nCand + c;
+            if (!runs[pair] || nSeg == 0) continue;
+            s->lastRan[(size_t)l * maxC + c] = 1;
+            for (int sg = 0; sg < nSeg; ++sg) {
+                const int row = (l * maxC + c) * kScoreMaxSegments + sg, src = l * kScoreMaxSegments + sg;
+                const int rng = cpq::scoreRngIndex(s->desc.rng_mode, ranBefore, nSeg, sg);
+                t.evals.push_back(cpq::ScoreEval{ row, src, pair * kScoreMaxSegments + sg, cpq::scoreAlpha(s->segs[l][sg].level) });
+                for (int ch = 0; ch < 2; ++ch) t.chains.push_back(cpq::ScoreChain{ 2 * src + ch, 2 * row + ch, pair, 2 * rng + ch });
+            }
+            ++ranBefore;
+        }
+    }
+    hipStream_t st = s->stream;
+    CPQ_SHIP(s, hipMemcpyAsync(s->countsDev, t.counts.data(), t.counts.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!t.chains.empty()) {
+        CPQ_SHIP(s, hipMemcpyAsync(s->chains, t.chains.data(), t.chains.size() * sizeof(cpq::ScoreChain), hipMemcpyHostToDevice, st));
+        CPQ_SHIP(s, hipMemcpyAsync(s->evals, t.evals.data(), t.evals.size() * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, st));
+    }
+    CPQ_SHIP(s, hipMemsetAsync(s->parts, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), st));
+    CPQ_SHIP(s, hipMemsetAsync(s->blended, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(double), st));
+    s->nChains = (int)t.chains.size();
+    s->nEvals = (int)t.evals.size();
+    return CPQ_OK;
+}
+
+int scoreLaunch(cpq_scorer* s, int nCand, const double* levelWeights)
+{
+    hipStream_t st = s->stream;
+    CPQ_SHIP(s, hipEventRecord(s->ev[0], st));
+    cpq::launch_score_lattice(st, s->seg, s->err, s->chains, s->nChains, s->coef, s->rng, s->p);
+    CPQ_SHIP(s, hipEventRecord(s->ev[1], st));
+    cpq::launch_score_spectrum(st, s->err, s->thr, s->evals, s->nEvals, s->tables.dev, s->parts, s->blended, false);
+    CPQ_SHIP(s, hipEventRecord(s->ev[2], st));
+    cpq::launch_score_reduce(st, s->blended, s->countsDev, s->state, s->desc.n_learners, nCand, levelWeights, s->scores);
+    CPQ_SHIP(s, hipGetLastError());
+    s->scored = true;
+    return CPQ_OK;
+}
+
+}  // namespace cpqi
 
 extern "C" {
 

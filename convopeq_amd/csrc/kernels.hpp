@@ -9,6 +9,7 @@
 #include "minphase_plan.hpp"
 #include "src_device_plan.hpp"
 #include "prog_plan.hpp"
+#include "learn_plan.hpp"
 
 namespace cpq {
 
@@ -387,5 +388,17 @@ void launch_prog_finish(hipStream_t stream, const double* hops, const ProgFinish
 // written.  launch_prog_apply: out = in * gain[row / 2] over c.rows rows, gain [c.rows / 2] on the device; in may be out.
 void launch_prog_peak(hipStream_t stream, const double* in, const PeakCall& c, double* pk);
 void launch_prog_apply(hipStream_t stream, const double* in, const ApplyCall& c, const double* gain, double* out);
+
+
+// ---- shaper learner (learn_kernels.hip): one generation of CmaEsOptimizer for every learner with active[learner] != 0, on states
+// [nLearners] in place.  launch_learn_ask draws z, factors the covariance and stores z, candidates and mapped [nLearners][18][9],
+// the clamped sets to coef [nLearners * 18][9] and the stability flags to flag [nLearners * 18] (the scorer's buffers for a call
+// of 18 candidates).  launch_learn_tell runs update() and the best tracking on scores [nLearners * 18] and stores the sort to
+// order [nLearners][18] and the generation's best score to history[learner * histStride + g].  Nothing here checks an index.
+void launch_learn_ask(hipStream_t stream, cpq_learn_state* states, const int* active, int nLearners, double margin, bool stabilityCheck,
+                      double* coef, int* flag, double* z, double* candidates, double* mapped);
+void launch_learn_tell(hipStream_t stream, cpq_learn_state* states, const int* active, int nLearners, const cpq_learn_params& p,
+                       const double* candidates, const double* mapped, const double* scores, int* order, double* history, int histStride,
+                       int g);
 
 }  // namespace cpq

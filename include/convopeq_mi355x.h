@@ -1175,8 +1175,9 @@ int32_t     cpq_diag_eq_chain_status(cpq_engine* e, uint32_t* launches, uint32_t
  * MklFftEvaluator::evaluate / computeMaskingThreshold (src/MklFftEvaluator.h).  It is an object of its own, independent of
  * cpq_engine, with the same device rules: CPQ_ERR_NO_DEVICE without a gfx950 device, no CPU fallback.  One scorer serves
  * n_learners learners, each with its own training segments; one call scores every candidate of every learner.  The optimiser
- * (CMA-ES), the capture queue and AudioSegmentBuffer, phases and modes, elite re-evaluation (call score again) and persistence
- * are the caller's.  A scored set reaches the shaper through cpq_dither_set_adaptive_coeffs.
+ * (CMA-ES) is cpq_learner, further down, which drives a scorer generation after generation on the device; the capture queue and
+ * AudioSegmentBuffer, elite re-evaluation (call score again) and persistence are the caller's.  A scored set reaches the shaper
+ * through cpq_dither_set_adaptive_coeffs.
  *
  * Generator semantics.  reset() of the reference's shaper clears the lattice states and not the generator, so within one
  * EvaluationContext the dither stream runs on across segments and candidates, and which worker scores which candidate is a race:
@@ -1310,6 +1311,109 @@ int32_t cpq_diag_score_lattice(int32_t bit_depth, int32_t n_src, const double* s
                                const uint64_t* rng);
 int32_t cpq_diag_score_reduce(int32_t n_learners, int32_t n_cand, const int32_t* counts, const int32_t* state,
                               const double* blended, const double* weights, double* scores);
+
+/* ------------------------------------------------------- shaper learner: the optimiser of the adaptive shaper, on the device */
+/* cpq_learner is the reference's CmaEsOptimizer (src/CmaEsOptimizer.h: dimension 9, population 18, elite 6) with the generation
+ * loop of NoiseShaperLearner (src/NoiseShaperLearner.cpp: evaluatePopulation and the best tracking at :716-729, :975-986) around a
+ * cpq_scorer.  One learner object serves the scorer's n_learners learners; each has its own state on the device.  cpq_learner_run
+ * builds and uploads the scorer's chain and evaluation tables once and enqueues, per generation, ask (k_learn_ask: normal
+ * variates, Cholesky factor, 18 candidates, their mapping into the scorer's coefficient buffer), the scorer's three kernels and
+ * tell (k_learn_tell: CmaEsOptimizer::update and the best tracking) on the scorer's stream; the host does nothing in between and
+ * the call returns without waiting.  The arithmetic is stated once (csrc/learn_plan.hpp) for the kernels and for the
+ * cpq_learn_*_host entries: they agree bit for bit except through log (normal variates) and tanh (mapping), which are each
+ * side's math library.
+ *
+ * Where this differs from the reference, and why:
+ *   normal variates   the reference seeds std::mt19937 from random_device and draws std::normal_distribution; neither stream is
+ *                     reproduced.  A learner draws xoshiro256++ words w (the dither stage's generator), u = (w >> 11) 2^-53, and
+ *                     pairs by Marsaglia's polar method: v = 2 u - 1, s = v1^2 + v2^2, accepted when 0 < s < 1,
+ *                     m = sqrt(-2 log(s) / s), z = (v1 m, v2 m), filling z[candidate][dimension] in order.  After 32 refused
+ *                     tries a pair is (0, 0) and rejected_pairs counts it: a generator state of four zero words cannot spin.
+ *                     A seed becomes four successive splitmix64 outputs.
+ *   the sort          ascending fitness, ties by the lower index, NaN after everything else (std::sort leaves ties open)
+ *   re-evaluation     evaluatePopulation scores its top three again and averages (:700-714).  cpq_learner needs a scorer in
+ *                     CPQ_SCORE_RNG_FRESH mode, where a second score of the same candidate is the same bits a, and
+ *                     (a + a) * 0.5 == a for every score a run can produce (2 a does not overflow below DBL_MAX / 2, and
+ *                     CPQ_SCORE_UNSTABLE and DBL_MAX themselves are not averaged into anything else): it is left out.
+ *   unstable sets     a candidate the stability check refuses is run all the same and scores CPQ_SCORE_UNSTABLE in the
+ *                     reduction, so that the tables of a run do not depend on its candidates
+ *   inactive          a learner holding fewer than two segments when a run starts is left alone (the reference waits for
+ *                     audio): neither its state nor its generation count moves
+ * Not here: the capture queue and AudioSegmentBuffer, persistence, wall-clock pacing. */
+#define CPQ_HAS_SHAPER_LEARNING 1
+#define CPQ_LEARN_DIM 9                 /* CmaEsOptimizer::kDim */
+#define CPQ_LEARN_POPULATION 18         /* kPopulation */
+#define CPQ_LEARN_ELITE 6               /* kElite */
+#define CPQ_LEARN_MAX_GENERATIONS 4096  /* of one cpq_learner_run */
+#define CPQ_LEARN_MAX_TRIES 32          /* refused tries of the polar method before a pair becomes (0, 0) */
+typedef struct cpq_learner cpq_learner;
+typedef struct {                        /* CmaEsOptimizer::Params and NoiseShaperLearner::currentLevelWeights */
+    double sigma_min, sigma_max, cov_retention_target, cov_retention_step, level_weights[4];
+} cpq_learn_params;
+typedef struct {
+    double   mean[9], cov_upper[45];    /* serializeTo's layout: rows of the upper triangle */
+    double   sigma, cov_retention;      /* covRetentionCurrent */
+    uint64_t rng[4];                    /* xoshiro256++; four zero words are refused */
+    double   best_score;                /* DBL_MAX until a generation's best is below it */
+    double   best_raw[9];               /* the unconstrained candidate that earned best_score */
+    double   best_scored[9];            /* its mapped set, the one that was scored: for cpq_dither_set_adaptive_coeffs */
+    int32_t  generations, rejected_pairs;
+} cpq_learn_state;
+typedef enum { CPQ_LEARN_SHORTEST = 0, CPQ_LEARN_SHORT, CPQ_LEARN_MIDDLE, CPQ_LEARN_LONG, CPQ_LEARN_ULTRA, CPQ_LEARN_CONTINUOUS } cpq_learn_mode;
+/* Borrows the scorer, its stream, its buffers and its segments: the scorer must outlive the learner, and a cpq_scorer_score call
+ * between runs is allowed (a run rebuilds what it needs).  CPQ_ERR_INVALID_ARG: null argument, a scorer with max_candidates < 18
+ * or a generator mode other than CPQ_SCORE_RNG_FRESH (the reason in cpq_last_error(NULL)); CPQ_ERR_OOM. */
+int32_t cpq_learner_create(cpq_scorer* scorer, cpq_learner** out);
+void    cpq_learner_destroy(cpq_learner* l);
+const char* cpq_learner_last_error(const cpq_learner* l);
+/* initFromParcor (src/CmaEsOptimizer.h:97-105) of one learner or of CPQ_ALL_STREAMS, with the generator seeded from `seed`
+ * (every learner from seed + its index), best_score DBL_MAX, the counters 0.  Synchronises. */
+int32_t cpq_learner_init(cpq_learner* l, int32_t learner, const double parcor[9], uint64_t seed);
+/* Acts on the next run.  Defaults: 0.03, 0.30, 0.92, 0, the scorer's level weights.  Refused unless every value is finite,
+ * 0 < sigma_min <= sigma_max, 0 <= cov_retention_target <= 1, cov_retention_step >= 0, the weights >= 0. */
+int32_t cpq_learner_set_params(cpq_learner* l, const cpq_learn_params* p);
+/* n_generations in 1 .. CPQ_LEARN_MAX_GENERATIONS; enqueues and returns.  CPQ_ERR_NOT_READY: a learner holding two or more
+ * segments was never initialised.  cpq_scorer_read_error afterwards names the last generation's rows. */
+int32_t cpq_learner_run(cpq_learner* l, int32_t n_generations);
+/* One learner's state.  Both synchronise.  set_state refuses a non-finite mean, covariance, sigma or retention, a generator of
+ * four zero words and negative counters. */
+int32_t cpq_learner_get_state(cpq_learner* l, int32_t learner, cpq_learn_state* out);
+int32_t cpq_learner_set_state(cpq_learner* l, int32_t learner, const cpq_learn_state* in);
+/* The last generation a run made for this learner: z, candidates, mapped [18][9], scores [18], order [18] (the sort); any may be
+ * NULL.  CPQ_ERR_NOT_READY before the learner's first generation.  Synchronises. */
+int32_t cpq_learner_read_generation(cpq_learner* l, int32_t learner, double* z, double* candidates, double* mapped, double* scores,
+                                    int32_t* order);
+/* best_per_generation[0 .. *n - 1] (room for the last run's n_generations): every generation's lowest score, of the last run;
+ * *n = 0 for a learner the run left alone.  Either may be NULL.  Synchronises. */
+int32_t cpq_learner_read_history(cpq_learner* l, int32_t learner, double* best_per_generation, int32_t* n);
+/* What the reference publishes: tanh(sanitize(tanh(best_raw))) -- toParcor at NoiseShaperLearner.cpp:975, then tanh again where
+ * the published set is applied (:1465).  This is the reference's own double mapping, computed on the host with std::tanh; the
+ * set that earned best_score is best_scored. */
+int32_t cpq_learner_published(cpq_learner* l, int32_t learner, double k[9]);
+/* Diagnostic: events around ask and around tell of the last run's last generation, in milliseconds.  Synchronises. */
+int32_t cpq_learner_last_timing(cpq_learner* l, double* ask_ms, double* tell_ms);
+/* The optimiser on the host (csrc/learn_plan.hpp), no device needed.  Null arguments are refused.
+ * cpq_learn_init_host: initFromParcor (atanh of the set clamped to +-0.995, sigma 0.12, identity covariance, retention =
+ *   params->cov_retention_target; params NULL: the defaults), the generator from `seed`.
+ * cpq_learn_normals_host: the 162 variates of one generation from state->rng, which advances; *words (may be NULL) = generator
+ *   words drawn; state->rejected_pairs counts the pairs given up.
+ * cpq_learn_ask_host: CmaEsOptimizer::sample with the variates given: candidates [18][9].
+ * cpq_learn_tell_host: CmaEsOptimizer::update, then the best tracking and generations + 1.  mapped [18][9] (may be NULL:
+ *   best_scored stays) are the sets that were scored; order [18] (may be NULL) receives the sort.
+ * cpq_learn_phase: computePhase (:227-258): 1, 2 or 3; CPQ_ERR_INVALID_ARG for an unknown mode or seconds not finite.
+ * cpq_learn_phase_params: applyPhaseParams (:260-317): retention target and step and the level weights of (mode, phase 1..3),
+ *   sigma_min / sigma_max at their defaults; *generation_interval_s (may be NULL) = generationIntervalSeconds. */
+int32_t cpq_learn_init_host(const double parcor[9], uint64_t seed, const cpq_learn_params* params, cpq_learn_state* out);
+int32_t cpq_learn_normals_host(cpq_learn_state* state, double z[162], int32_t* words);
+int32_t cpq_learn_ask_host(const cpq_learn_state* state, const double z[162], double candidates[162]);
+int32_t cpq_learn_tell_host(cpq_learn_state* state, const cpq_learn_params* params, const double candidates[162],
+                            const double mapped[162], const double fitness[18], int32_t order[18]);
+int32_t cpq_learn_phase(int32_t mode, double playback_seconds);
+int32_t cpq_learn_phase_params(int32_t mode, int32_t phase, cpq_learn_params* out, double* generation_interval_s);
+/* k_learn_tell alone, on the conventions of the cpq_diag_score_* entries above: states [n_learners], in and out; candidates,
+ * mapped [n_learners][18][9]; fitness [n_learners][18].  Refused unless 1 <= n_learners <= 2^20. */
+int32_t cpq_diag_learn_tell(int32_t n_learners, cpq_learn_state* states, const cpq_learn_params* params, const double* candidates,
+                            const double* mapped, const double* fitness);
 
 /* The complex fp64 transforms of the minimum-phase conversion alone (minphase_kernels.hip): `rows` transforms of 2^log2n points,
  * re_im and out [rows][2^log2n][2], natural order in and out, on the path the size selects (up to 4096 points the LDS transform,

@@ -453,6 +453,50 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The reference's CMA-ES over a ShaperScorer's learners (cpq_learner): whole generations on the device.  The scorer is borrowed
+// and must outlive the learner.
+class ShaperLearner {
+public:
+    explicit ShaperLearner(ShaperScorer& scorer) { status_ = cpq_learner_create(scorer.get(), &l_); }
+    ~ShaperLearner() { cpq_learner_destroy(l_); }
+    ShaperLearner(const ShaperLearner&) = delete;
+    ShaperLearner& operator=(const ShaperLearner&) = delete;
+    bool valid() const noexcept { return l_ != nullptr; }
+    // initFromParcor of one learner or CPQ_ALL_STREAMS; learner i draws from seed + i
+    bool init(int learner, const double parcor[9], uint64_t seed) { return (status_ = cpq_learner_init(l_, learner, parcor, seed)) == CPQ_OK; }
+    bool setParams(const cpq_learn_params& p) { return (status_ = cpq_learner_set_params(l_, &p)) == CPQ_OK; }
+    // applyPhaseParams(mode, computePhase(mode, playbackSeconds)); *generationIntervalSeconds may be null
+    bool applyPhase(cpq_learn_mode mode, double playbackSeconds, double* generationIntervalSeconds = nullptr)
+    {
+        cpq_learn_params p;
+        const int phase = cpq_learn_phase(mode, playbackSeconds);
+        if (phase < 1) { status_ = phase; return false; }
+        if ((status_ = cpq_learn_phase_params(mode, phase, &p, generationIntervalSeconds)) != CPQ_OK) return false;
+        return setParams(p);
+    }
+    // enqueues numGenerations of ask, score, tell and returns; the getters below wait
+    bool run(int numGenerations) { return (status_ = cpq_learner_run(l_, numGenerations)) == CPQ_OK; }
+    bool getState(int learner, cpq_learn_state& out) { return (status_ = cpq_learner_get_state(l_, learner, &out)) == CPQ_OK; }
+    bool setState(int learner, const cpq_learn_state& in) { return (status_ = cpq_learner_set_state(l_, learner, &in)) == CPQ_OK; }
+    // best_per_generation has room for the last run's generations; returns how many were written, or -1
+    int history(int learner, double* bestPerGeneration)
+    {
+        int32_t n = 0;
+        status_ = cpq_learner_read_history(l_, learner, bestPerGeneration, &n);
+        return status_ == CPQ_OK ? n : -1;
+    }
+    // the reference's published set, tanh(toParcor(best)); the set that was scored is cpq_learn_state::best_scored
+    bool published(int learner, double k[9]) { return (status_ = cpq_learner_published(l_, learner, k)) == CPQ_OK; }
+    cpq_learner* get() const noexcept { return l_; }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return cpq_learner_last_error(l_); }
+
+private:
+    cpq_learner* l_ = nullptr;
+    int status_ = CPQ_OK;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Streaming sample-rate conversion of nChannels planar rows (cpq_src): one object per source rate in front of an Engine, computing
 // on the host (CPQ_SRC_HOST) or on the device (CPQ_SRC_DEVICE), with equal bits.
 class StreamResampler {
