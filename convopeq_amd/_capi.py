@@ -32,6 +32,7 @@ CPQ_ORDER_EQ_THEN_CONV = 1
 KERNEL_IDS = {"k_rfft_fwd_ols": 0, "k_fdl_mac": 1, "k_fdl_mac_dcnyq": 2, "k_rfft_inv_ols": 3, "k_svf_cascade": 4,
               "k_svf_cascade_tp": 5, "k_convproc_mix": 6, "k_outfilter_cascade": 7, "k_os_halfband": 8, "k_meter": 9,
               "k_pcm": 10, "k_out": 11, "k_dither": 12}
+CPQ_K_SOFTCLIP = 14         # id 13 stays unassigned (cpq_kernel_name(13) is "?"); profile_read lists "k_soft_clip" when it ran
 CPQ_LEVEL_NUC = 0
 CPQ_LEVEL_PROCESSOR = 1
 CPQ_EQ_MODE_AUTO = 0
@@ -297,6 +298,14 @@ SYMBOLS = {
     "cpq_meter_process": (C.c_int32, [_E, c_double_p, C.c_int32]),
     "cpq_meter_process_device": (C.c_int32, [_E, C.c_void_p, C.c_int32]),
     "cpq_meter_read_blocks": (C.c_int32, [_E, C.POINTER(MeterBlock), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "cpq_soft_clip_params": (C.c_int32, [C.c_float, c_double_p, c_double_p, c_double_p]),
+    "cpq_soft_clip_host": (C.c_int32, [c_double_p, C.c_int32, C.c_int32, C.c_float]),
+    "cpq_soft_clip_latency": (C.c_double, [C.c_int32]),
+    "cpq_engine_set_soft_clip": (C.c_int32, [_E, C.c_int32, C.c_int32, C.c_float]),
+    "cpq_soft_clip_reset": (C.c_int32, [_E]),
+    "cpq_soft_clip_process": (C.c_int32, [_E, c_double_p, c_double_p, C.c_int32, C.c_int32]),
+    "cpq_soft_clip_process_device": (C.c_int32, [_E, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "cpq_soft_clip_read_telemetry": (C.c_int32, [_E, C.c_int32, C.POINTER(OsTelemetry)]),
     "cpq_out_design": (C.c_int32, [C.c_double, c_double_p, c_double_p]),
     "cpq_engine_set_output_stage": (C.c_int32, [_E, C.c_int32]),
     "cpq_out_reset": (C.c_int32, [_E]),

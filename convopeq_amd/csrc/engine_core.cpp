@@ -227,6 +227,7 @@ const char* cpq_kernel_name(int32_t id)
         case CPQ_K_PCM: return "k_pcm";
         case CPQ_K_OUT: return "k_out";
         case CPQ_K_DITHER: return "k_dither";
+        case CPQ_K_SOFTCLIP: return "k_soft_clip";
         default: return "?";
     }
 }
@@ -433,6 +434,8 @@ int32_t cpq_engine_create(const cpq_engine_desc* d, cpq_engine** out)
     e->mixRamp.assign(d->n_streams, MixRamp{});
     e->agcOnHost.assign(d->n_streams, 0);
     e->gainRamp.assign(d->n_streams, GainRamp{});
+    e->scOnHost.assign(d->n_streams, 0);
+    e->scAmountHost.assign(d->n_streams, 0.0f);
     if (hipMemcpy(e->irSlot, e->irSlotHost.data(), sizeof(int) * e->nCh, hipMemcpyHostToDevice) != hipSuccess) {
         cpq_engine_destroy(e);
         return fail(nullptr, CPQ_ERR_DEVICE, "irSlot upload failed");
@@ -515,6 +518,7 @@ int32_t cpq_engine_prepare(cpq_engine* e, double sampleRate, int32_t maxBlock)
     for (size_t s = 0; s < e->mixRamp.size(); ++s) e->mixRamp[s].ramp.setCurrentAndTargetValue((double)e->procParams[s].mix);   // Lifecycle.cpp:370-371
     for (auto& r : e->gainRamp) r.snap();       // setCurrentAndTargetValue (Core.cpp:765)
     CPQ_TRY(resetOversampler(e));       // oversampling.prepare -> release(): histories and flags cleared, counters kept
+    CPQ_TRY(resetSoftClipStage(e));     // softClipOS.prepareSingleStage -> release(): the same for the clipper's local 2x stage
     CPQ_TRY(refreshBaseRateStages(e));
     return zeroRuntimeState(e, true, true);
 }
@@ -623,7 +627,10 @@ int32_t cpq_engine_set_conv_bypass(cpq_engine* e, int32_t bypassed)
 // the output stage on that is where the reference's meters sit: after the scrub (:665-693), before the limiter (:703-710)
 int cpqi::meteredChain(cpq_engine* e, const double* a, double* b, int n)
 {
+    const bool localClip = e->osFactor == 1 && e->anySoftClip;       // factor > 1: enqueueOsChain clips the oversampled block
+    if (localClip) CPQ_TRY(ensureSoftClipStage(e));                   // what the local 2x stage owns, before anything is enqueued
     int rc = e->osFactor > 1 ? enqueueOsChain(e, a, b, n) : enqueueBoth(e, a, b, n);
+    if (rc == CPQ_OK && localClip) rc = enqueueSoftClipLocal(e, b, n);
     const bool dither = e->ditherShaper != CPQ_DITHER_OFF;            // the shaper then applies the headroom and the scrub itself
     if (rc == CPQ_OK) rc = enqueueOutPre(e, b, n, b, n, n, !dither);  // each half returns at once when its flags are off
     if (rc == CPQ_OK && dither) rc = enqueueDither(e, b, n, b, n, n);

@@ -10,6 +10,7 @@
 //   engine_eq.cpp    EQ and output filter: design into one host image of a stream's tables, the one routine that uploads it,
 //                    and the EQ call carried out piece by piece as host_replay.hpp plans it
 //   engine_os.cpp    half-band oversampler around the routing: stage buffers, per-stream state machine
+//   engine_softclip.cpp  soft clipper between the make-up gain and the down stages; at factor 1 with its local 2x pair
 //   engine_pcm.cpp   packed PCM in and out: the converters around the whole-chain call
 //   engine_out.cpp   output stage: DC blocker, headroom, limiter and clamp on the delivered rows
 //   engine_dither.cpp  dither stage: the fixed 4- and 15-tap and the adaptive lattice noise shaper between the output stage's two halves
@@ -53,6 +54,7 @@
 #include "host_replay.hpp"
 #include "nuc_replay.hpp"
 #include "resample_design.hpp"
+#include "softclip_design.hpp"
 #include "kernels.hpp"
 
 using cpq::kBands;
@@ -304,8 +306,20 @@ struct cpq_engine {
     cpqi::DeviceBuffer<double> osTmp[2];    // [nCh][maxCall / 2] stage-to-stage buffers (allocated on first use)
     cpqi::DeviceBuffer<double> osWork;                   // [nCh][tMax * P] the routing's block at the internal rate
 
+    // soft clipper (engine_softclip.cpp): a table row per stream; at factor 1 its local 2x pair, a second oversampler instance of
+    // one stage with state of its own (one group, allocated by the first call that runs it) and the pair's 2n-sample rows
+    std::vector<char> scOnHost;                         // per stream
+    std::vector<float> scAmountHost;
+    bool anySoftClip = false;                           // some stream clips; false: nothing is launched
+    cpqi::DeviceBuffer<double> scTab;                   // [streams][kSoftClipTabDoubles]
+    OsStageDev scStage;                                 // 31 taps, 90 dB: the design of the third IIR-like stage
+    cpqi::DeviceBuffer<double> scCoef, scUp[2], scDown[2];   // [convCount], [nCh][upKeep], [nCh][downKeep]
+    cpqi::DeviceBuffer<int> scFlags, scNonSilent;       // [streams][4], [nCh]
+    cpqi::DeviceBuffer<unsigned long long> scCounts;    // [streams][2]
+    cpqi::DeviceBuffer<double> scWork;                  // [nCh][2 maxCall] the block at twice the rate
+
     // meters (engine_meter.cpp): LoudnessMeter and TruePeakDetector on the base-rate output rows, one record per callback
-    int meterFlags = 0;                                 // CPQ_METER_*; 0 = off
+    int meterFlags = 0;                                // CPQ_METER_*; 0 = off
     cpqi::DeviceBuffer<double> meterTab;                // K-weighting section tables, then the two stages' FIR branches
     cpqi::DeviceBuffer<double> meterState;              // [nCh][8] x1 x2 | pre y1 y2 | rlb y1 y2
     cpqi::DeviceBuffer<double> meterHist[2];            // [nCh][32] last scrubbed inputs (true peak), ping-pong
@@ -467,6 +481,30 @@ int enqueueConvProc(cpq_engine* e, const double* dIn, double* dOut, int n);
 void freeOversampler(cpq_engine* e);
 int resetOversampler(cpq_engine* e);            // reset(): histories and flags, not the counters
 int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase);
+// One CustomInputOversampler as the stage kernels are to drive it: its stages, its per-stream flags [4] and counts [2], the
+// silence tests [stage][nCh of the instance], and the channels ch0 .. ch0 + nCh - 1 of it that take part (whole streams; a part
+// of an instance only where it has a single stage).  Rows are the engine's [channel][stride]; channel ch0 is at ch0 * stride.
+struct OsView {
+    cpq_engine::OsStageDev* stage;
+    int nStages;
+    int* flags;
+    unsigned long long* counts;
+    int* nonSilent;
+    int ch0, nCh;
+};
+// processUp / processDown of the view's channels, under CPQ_K_OS.  Neither moves the ping-pong selectors: the caller flips a
+// direction once every channel of the instance has run it, and flips up before any down (whose prologue tests the new histories)
+int enqueueOsUp(cpq_engine* e, const OsView& v, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
+int enqueueOsDown(cpq_engine* e, const OsView& v, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase);
+void flipOsUp(const OsView& v);
+void flipOsDown(const OsView& v);
+// engine_softclip.cpp
+// the clipper in place on rows at the processing rate, callbacks of cb samples; launches nothing while no stream clips
+int enqueueSoftClipRows(cpq_engine* e, double* rows, int64_t stride, int n, int cb);
+// factor 1: softClipOS.processUp, the clipper on 2 n samples, softClipOS.processDown back into the rows, for the streams that clip
+int ensureSoftClipStage(cpq_engine* e);
+int enqueueSoftClipLocal(cpq_engine* e, double* rows, int n);
+int resetSoftClipStage(cpq_engine* e);          // histories and flags of the local stage, not its counters; nothing before it exists
 // engine_meter.cpp
 constexpr int kMeterRing = 4096;                // LockFreeRingBuffer<BlockPower, 4096>
 int refreshMeters(cpq_engine* e);               // redesign for the present base rate and reset; nothing while metering is off

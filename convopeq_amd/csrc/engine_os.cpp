@@ -3,6 +3,8 @@
 // The stage kernels, guards and per-stream state machine are in os_kernels.hip; the host sizes the buffers, uploads the
 // coefficients and flips the history ping-pong selectors.  cpq_os_up / cpq_os_down take the refusals of checkBaseRows (any
 // call length) and the two-buffer hostRoundTrip; a new factor ends in refreshBaseRateStages (all three: engine_core.cpp).
+// enqueueOsUp / enqueueOsDown take the instance they drive as an OsView: the engine's own stages, or the single 31-tap stage of
+// the soft clipper's local 2x pair (engine_softclip.cpp), over all of its channels or a run of them.
 #include "engine_internal.hpp"
 
 namespace cpqi {
@@ -40,39 +42,46 @@ static int ensureOsTmp(cpq_engine* e)
     return CPQ_OK;
 }
 
-static cpq::OsStageArgs stageArgs(cpq_engine* e, int i)
+static cpq::OsStageArgs stageArgs(const OsView& v, int i)
 {
-    const auto& s = e->osStage[i];
+    const auto& s = v.stage[i];
     cpq::OsStageArgs a{};
     a.coef = s.coef;
     a.convCount = s.convCount;
     a.centerCoeff = s.centerCoeff;
-    a.nCh = e->nCh;
-    a.flags = e->osFlags;
-    a.counts = e->osCounts;
+    a.nCh = v.nCh;
+    a.flags = v.flags + 4 * (v.ch0 / 2);
+    a.counts = v.counts + 2 * (v.ch0 / 2);
     return a;
 }
 
-// processUp: in [nCh][inStride] (nBase samples) -> out [nCh][outStride] (nBase * F samples)
-static int enqueueUp(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+static OsView mainView(cpq_engine* e)
 {
-    if (e->osStages > 1) CPQ_TRY(ensureOsTmp(e));
+    return OsView{ e->osStage, e->osStages, e->osFlags, e->osCounts, e->osNonSilent, 0, e->nCh };
+}
+
+void flipOsUp(const OsView& v) { for (int i = 0; i < v.nStages; ++i) v.stage[i].upSel ^= 1; }
+void flipOsDown(const OsView& v) { for (int i = 0; i < v.nStages; ++i) v.stage[i].downSel ^= 1; }
+
+// processUp: in [nCh][inStride] (nBase samples) -> out [nCh][outStride] (nBase * F samples)
+int enqueueOsUp(cpq_engine* e, const OsView& v, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+{
+    if (v.nStages > 1) CPQ_TRY(ensureOsTmp(e));
     ProfScope p(e, CPQ_K_OS);
-    const double* src = in;
+    const double* src = in + v.ch0 * inStride;
     int64_t srcStride = inStride;
     int n = nBase;
-    for (int i = 0; i < e->osStages; ++i) {
-        auto& s = e->osStage[i];
-        const bool last = i == e->osStages - 1;
-        double* dst = last ? out : e->osTmp[i & 1];
+    for (int i = 0; i < v.nStages; ++i) {
+        const auto& s = v.stage[i];
+        const bool last = i == v.nStages - 1;
+        double* dst = last ? out + v.ch0 * outStride : e->osTmp[i & 1];
         const int64_t dstStride = last ? outStride : 2 * (int64_t)n;
-        cpq::OsStageArgs a = stageArgs(e, i);
+        cpq::OsStageArgs a = stageArgs(v, i);
         a.in = src; a.inStride = srcStride; a.out = dst; a.outStride = dstStride;
-        a.histOld = s.up[s.upSel]; a.histNew = s.up[s.upSel ^ 1]; a.keep = s.upKeep;
+        a.histOld = s.up[s.upSel] + (int64_t)v.ch0 * s.upKeep; a.histNew = s.up[s.upSel ^ 1] + (int64_t)v.ch0 * s.upKeep; a.keep = s.upKeep;
         a.centerOffset = s.centerDelay;
         a.n = n;
         cpq::launch_os_interp(e->stream, a);
-        s.upSel ^= 1;
         src = dst; srcStride = dstStride; n *= 2;
     }
     CPQ_HIP(e, hipGetLastError());
@@ -80,40 +89,57 @@ static int enqueueUp(cpq_engine* e, const double* in, int64_t inStride, double* 
 }
 
 // processDown: in [nCh][inStride] (nBase * F samples) -> out [nCh][outStride] (nBase samples)
-static int enqueueDown(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+int enqueueOsDown(cpq_engine* e, const OsView& v, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
 {
-    if (e->osStages > 1) CPQ_TRY(ensureOsTmp(e));
+    if (v.nStages > 1) CPQ_TRY(ensureOsTmp(e));
     ProfScope p(e, CPQ_K_OS);
     cpq::OsHistories hs{};
-    for (int i = 0; i < e->osStages; ++i) {
-        const auto& s = e->osStage[i];
-        hs.up[i] = s.up[s.upSel];
-        hs.down[i] = s.down[s.downSel];
+    for (int i = 0; i < v.nStages; ++i) {
+        const auto& s = v.stage[i];
+        hs.up[i] = s.up[s.upSel] + (int64_t)v.ch0 * s.upKeep;
+        hs.down[i] = s.down[s.downSel] + (int64_t)v.ch0 * s.downKeep;
         hs.upKeep[i] = s.upKeep;
         hs.downKeep[i] = s.downKeep;
     }
-    cpq::launch_os_down_state(e->stream, hs, e->osStages, e->desc.n_streams, e->osFlags, e->osCounts, e->osNonSilent);
-    const int top = e->osStages - 1;
+    int* nonSilent = v.nonSilent + v.ch0;
+    cpq::launch_os_down_state(e->stream, hs, v.nStages, v.nCh / 2, v.flags + 4 * (v.ch0 / 2), v.counts + 2 * (v.ch0 / 2), nonSilent);
+    const int top = v.nStages - 1;
     int n = nBase << top;                                   // outputs of the top stage
-    cpq::launch_os_scan(e->stream, in, inStride, 2 * n, e->nCh, e->osNonSilent + (size_t)top * e->nCh);
-    const double* src = in;
+    const double* src = in + v.ch0 * inStride;
+    cpq::launch_os_scan(e->stream, src, inStride, 2 * n, v.nCh, nonSilent + (size_t)top * v.nCh);
     int64_t srcStride = inStride;
     for (int i = top; i >= 0; --i) {
-        auto& s = e->osStage[i];
-        double* dst = i == 0 ? out : e->osTmp[i & 1];
+        const auto& s = v.stage[i];
+        double* dst = i == 0 ? out + v.ch0 * outStride : e->osTmp[i & 1];
         const int64_t dstStride = i == 0 ? outStride : (int64_t)n;
-        cpq::OsStageArgs a = stageArgs(e, i);
+        cpq::OsStageArgs a = stageArgs(v, i);
         a.in = src; a.inStride = srcStride; a.out = dst; a.outStride = dstStride;
-        a.histOld = s.down[s.downSel]; a.histNew = s.down[s.downSel ^ 1]; a.keep = s.downKeep;
+        a.histOld = s.down[s.downSel] + (int64_t)v.ch0 * s.downKeep; a.histNew = s.down[s.downSel ^ 1] + (int64_t)v.ch0 * s.downKeep; a.keep = s.downKeep;
         a.centerOffset = s.centerTap;
         a.n = n;
-        cpq::launch_os_decim(e->stream, a, e->osNonSilent + (size_t)i * e->nCh,
-                             i > 0 ? e->osNonSilent + (size_t)(i - 1) * e->nCh : nullptr);
-        s.downSel ^= 1;
+        cpq::launch_os_decim(e->stream, a, nonSilent + (size_t)i * v.nCh,
+                             i > 0 ? nonSilent + (size_t)(i - 1) * v.nCh : nullptr);
         src = dst; srcStride = dstStride; n /= 2;
     }
     CPQ_HIP(e, hipGetLastError());
     return CPQ_OK;
+}
+
+// the engine's own instance: one call of each direction, then the histories it wrote become the current ones
+static int enqueueUp(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+{
+    const OsView v = mainView(e);
+    const int rc = enqueueOsUp(e, v, in, inStride, out, outStride, nBase);
+    if (rc == CPQ_OK) flipOsUp(v);
+    return rc;
+}
+
+static int enqueueDown(cpq_engine* e, const double* in, int64_t inStride, double* out, int64_t outStride, int nBase)
+{
+    const OsView v = mainView(e);
+    const int rc = enqueueOsDown(e, v, in, inStride, out, outStride, nBase);
+    if (rc == CPQ_OK) flipOsDown(v);
+    return rc;
 }
 
 // whole path with factor > 1: up -> routing on nBase * F samples in the internal work buffer (in place) -> down
@@ -123,6 +149,7 @@ int enqueueOsChain(cpq_engine* e, const double* dIn, double* dOut, int nBase)
     const int n = nBase * e->osFactor;
     CPQ_TRY(enqueueUp(e, dIn, nBase, e->osWork, n, nBase));
     CPQ_TRY(enqueueBoth(e, e->osWork, e->osWork, n));
+    CPQ_TRY(enqueueSoftClipRows(e, e->osWork, n, n, e->B));     // after the make-up gain, before processDown (:479-488)
     return enqueueDown(e, e->osWork, n, dOut, nBase, nBase);
 }
 
@@ -151,6 +178,7 @@ int32_t cpq_engine_set_oversampling(cpq_engine* e, int32_t factor, int32_t type)
     CPQ_HIP(e, hipSetDevice(e->device));
     CPQ_HIP(e, hipStreamSynchronize(e->stream));
     freeOversampler(e);
+    CPQ_TRY(resetSoftClipStage(e));     // DSPCore::prepare designs softClipOS again: its histories and flags start clear
     const int S = e->desc.n_streams;
     if (!e->osFlags) {
         CPQ_TRY(allocAll(e, { { e->osFlags, (size_t)4 * S }, { e->osCounts, (size_t)2 * S }, { e->osNonSilent, (size_t)3 * e->nCh } },

@@ -290,6 +290,11 @@ void launch_out_pre(hipStream_t stream, const double* in, int64_t inStride, doub
 void launch_out_post(hipStream_t stream, const double* in, int64_t inStride, double* out, int64_t outStride, int n, int nStreams,
                      bool limiter, bool clamp, double release, double* env);
 
+// ---- soft clipper (softclip_kernels.hip): softClipBlockAVX2 in place on rows [nCh][n], callbacks of cb samples (the last one
+// of the call shorter); channel c reads row c / 2 of tab ([streams][kSoftClipTabDoubles], softclip_design.hpp), a row whose first
+// entry is 0 leaves its stream's rows alone
+void launch_soft_clip(hipStream_t stream, double* data, int64_t stride, int n, int cb, int nCh, const double* tab);
+
 // ---- dither stage (dither_kernels.hip): headroom, the 4- or 15-tap or the 9th-order lattice noise shaper and (scrub) the scrub
 // on rows [nCh][n]; in and out may be the same rows.  err [kDitherMaxOrder][nCh] (tap k of channel c at k * nCh + c, k = 0 the
 // newest; the lattice's states in rows 0 .. 8) and rng [4][nCh] are carried across calls.  order: 4, 16 or kLatticeOrder, which

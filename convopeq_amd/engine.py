@@ -122,6 +122,29 @@ def out_design(rate):
     return alpha, rel.value
 
 
+def soft_clip_params(amount):
+    """cpq_soft_clip_params: (threshold, knee, asymmetry) of a saturation amount in 0 .. 1."""
+    t, k, a = C.c_double(), C.c_double(), C.c_double()
+    rc = K.load().cpq_soft_clip_params(float(amount), C.byref(t), C.byref(k), C.byref(a))
+    if rc != 0:
+        raise CpqError(rc, "cpq_soft_clip_params")
+    return t.value, k.value, a.value
+
+
+def soft_clip_host(x, callback_len, amount):
+    """cpq_soft_clip_host: the host restatement of the soft clipper on one row, walked in callbacks of callback_len samples."""
+    y = np.array(x, dtype=np.float64).reshape(-1)
+    rc = K.load().cpq_soft_clip_host(_dp(y), y.size, int(callback_len), float(amount))
+    if rc != 0:
+        raise CpqError(rc, "cpq_soft_clip_host")
+    return y
+
+
+def soft_clip_latency(factor):
+    """cpq_soft_clip_latency: base-rate samples the soft clipper adds at an oversampling factor (15 at factor 1, else 0)."""
+    return K.load().cpq_soft_clip_latency(int(factor))
+
+
 def dither_design(rate, shaper, bit_depth):
     """cpq_dither_design: (coefficients float64[16], scale) of a noise shaper's prepare(rate, bit_depth)."""
     coeffs, scale = np.empty(16), C.c_double()
@@ -522,6 +545,29 @@ class BatchedEngine:
         rec = np.frombuffer(buf, dtype=dt).reshape(self.n_streams, max_blocks)[:, :n.value].copy()
         return rec, dropped.value
 
+    # ---- soft clipper (between the make-up gain and the down stages; at factor 1 with its local 2x pair)
+    def set_soft_clip(self, stream, enabled, saturation_amount=0.0):
+        self._ck(self._lib.cpq_engine_set_soft_clip(self._h, int(stream), int(bool(enabled)), float(saturation_amount)))
+
+    def soft_clip_reset(self):
+        self._ck(self._lib.cpq_soft_clip_reset(self._h))
+
+    def soft_clip_process(self, x, callback_len):
+        """The kernel alone on rows [n_channels, n], walked in callbacks of callback_len samples."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.ndim == 2 and x.shape[0] == self.n_channels
+        y = np.empty_like(x)
+        self._ck(self._lib.cpq_soft_clip_process(self._h, _dp(x), _dp(y), x.shape[1], int(callback_len)))
+        return y
+
+    def soft_clip_process_device(self, d_in, d_out, n_samples, callback_len):
+        self._ck(self._lib.cpq_soft_clip_process_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_samples, int(callback_len)))
+
+    def soft_clip_telemetry(self, stream):
+        t = K.OsTelemetry()
+        self._ck(self._lib.cpq_soft_clip_read_telemetry(self._h, stream, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in K.OsTelemetry._fields_ if f != "reserved"}
+
     # ---- output stage (DC blocker, headroom + scrub, limiter, clamp on the base-rate rows)
     def set_output_stage(self, flags):
         self._ck(self._lib.cpq_engine_set_output_stage(self._h, int(flags)))
@@ -645,6 +691,10 @@ class BatchedEngine:
             if name in ("k_os_halfband", "k_meter", "k_pcm", "k_out", "k_dither") and n.value == 0:
                 continue        # listed only for engines that oversample / meter / take packed PCM / run the output stage / dither
             out[name] = (n.value, ms.value)
+        n, ms = C.c_int64(), C.c_double()
+        self._ck(self._lib.cpq_profile_read(self._h, K.CPQ_K_SOFTCLIP, C.byref(n), C.byref(ms)))
+        if n.value:
+            out["k_soft_clip"] = (n.value, ms.value)      # listed only for engines that ran the soft clipper
         return out
 
     def eq_chain_status(self):

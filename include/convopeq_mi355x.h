@@ -39,6 +39,8 @@ extern "C" {
 #define CPQ_HAS_DITHER 1
 /* likewise: defined when the adaptive 9th-order lattice shaper (CPQ_DITHER_ADAPTIVE9, cpq_dither_*_adaptive_coeffs) exists */
 #define CPQ_HAS_ADAPTIVE_DITHER 1
+/* likewise: defined when the soft clipper (cpq_engine_set_soft_clip, cpq_soft_clip_*) exists */
+#define CPQ_HAS_SOFT_CLIP 1
 
 typedef enum {
     CPQ_OK               =  0,
@@ -808,6 +810,49 @@ int32_t cpq_meter_process_device(cpq_engine* e, const double* d_in, int32_t n_sa
  * last read (either may be NULL).  CPQ_ERR_NOT_READY while metering is off. */
 int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t max_blocks, int32_t* n_blocks, int64_t* n_dropped);
 
+/* ---------------------------------------------------------------- soft clipper */
+/* The soft clipper DSPCore::processDouble runs between the output make-up gain and the oversampler's down stages
+ * (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:471-503; softClipBlockAVX2 :133-224), memoryless, per channel.
+ * With sat = (double)saturation_amount: threshold = 0.95 - 0.45 sat, knee = 0.05 + 0.35 sat, asymmetry = 0.10 sat.  A sample
+ * with |x| <= threshold - knee (and a NaN) passes unchanged.  The reference clips callback by callback with two arithmetic paths,
+ * and so does this stage, bit for bit: sample i of a callback of len samples takes the 4-wide body while i < len / 4 * 4
+ * (reciprocals of the knee, three fused multiply-adds, the Pade tanh on an argument clamped to +-4.5) and the scalar tail after
+ * that (true divisions, nothing fused, tanh = +-1 beyond 4.5).  An infinity becomes a NaN on either path.
+ *   factor > 1   in place on the oversampled block, one callback = block_size samples at the processing rate
+ *   factor 1     a local 2x pair around it (softClipOS: one half-band stage of 31 taps at 90 dB, the design of the third
+ *                CPQ_OS_IIR stage, driven like the main oversampler: histories, guards, auto-clear and hard fallback -- a stream
+ *                in hard fallback delivers silence -- and the 3/4 pass-band gain of an up / down pair), one callback =
+ *                2 * block_size samples; the pair delays the stream by 15 base-rate samples
+ * The ragged last chunk of a CPQ_CALLS_ANY call is a callback of its own length.  The stage runs inside
+ * cpq_engine_process_block[_device] and the PCM calls, before the output stage, the meters, the dither stage and the pack.
+ * Not built: the 1 Hz DC blocker on the oversampled block, the full-bypass dry blend, the fade-in, the fixed latency delay. */
+/* threshold, knee and asymmetry of an amount; CPQ_ERR_INVALID_ARG for a null pointer or an amount that is not finite or
+ * outside 0 .. 1, the range the reference's setSaturationAmount admits.  Host only. */
+int32_t cpq_soft_clip_params(float saturation_amount, double* threshold, double* knee, double* asymmetry);
+/* The reference's walk over one row in place on the host, sequentially: n_samples in callbacks of callback_len (the last one
+ * shorter).  The statement the kernel is tested against.  Host only. */
+int32_t cpq_soft_clip_host(double* data, int32_t n_samples, int32_t callback_len, float saturation_amount);
+/* base-rate samples the stage adds: 15.0 at factor 1 (the local 2x pair), 0.0 at any other factor.  Host only. */
+double  cpq_soft_clip_latency(int32_t factor);
+/* One stream or CPQ_ALL_STREAMS: enabled != 0 clips with the amount, 0 lets the stream's rows pass untouched (the amount is
+ * kept).  The default is off for every stream; while no stream clips nothing is launched or allocated and the engine's output
+ * is what it was without this call.  CPQ_ERR_INVALID_ARG for a stream out of range or an amount that is not finite or outside
+ * 0 .. 1, before any state moves.  A change of `enabled` of any stream clears the local 2x stage's histories and flags of every
+ * stream, as do cpq_engine_prepare and cpq_engine_set_oversampling; a change of the amount alone does not.  Synchronises the
+ * engine's stream. */
+int32_t cpq_engine_set_soft_clip(cpq_engine* e, int32_t stream, int32_t enabled, float saturation_amount);
+/* histories and flags of the local 2x stage to zero (its counters stay).  CPQ_ERR_NOT_READY while no stream clips (so for the
+ * two calls below). */
+int32_t cpq_soft_clip_reset(cpq_engine* e);
+/* The kernel alone on caller rows [channel][n_samples] with the engine's table: n_samples is 1 .. block_size *
+ * max_blocks_per_call, callback_len >= 1 is the callback length to walk them in (any value: the rows are at whatever rate the
+ * caller says).  in and out may be the same buffer; both 16-byte aligned.  _device: device pointers, enqueued on the engine's
+ * stream, no synchronisation.  The local 2x pair is not run.  Every refusal happens before anything is enqueued. */
+int32_t cpq_soft_clip_process(cpq_engine* e, const double* in, double* out, int32_t n_samples, int32_t callback_len);
+int32_t cpq_soft_clip_process_device(cpq_engine* e, const double* d_in, double* d_out, int32_t n_samples, int32_t callback_len);
+/* cpq_os_read_telemetry for the local 2x stage: its own events, auto-clears and hard fallback; all zero before it first ran */
+int32_t cpq_soft_clip_read_telemetry(cpq_engine* e, int32_t stream, cpq_os_telemetry* out);
+
 /* ---------------------------------------------------------------- output stage */
 /* The base-rate steps DSPCore::processOutputDouble runs on the chain's result when dither is off
  * (src/audioengine/AudioEngine.Processing.DSPCoreDouble.cpp:577-744), in its order:
@@ -823,7 +868,8 @@ int32_t cpq_meter_read_blocks(cpq_engine* e, cpq_meter_block* out, int32_t max_b
  * The stage runs on the base-rate rows at the end of cpq_engine_process_block[_device] and of the PCM calls: after the
  * oversampler's down stages, before the pack, one callback = block_size / factor samples (the ragged last chunk of a
  * CPQ_CALLS_ANY call is a callback of its own length).  With the stage on the meters read where the reference's do: after the
- * scrub, before the limiter.  Not built: the soft clipper, the fade-in, the fixed latency delay (dither: the next section). */
+ * scrub, before the limiter.  The soft clipper (the section above) runs before this stage.  Not built: the fade-in, the fixed
+ * latency delay (dither: the next section). */
 #define CPQ_OUT_DC_BLOCK 1
 #define CPQ_OUT_HEADROOM 2
 #define CPQ_OUT_LIMITER  4
@@ -978,7 +1024,9 @@ typedef enum {
     CPQ_K_PCM      = 10,  /* packed PCM converters (k_pcm_unpack / k_pcm_pack) */
     CPQ_K_OUT      = 11,  /* output stage (k_out_pre / k_out_headroom / k_out_post) */
     CPQ_K_DITHER   = 12,  /* dither stage (k_dither, k_dither_lattice) */
-    CPQ_K_COUNT    = 13
+    /* 13 stays unassigned: cpq_kernel_name(13) has answered "?" since the dither stage and keeps doing so; its counters read 0 */
+    CPQ_K_SOFTCLIP = 14,  /* soft clipper (k_soft_clip); its local 2x pair at factor 1 counts under CPQ_K_OS */
+    CPQ_K_COUNT    = 15
 } cpq_kernel_id;
 int32_t     cpq_profile_enable(cpq_engine* e, int32_t on);
 int32_t     cpq_profile_reset(cpq_engine* e);
@@ -1281,7 +1329,7 @@ int32_t cpq_score_select_segments(const double* left, const double* right, int32
  * and before a device is looked for, unless the rules of its "Refused unless" hold and every pointer is non-null; no buffer may
  * exceed 2^28 elements.  Need a gfx950 device (CPQ_ERR_NO_DEVICE); an allocation or HIP failure is CPQ_ERR_DEVICE.  Like every
  * addition since revision 1 they leave CPQ_ABI_REVISION as it is (a caller that may meet an older library looks the symbols up),
- * and as diagnostics of kernels no engine profiles they leave CPQ_K_COUNT at 13.
+ * and as diagnostics of kernels no engine profiles they add no cpq_kernel_id.
  *
  * cpq_diag_score_spectrum: launch_score_spectrum as cpq_scorer makes it, with the tables of sample_rate_hz (built and uploaded by
  *   the scorer's own function).  rows: [n_rows][2][4096] (L, R); thr: [n_thr][2049], in and out; evals: [n_evals], evaluation i

@@ -345,6 +345,28 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// DSPCore's soft clipper (state.softClipEnabled / state.saturationAmount) for the streams of an engine.  Once enabled,
+// cpq_engine_process_block clips between the make-up gain and the oversampler's down stages -- at factor 1 inside a local 2x
+// pair that adds latency() base-rate samples.
+class BatchedSoftClip {
+public:
+    explicit BatchedSoftClip(Engine& e) : e_(e) {}
+    // stream: an index or CPQ_ALL_STREAMS; saturationAmount in 0 .. 1
+    bool set(int stream, bool enabled, float saturationAmount)
+    {
+        return (status_ = cpq_engine_set_soft_clip(e_.get(), stream, enabled ? 1 : 0, saturationAmount)) == CPQ_OK;
+    }
+    static double latency(int oversamplingFactor) { return cpq_soft_clip_latency(oversamplingFactor); }
+    void reset() { status_ = cpq_soft_clip_reset(e_.get()); }
+    int lastStatus() const noexcept { return status_; }
+    const char* lastError() const noexcept { return e_.lastError(); }
+
+private:
+    Engine& e_;
+    int status_ = CPQ_OK;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // DSPCore's output stage (processOutputDouble with dither off: DC blocker, headroom + scrub, SimplePeakLimiter, clamp) for
 // every stream of an engine.  Once prepared, cpq_engine_process_block passes its own output through it; process runs it on
 // caller blocks, in place, without the chain.
