@@ -441,6 +441,7 @@ SYMBOLS = {
     "cpq_learn_phase": (C.c_int32, [C.c_int32, C.c_double]),
     "cpq_learn_phase_params": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(LearnParams), c_double_p]),
     "cpq_diag_learn_tell": (C.c_int32, [C.c_int32, C.POINTER(LearnState), C.POINTER(LearnParams), c_double_p, c_double_p, c_double_p]),
+    "cpq_diag_prog_finish": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_double, c_double_p, C.POINTER(LoudnessResult), c_double_p, _i32p]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 //   mix_kernels.hip                  cpq_diag_direct_head, _agc, _ring_chunks, _convproc_mix, _tail_reader, _rows    test_gpu_mix_kernels.py
 //   score_kernels.hip                cpq_diag_score_spectrum, _score_lattice, _score_reduce                 tests/test_gpu_score_kernels.py
 //   learn_kernels.hip                cpq_diag_learn_tell                                                    tests/test_gpu_learn_kernels.py
+//   prog_kernels.hip                 cpq_diag_prog_finish                                                   tests/test_gpu_prog_finish.py
 //   chained EQ spans of an engine    cpq_diag_eq_chain_status                                             tests/test_gpu_eq_chained.py
 // One convention for all but the last: host pointers, own device buffers of exactly the documented sizes (Scope), the null
 // stream, no engine; what a kernel may write is filled with 0xFF bytes (NaN) unless the caller supplies its contents, and comes
@@ -795,6 +796,43 @@ int32_t cpq_diag_learn_tell(int32_t nLearners, cpq_learn_state* states, const cp
     }
     d.get(states, dStates, L);
     return d.rc;
+}
+
+// k_prog_finish alone on caller-filled hop sums: the ProgFinish engine_prog.cpp builds, with n_hops and max_hops the caller's
+int32_t cpq_diag_prog_finish(int32_t nStreams, int32_t nHops, int32_t maxHops, double sampleRate, const double* hops,
+                             cpq_loudness_result* out, double* z, int32_t* counts)
+{
+    if (!hops || !out) return fail(nullptr, CPQ_ERR_INVALID_ARG, "prog_finish: null buffer");
+    if (nStreams < 1 || nStreams > 32767) return fail(nullptr, CPQ_ERR_INVALID_ARG, "prog_finish: n_streams %d outside 1..32767", nStreams);
+    if (maxHops < 1 || nHops < 0 || nHops > maxHops)
+        return fail(nullptr, CPQ_ERR_INVALID_ARG, "prog_finish: max_hops %d must be >= 1 and n_hops %d in 0..max_hops", maxHops, nHops);
+    cpq::ProgFinish f;
+    f.H = cpq::progHop(sampleRate);
+    if (!f.H) return fail(nullptr, CPQ_ERR_INVALID_ARG, "prog_finish: sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sampleRate);
+    if (cpq::progShortCount(nHops) > cpq::kProgSortMax)
+        return fail(nullptr, CPQ_ERR_INVALID_ARG, "prog_finish: n_hops %d holds more than %d short-term blocks at the 1 s step", nHops, cpq::kProgSortMax);
+    if (!fits(nStreams, maxHops)) return fail(nullptr, CPQ_ERR_INVALID_ARG, "prog_finish: n_streams * max_hops above 2^28");
+    if (!haveDevice()) return CPQ_ERR_NO_DEVICE;
+    f.nHops = nHops; f.maxHops = maxHops; f.zAbs = cpq::progAbsGate();
+
+    Scope d;
+    const size_t S = (size_t)nStreams;
+    const double* dHops = d.put(hops, S * (size_t)maxHops);
+    cpq::ProgRecord* dRec = d.put<cpq::ProgRecord>(nullptr, S);
+    if (d.rc == CPQ_OK) {
+        cpq::launch_prog_finish(nullptr, dHops, f, nStreams, dRec);
+        d.launched();
+    }
+    std::vector<cpq::ProgRecord> rec(S);
+    d.get(rec.data(), dRec, S);
+    if (d.rc != CPQ_OK) return d.rc;
+    for (size_t s = 0; s < S; ++s) {
+        const cpq::ProgRecord& r = rec[s];
+        out[s] = cpq::progResult(r, nHops);
+        if (z) { const double v[6] = { r.zInt, r.zGate, r.zMomMax, r.zShortMax, r.zLo, r.zHi }; std::copy_n(v, 6, z + 6 * s); }
+        if (counts) { const int32_t v[4] = { r.nAbs, r.nRel, r.nShortAbs, r.nShortKept }; std::copy_n(v, 4, counts + 4 * s); }
+    }
+    return CPQ_OK;
 }
 
 // ---------------------------------------------------------------- the complex transforms of minphase_kernels.hip (tests/test_gpu_ir_minphase.py)

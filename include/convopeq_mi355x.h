@@ -1462,6 +1462,15 @@ int32_t cpq_learn_phase_params(int32_t mode, int32_t phase, cpq_learn_params* ou
  * mapped [n_learners][18][9]; fitness [n_learners][18].  Refused unless 1 <= n_learners <= 2^20. */
 int32_t cpq_diag_learn_tell(int32_t n_learners, cpq_learn_state* states, const cpq_learn_params* params, const double* candidates,
                             const double* mapped, const double* fitness);
+/* k_prog_finish alone (prog_kernels.hip), on the same conventions: hops [n_streams][max_hops] on the host, of which the kernel is
+ * given the first n_hops of every row (what lies behind them must not matter); out [n_streams] as cpq_loudness_finish makes it.
+ * What the kernel itself delivers, before any logarithm (csrc/prog_plan.hpp, ProgRecord), goes to z [n_streams][6]: the mean
+ * squares zInt, zGate, zMomMax, zShortMax, zLo, zHi, and to counts [n_streams][4]: nAbs, nRel, nShortAbs, nShortKept; either
+ * may be NULL.  Refused unless: hops and out not NULL, 1 <= n_streams <= 32767, max_hops >= 1, 0 <= n_hops <= max_hops,
+ * sample_rate one cpq_loudness_create takes, at most 8192 short-term blocks at the 1 s step in n_hops, n_streams * max_hops
+ * <= 2^28. */
+int32_t cpq_diag_prog_finish(int32_t n_streams, int32_t n_hops, int32_t max_hops, double sample_rate, const double* hops,
+                             cpq_loudness_result* out, double* z, int32_t* counts);
 
 /* The complex fp64 transforms of the minimum-phase conversion alone (minphase_kernels.hip): `rows` transforms of 2^log2n points,
  * re_im and out [rows][2^log2n][2], natural order in and out, on the path the size selects (up to 4096 points the LDS transform,

@@ -68,15 +68,44 @@ def inputs():
     }
 
 
+# rates whose hop grid meets the 2048-sample span grid (H = 1024: every second hop ends on a span end; H = 2048: a hop is a span)
+# and the rate of the longest hop (H = 76800: a hop lies across 38 spans); samples per row
+GRID_RATES = {10240: 2 * 10240, 20480: 2 * 20480, 768000: 160000}
+
+
 def rate_inputs():
-    """rate -> 2 s of rows [2, n]: a tone pair over noise"""
+    """rate -> 2 s of rows [2, n] (GRID_RATES: their own lengths): a tone pair over noise"""
     out = {}
-    for rate in (44100, 48000):
-        t = np.arange(2 * rate)
+    for rate, n in ((44100, 2 * 44100), (48000, 2 * 48000)) + tuple(GRID_RATES.items()):
+        t = np.arange(n)
         rng = np.random.default_rng(rate)
         out[rate] = np.stack([0.2 * np.sin(2.0 * math.pi * 997.0 * t / rate), 0.1 * np.sin(2.0 * math.pi * 3001.0 * t / rate)]) \
-            + 0.01 * rng.standard_normal((2, 2 * rate))
+            + 0.01 * rng.standard_normal((2, n))
     return out
+
+
+SPIKE = 9.9e299                     # passes the scrub (|v| < 1e300); its K-weighted square overflows
+
+
+def spiked():
+    """5 s of the -23 dBFS tone with one sample of 9.9e299 in each channel, both in hop 1: that hop sum is +inf, and the filters
+    ring down from 1e300 through the hops behind it (pole radius 0.97 at 8000 Hz: about 30 hops until the tone is back)"""
+    x = tone(5, -23.0)
+    x[0, 1234] = SPIKE
+    x[1, 1300] = -SPIKE
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def spiked_reference():
+    """dict(x, E, E_ld, d): the fp64 and long-double models' hop sums and, per hop, their distance d (inf - finite where the fp64
+    square overflowed and the long-double one did not: those hops are compared for being +inf, not to a bar)"""
+    x = spiked()
+    with np.errstate(over="ignore", invalid="ignore"):
+        e64 = P.hop_sums(x, RATE, np.float64)[0]
+        eld = P.hop_sums(np.concatenate([x, x]), RATE, np.longdouble)[0]
+        d = np.abs(e64.astype(np.longdouble) - eld).astype(np.float64)
+    return dict(x=x, E=e64, E_ld=eld, d=d)
 
 
 def stream_programme(s, seconds=3.5):

@@ -108,10 +108,12 @@ def finish(E, H, dtype=np.float64):
     ms = ca.sum() / dtype(len(ca)) if len(ca) else dtype(0.0)
     k = np.sort(ca[ca > 0.01 * ms])
     n = len(k)
+    r["n_cand"], r["n_short_abs"], r["z_short_mean"] = len(c), len(ca), ms
     r["n_short_kept"] = n
     r["z_lo"], r["z_hi"] = (k[(10 * (n - 1) + 50) // 100], k[(95 * (n - 1) + 50) // 100]) if n else (dtype(0.0), dtype(0.0))
     r["range"] = lf(r["z_hi"]) - lf(r["z_lo"]) if n else 0.0
-    # how far the decisions stand from their gates, in LU
-    r["gate_margin"] = min(_dist(zm, Z_ABS), _dist(a, 0.1 * float(m1)), _dist(c, Z_ABS), _dist(ca, 0.01 * float(ms)))
-    r["short_gap"] = float(np.min(np.diff(10.0 * np.log10(k.astype(np.float64))))) if n > 1 else math.inf
+    # how far the decisions stand from their gates, in LU (hop sums of inf leave nan here: no distance)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r["gate_margin"] = min(_dist(zm, Z_ABS), _dist(a, 0.1 * float(m1)), _dist(c, Z_ABS), _dist(ca, 0.01 * float(ms)))
+        r["short_gap"] = float(np.min(np.diff(10.0 * np.log10(k.astype(np.float64))))) if n > 1 else math.inf
     return r

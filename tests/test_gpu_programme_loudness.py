@@ -102,6 +102,44 @@ def test_hop_sums_at_other_rates(amd, rate):
     check_hops(hops[0], ref, rate // 10, f"{rate} Hz, calls of 5000")
 
 
+@pytest.mark.parametrize("rate", tuple(I.GRID_RATES))
+def test_hop_sums_where_the_hop_grid_meets_the_span_grid(amd, rate):
+    """10240 Hz: H = 1024, every second hop ends exactly on the end of a 2048-sample span (nothing is handed over to the next
+    span); 20480 Hz: a hop is a span; 768000 Hz: H = 76800, a hop lies across 38 spans and is handed over 37 times"""
+    ref = I.rate_reference(rate)
+    n, seconds = ref["x"].shape[1], 3 if rate < 100000 else 1
+    assert n == I.GRID_RATES[rate] and len(ref["E"]) == n // (rate // 10) >= 2
+    hops, _ = run(amd, ref["x"], rate=rate, seconds=seconds)
+    check_hops(hops[0], ref, rate // 10, f"{rate} Hz, one call")
+    for piece in (1023, 1024, 1025, 2048) if rate < 100000 else (5000,):
+        hops, _ = run(amd, ref["x"], splits(n, piece), rate=rate, seconds=seconds)
+        check_hops(hops[0], ref, rate // 10, f"{rate} Hz, calls of {piece}")
+
+
+def test_a_sample_whose_square_overflows(amd):
+    """9.9e299 passes the scrub; its K-weighted square does not fit: that hop sum is +inf on the device as in the model, and so
+    are those behind it while the filters ring down through 1e154.  Every finite hop meets the bar, taken per hop here (the ring
+    spans 300 decades: max(8 d, 4 H 2^-52 E) with d that hop's own distance between the fp64 and the long-double model).  The
+    finish on such hop sums is the host's, bit for bit: nothing passes the relative gate of an infinite mean"""
+    ref = I.spiked_reference()
+    hops, res = run(amd, ref["x"])
+    got, want = hops[0], ref["E"]
+    print("device", got.tolist())
+    print("model ", want.tolist())
+    assert got.shape == want.shape and np.isinf(want[1]) and want[1] > 0 and not np.isnan(got).any()
+    assert np.array_equal(np.isinf(got), np.isinf(want)) and np.all(got[np.isinf(got)] > 0)
+    fin = np.isfinite(want)
+    assert fin[0] and fin[16:].all() and np.count_nonzero(fin) >= 35
+    bar = I.hop_bar(dict(d_ref=ref["d"][fin], E=want[fin]), I.H)
+    diff = np.abs(got[fin] - want[fin])
+    print("diff / bar", (diff / bar).tolist())
+    assert np.all(diff <= bar), np.flatnonzero(fin)[diff > bar]
+    host = amd.loudness_finish_host(got, I.RATE)
+    assert host == res[0], (host, res[0])
+    assert res[0]["n_abs"] == 47 and res[0]["n_rel"] == 0 and res[0]["integrated"] == -math.inf and res[0]["relative_gate"] == math.inf
+    assert res[0]["momentary_max"] == math.inf and res[0]["short_term_max"] == math.inf and res[0]["n_short_kept"] == 0
+
+
 def check_finish(res, E, label):
     """the device's figures of one stream against the numpy finish on its own hop sums E"""
     want = P.finish(E, I.H)

@@ -1,6 +1,7 @@
 """csrc/prog_plan.hpp without a GPU: the plan of a call and both kernels of prog_kernels.hip restated as host loops, under
 sanitizers (tests/sanitize/prog_plan_check.cpp), with the host finish held against the numpy model's recorded values
-(tests/golden/prog_finish_cases.txt, written by record_cases() below from tests/prog_inputs.py's programmes)."""
+(tests/golden/prog_finish_cases.txt, written by record_cases() below from tests/prog_inputs.py's programmes) and, to the bit,
+against its values on the planted ties and padded programmes of tests/prog_finish_inputs.py (prog_finish_edge_cases.txt)."""
 import os
 import subprocess
 
@@ -11,6 +12,7 @@ import prog_model as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = os.path.join(HERE, "golden", "prog_finish_cases.txt")
+EDGE_CASES = os.path.join(HERE, "golden", "prog_finish_edge_cases.txt")
 Z_KEYS = ("z_gate", "z_int", "z_mom_max", "z_short_max", "z_lo", "z_hi")
 N_KEYS = ("n_blocks", "n_abs", "n_rel", "n_short_kept")
 
@@ -55,7 +57,8 @@ def test_plan_and_kernels_as_host_loops_under_sanitizers(tmp_path):
     subprocess.run(["g++", "-O1", "-g", "-std=c++20", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=undefined", "-I" + csrc, "-I" + os.path.join(root, "include"),
                     os.path.join(HERE, "sanitize", "prog_plan_check.cpp"), "-o", str(exe)], check=True)
-    r = subprocess.run([str(exe), CASES], capture_output=True, text=True, timeout=240)
+    r = subprocess.run([str(exe), CASES, EDGE_CASES], capture_output=True, text=True, timeout=240)
     print(r.stdout[-3000:])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "\n0 failed checks" in r.stdout and "FAILED" not in r.stdout
+    assert "recorded cases in " + CASES in r.stdout and "recorded cases in " + EDGE_CASES in r.stdout
