@@ -45,6 +45,8 @@ CPQ_RESAMPLE_MINIMUM_PHASE = 1
 CPQ_RESAMPLE_MAX_FACTOR = 1280
 CPQ_SRC_HOST = 1
 CPQ_SRC_DEVICE = 2
+CPQ_LIM_HOST = 1
+CPQ_LIM_DEVICE = 2
 CPQ_OS_IIR = 0
 CPQ_OS_LINEAR_PHASE = 1
 CPQ_METER_LOUDNESS = 1
@@ -168,6 +170,10 @@ class LoudnessResult(C.Structure):
 
 class LoudnessPeaks(C.Structure):
     _fields_ = [("true_peak", C.c_double * 2), ("sample_peak", C.c_double * 2)]
+
+
+class LimiterTelemetry(C.Structure):
+    _fields_ = [("min_gain", C.c_double), ("limited_samples", C.c_int64)]
 
 
 class OsStageInfo(C.Structure):
@@ -367,6 +373,21 @@ SYMBOLS = {
     "cpq_loudness_gain_limited": (C.c_int32, [C.POINTER(LoudnessResult), C.POINTER(LoudnessPeaks), C.c_double, C.c_double, c_double_p,
                                               C.POINTER(C.c_int32)]),
     "cpq_loudness_apply_device": (C.c_int32, [C.c_void_p, c_double_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "cpq_limiter_default_window": (C.c_int32, [C.c_double]),
+    "cpq_limiter_create": (C.c_int32, [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "cpq_limiter_destroy": (None, [C.c_void_p]),
+    "cpq_limiter_last_error": (C.c_char_p, [C.c_void_p]),
+    "cpq_limiter_set_stream": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "cpq_limiter_reset": (C.c_int32, [C.c_void_p]),
+    "cpq_limiter_latency": (C.c_int32, [C.c_void_p]),
+    "cpq_limiter_window": (C.c_int32, [C.c_void_p]),
+    "cpq_limiter_set_gains": (C.c_int32, [C.c_void_p, c_double_p]),
+    "cpq_limiter_process_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "cpq_limiter_process": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "cpq_limiter_flush_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "cpq_limiter_flush": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "cpq_limiter_read_telemetry": (C.c_int32, [C.c_void_p, C.POINTER(LimiterTelemetry)]),
+    "cpq_limiter_last_kernel_ms": (C.c_double, [C.c_void_p]),
     "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
     "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
     "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),

@@ -24,6 +24,8 @@
 //                    engine; the plan of a call is minphase_plan.hpp's, the host steps around it are ir_ingest.hpp's
 //   engine_prog.cpp  cpq_loudness, an object of its own: gated programme loudness per stream; the plan of a call and the
 //                    definition are prog_plan.hpp's (uses only fail, checkCurrentDevice and the device buffers of this header)
+//   engine_lim.cpp   cpq_limiter, an object of its own: look-ahead true-peak limiter per stream; the definition and the plan of a
+//                    call are lim_plan.hpp's, the host object lim_host.hpp's (uses only fail, checkCurrentDevice and the device buffers)
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp, and so are the EQ's plan of a call (gain segments, bypass classes, band resets, pieces) and the processor-level
 // stage's (who rests, mix prefixes, latency ranges): HIP-free steppers and planners that return plain data; the engine files

@@ -9,6 +9,7 @@
 #include "minphase_plan.hpp"
 #include "src_device_plan.hpp"
 #include "prog_plan.hpp"
+#include "lim_plan.hpp"
 #include "learn_plan.hpp"
 
 namespace cpq {
@@ -393,6 +394,14 @@ void launch_prog_finish(hipStream_t stream, const double* hops, const ProgFinish
 // written.  launch_prog_apply: out = in * gain[row / 2] over c.rows rows, gain [c.rows / 2] on the device; in may be out.
 void launch_prog_peak(hipStream_t stream, const double* in, const PeakCall& c, double* pk);
 void launch_prog_apply(hipStream_t stream, const double* in, const ApplyCall& c, const double* gain, double* out);
+
+// ---- look-ahead true-peak limiter (lim_kernels.hip), the device object of cpq_limiter: the call lim_plan.hpp states in `a`, over
+// hist [2 streams][a.hBound], gains [streams], the caller's rows in and out (which do not overlap) and part [streams][a.partStride].
+// launch_lim_apply writes out[row][0 ... a.nOut) and one partial per tile; launch_lim_keep then moves the kept tail of u to the front
+// of hist and folds the partials into tel [streams].  Both go to one stream, in that order.  Nothing here checks an index: `a` is
+// engine_lim.cpp's, built from a planned and validated call.
+void launch_lim_apply(hipStream_t stream, const double* hist, const double* gains, const double* in, double* out, LimPartial* part, const LimLaunch& a);
+void launch_lim_keep(hipStream_t stream, double* hist, const double* gains, const double* in, const LimPartial* part, LimPartial* tel, const LimLaunch& a);
 
 
 // ---- shaper learner (learn_kernels.hip): one generation of CmaEsOptimizer for every learner with active[learner] != 0, on states

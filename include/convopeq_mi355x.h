@@ -730,6 +730,79 @@ int32_t cpq_loudness_gain_limited(const cpq_loudness_result* r, const cpq_loudne
 int32_t cpq_loudness_apply_device(cpq_loudness* p, const double* gains, const double* d_in, int64_t in_stride, double* d_out,
                                   int64_t out_stride, int32_t n_samples);
 
+/* ---------------------------------------------------------------- look-ahead true-peak limiter per programme */
+/* cpq_limiter: where the ceiling would win in cpq_loudness_gain_limited, apply the loudness gain and pull down only the
+ * neighbourhood of the peaks that would pass the ceiling.  An object of its own beside the engine, n_streams stereo programmes at
+ * once, rows planar float64 at (2 s + channel) * stride + i.  The result is defined to the bit (csrc/lim_plan.hpp, DESIGN.md
+ * 4.18), equal for every split of a programme into calls and equal from the object that computes on the host (CPQ_LIM_HOST, no
+ * GPU needed) and the one that computes on the device (CPQ_LIM_DEVICE, gfx950 kernels).  With c the linear ceiling, W the window,
+ * M = W + 12, D = W + 11 and g the stream's pre-gain:
+ *     u[ch][i] = x[ch][i] * g, a product that is not finite or reaches 1e300 in magnitude read as 0.0 (so a sample that is not
+ *                finite comes out as 0.0)
+ *     p[i]     = the largest of |u[0][i]|, |u[1][i]| and the BS.1770-4 Annex 2 interpolator's phases in use over u[ch][i - 11 ... i]
+ *                of both channels (all four phases below 88200 Hz, 0 and 2 below 176400 Hz, none from there on: cpq_loudness's rule)
+ *     r[i]     = p[i] > c ? c / p[i] : 1.0          m[i] = min(r[i - M + 1 ... i])
+ *     a[i]     = (m[i] + m[i - 1] + ... + m[i - W + 1]) / W, added in that order
+ *     y[ch][i] = u[ch][i - D] * a[i]
+ * with everything before the programme 0.0 (r = 1.0).  The channels of a stream are linked.  A call of n samples emits n outputs;
+ * the first D of a programme are zeros; a flush emits the last D and leaves the object at the start of a new programme.
+ * |y| <= c + (W + 3) ulp(c).  The true peak of y may pass c by the slope of a inside the interpolator's 12 taps: RESULTS.md has
+ * the measured overshoot.  There is no release recurrence and no iteration to a loudness target.
+ *
+ * cpq_limiter_create refuses, in this order: a null out, n_streams outside 1 ... 32767, unknown flags, both flags, a sample_rate
+ * that is not finite and > 0, a ceiling_dbtp outside -200 ... 200, a window_samples that is neither 0 nor in 8 ... 1024 (all
+ * CPQ_ERR_INVALID_ARG); a rate that is not a whole number of Hz in 8000 ... 768000 divisible by 10, then flags == 0 (the caller says
+ * where the rows are computed; both CPQ_ERR_UNSUPPORTED); CPQ_LIM_DEVICE without a gfx950 device (CPQ_ERR_NO_DEVICE).
+ * window_samples = 0 takes cpq_limiter_default_window(sample_rate) = round(0.0015 * rate) clamped to 8 ... 1024.  The reason of
+ * a refused create is in cpq_last_error(NULL). */
+#define CPQ_HAS_TRUE_PEAK_LIMITER 1
+#define CPQ_LIM_HOST   1u
+#define CPQ_LIM_DEVICE 2u
+typedef struct cpq_limiter cpq_limiter;
+typedef struct {
+    double  min_gain;           /* the smallest a of the programme's outputs so far; 1.0 where nothing was limited */
+    int64_t limited_samples;    /* outputs with a < 1.0 */
+} cpq_limiter_telemetry;
+int32_t cpq_limiter_default_window(double sample_rate);     /* CPQ_ERR_INVALID_ARG (negative) for a rate not finite and > 0 */
+int32_t cpq_limiter_create(int32_t n_streams, double sample_rate, double ceiling_dbtp, int32_t window_samples, uint32_t flags,
+                           cpq_limiter** out);
+void cpq_limiter_destroy(cpq_limiter* p);
+const char* cpq_limiter_last_error(const cpq_limiter* p);
+/* Device object only (a host object: CPQ_ERR_INVALID_ARG).  Synchronises the stream used so far, then later calls enqueue on
+ * `stream` (a hipStream_t; NULL: the null stream). */
+int32_t cpq_limiter_set_stream(cpq_limiter* p, void* stream);
+/* Back to the start of a programme without the last D outputs: host state only.  The gains stay. */
+int32_t cpq_limiter_reset(cpq_limiter* p);
+int32_t cpq_limiter_latency(const cpq_limiter* p);          /* D = window + 11 samples */
+int32_t cpq_limiter_window(const cpq_limiter* p);
+/* gains[n_streams], the pre-gain of every stream (default 1.0; they stay over flush and reset).  Refused in this order: a null
+ * object (no message) or null gains, a gain that is not finite or is negative (CPQ_ERR_INVALID_ARG), a programme that has
+ * started (CPQ_ERR_NOT_READY: flush or reset first).  On a device object it synchronises the stream. */
+int32_t cpq_limiter_set_gains(cpq_limiter* p, const double* gains);
+/* n_samples more of every programme, device rows in and out, asynchronous on the object's stream: d_in must stay as it is
+ * until that stream has reached the call.  Refused before any state moves, in this order, all CPQ_ERR_INVALID_ARG: a null object
+ * (no message), a host object, a null buffer, n_samples outside 1 ... 2^30, a stride below n_samples, a buffer that is not
+ * 16-byte aligned, rows of d_in and d_out that overlap in part.  In place (d_out == d_in, equal strides) is allowed and costs a
+ * device copy of the call's rows into a buffer of the object, since a tile reads its neighbours' input; apart is the fast path.
+ * Rows move 16 bytes at a time where both strides are even.  CPQ_ERR_OOM / CPQ_ERR_DEVICE: the state is as before the call. */
+int32_t cpq_limiter_process_device(cpq_limiter* p, const double* d_in, int64_t in_stride, double* d_out, int64_t out_stride,
+                                   int32_t n_samples);
+/* The same on host rows, on either object (the device object copies through buffers it owns and synchronises); the same
+ * refusals in the same order without the host-object and alignment rules. */
+int32_t cpq_limiter_process(cpq_limiter* p, const double* in, int64_t in_stride, double* out, int64_t out_stride, int32_t n_samples);
+/* The last D = cpq_limiter_latency outputs of every programme to rows of at least D samples, then the object is at the start of
+ * a new programme (gains and telemetry stay; the next call starts the telemetry over).  Refused in this order, all
+ * CPQ_ERR_INVALID_ARG: a null object, (flush_device) a host object, a null buffer, a stride below D, (flush_device) a buffer that
+ * is not 16-byte aligned. */
+int32_t cpq_limiter_flush_device(cpq_limiter* p, double* d_out, int64_t out_stride);
+int32_t cpq_limiter_flush(cpq_limiter* p, double* out, int64_t out_stride);
+/* out[n_streams]: the telemetry of the programme in progress, or of the one a flush just ended; { 1.0, 0 } after create and
+ * reset.  It counts every output emitted, so it does not depend on how the programme was split into calls.  Synchronises the
+ * object's stream.  CPQ_ERR_INVALID_ARG: a null object or result. */
+int32_t cpq_limiter_read_telemetry(cpq_limiter* p, cpq_limiter_telemetry* out);
+/* Device time of the two launches of the last call of a device object, waiting for them; -1 on a host object or before a call. */
+double cpq_limiter_last_kernel_ms(cpq_limiter* p);
+
 /* ---------------------------------------------------------------- minimum-phase conversion on the device */
 /* cpq_ir_convert_to_minimum_phase for a whole IR library: convertToMinimumPhase (ResampleAndFallback.cpp:333-469) per row (a row
  * is one channel of one IR of n samples), rows of one FFT size N = nextPow2(4 n) batched into one sequence of launches:
