@@ -16,16 +16,21 @@
 //   engine_dither.cpp  dither stage: the fixed 4- and 15-tap and the adaptive lattice noise shaper between the output stage's two halves
 //   engine_meter.cpp  loudness and true-peak metering of the delivered rows
 //   engine_diag.cpp  every cpq_diag_* entry point: single launchers on caller-filled buffers, no engine
-//   engine_score.cpp  cpq_scorer, an object of its own: the fitness function of the adaptive shaper's learner (uses only fail and
-//                    the device buffers of this header)
-//   engine_resample.cpp  cpq_ir_resample / _batch: the device side of the IR sample-rate conversion, no engine (uses only fail and
-//                    the device buffers of this header; design, checks, host path and tail trim are resample_design.cpp's)
+//   engine_score.cpp  cpq_scorer, an object of its own: the fitness function of the adaptive shaper's learner; engine_learn.cpp,
+//                    cpq_learner around it (score_internal.hpp; of this header they use fail, CPQ_TRY and the scorer's tables)
+//   engine_resample.cpp  cpq_ir_resample / _batch: the device side of the IR sample-rate conversion, no engine (uses only fail,
+//                    checkCurrentDevice and CPQ_TRY of this header; design, checks, host path and tail trim are resample_design.cpp's)
 //   engine_minphase.cpp  cpq_ir_minimum_phase / _batch, cpq_ir_prepare_batch: the device side of the minimum-phase conversion, no
 //                    engine; the plan of a call is minphase_plan.hpp's, the host steps around it are ir_ingest.hpp's
+//   engine_src.cpp   cpq_src, an object of its own: streaming sample-rate conversion; the plan of a call is src_plan.hpp's, the
+//                    host object src_host.hpp's
 //   engine_prog.cpp  cpq_loudness, an object of its own: gated programme loudness per stream; the plan of a call and the
-//                    definition are prog_plan.hpp's (uses only fail, checkCurrentDevice and the device buffers of this header)
+//                    definition are prog_plan.hpp's
 //   engine_lim.cpp   cpq_limiter, an object of its own: look-ahead true-peak limiter per stream; the definition and the plan of a
-//                    call are lim_plan.hpp's, the host object lim_host.hpp's (uses only fail, checkCurrentDevice and the device buffers)
+//                    call are lim_plan.hpp's, the host object lim_host.hpp's
+//   object_support.hpp  what four of those objects and the two loader calls share (engine_prog / lim / score / learn /
+//                    resample / minphase.cpp; engine_src.cpp keeps its own copies): failTo, CPQ_OBJ_HIP, the owner of timing events, the row stage, setStream, guardAlloc.
+//                    Of the helpers declared below, cpq_src, cpq_loudness and cpq_limiter use only checkCurrentDevice and CPQ_TRY.
 // The per-stream ramps and fades those files replay on the host (total gain, EQ bypass, mix, latency) are the structs of
 // host_replay.hpp, and so are the EQ's plan of a call (gain segments, bypass classes, band resets, pieces) and the processor-level
 // stage's (who rests, mix prefixes, latency ranges): HIP-free steppers and planners that return plain data; the engine files

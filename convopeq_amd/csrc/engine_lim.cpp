@@ -3,8 +3,8 @@
 // device object (CPQ_LIM_DEVICE) launches lim_kernels.hip's k_lim_apply and k_lim_keep with the launch lim_plan.hpp states from the
 // same plan: this file checks, allocates, launches and copies, and holds no arithmetic of its own.
 //
-// The device object keeps the rules of the device object of cpq_src.  No device-side tables: what the kernels
-// index with arrives by value (the gains are values, not indices).  Cleared at create: hist is zeroed and the gains are uploaded
+// The device object keeps the rules of the device object of cpq_src, with object_support.hpp where they share.
+// No device-side tables: what the kernels index with arrives by value (the gains are values, not indices).  Cleared at create: hist is zeroed and the gains are uploaded
 // synchronously; reset and flush are host state only, since a history extent of 0 means that no history sample is read and the
 // first call of a programme starts the telemetry over.  One stream: both launches of a call go to the object's stream, apply
 // first, and the state advances only after both were enqueued without an error.
@@ -14,6 +14,9 @@
 #include "engine_internal.hpp"
 
 #include "lim_host.hpp"
+#include "object_support.hpp"
+
+using cpqi::failTo;
 
 static_assert(sizeof(cpq_limiter_telemetry) == sizeof(cpq::LimPartial) && offsetof(cpq_limiter_telemetry, limited_samples) == offsetof(cpq::LimPartial, limited),
               "the telemetry is copied out as the kernels fold it");
@@ -29,72 +32,33 @@ struct cpq_limiter {
     cpqi::DeviceBuffer<double> hist, gains;             // [2 S][limHalo(W)], [S]
     cpqi::DeviceBuffer<cpq::LimPartial> tel, part;      // [S], [S][partCap]
     int partCap = 0;
-    cpqi::DeviceBuffer<double> rowsIn, rowsOut;         // [2 S][capIn], [2 S][capOut]: host rows, and the copy of a call in place
-    int capIn = 0, capOut = 0;
-    hipEvent_t ev[2] = {};
+    cpqi::RowStage rowsIn, rowsOut;                     // [2 S][cap]: host rows, and in rowsIn the copy of a call in place
     bool timed = false;
-    ~cpq_limiter()
-    {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    cpqi::TimingEvents<2> ev;                           // the last member: destroyed before the buffers are freed
 };
 
 namespace {
 
-int lfail(cpq_limiter* p, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (p) p->lastError = buf;
-    else return cpqi::fail(nullptr, code, "%s", buf);       // before an object exists: cpq_last_error(NULL) has it
-    return code;
-}
-
-#define CPQ_LIM_HIP(p, call)                                                                          \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) {                                                                    \
-            (void)hipGetLastError();                                                                  \
-            return lfail((p), CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__));      \
-        }                                                                                             \
-    } while (0)
-
 // the refusals of a call, host rows or device rows alike, all before any state moves.  n: the samples a row takes and gives
 int checkRows(cpq_limiter* p, const double* in, int64_t inStride, const double* out, int64_t outStride, int32_t n, bool deviceRows)
 {
-    if (!in || !out) return lfail(p, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (n < 1 || n > cpq::kLimMaxCall) return lfail(p, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, cpq::kLimMaxCall);
-    if (inStride < n || outStride < n)
-        return lfail(p, CPQ_ERR_INVALID_ARG, "row strides %lld and %lld, rows of %d", (long long)inStride, (long long)outStride, n);
+    CPQ_TRY(cpqi::checkRowPair(&p->lastError, in, inStride, out, outStride, n, cpq::kLimMaxCall, deviceRows));
     const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
-    if (deviceRows && ((a | b) & 15u)) return lfail(p, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
-    if (((a | b) & 7u) || cpq::limRowsOverlap(a / 8, inStride, b / 8, outStride, 2 * p->streams, n))
-        return lfail(p, CPQ_ERR_INVALID_ARG, "input and output rows overlap in part: in place takes the same pointer and stride");
+    if (((a | b) & 7u) || cpq::progApplyOverlap(a / 8, inStride, b / 8, outStride, 2 * p->streams, n))
+        return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, cpqi::kRowsOverlap);
     return CPQ_OK;
 }
 
 int checkFlush(cpq_limiter* p, const double* out, int64_t outStride, bool deviceRows)
 {
-    if (!out) return lfail(p, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (outStride < cpq::limD(p->W)) return lfail(p, CPQ_ERR_INVALID_ARG, "row stride %lld below the %d samples of a flush", (long long)outStride, cpq::limD(p->W));
-    if (deviceRows && (reinterpret_cast<uintptr_t>(out) & 15u)) return lfail(p, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    if (!out) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (outStride < cpq::limD(p->W)) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "row stride %lld below the %d samples of a flush", (long long)outStride, cpq::limD(p->W));
+    if (deviceRows && (reinterpret_cast<uintptr_t>(out) & 15u)) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
     return CPQ_OK;
 }
 
-// buf to rows of at least n samples, an even count; nothing in flight reads the allocation that goes
-int growRows(cpq_limiter* p, cpqi::DeviceBuffer<double>& buf, int& cap, int n)
-{
-    const int need = (n + 1) & ~1;
-    if (need <= cap) return CPQ_OK;
-    CPQ_LIM_HIP(p, hipStreamSynchronize(p->stream));
-    if (cpqi::grow(nullptr, buf, cap, need, 2 * (size_t)p->streams, "row buffer") != CPQ_OK)
-        return lfail(p, CPQ_ERR_OOM, "row buffer of %d samples could not be allocated", need);
-    return CPQ_OK;
-}
+// a stage to rows of at least n samples, an even count: the wide path of the kernels wants even strides
+int growRows(cpq_limiter* p, cpqi::RowStage& rows, int n) { return rows.ensure(&p->lastError, p->stream, (n + 1) & ~1); }
 
 // a checked call on device rows that do not overlap: enqueued on the object's stream, the state advanced once everything was
 int runDevice(cpq_limiter* p, const double* dIn, int64_t inStride, double* dOut, int64_t outStride, int n, bool flush)
@@ -102,16 +66,16 @@ int runDevice(cpq_limiter* p, const double* dIn, int64_t inStride, double* dOut,
     const cpq::LimCall call = cpq::limPlan(p->W, p->h.s, n, flush);
     const int tiles = (call.nOut + cpq::kLimTile - 1) / cpq::kLimTile;
     if (tiles > p->partCap) {
-        CPQ_LIM_HIP(p, hipStreamSynchronize(p->stream));
+        CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
         if (cpqi::grow(nullptr, p->part, p->partCap, tiles, (size_t)p->streams, "tile partials") != CPQ_OK)
-            return lfail(p, CPQ_ERR_OOM, "the partials of %d tiles could not be allocated", tiles);
+            return failTo(&p->lastError, CPQ_ERR_OOM, "the partials of %d tiles could not be allocated", tiles);
     }
     const cpq::LimLaunch a = cpq::limLaunch(p->W, p->mask, p->c, call, p->streams, inStride, outStride, p->partCap);
-    CPQ_LIM_HIP(p, hipEventRecord(p->ev[0], p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipEventRecord(p->ev[0], p->stream));
     cpq::launch_lim_apply(p->stream, p->hist, p->gains, dIn, dOut, p->part, a);
     cpq::launch_lim_keep(p->stream, p->hist, p->gains, dIn, p->part, p->tel, a);
-    CPQ_LIM_HIP(p, hipGetLastError());
-    CPQ_LIM_HIP(p, hipEventRecord(p->ev[1], p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipGetLastError());
+    CPQ_OBJ_HIP(&p->lastError, hipEventRecord(p->ev[1], p->stream));
     p->h.s = call.next;
     p->telValid = true;
     p->timed = true;
@@ -122,27 +86,32 @@ int runDevice(cpq_limiter* p, const double* dIn, int64_t inStride, double* dOut,
 int runDeviceRows(cpq_limiter* p, const double* dIn, int64_t inStride, double* dOut, int64_t outStride, int n)
 {
     if (dIn != dOut) return runDevice(p, dIn, inStride, dOut, outStride, n, false);
-    CPQ_TRY(growRows(p, p->rowsIn, p->capIn, n));
-    CPQ_LIM_HIP(p, hipMemcpy2DAsync(p->rowsIn, (size_t)p->capIn * sizeof(double), dIn, (size_t)inStride * sizeof(double), (size_t)n * sizeof(double),
-                                    2 * (size_t)p->streams, hipMemcpyDeviceToDevice, p->stream));
-    return runDevice(p, p->rowsIn, p->capIn, dOut, outStride, n, false);
+    CPQ_TRY(growRows(p, p->rowsIn, n));
+    CPQ_TRY(p->rowsIn.upload(&p->lastError, dIn, inStride, n, hipMemcpyDeviceToDevice, p->stream));
+    return runDevice(p, p->rowsIn.buf, p->rowsIn.cap, dOut, outStride, n, false);
 }
 
 // host rows through the object's buffers; in: null at a flush
 int runDeviceHostRows(cpq_limiter* p, const double* in, int64_t inStride, double* out, int64_t outStride, int n, bool flush)
 {
-    const size_t rows = 2 * (size_t)p->streams;
     const int nOut = flush ? cpq::limD(p->W) : n;
-    if (!flush) CPQ_TRY(growRows(p, p->rowsIn, p->capIn, n));
-    CPQ_TRY(growRows(p, p->rowsOut, p->capOut, nOut));
-    if (!flush)
-        CPQ_LIM_HIP(p, hipMemcpy2DAsync(p->rowsIn, (size_t)p->capIn * sizeof(double), in, (size_t)inStride * sizeof(double), (size_t)n * sizeof(double),
-                                        rows, hipMemcpyHostToDevice, p->stream));
-    CPQ_TRY(runDevice(p, flush ? nullptr : p->rowsIn.get(), p->capIn, p->rowsOut, p->capOut, n, flush));
-    CPQ_LIM_HIP(p, hipMemcpy2DAsync(out, (size_t)outStride * sizeof(double), p->rowsOut, (size_t)p->capOut * sizeof(double), (size_t)nOut * sizeof(double),
-                                    rows, hipMemcpyDeviceToHost, p->stream));
-    CPQ_LIM_HIP(p, hipStreamSynchronize(p->stream));
+    if (!flush) CPQ_TRY(growRows(p, p->rowsIn, n));
+    CPQ_TRY(growRows(p, p->rowsOut, nOut));
+    if (!flush) CPQ_TRY(p->rowsIn.upload(&p->lastError, in, inStride, n, hipMemcpyHostToDevice, p->stream));
+    CPQ_TRY(runDevice(p, flush ? nullptr : p->rowsIn.buf.get(), p->rowsIn.cap, p->rowsOut.buf, p->rowsOut.cap, n, flush));
+    CPQ_TRY(p->rowsOut.download(&p->lastError, out, outStride, nOut, hipMemcpyDeviceToHost, p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
     return CPQ_OK;
+}
+
+// the host object's rows
+int hostProcess(cpq_limiter* p, const double* in, int64_t inStride, int n, double* out, int64_t outStride, bool flush)
+{
+    return cpqi::guardAlloc(&p->lastError, [&] {
+        p->h.process(in, inStride, n, out, outStride, flush);
+        p->telValid = true;
+        return (int)CPQ_OK;
+    });
 }
 
 int createDevice(cpq_limiter* p)
@@ -150,9 +119,9 @@ int createDevice(cpq_limiter* p)
     const size_t S = (size_t)p->streams;
     CPQ_TRY(cpqi::allocAll(nullptr, { { p->hist, 2 * S * (size_t)cpq::limHalo(p->W), true }, { p->gains, S }, { p->tel, S, true } },
                            "history of %d streams at a window of %d could not be allocated", p->streams, p->W));
-    for (auto& e : p->ev) CPQ_LIM_HIP(nullptr, hipEventCreate(&e));
-    CPQ_LIM_HIP(nullptr, hipMemcpy(p->gains, p->h.gains.data(), S * sizeof(double), hipMemcpyHostToDevice));
-    CPQ_LIM_HIP(nullptr, hipDeviceSynchronize());       // the clears have run before the first call, whatever its stream
+    CPQ_TRY(p->ev.create(nullptr));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(p->gains, p->h.gains.data(), S * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipDeviceSynchronize());       // the clears have run before the first call, whatever its stream
     return CPQ_OK;
 }
 
@@ -168,19 +137,19 @@ int32_t cpq_limiter_default_window(double sample_rate)
 
 int32_t cpq_limiter_create(int32_t n_streams, double sample_rate, double ceiling_dbtp, int32_t window_samples, uint32_t flags, cpq_limiter** out)
 {
-    if (!out) return lfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    if (!out) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
-    if (n_streams < 1 || n_streams > 32767) return lfail(nullptr, CPQ_ERR_INVALID_ARG, "n_streams %d outside 1..32767", n_streams);
-    if (flags & ~(uint32_t)(CPQ_LIM_HOST | CPQ_LIM_DEVICE)) return lfail(nullptr, CPQ_ERR_INVALID_ARG, "unknown flags");
-    if ((flags & CPQ_LIM_HOST) && (flags & CPQ_LIM_DEVICE)) return lfail(nullptr, CPQ_ERR_INVALID_ARG, "CPQ_LIM_HOST and CPQ_LIM_DEVICE exclude each other");
-    if (!(sample_rate > 0.0) || !std::isfinite(sample_rate)) return lfail(nullptr, CPQ_ERR_INVALID_ARG, "sample_rate must be finite and > 0");
-    if (!(ceiling_dbtp >= -200.0) || !(ceiling_dbtp <= 200.0)) return lfail(nullptr, CPQ_ERR_INVALID_ARG, "ceiling_dbtp outside -200..200");
+    if (n_streams < 1 || n_streams > 32767) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "n_streams %d outside 1..32767", n_streams);
+    if (flags & ~(uint32_t)(CPQ_LIM_HOST | CPQ_LIM_DEVICE)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "unknown flags");
+    if ((flags & CPQ_LIM_HOST) && (flags & CPQ_LIM_DEVICE)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "CPQ_LIM_HOST and CPQ_LIM_DEVICE exclude each other");
+    if (!(sample_rate > 0.0) || !std::isfinite(sample_rate)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "sample_rate must be finite and > 0");
+    if (!(ceiling_dbtp >= -200.0) || !(ceiling_dbtp <= 200.0)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "ceiling_dbtp outside -200..200");
     if (window_samples != 0 && (window_samples < cpq::kLimMinWindow || window_samples > cpq::kLimMaxWindow))
-        return lfail(nullptr, CPQ_ERR_INVALID_ARG, "window_samples %d is neither 0 nor in %d..%d", window_samples, cpq::kLimMinWindow, cpq::kLimMaxWindow);
+        return failTo(nullptr, CPQ_ERR_INVALID_ARG, "window_samples %d is neither 0 nor in %d..%d", window_samples, cpq::kLimMinWindow, cpq::kLimMaxWindow);
     if (!cpq::progHop(sample_rate))
-        return lfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
-    if (!flags) return lfail(nullptr, CPQ_ERR_UNSUPPORTED, "say CPQ_LIM_HOST or CPQ_LIM_DEVICE");
-    try {
+        return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
+    if (!flags) return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "say CPQ_LIM_HOST or CPQ_LIM_DEVICE");
+    return cpqi::guardAlloc(nullptr, [&]() -> int {
         std::unique_ptr<cpq_limiter, void (*)(cpq_limiter*)> p(new cpq_limiter(), cpq_limiter_destroy);
         p->streams = n_streams;
         p->rate = sample_rate;
@@ -189,6 +158,7 @@ int32_t cpq_limiter_create(int32_t n_streams, double sample_rate, double ceiling
         p->c = std::pow(10.0, ceiling_dbtp / 20.0);
         p->device = (flags & CPQ_LIM_DEVICE) != 0;
         p->h.init(p->W, p->mask, p->c, n_streams);
+        p->rowsIn.rows = p->rowsOut.rows = 2 * (size_t)n_streams;
         if (p->device) {
             p->h.hist = std::vector<double>();          // the history is on the device
             CPQ_TRY(cpqi::checkCurrentDevice());
@@ -196,9 +166,7 @@ int32_t cpq_limiter_create(int32_t n_streams, double sample_rate, double ceiling
         }
         *out = p.release();
         return CPQ_OK;
-    } catch (const std::exception&) {
-        return lfail(nullptr, CPQ_ERR_OOM, "host allocation failed");
-    }
+    });
 }
 
 void cpq_limiter_destroy(cpq_limiter* p) { delete p; }
@@ -208,10 +176,8 @@ const char* cpq_limiter_last_error(const cpq_limiter* p) { return p ? p->lastErr
 int32_t cpq_limiter_set_stream(cpq_limiter* p, void* stream)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!p->device) return lfail(p, CPQ_ERR_INVALID_ARG, "cpq_limiter_set_stream on a host object");
-    CPQ_LIM_HIP(p, hipStreamSynchronize(p->stream));        // what was enqueued has run before a call on the new stream touches hist
-    p->stream = (hipStream_t)stream;
-    return CPQ_OK;
+    if (!p->device) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "cpq_limiter_set_stream on a host object");
+    return cpqi::setStream(&p->lastError, p->stream, stream);
 }
 
 int32_t cpq_limiter_reset(cpq_limiter* p)
@@ -229,14 +195,14 @@ int32_t cpq_limiter_window(const cpq_limiter* p) { return p ? p->W : CPQ_ERR_INV
 int32_t cpq_limiter_set_gains(cpq_limiter* p, const double* gains)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!gains) return lfail(p, CPQ_ERR_INVALID_ARG, "null gains");
+    if (!gains) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "null gains");
     for (int s = 0; s < p->streams; ++s)
-        if (!std::isfinite(gains[s]) || gains[s] < 0.0) return lfail(p, CPQ_ERR_INVALID_ARG, "the gain of stream %d is not finite and >= 0", s);
+        if (!std::isfinite(gains[s]) || gains[s] < 0.0) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "the gain of stream %d is not finite and >= 0", s);
     if (p->h.s.pos)
-        return lfail(p, CPQ_ERR_NOT_READY, "gains are set at the start of a programme: %lld samples were taken; flush or reset first", p->h.s.pos);
+        return failTo(&p->lastError, CPQ_ERR_NOT_READY, "gains are set at the start of a programme: %lld samples were taken; flush or reset first", p->h.s.pos);
     if (p->device) {
-        CPQ_LIM_HIP(p, hipStreamSynchronize(p->stream));    // the last programme's launches have read the gains they ran with
-        CPQ_LIM_HIP(p, hipMemcpy(p->gains, gains, (size_t)p->streams * sizeof(double), hipMemcpyHostToDevice));
+        CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));    // the last programme's launches have read the gains they ran with
+        CPQ_OBJ_HIP(&p->lastError, hipMemcpy(p->gains, gains, (size_t)p->streams * sizeof(double), hipMemcpyHostToDevice));
     }
     std::copy(gains, gains + p->streams, p->h.gains.begin());
     return CPQ_OK;
@@ -245,7 +211,7 @@ int32_t cpq_limiter_set_gains(cpq_limiter* p, const double* gains)
 int32_t cpq_limiter_process_device(cpq_limiter* p, const double* d_in, int64_t in_stride, double* d_out, int64_t out_stride, int32_t n_samples)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!p->device) return lfail(p, CPQ_ERR_INVALID_ARG, "cpq_limiter_process_device on a host object");
+    if (!p->device) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "cpq_limiter_process_device on a host object");
     CPQ_TRY(checkRows(p, d_in, in_stride, d_out, out_stride, n_samples, true));
     return runDeviceRows(p, d_in, in_stride, d_out, out_stride, n_samples);
 }
@@ -255,19 +221,13 @@ int32_t cpq_limiter_process(cpq_limiter* p, const double* in, int64_t in_stride,
     if (!p) return CPQ_ERR_INVALID_ARG;
     CPQ_TRY(checkRows(p, in, in_stride, out, out_stride, n_samples, false));
     if (p->device) return runDeviceHostRows(p, in, in_stride, out, out_stride, n_samples, false);
-    try {
-        p->h.process(in, in_stride, n_samples, out, out_stride, false);
-        p->telValid = true;
-        return CPQ_OK;
-    } catch (const std::exception&) {
-        return lfail(p, CPQ_ERR_OOM, "host allocation failed");
-    }
+    return hostProcess(p, in, in_stride, n_samples, out, out_stride, false);
 }
 
 int32_t cpq_limiter_flush_device(cpq_limiter* p, double* d_out, int64_t out_stride)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!p->device) return lfail(p, CPQ_ERR_INVALID_ARG, "cpq_limiter_flush_device on a host object");
+    if (!p->device) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "cpq_limiter_flush_device on a host object");
     CPQ_TRY(checkFlush(p, d_out, out_stride, true));
     return runDevice(p, nullptr, 0, d_out, out_stride, 0, true);
 }
@@ -277,22 +237,16 @@ int32_t cpq_limiter_flush(cpq_limiter* p, double* out, int64_t out_stride)
     if (!p) return CPQ_ERR_INVALID_ARG;
     CPQ_TRY(checkFlush(p, out, out_stride, false));
     if (p->device) return runDeviceHostRows(p, nullptr, 0, out, out_stride, 0, true);
-    try {
-        p->h.process(nullptr, 0, 0, out, out_stride, true);
-        p->telValid = true;
-        return CPQ_OK;
-    } catch (const std::exception&) {
-        return lfail(p, CPQ_ERR_OOM, "host allocation failed");
-    }
+    return hostProcess(p, nullptr, 0, 0, out, out_stride, true);
 }
 
 int32_t cpq_limiter_read_telemetry(cpq_limiter* p, cpq_limiter_telemetry* out)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!out) return lfail(p, CPQ_ERR_INVALID_ARG, "null result");
-    if (p->device) CPQ_LIM_HIP(p, hipStreamSynchronize(p->stream));
+    if (!out) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "null result");
+    if (p->device) CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
     if (p->device && p->telValid) {
-        CPQ_LIM_HIP(p, hipMemcpy(out, p->tel, (size_t)p->streams * sizeof(cpq::LimPartial), hipMemcpyDeviceToHost));
+        CPQ_OBJ_HIP(&p->lastError, hipMemcpy(out, p->tel, (size_t)p->streams * sizeof(cpq::LimPartial), hipMemcpyDeviceToHost));
         return CPQ_OK;
     }
     for (int s = 0; s < p->streams; ++s) {
@@ -305,12 +259,11 @@ int32_t cpq_limiter_read_telemetry(cpq_limiter* p, cpq_limiter_telemetry* out)
 double cpq_limiter_last_kernel_ms(cpq_limiter* p)
 {
     if (!p || !p->device || !p->timed) return -1.0;
-    float ms = 0.0f;
-    if (hipEventSynchronize(p->ev[1]) != hipSuccess || hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) != hipSuccess) {
+    if (hipEventSynchronize(p->ev[1]) != hipSuccess) {
         (void)hipGetLastError();
         return -1.0;
     }
-    return ms;
+    return p->ev.elapsed(0, 1);
 }
 
 }  // extern "C"

@@ -11,26 +11,11 @@
 // against the cap (at most 160 KB).
 #include "engine_internal.hpp"
 #include "ir_ingest.hpp"
+#include "object_support.hpp"
 
 namespace {
 
 thread_local double g_lastKernelMs = -1.0;
-
-#define CPQ_MP_HIP(call)                                                                                  \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess)                                                                          \
-            return cpqi::fail(nullptr, CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__)); \
-    } while (0)
-
-struct Events {
-    hipEvent_t ev[2] = {};
-    ~Events()
-    {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
 
 bool validBuffer(const cpq_ir_buffer* b) { return b && b->data && b->n_channels > 0 && b->n_samples > 0; }
 
@@ -38,7 +23,7 @@ const double2* c2(const double* p) { return reinterpret_cast<const double2*>(p);
 
 // one chunk of a group: its rows up, the plan's launches, the rows down into out[.]; marked[i] is set where a row of IR i was flagged
 int runChunk(const cpq_ir_buffer* const* in, const cpq::MinphaseGroup& g, const cpq::MinphaseChunk& c, cpq::MinphaseTables tables,
-             cpq_ir_buffer* out, std::vector<char>& marked, Events& t, double& kernelMs)
+             cpq_ir_buffer* out, std::vector<char>& marked, const cpqi::TimingEvents<2>& t, double& kernelMs)
 {
     std::vector<cpq::MinphaseRow> rows(c.count);
     long long off = 0;
@@ -54,32 +39,32 @@ int runChunk(const cpq_ir_buffer* const* in, const cpq::MinphaseGroup& g, const 
     const size_t nZ = big ? c.count << g.log2n : 1;
     CPQ_TRY(cpqi::allocAll(nullptr, { { x, (size_t)c.samples }, { y, (size_t)c.samples }, { z, nZ }, { dRows, c.count }, { flags, c.count } },
                            "minimum-phase buffers for %zu rows of %lld points could not be allocated", c.count, 1LL << g.log2n));
-    CPQ_MP_HIP(hipMemcpy(dRows, rows.data(), rows.size() * sizeof(rows[0]), hipMemcpyHostToDevice));
-    CPQ_MP_HIP(hipMemset(flags, 0, c.count * sizeof(int)));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(dRows, rows.data(), rows.size() * sizeof(rows[0]), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipMemset(flags, 0, c.count * sizeof(int)));
     std::vector<double> host((size_t)c.samples);          // the rows back to back: one copy each way
     for (size_t r = 0; r < c.count; ++r) {
         const cpq::MinphaseRowRef& ref = g.rows[c.first + r];
         std::memcpy(host.data() + rows[r].off, in[ref.ir]->data + (size_t)ref.ch * (size_t)ref.n, (size_t)ref.n * sizeof(double));
     }
-    CPQ_MP_HIP(hipMemcpy(x, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
-    CPQ_MP_HIP(hipEventRecord(t.ev[0], nullptr));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(x, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipEventRecord(t[0], nullptr));
     for (const cpq::MinphaseLaunch& l : cpq::minphaseLaunches(g, (long long)c.count)) {
         if (l.kernel == cpq::kMinphaseKSmall) cpq::launch_minphase_small(nullptr, x, y, dRows, flags, tables, g.log2n, (long long)c.count);
         else if (l.kernel == cpq::kMinphaseKCols)
             cpq::launch_cfft_cols(nullptr, l.op, z, x, y, dRows, flags, tables, g.log2n1, g.log2n2, (long long)c.count);
         else cpq::launch_cfft_rows(nullptr, l.op, z, flags, tables, g.log2n1, g.log2n2, (long long)c.count, 1.0);
-        CPQ_MP_HIP(hipGetLastError());
+        CPQ_OBJ_HIP(nullptr, hipGetLastError());
     }
-    CPQ_MP_HIP(hipEventRecord(t.ev[1], nullptr));
+    CPQ_OBJ_HIP(nullptr, hipEventRecord(t[1], nullptr));
     std::vector<int> hostFlags(c.count);
-    CPQ_MP_HIP(hipMemcpy(host.data(), y, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(host.data(), y, host.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t r = 0; r < c.count; ++r) {
         const cpq::MinphaseRowRef& ref = g.rows[c.first + r];
         std::memcpy(out[ref.ir].data + (size_t)ref.ch * (size_t)ref.n, host.data() + rows[r].off, (size_t)ref.n * sizeof(double));
     }
-    CPQ_MP_HIP(hipMemcpy(hostFlags.data(), flags, c.count * sizeof(int), hipMemcpyDeviceToHost));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(hostFlags.data(), flags, c.count * sizeof(int), hipMemcpyDeviceToHost));
     float ms = 0.0f;
-    CPQ_MP_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    CPQ_OBJ_HIP(nullptr, hipEventElapsedTime(&ms, t[0], t[1]));
     kernelMs += ms;
     for (size_t r = 0; r < c.count; ++r)
         if (hostFlags[r]) marked[(size_t)g.rows[c.first + r].ir] = 1;
@@ -116,12 +101,12 @@ int minphaseBatch(const cpq_ir_buffer* const* in, int n, long long workspace, cp
         if (!out[i].data) return cpqi::fail(nullptr, CPQ_ERR_OOM, "IR %d: host allocation of the converted IR failed", i);
     }
 
-    Events t;
-    for (auto& e : t.ev) CPQ_MP_HIP(hipEventCreate(&e));
+    cpqi::TimingEvents<2> t;
+    CPQ_TRY(t.create(nullptr));
     const std::vector<double> roots = cpq::minphaseStageRoots();
     cpqi::DeviceBuffer<double> dRoots;
     CPQ_TRY(cpqi::allocAll(nullptr, { { dRoots, roots.size() } }, "the twiddle table could not be allocated"));
-    CPQ_MP_HIP(hipMemcpy(dRoots, roots.data(), roots.size() * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(dRoots, roots.data(), roots.size() * sizeof(double), hipMemcpyHostToDevice));
     std::vector<char> marked((size_t)n, 0);
     double kernelMs = 0.0;
     for (size_t g = 0; g < groups.size(); ++g) {
@@ -130,8 +115,8 @@ int minphaseBatch(const cpq_ir_buffer* const* in, int n, long long workspace, cp
         cpqi::DeviceBuffer<double> dHi, dLo;
         CPQ_TRY(cpqi::allocAll(nullptr, { { dHi, hi.size() }, { dLo, lo.size() } }, "the twiddle tables of %lld points could not be allocated",
                                1LL << groups[g].log2n));
-        CPQ_MP_HIP(hipMemcpy(dHi, hi.data(), hi.size() * sizeof(double), hipMemcpyHostToDevice));
-        CPQ_MP_HIP(hipMemcpy(dLo, lo.data(), lo.size() * sizeof(double), hipMemcpyHostToDevice));
+        CPQ_OBJ_HIP(nullptr, hipMemcpy(dHi, hi.data(), hi.size() * sizeof(double), hipMemcpyHostToDevice));
+        CPQ_OBJ_HIP(nullptr, hipMemcpy(dLo, lo.data(), lo.size() * sizeof(double), hipMemcpyHostToDevice));
         const cpq::MinphaseTables tables{ c2(dRoots), c2(dHi), c2(dLo) };
         for (const cpq::MinphaseChunk& c : chunks[g]) CPQ_TRY(runChunk(in, groups[g], c, tables, out, marked, t, kernelMs));
     }
@@ -190,12 +175,7 @@ int32_t cpq_ir_minimum_phase_batch(const cpq_ir_buffer* const* in, int32_t n, in
     if (n < 0 || workspace_bytes < 0) return cpqi::fail(nullptr, CPQ_ERR_INVALID_ARG, "a negative count or workspace_bytes");
     if (n > 0 && (!in || !out || !status)) return cpqi::fail(nullptr, CPQ_ERR_INVALID_ARG, "null buffer list, output or status");
     for (int i = 0; i < n; ++i) std::memset(&out[i], 0, sizeof(out[i]));
-    int rc;
-    try {
-        rc = minphaseBatch(in, n, workspace_bytes, out, status);
-    } catch (const std::exception&) {
-        rc = cpqi::fail(nullptr, CPQ_ERR_OOM, "host allocation failed");
-    }
+    const int rc = cpqi::guardAlloc(nullptr, [&] { return minphaseBatch(in, n, workspace_bytes, out, status); });
     if (rc != CPQ_OK) freeAll(out, n);
     return rc;
 }
@@ -218,12 +198,7 @@ int32_t cpq_ir_prepare_batch(const cpq_ir_buffer* const* loaded, int32_t n, doub
     if (n < 0) return cpqi::fail(nullptr, CPQ_ERR_INVALID_ARG, "a negative count");
     if (n > 0 && (!loaded || !out)) return cpqi::fail(nullptr, CPQ_ERR_INVALID_ARG, "null buffer list or output");
     for (int i = 0; i < n; ++i) std::memset(&out[i], 0, sizeof(out[i]));
-    int rc;
-    try {
-        rc = prepareBatch(loaded, n, sample_rate, target_ir_length_sec, phase_mode, current_ir, current_scale, out);
-    } catch (const std::exception&) {
-        rc = cpqi::fail(nullptr, CPQ_ERR_OOM, "host allocation failed");
-    }
+    const int rc = cpqi::guardAlloc(nullptr, [&] { return prepareBatch(loaded, n, sample_rate, target_ir_length_sec, phase_mode, current_ir, current_scale, out); });
     if (rc != CPQ_OK)
         for (int i = 0; i < n; ++i) {
             cpq_ir_prepared_free(&out[i]);

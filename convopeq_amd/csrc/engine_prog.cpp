@@ -1,11 +1,15 @@
 // engine_prog.cpp -- cpq_loudness: gated programme loudness (EBU R 128) per stream, an object of its own beside cpq_engine.  The
 // definition and the plan of a call are prog_plan.hpp's, the kernels prog_kernels.hip's: this file checks, allocates, launches and
-// copies, and holds no arithmetic of its own.  The rules are the device object of cpq_src's.  No device-side
-// tables of the call: what the kernels index with arrives by value.  Zeroed at create: hop sums, partial hops and filter states
+// copies, and holds no arithmetic of its own.  The rules are the device object of cpq_src's, and what can be
+// shared of keeping them is object_support.hpp's.  No device-side tables of the call: what the kernels index with arrives by value.  Zeroed at create: hop sums, partial hops and filter states
 // are cleared synchronously before create returns.  One stream: everything is enqueued on the object's stream, and the position
 // advances only after the launch was enqueued without an error.  With cpq_loudness_set_true_peak a call also enqueues k_prog_peak
 // behind k_prog_hops (the position advances after both); cpq_loudness_apply_device touches no programme state.
 #include "engine_internal.hpp"
+
+#include "object_support.hpp"
+
+using cpqi::failTo;
 
 struct cpq_loudness {
     cpq_loudness_desc desc{};
@@ -15,8 +19,7 @@ struct cpq_loudness {
     hipStream_t stream = nullptr;
     cpqi::DeviceBuffer<double> tab, state, part, hops;      // section tables; [2 S][8]; [2 S]; [S][maxHops]
     cpqi::DeviceBuffer<cpq::ProgRecord> rec;                // [S]
-    cpqi::DeviceBuffer<double> rows;                        // [2 S][rowsCap]: the host rows of cpq_loudness_process
-    int rowsCap = 0;
+    cpqi::RowStage rows;                                    // [2 S][rows.cap]: the host rows of cpq_loudness_process
     cpqi::DeviceBuffer<double> pk;                          // [2 S][kPeakState]: true peak per programme, allocated by its switch
     bool peakOn = false;
     cpqi::DeviceBuffer<double> gains;                       // [S]: the gains of cpq_loudness_apply_device
@@ -24,50 +27,29 @@ struct cpq_loudness {
 
 namespace {
 
-int pfail(cpq_loudness* p, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (p) p->lastError = buf;
-    else return cpqi::fail(nullptr, code, "%s", buf);       // before an object exists: cpq_last_error(NULL) has it
-    return code;
-}
-
-#define CPQ_PROG_HIP(p, call)                                                                         \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) {                                                                    \
-            (void)hipGetLastError();                                                                  \
-            return pfail((p), CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__));      \
-        }                                                                                             \
-    } while (0)
-
 constexpr size_t kTabDoubles = 2 * (size_t)cpq::kMeterSectionDoubles;
 
 // the refusals of a call, host rows or device rows alike, all before any state moves; c: the plan of the call
 int checkCall(cpq_loudness* p, const double* rows, int64_t stride, int32_t n, cpq::ProgCall& c)
 {
-    if (!rows) return pfail(p, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (n < 1 || n > cpq::kProgMaxCall) return pfail(p, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, cpq::kProgMaxCall);
-    if (stride < n) return pfail(p, CPQ_ERR_INVALID_ARG, "row stride %lld shorter than its row of %d", (long long)stride, n);
-    if (reinterpret_cast<uintptr_t>(rows) & 15u) return pfail(p, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
+    if (!rows) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (n < 1 || n > cpq::kProgMaxCall) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n, cpq::kProgMaxCall);
+    if (stride < n) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "row stride %lld shorter than its row of %d", (long long)stride, n);
+    if (reinterpret_cast<uintptr_t>(rows) & 15u) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
     if (!cpq::progPlan(p->pos, n, p->H, p->maxHops, p->desc.n_streams, stride, c))
-        return pfail(p, CPQ_ERR_UNSUPPORTED, "%d samples after %lld pass the %d hops of max_seconds=%g", n, p->pos, p->maxHops, p->desc.max_seconds);
+        return failTo(&p->lastError, CPQ_ERR_UNSUPPORTED, "%d samples after %lld pass the %d hops of max_seconds=%g", n, p->pos, p->maxHops, p->desc.max_seconds);
     return CPQ_OK;
 }
 
 int runDevice(cpq_loudness* p, const double* dRows, const cpq::ProgCall& c)
 {
     cpq::launch_prog_hops(p->stream, dRows, c, p->tab, p->state, p->part, p->hops);
-    CPQ_PROG_HIP(p, hipGetLastError());
+    CPQ_OBJ_HIP(&p->lastError, hipGetLastError());
     if (p->peakOn) {
         cpq::PeakCall k;
         k.n = c.n; k.mask = cpq::progPeakMask(p->desc.sample_rate); k.rows = 2 * c.streams; k.stride = c.stride;
         cpq::launch_prog_peak(p->stream, dRows, k, p->pk);
-        CPQ_PROG_HIP(p, hipGetLastError());
+        CPQ_OBJ_HIP(&p->lastError, hipGetLastError());
     }
     p->pos += c.n;
     return CPQ_OK;
@@ -75,11 +57,11 @@ int runDevice(cpq_loudness* p, const double* dRows, const cpq::ProgCall& c)
 
 int clearState(cpq_loudness* p)
 {
-    CPQ_PROG_HIP(p, hipMemsetAsync(p->state, 0, p->state.count() * sizeof(double), p->stream));
-    CPQ_PROG_HIP(p, hipMemsetAsync(p->part, 0, p->part.count() * sizeof(double), p->stream));
-    CPQ_PROG_HIP(p, hipMemsetAsync(p->hops, 0, p->hops.count() * sizeof(double), p->stream));
-    if (p->pk) CPQ_PROG_HIP(p, hipMemsetAsync(p->pk, 0, p->pk.count() * sizeof(double), p->stream));
-    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipMemsetAsync(p->state, 0, p->state.count() * sizeof(double), p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipMemsetAsync(p->part, 0, p->part.count() * sizeof(double), p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipMemsetAsync(p->hops, 0, p->hops.count() * sizeof(double), p->stream));
+    if (p->pk) CPQ_OBJ_HIP(&p->lastError, hipMemsetAsync(p->pk, 0, p->pk.count() * sizeof(double), p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
     p->pos = 0;
     return CPQ_OK;
 }
@@ -95,8 +77,8 @@ int createDevice(cpq_loudness* p)
     cpq::meterKWeighting(p->desc.sample_rate, pre, rlb);
     cpq::meterSectionTables(pre, tab.data());
     cpq::meterSectionTables(rlb, tab.data() + cpq::kMeterSectionDoubles);
-    CPQ_PROG_HIP(nullptr, hipMemcpy(p->tab, tab.data(), kTabDoubles * sizeof(double), hipMemcpyHostToDevice));
-    CPQ_PROG_HIP(nullptr, hipDeviceSynchronize());      // the clears have run before the first call, whatever its stream
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(p->tab, tab.data(), kTabDoubles * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipDeviceSynchronize());      // the clears have run before the first call, whatever its stream
     return CPQ_OK;
 }
 
@@ -106,29 +88,28 @@ extern "C" {
 
 int32_t cpq_loudness_create(const cpq_loudness_desc* d, cpq_loudness** out)
 {
-    if (!d || !out) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    if (!d || !out) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
-    if (d->n_streams < 1 || d->n_streams > 32767) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "n_streams %d outside 1..32767", d->n_streams);
-    if (d->flags) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "unknown flags");
-    if (!(d->sample_rate > 0.0) || !std::isfinite(d->sample_rate)) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "sample_rate must be finite and > 0");
+    if (d->n_streams < 1 || d->n_streams > 32767) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "n_streams %d outside 1..32767", d->n_streams);
+    if (d->flags) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "unknown flags");
+    if (!(d->sample_rate > 0.0) || !std::isfinite(d->sample_rate)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "sample_rate must be finite and > 0");
     const long long maxHops = cpq::progMaxHops(d->max_seconds);
-    if (!maxHops) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "max_seconds must be finite and > 0");
+    if (!maxHops) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "max_seconds must be finite and > 0");
     const int H = cpq::progHop(d->sample_rate);
-    if (!H) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", d->sample_rate);
+    if (!H) return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", d->sample_rate);
     if (cpq::progShortCount(maxHops) > cpq::kProgSortMax)
-        return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "max_seconds=%g holds more than %d short-term blocks at the 1 s step", d->max_seconds, cpq::kProgSortMax);
-    try {
+        return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "max_seconds=%g holds more than %d short-term blocks at the 1 s step", d->max_seconds, cpq::kProgSortMax);
+    return cpqi::guardAlloc(nullptr, [&]() -> int {
         std::unique_ptr<cpq_loudness, void (*)(cpq_loudness*)> p(new cpq_loudness(), cpq_loudness_destroy);
         p->desc = *d;
+        p->rows.rows = 2 * (size_t)d->n_streams;
         p->H = H;
         p->maxHops = (int)maxHops;
         CPQ_TRY(cpqi::checkCurrentDevice());
         CPQ_TRY(createDevice(p.get()));
         *out = p.release();
         return CPQ_OK;
-    } catch (const std::exception&) {
-        return pfail(nullptr, CPQ_ERR_OOM, "host allocation failed");
-    }
+    });
 }
 
 void cpq_loudness_destroy(cpq_loudness* p) { delete p; }
@@ -144,9 +125,7 @@ int32_t cpq_loudness_reset(cpq_loudness* p)
 int32_t cpq_loudness_set_stream(cpq_loudness* p, void* stream)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));       // what was enqueued has run before a call on the new stream touches the state
-    p->stream = (hipStream_t)stream;
-    return CPQ_OK;
+    return cpqi::setStream(&p->lastError, p->stream, stream);
 }
 
 int32_t cpq_loudness_process_device(cpq_loudness* p, const double* d_rows, int64_t row_stride, int32_t n_samples)
@@ -162,71 +141,63 @@ int32_t cpq_loudness_process(cpq_loudness* p, const double* rows, int64_t row_st
     if (!p) return CPQ_ERR_INVALID_ARG;
     cpq::ProgCall c;
     CPQ_TRY(checkCall(p, rows, row_stride, n_samples, c));
-    const size_t nRows = 2 * (size_t)p->desc.n_streams;
-    if (n_samples > p->rowsCap) CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));       // no call in flight reads the buffer that goes
-    if (cpqi::grow(nullptr, p->rows, p->rowsCap, n_samples, nRows, "row buffer") != CPQ_OK)
-        return pfail(p, CPQ_ERR_OOM, "row buffer of %d samples could not be allocated", n_samples);
-    c.stride = p->rowsCap;
-    CPQ_PROG_HIP(p, hipMemcpy2DAsync(p->rows, (size_t)p->rowsCap * sizeof(double), rows, (size_t)row_stride * sizeof(double),
-                                     (size_t)n_samples * sizeof(double), nRows, hipMemcpyHostToDevice, p->stream));
-    CPQ_TRY(runDevice(p, p->rows, c));
-    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    CPQ_TRY(p->rows.ensure(&p->lastError, p->stream, n_samples));
+    c.stride = p->rows.cap;
+    CPQ_TRY(p->rows.upload(&p->lastError, rows, row_stride, n_samples, hipMemcpyHostToDevice, p->stream));
+    CPQ_TRY(runDevice(p, p->rows.buf, c));
+    CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
     return CPQ_OK;
 }
 
 int32_t cpq_loudness_finish(cpq_loudness* p, cpq_loudness_result* out)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!out) return pfail(p, CPQ_ERR_INVALID_ARG, "null result");
-    try {
+    if (!out) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "null result");
+    return cpqi::guardAlloc(&p->lastError, [&]() -> int {
         const int S = p->desc.n_streams;
         cpq::ProgFinish f;
         f.nHops = (int)(p->pos / p->H); f.H = p->H; f.maxHops = p->maxHops; f.zAbs = cpq::progAbsGate();
         std::vector<cpq::ProgRecord> rec((size_t)S);
         cpq::launch_prog_finish(p->stream, p->hops, f, S, p->rec);
-        CPQ_PROG_HIP(p, hipGetLastError());
-        CPQ_PROG_HIP(p, hipMemcpyAsync(rec.data(), p->rec, rec.size() * sizeof(cpq::ProgRecord), hipMemcpyDeviceToHost, p->stream));
-        CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+        CPQ_OBJ_HIP(&p->lastError, hipGetLastError());
+        CPQ_OBJ_HIP(&p->lastError, hipMemcpyAsync(rec.data(), p->rec, rec.size() * sizeof(cpq::ProgRecord), hipMemcpyDeviceToHost, p->stream));
+        CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
         for (int s = 0; s < S; ++s) out[s] = cpq::progResult(rec[(size_t)s], f.nHops);
         return CPQ_OK;
-    } catch (const std::exception&) {
-        return pfail(p, CPQ_ERR_OOM, "host allocation failed");
-    }
+    });
 }
 
 int32_t cpq_loudness_read_hops(cpq_loudness* p, int32_t stream, double* out, int64_t capacity, int64_t* n)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (stream < 0 || stream >= p->desc.n_streams) return pfail(p, CPQ_ERR_INVALID_ARG, "stream %d outside 0..%d", stream, p->desc.n_streams - 1);
-    if (!n || capacity < 0 || (capacity > 0 && !out)) return pfail(p, CPQ_ERR_INVALID_ARG, "bad hop buffer");
-    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    if (stream < 0 || stream >= p->desc.n_streams) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "stream %d outside 0..%d", stream, p->desc.n_streams - 1);
+    if (!n || capacity < 0 || (capacity > 0 && !out)) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "bad hop buffer");
+    CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
     const int64_t have = p->pos / p->H, cnt = std::min(have, capacity);
     if (cnt > 0)
-        CPQ_PROG_HIP(p, hipMemcpy(out, p->hops.get() + (size_t)stream * (size_t)p->maxHops, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
+        CPQ_OBJ_HIP(&p->lastError, hipMemcpy(out, p->hops.get() + (size_t)stream * (size_t)p->maxHops, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
     *n = have;
     return CPQ_OK;
 }
 
 int32_t cpq_loudness_finish_host(const double* hops, int64_t n_hops, double sample_rate, cpq_loudness_result* out)
 {
-    if (!out || n_hops < 0 || (n_hops > 0 && !hops)) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    if (!out || n_hops < 0 || (n_hops > 0 && !hops)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
     cpq::ProgFinish f;
     f.H = cpq::progHop(sample_rate);
-    if (!f.H) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
-    if (cpq::progShortCount(n_hops) > cpq::kProgSortMax) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "more than %d short-term blocks at the 1 s step", cpq::kProgSortMax);
+    if (!f.H) return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
+    if (cpq::progShortCount(n_hops) > cpq::kProgSortMax) return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "more than %d short-term blocks at the 1 s step", cpq::kProgSortMax);
     f.nHops = (int)n_hops; f.maxHops = (int)n_hops; f.zAbs = cpq::progAbsGate();
-    try {
+    return cpqi::guardAlloc(nullptr, [&] {
         *out = cpq::progResult(cpq::progFinishHost(hops, f), n_hops);
-        return CPQ_OK;
-    } catch (const std::exception&) {
-        return pfail(nullptr, CPQ_ERR_OOM, "host allocation failed");
-    }
+        return (int)CPQ_OK;
+    });
 }
 
 int32_t cpq_loudness_gain(const cpq_loudness_result* r, double target_lufs, double* gain)
 {
     if (!r || !gain || !std::isfinite(target_lufs)) return CPQ_ERR_INVALID_ARG;
-    if (!std::isfinite(r->integrated)) return pfail(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
+    if (!std::isfinite(r->integrated)) return failTo(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
     *gain = std::pow(10.0, (target_lufs - r->integrated) / 20.0);
     return CPQ_OK;
 }
@@ -234,9 +205,9 @@ int32_t cpq_loudness_gain(const cpq_loudness_result* r, double target_lufs, doub
 int32_t cpq_loudness_set_true_peak(cpq_loudness* p, int32_t on)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (on != 0 && on != 1) return pfail(p, CPQ_ERR_INVALID_ARG, "on must be 0 or 1");
-    if (p->pos) return pfail(p, CPQ_ERR_NOT_READY, "true peak is switched at the start of a programme: %lld samples were taken; reset first", p->pos);
-    CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+    if (on != 0 && on != 1) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "on must be 0 or 1");
+    if (p->pos) return failTo(&p->lastError, CPQ_ERR_NOT_READY, "true peak is switched at the start of a programme: %lld samples were taken; reset first", p->pos);
+    CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
     if (!on) {
         p->peakOn = false;
         p->pk.reset();
@@ -244,11 +215,11 @@ int32_t cpq_loudness_set_true_peak(cpq_loudness* p, int32_t on)
     }
     if (!p->pk) {
         const int rc = cpqi::allocAll(nullptr, { { p->pk, 2 * (size_t)p->desc.n_streams * cpq::kPeakState, true } }, "peak state");
-        if (rc != CPQ_OK) return pfail(p, rc, "the peak state of %d streams could not be allocated", p->desc.n_streams);
+        if (rc != CPQ_OK) return failTo(&p->lastError, rc, "the peak state of %d streams could not be allocated", p->desc.n_streams);
     } else {
-        CPQ_PROG_HIP(p, hipMemset(p->pk, 0, p->pk.count() * sizeof(double)));
+        CPQ_OBJ_HIP(&p->lastError, hipMemset(p->pk, 0, p->pk.count() * sizeof(double)));
     }
-    CPQ_PROG_HIP(p, hipDeviceSynchronize());        // cleared before the first call, whatever its stream
+    CPQ_OBJ_HIP(&p->lastError, hipDeviceSynchronize());        // cleared before the first call, whatever its stream
     p->peakOn = true;
     return CPQ_OK;
 }
@@ -256,13 +227,13 @@ int32_t cpq_loudness_set_true_peak(cpq_loudness* p, int32_t on)
 int32_t cpq_loudness_read_peaks(cpq_loudness* p, cpq_loudness_peaks* out)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!out) return pfail(p, CPQ_ERR_INVALID_ARG, "null result");
-    if (!p->peakOn) return pfail(p, CPQ_ERR_NOT_READY, "true peak is not switched on (cpq_loudness_set_true_peak)");
-    try {
+    if (!out) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "null result");
+    if (!p->peakOn) return failTo(&p->lastError, CPQ_ERR_NOT_READY, "true peak is not switched on (cpq_loudness_set_true_peak)");
+    return cpqi::guardAlloc(&p->lastError, [&]() -> int {
         const int S = p->desc.n_streams;
         std::vector<double> st(p->pk.count());
-        CPQ_PROG_HIP(p, hipMemcpyAsync(st.data(), p->pk, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        CPQ_PROG_HIP(p, hipStreamSynchronize(p->stream));
+        CPQ_OBJ_HIP(&p->lastError, hipMemcpyAsync(st.data(), p->pk, st.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        CPQ_OBJ_HIP(&p->lastError, hipStreamSynchronize(p->stream));
         for (int s = 0; s < S; ++s)
             for (int ch = 0; ch < 2; ++ch) {
                 const double* r = st.data() + (size_t)(2 * s + ch) * cpq::kPeakState;
@@ -270,17 +241,15 @@ int32_t cpq_loudness_read_peaks(cpq_loudness* p, cpq_loudness_peaks* out)
                 out[s].sample_peak[ch] = r[cpq::kPeakSp];
             }
         return CPQ_OK;
-    } catch (const std::exception&) {
-        return pfail(p, CPQ_ERR_OOM, "host allocation failed");
-    }
+    });
 }
 
 int32_t cpq_loudness_peaks_host(const double* rows, int64_t row_stride, int32_t n_rows, int64_t n_samples, double sample_rate,
                                 double* true_peak, double* sample_peak)
 {
-    if (!rows || !true_peak || !sample_peak) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
-    if (n_rows < 1 || n_samples < 0 || row_stride < n_samples) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "bad rows");
-    if (!cpq::progHop(sample_rate)) return pfail(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
+    if (!rows || !true_peak || !sample_peak) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    if (n_rows < 1 || n_samples < 0 || row_stride < n_samples) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "bad rows");
+    if (!cpq::progHop(sample_rate)) return failTo(nullptr, CPQ_ERR_UNSUPPORTED, "sample_rate %g is not a whole number of Hz in 8000..768000 that is divisible by 10", sample_rate);
     const int mask = cpq::progPeakMask(sample_rate);
     for (int32_t r = 0; r < n_rows; ++r) {
         double st[cpq::kPeakState] = {};
@@ -297,10 +266,10 @@ int32_t cpq_loudness_gain_limited(const cpq_loudness_result* r, const cpq_loudne
     if (!r || !pk || !gain || !limited || !std::isfinite(target_lufs) || !std::isfinite(max_true_peak_dbtp)) return CPQ_ERR_INVALID_ARG;
     double peak = 0.0;
     for (double v : { pk->true_peak[0], pk->true_peak[1], pk->sample_peak[0], pk->sample_peak[1] }) {
-        if (!std::isfinite(v) || v < 0.0) return pfail(nullptr, CPQ_ERR_INVALID_ARG, "a peak is not a finite linear value >= 0");
+        if (!std::isfinite(v) || v < 0.0) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "a peak is not a finite linear value >= 0");
         peak = v > peak ? v : peak;
     }
-    if (!std::isfinite(r->integrated)) return pfail(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
+    if (!std::isfinite(r->integrated)) return failTo(nullptr, CPQ_ERR_NOT_READY, "nothing passed the gates: no integrated loudness");
     bool lim = false;
     *gain = cpq::progGainLimited(r->integrated, peak, target_lufs, max_true_peak_dbtp, lim);
     *limited = lim ? 1 : 0;
@@ -311,23 +280,20 @@ int32_t cpq_loudness_apply_device(cpq_loudness* p, const double* gains, const do
                                   int32_t n_samples)
 {
     if (!p) return CPQ_ERR_INVALID_ARG;
-    if (!gains || !d_in || !d_out) return pfail(p, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (n_samples < 1 || n_samples > cpq::kProgMaxCall) return pfail(p, CPQ_ERR_INVALID_ARG, "n_samples=%d outside 1..%d", n_samples, cpq::kProgMaxCall);
-    if (in_stride < n_samples || out_stride < n_samples)
-        return pfail(p, CPQ_ERR_INVALID_ARG, "row strides %lld and %lld, rows of %d", (long long)in_stride, (long long)out_stride, n_samples);
+    if (!gains) d_in = nullptr;         // null gains are a null buffer, the first refusal
+    CPQ_TRY(cpqi::checkRowPair(&p->lastError, d_in, in_stride, d_out, out_stride, n_samples, cpq::kProgMaxCall, true));
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
-    if ((a | b) & 15u) return pfail(p, CPQ_ERR_INVALID_ARG, "buffers must be 16-byte aligned");
     const int S = p->desc.n_streams;
     for (int s = 0; s < S; ++s)
-        if (!std::isfinite(gains[s])) return pfail(p, CPQ_ERR_INVALID_ARG, "the gain of stream %d is not finite", s);
+        if (!std::isfinite(gains[s])) return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, "the gain of stream %d is not finite", s);
     if (cpq::progApplyOverlap(a / 8, in_stride, b / 8, out_stride, 2 * S, n_samples))
-        return pfail(p, CPQ_ERR_INVALID_ARG, "input and output rows overlap in part: in place takes the same pointer and stride");
+        return failTo(&p->lastError, CPQ_ERR_INVALID_ARG, cpqi::kRowsOverlap);
     cpq::ApplyCall c;
     c.n = n_samples; c.rows = 2 * S; c.inStride = in_stride; c.outStride = out_stride;
     c.wide = in_stride % 2 == 0 && out_stride % 2 == 0;
-    CPQ_PROG_HIP(p, hipMemcpyAsync(p->gains, gains, (size_t)S * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    CPQ_OBJ_HIP(&p->lastError, hipMemcpyAsync(p->gains, gains, (size_t)S * sizeof(double), hipMemcpyHostToDevice, p->stream));
     cpq::launch_prog_apply(p->stream, d_in, c, p->gains, d_out);
-    CPQ_PROG_HIP(p, hipGetLastError());
+    CPQ_OBJ_HIP(&p->lastError, hipGetLastError());
     return CPQ_OK;
 }
 

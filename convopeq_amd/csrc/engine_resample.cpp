@@ -9,25 +9,11 @@
 // one upload, one launch, one download; the trim is host work on the downloaded rows.
 #include "engine_internal.hpp"
 
+#include "object_support.hpp"
+
 namespace {
 
 thread_local double g_lastKernelMs = -1.0;
-
-#define CPQ_RS_HIP(call)                                                                                  \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess)                                                                          \
-            return cpqi::fail(nullptr, CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__)); \
-    } while (0)
-
-struct Events {
-    hipEvent_t ev[2] = {};
-    ~Events()
-    {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
 
 // the IRs `members` of the batch share a source rate and the design d: their rows through one launch, then the trim into out[i]
 int runGroup(const cpq_ir_buffer* const* in, const std::vector<int>& members, const cpq::ResampleDesign& d, double targetRate,
@@ -55,25 +41,25 @@ int runGroup(const cpq_ir_buffer* const* in, const std::vector<int>& members, co
     CPQ_TRY(cpqi::allocAll(nullptr, { { taps, d.taps.size() }, { x, (size_t)inTotal }, { y, (size_t)outTotal }, { dRows, rows.size() },
                                       { dTiles, tiles.size() } },
                            "resample buffers for %lld input and %lld output samples could not be allocated", inTotal, outTotal));
-    Events t;
-    for (auto& e : t.ev) CPQ_RS_HIP(hipEventCreate(&e));
-    CPQ_RS_HIP(hipMemcpy(taps, d.taps.data(), d.taps.size() * sizeof(double), hipMemcpyHostToDevice));
-    CPQ_RS_HIP(hipMemcpy(dRows, rows.data(), rows.size() * sizeof(rows[0]), hipMemcpyHostToDevice));
-    CPQ_RS_HIP(hipMemcpy(dTiles, tiles.data(), tiles.size() * sizeof(tiles[0]), hipMemcpyHostToDevice));
+    cpqi::TimingEvents<2> t;
+    CPQ_TRY(t.create(nullptr));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(taps, d.taps.data(), d.taps.size() * sizeof(double), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(dRows, rows.data(), rows.size() * sizeof(rows[0]), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(dTiles, tiles.data(), tiles.size() * sizeof(tiles[0]), hipMemcpyHostToDevice));
     size_t r = 0;
     for (int i : members) {     // a buffer's channels are contiguous: one copy per IR
         const size_t count = (size_t)in[i]->n_channels * (size_t)in[i]->n_samples;
-        CPQ_RS_HIP(hipMemcpy(x.get() + rows[r].inOff, in[i]->data, count * sizeof(double), hipMemcpyHostToDevice));
+        CPQ_OBJ_HIP(nullptr, hipMemcpy(x.get() + rows[r].inOff, in[i]->data, count * sizeof(double), hipMemcpyHostToDevice));
         r += (size_t)in[i]->n_channels;
     }
-    CPQ_RS_HIP(hipEventRecord(t.ev[0], nullptr));
+    CPQ_OBJ_HIP(nullptr, hipEventRecord(t[0], nullptr));
     cpq::launch_ir_resample(nullptr, taps, d.L, d.M, d.T, x, y, dRows, dTiles, (int)tiles.size());
-    CPQ_RS_HIP(hipGetLastError());
-    CPQ_RS_HIP(hipEventRecord(t.ev[1], nullptr));
+    CPQ_OBJ_HIP(nullptr, hipGetLastError());
+    CPQ_OBJ_HIP(nullptr, hipEventRecord(t[1], nullptr));
     std::vector<double> host((size_t)outTotal);
-    CPQ_RS_HIP(hipMemcpy(host.data(), y, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    CPQ_OBJ_HIP(nullptr, hipMemcpy(host.data(), y, host.size() * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.0f;
-    CPQ_RS_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    CPQ_OBJ_HIP(nullptr, hipEventElapsedTime(&ms, t[0], t[1]));
     kernelMs += ms;
 
     r = 0;
@@ -129,12 +115,7 @@ int32_t cpq_ir_resample_batch(const cpq_ir_buffer* const* in, int32_t n, double 
     if (!out || n < 0) return cpqi::fail(nullptr, CPQ_ERR_INVALID_ARG, "null output or a negative count");
     for (int i = 0; i < n; ++i) std::memset(&out[i], 0, sizeof(out[i]));
     if (n > 0 && !in) return cpqi::fail(nullptr, CPQ_ERR_INVALID_ARG, "null buffer list");
-    int rc;
-    try {
-        rc = resampleBatch(in, n, target_rate, phase, out);
-    } catch (const std::exception&) {
-        rc = cpqi::fail(nullptr, CPQ_ERR_OOM, "host allocation failed");
-    }
+    const int rc = cpqi::guardAlloc(nullptr, [&] { return resampleBatch(in, n, target_rate, phase, out); });
     if (rc != CPQ_OK)
         for (int i = 0; i < n; ++i) {
             cpq_ir_buffer_free(&out[i]);

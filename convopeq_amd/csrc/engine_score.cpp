@@ -73,25 +73,6 @@ using cpq::kScoreLen;
 using cpq::kScoreMaxSegments;
 using cpq::kScoreRecent;
 
-int sfail(cpq_scorer* s, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (s) s->lastError = buf;
-    else return cpqi::fail(nullptr, code, "%s", buf);       // before a scorer exists: cpq_last_error(NULL) has it
-    return code;
-}
-
-#define CPQ_SHIP(s, call)                                                                            \
-    do {                                                                                             \
-        hipError_t err__ = (call);                                                                   \
-        if (err__ != hipSuccess)                                                                     \
-            return sfail((s), CPQ_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(err__));     \
-    } while (0)
-
 // LatticeNoiseShaper::rngState
 constexpr unsigned long long kRngDefault[2][4] = {
     { 0x123456789ABCDEF0ULL, 0xFEDCBA9876543210ULL, 0x0123456789ABCDEFULL, 0xEFCDAB8967452301ULL },
@@ -101,15 +82,15 @@ int uploadRng(cpq_scorer* s)
 {
     std::vector<unsigned long long> table;
     cpq::scoreRngTable(s->rngStart, s->desc.max_candidates * kScoreMaxSegments, table);
-    CPQ_SHIP(s, hipSetDevice(s->device));
-    CPQ_SHIP(s, hipStreamSynchronize(s->stream));
-    CPQ_SHIP(s, hipMemcpy(s->rng, table.data(), table.size() * sizeof(table[0]), hipMemcpyHostToDevice));
+    CPQ_OBJ_HIP(&s->lastError, hipSetDevice(s->device));
+    CPQ_OBJ_HIP(&s->lastError, hipStreamSynchronize(s->stream));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpy(s->rng, table.data(), table.size() * sizeof(table[0]), hipMemcpyHostToDevice));
     return CPQ_OK;
 }
 
 int checkLearner(cpq_scorer* s, int learner)
 {
-    if (learner < 0 || learner >= s->desc.n_learners) return sfail(s, CPQ_ERR_INVALID_ARG, "learner %d outside 0..%d", learner, s->desc.n_learners - 1);
+    if (learner < 0 || learner >= s->desc.n_learners) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "learner %d outside 0..%d", learner, s->desc.n_learners - 1);
     return CPQ_OK;
 }
 
@@ -129,14 +110,14 @@ int buildSegments(cpq_scorer* s, int learner, const double* l, const double* r, 
         gain[i] = segs[i].gain;
         evals[i] = cpq::ScoreEval{ learner * kScoreMaxSegments + i, learner * kScoreMaxSegments + i, 0, 0.0 };
     }
-    CPQ_SHIP(s, hipMemcpyAsync(s->segStart, start, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    CPQ_SHIP(s, hipMemcpyAsync(s->segGain, gain, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    CPQ_SHIP(s, hipMemcpyAsync(s->evals, evals, n * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, s->stream));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->segStart, start, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->segGain, gain, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->evals, evals, n * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, s->stream));
     cpq::launch_score_level(s->stream, s->recent, kScoreRecent, s->segStart, s->segGain,
                             s->seg.get() + (size_t)learner * kScoreMaxSegments * 2 * kScoreLen, n);
     cpq::launch_score_spectrum(s->stream, s->seg, s->thr, s->evals, n, s->tables.dev, nullptr, nullptr, true);
-    CPQ_SHIP(s, hipGetLastError());
-    CPQ_SHIP(s, hipStreamSynchronize(s->stream));            // the tables above are this frame's
+    CPQ_OBJ_HIP(&s->lastError, hipGetLastError());
+    CPQ_OBJ_HIP(&s->lastError, hipStreamSynchronize(s->stream));            // the tables above are this frame's
     return CPQ_OK;
 }
 
@@ -144,8 +125,8 @@ int setAudio(cpq_scorer* s, int learner, const double* left, const double* right
 {
     if (!s) return CPQ_ERR_INVALID_ARG;
     CPQ_TRY(checkLearner(s, learner));
-    if (n < 0) return sfail(s, CPQ_ERR_INVALID_ARG, "%d samples", n);
-    if (n > 0 && (!left || !right)) return sfail(s, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (n < 0) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "%d samples", n);
+    if (n > 0 && (!left || !right)) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "null buffer");
     const int usable = std::min(n, kScoreRecent);
     if (usable < kScoreLen) {                               // copiedSamples < AudioSegment::kLength: no segments, no error
         s->nSeg[learner] = 0;
@@ -153,16 +134,16 @@ int setAudio(cpq_scorer* s, int learner, const double* left, const double* right
         if (nSegments) *nSegments = 0;
         return CPQ_OK;
     }
-    CPQ_SHIP(s, hipSetDevice(s->device));
-    CPQ_SHIP(s, hipStreamSynchronize(s->stream));
+    CPQ_OBJ_HIP(&s->lastError, hipSetDevice(s->device));
+    CPQ_OBJ_HIP(&s->lastError, hipStreamSynchronize(s->stream));
     const double* rows[2] = { left + (n - usable), right + (n - usable) };
     std::vector<double> host[2];
     for (int ch = 0; ch < 2; ++ch) {
-        CPQ_SHIP(s, hipMemcpy(s->recent.get() + (size_t)ch * kScoreRecent, rows[ch], usable * sizeof(double),
+        CPQ_OBJ_HIP(&s->lastError, hipMemcpy(s->recent.get() + (size_t)ch * kScoreRecent, rows[ch], usable * sizeof(double),
                               onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         if (onDevice) {                                     // the selection is host work: it reads a copy
             host[ch].resize(usable);
-            CPQ_SHIP(s, hipMemcpy(host[ch].data(), s->recent.get() + (size_t)ch * kScoreRecent, usable * sizeof(double), hipMemcpyDeviceToHost));
+            CPQ_OBJ_HIP(&s->lastError, hipMemcpy(host[ch].data(), s->recent.get() + (size_t)ch * kScoreRecent, usable * sizeof(double), hipMemcpyDeviceToHost));
             rows[ch] = host[ch].data();
         }
     }
@@ -172,7 +153,7 @@ int setAudio(cpq_scorer* s, int learner, const double* left, const double* right
 int score(cpq_scorer* s, const double* mapped, int nCand, double* scores, cpq_score_parts* parts)
 {
     const int L = s->desc.n_learners;
-    CPQ_SHIP(s, hipSetDevice(s->device));
+    CPQ_OBJ_HIP(&s->lastError, hipSetDevice(s->device));
     const int nPairs = L * nCand;
     std::vector<double> coef((size_t)nPairs * cpq::kLatticeOrder);
     std::vector<int> state(nPairs);
@@ -186,21 +167,21 @@ int score(cpq_scorer* s, const double* mapped, int nCand, double* scores, cpq_sc
     }
     hipStream_t st = s->stream;
     cpqi::ScoreCallTables t;
-    CPQ_SHIP(s, hipMemcpyAsync(s->coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    CPQ_SHIP(s, hipMemcpyAsync(s->state, state.data(), state.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->state, state.data(), state.size() * sizeof(int), hipMemcpyHostToDevice, st));
     CPQ_TRY(cpqi::scoreBuildTables(s, nCand, runs.data(), t));
     CPQ_TRY(cpqi::scoreLaunch(s, nCand, s->desc.level_weights));
-    CPQ_SHIP(s, hipMemcpyAsync(scores, s->scores, (size_t)nPairs * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (parts) CPQ_SHIP(s, hipMemcpyAsync(parts, s->parts, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), hipMemcpyDeviceToHost, st));
-    CPQ_SHIP(s, hipStreamSynchronize(st));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(scores, s->scores, (size_t)nPairs * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (parts) CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(parts, s->parts, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), hipMemcpyDeviceToHost, st));
+    CPQ_OBJ_HIP(&s->lastError, hipStreamSynchronize(st));
     return CPQ_OK;
 }
 
 int checkScore(cpq_scorer* s, const double* k, int nCand, const double* scores)
 {
     if (!s) return CPQ_ERR_INVALID_ARG;
-    if (!k || !scores) return sfail(s, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (nCand < 1 || nCand > s->desc.max_candidates) return sfail(s, CPQ_ERR_INVALID_ARG, "%d candidates outside 1..%d", nCand, s->desc.max_candidates);
+    if (!k || !scores) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (nCand < 1 || nCand > s->desc.max_candidates) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "%d candidates outside 1..%d", nCand, s->desc.max_candidates);
     return CPQ_OK;
 }
 
@@ -216,9 +197,9 @@ namespace cpqi {
 int scoreBuildTables(cpq_scorer* s, int nCand, const char* runs, ScoreCallTables& t)
 {
     const int L = s->desc.n_learners, maxC = s->desc.max_candidates;
-    CPQ_SHIP(s, hipSetDevice(s->device));
+    CPQ_OBJ_HIP(&s->lastError, hipSetDevice(s->device));
     if (!s->err && !s->err.alloc((size_t)L * maxC * kScoreMaxSegments * 2 * kScoreLen))
-        return sfail(s, CPQ_ERR_OOM, "the error rows of %d learners x %d candidates could not be allocated", L, maxC);
+        return failTo(&s->lastError, CPQ_ERR_OOM, "the error rows of %d learners x %d candidates could not be allocated", L, maxC);
     const int nPairs = L * nCand;
     t.counts.assign((size_t)L * cpq::kScoreLevels, 0);
     t.chains.clear();
@@ -243,13 +224,13 @@ int scoreBuildTables(cpq_scorer* s, int nCand, const char* runs, ScoreCallTables
         }
     }
     hipStream_t st = s->stream;
-    CPQ_SHIP(s, hipMemcpyAsync(s->countsDev, t.counts.data(), t.counts.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->countsDev, t.counts.data(), t.counts.size() * sizeof(int), hipMemcpyHostToDevice, st));
     if (!t.chains.empty()) {
-        CPQ_SHIP(s, hipMemcpyAsync(s->chains, t.chains.data(), t.chains.size() * sizeof(cpq::ScoreChain), hipMemcpyHostToDevice, st));
-        CPQ_SHIP(s, hipMemcpyAsync(s->evals, t.evals.data(), t.evals.size() * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, st));
+        CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->chains, t.chains.data(), t.chains.size() * sizeof(cpq::ScoreChain), hipMemcpyHostToDevice, st));
+        CPQ_OBJ_HIP(&s->lastError, hipMemcpyAsync(s->evals, t.evals.data(), t.evals.size() * sizeof(cpq::ScoreEval), hipMemcpyHostToDevice, st));
     }
-    CPQ_SHIP(s, hipMemsetAsync(s->parts, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), st));
-    CPQ_SHIP(s, hipMemsetAsync(s->blended, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(double), st));
+    CPQ_OBJ_HIP(&s->lastError, hipMemsetAsync(s->parts, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(cpq_score_parts), st));
+    CPQ_OBJ_HIP(&s->lastError, hipMemsetAsync(s->blended, 0, (size_t)nPairs * kScoreMaxSegments * sizeof(double), st));
     s->nChains = (int)t.chains.size();
     s->nEvals = (int)t.evals.size();
     return CPQ_OK;
@@ -258,13 +239,13 @@ int scoreBuildTables(cpq_scorer* s, int nCand, const char* runs, ScoreCallTables
 int scoreLaunch(cpq_scorer* s, int nCand, const double* levelWeights)
 {
     hipStream_t st = s->stream;
-    CPQ_SHIP(s, hipEventRecord(s->ev[0], st));
+    CPQ_OBJ_HIP(&s->lastError, hipEventRecord(s->ev[0], st));
     cpq::launch_score_lattice(st, s->seg, s->err, s->chains, s->nChains, s->coef, s->rng, s->p);
-    CPQ_SHIP(s, hipEventRecord(s->ev[1], st));
+    CPQ_OBJ_HIP(&s->lastError, hipEventRecord(s->ev[1], st));
     cpq::launch_score_spectrum(st, s->err, s->thr, s->evals, s->nEvals, s->tables.dev, s->parts, s->blended, false);
-    CPQ_SHIP(s, hipEventRecord(s->ev[2], st));
+    CPQ_OBJ_HIP(&s->lastError, hipEventRecord(s->ev[2], st));
     cpq::launch_score_reduce(st, s->blended, s->countsDev, s->state, s->desc.n_learners, nCand, levelWeights, s->scores);
-    CPQ_SHIP(s, hipGetLastError());
+    CPQ_OBJ_HIP(&s->lastError, hipGetLastError());
     s->scored = true;
     return CPQ_OK;
 }
@@ -275,37 +256,37 @@ extern "C" {
 
 int32_t cpq_scorer_create(const cpq_scorer_desc* d, cpq_scorer** out)
 {
-    if (!d || !out) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
+    if (!d || !out) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
-    if (d->n_learners < 1 || d->max_candidates < 1) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "n_learners and max_candidates must be >= 1");
+    if (d->n_learners < 1 || d->max_candidates < 1) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "n_learners and max_candidates must be >= 1");
     if (d->max_candidates > CPQ_SCORE_MAX_CANDIDATES)       // the start-state table is stepped word by word on the host
-        return sfail(nullptr, CPQ_ERR_INVALID_ARG, "max_candidates %d above %d", d->max_candidates, CPQ_SCORE_MAX_CANDIDATES);
-    if ((int64_t)d->n_learners * d->max_candidates > (1 << 20)) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "more than 2^20 candidates per call");
-    if (!(d->sample_rate_hz > 0.0) || !std::isfinite(d->sample_rate_hz)) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "sample rate must be finite and > 0");
-    if (d->bit_depth < 1 || d->bit_depth > 32) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "bit depth %d outside 1..32", d->bit_depth);
+        return failTo(nullptr, CPQ_ERR_INVALID_ARG, "max_candidates %d above %d", d->max_candidates, CPQ_SCORE_MAX_CANDIDATES);
+    if ((int64_t)d->n_learners * d->max_candidates > (1 << 20)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "more than 2^20 candidates per call");
+    if (!(d->sample_rate_hz > 0.0) || !std::isfinite(d->sample_rate_hz)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "sample rate must be finite and > 0");
+    if (d->bit_depth < 1 || d->bit_depth > 32) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "bit depth %d outside 1..32", d->bit_depth);
     for (double w : d->level_weights)
-        if (!(w >= 0.0) || !std::isfinite(w)) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "level weights must be finite and >= 0");
-    if (!(d->coeff_safety_margin > 0.0) || !(d->coeff_safety_margin <= 1.0)) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "safety margin outside (0, 1]");
-    if (d->rng_mode != CPQ_SCORE_RNG_FRESH && d->rng_mode != CPQ_SCORE_RNG_CHAINED) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "unknown generator mode %d", d->rng_mode);
-    if (d->stability_check != 0 && d->stability_check != 1) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "stability_check must be 0 or 1");
+        if (!(w >= 0.0) || !std::isfinite(w)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "level weights must be finite and >= 0");
+    if (!(d->coeff_safety_margin > 0.0) || !(d->coeff_safety_margin <= 1.0)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "safety margin outside (0, 1]");
+    if (d->rng_mode != CPQ_SCORE_RNG_FRESH && d->rng_mode != CPQ_SCORE_RNG_CHAINED) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "unknown generator mode %d", d->rng_mode);
+    if (d->stability_check != 0 && d->stability_check != 1) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "stability_check must be 0 or 1");
 
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) {
         (void)hipGetLastError();
-        return sfail(nullptr, CPQ_ERR_NO_DEVICE, "no HIP device visible: the gfx950 kernels cannot run (no CPU fallback)");
+        return failTo(nullptr, CPQ_ERR_NO_DEVICE, "no HIP device visible: the gfx950 kernels cannot run (no CPU fallback)");
     }
     int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return sfail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDevice failed");
+    if (hipGetDevice(&device) != hipSuccess) return failTo(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDevice failed");
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return sfail(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return failTo(nullptr, CPQ_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return sfail(nullptr, CPQ_ERR_NO_DEVICE, "device %d is %s; this library ships gfx950 code only", device, prop.gcnArchName);
+        return failTo(nullptr, CPQ_ERR_NO_DEVICE, "device %d is %s; this library ships gfx950 code only", device, prop.gcnArchName);
 
     std::unique_ptr<cpq_scorer, void (*)(cpq_scorer*)> s(new (std::nothrow) cpq_scorer(), cpq_scorer_destroy);
-    if (!s) return sfail(nullptr, CPQ_ERR_OOM, "host allocation failed");
+    if (!s) return failTo(nullptr, CPQ_ERR_OOM, "host allocation failed");
     s->desc = *d;
     s->device = device;
-    if (!cpq::scoreTables(d->sample_rate_hz, s->tab)) return sfail(nullptr, CPQ_ERR_INVALID_ARG, "no Bark band layout at %g Hz", d->sample_rate_hz);
+    if (!cpq::scoreTables(d->sample_rate_hz, s->tab)) return failTo(nullptr, CPQ_ERR_INVALID_ARG, "no Bark band layout at %g Hz", d->sample_rate_hz);
     s->p = cpqi::scoreDitherParams(d->bit_depth);
     std::memcpy(s->rngStart, kRngDefault, sizeof(kRngDefault));
     const size_t L = (size_t)d->n_learners, pairs = L * d->max_candidates;
@@ -314,19 +295,18 @@ int32_t cpq_scorer_create(const cpq_scorer_desc* d, cpq_scorer** out)
     s->counts.assign(L, {});
     s->segs.resize(L);
     s->lastRan.assign(pairs, 0);
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return sfail(nullptr, CPQ_ERR_DEVICE, "hipStreamCreate failed");
-    for (auto& e : s->ev)
-        if (hipEventCreate(&e) != hipSuccess) return sfail(nullptr, CPQ_ERR_DEVICE, "hipEventCreate failed");
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return failTo(nullptr, CPQ_ERR_DEVICE, "hipStreamCreate failed");
+    if (s->ev.create(nullptr) != CPQ_OK) return failTo(nullptr, CPQ_ERR_DEVICE, "hipEventCreate failed");
     const bool ok = s->seg.alloc(L * kScoreMaxSegments * 2 * kScoreLen) && s->thr.alloc(L * kScoreMaxSegments * kScoreBins) &&
                     s->recent.alloc(2 * (size_t)kScoreRecent) && s->segGain.alloc(kScoreMaxSegments) && s->segStart.alloc(kScoreMaxSegments) &&
                     s->coef.alloc(pairs * cpq::kLatticeOrder) && s->blended.alloc(pairs * kScoreMaxSegments) && s->scores.alloc(pairs) &&
                     s->chains.alloc(pairs * kScoreMaxSegments * 2) && s->evals.alloc(pairs * kScoreMaxSegments) &&
                     s->parts.alloc(pairs * kScoreMaxSegments) && s->countsDev.alloc(L * cpq::kScoreLevels) && s->state.alloc(pairs) &&
                     s->rng.alloc((size_t)d->max_candidates * kScoreMaxSegments * 8);
-    if (!ok) return sfail(nullptr, CPQ_ERR_OOM, "scorer buffers for %d learners x %d candidates could not be allocated", d->n_learners, d->max_candidates);
+    if (!ok) return failTo(nullptr, CPQ_ERR_OOM, "scorer buffers for %d learners x %d candidates could not be allocated", d->n_learners, d->max_candidates);
     int rc = cpqi::uploadScoreTables(s->tab, s->tables, s->lastError);
     if (rc == CPQ_OK) rc = uploadRng(s.get());
-    if (rc != CPQ_OK) return sfail(nullptr, rc, "%s", s->lastError.c_str());
+    if (rc != CPQ_OK) return failTo(nullptr, rc, "%s", s->lastError.c_str());
     *out = s.release();
     return CPQ_OK;
 }
@@ -336,8 +316,6 @@ void cpq_scorer_destroy(cpq_scorer* s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    for (auto& e : s->ev)
-        if (e) (void)hipEventDestroy(e);
     delete s;
 }
 
@@ -366,11 +344,11 @@ int32_t cpq_scorer_read_thresholds(cpq_scorer* s, int32_t learner, int32_t segme
 {
     if (!s) return CPQ_ERR_INVALID_ARG;
     CPQ_TRY(checkLearner(s, learner));
-    if (!thresholds) return sfail(s, CPQ_ERR_INVALID_ARG, "null buffer");
-    if (segment < 0 || segment >= s->nSeg[learner]) return sfail(s, CPQ_ERR_INVALID_ARG, "segment %d outside the learner's %d", segment, s->nSeg[learner]);
-    CPQ_SHIP(s, hipSetDevice(s->device));
-    CPQ_SHIP(s, hipStreamSynchronize(s->stream));
-    CPQ_SHIP(s, hipMemcpy(thresholds, s->thr.get() + ((size_t)learner * kScoreMaxSegments + segment) * kScoreBins, kScoreBins * sizeof(double),
+    if (!thresholds) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "null buffer");
+    if (segment < 0 || segment >= s->nSeg[learner]) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "segment %d outside the learner's %d", segment, s->nSeg[learner]);
+    CPQ_OBJ_HIP(&s->lastError, hipSetDevice(s->device));
+    CPQ_OBJ_HIP(&s->lastError, hipStreamSynchronize(s->stream));
+    CPQ_OBJ_HIP(&s->lastError, hipMemcpy(thresholds, s->thr.get() + ((size_t)learner * kScoreMaxSegments + segment) * kScoreBins, kScoreBins * sizeof(double),
                           hipMemcpyDeviceToHost));
     return CPQ_OK;
 }
@@ -392,7 +370,7 @@ int32_t cpq_scorer_score_raw(cpq_scorer* s, const double* raw, int32_t nCand, do
 int32_t cpq_scorer_set_rng_start(cpq_scorer* s, const uint64_t state[2][4])
 {
     if (!s) return CPQ_ERR_INVALID_ARG;
-    if (!state) return sfail(s, CPQ_ERR_INVALID_ARG, "null state");
+    if (!state) return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "null state");
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "generator words travel as unsigned long long");
     std::memcpy(s->rngStart, state, sizeof(s->rngStart));
     return uploadRng(s);
@@ -403,24 +381,24 @@ int32_t cpq_scorer_read_error(cpq_scorer* s, int32_t learner, int32_t candidate,
     if (!s) return CPQ_ERR_INVALID_ARG;
     CPQ_TRY(checkLearner(s, learner));
     if (candidate < 0 || candidate >= s->desc.max_candidates || segment < 0 || segment >= kScoreMaxSegments)
-        return sfail(s, CPQ_ERR_INVALID_ARG, "candidate %d or segment %d out of range", candidate, segment);
+        return failTo(&s->lastError, CPQ_ERR_INVALID_ARG, "candidate %d or segment %d out of range", candidate, segment);
     if (!s->scored || !s->lastRan[(size_t)learner * s->desc.max_candidates + candidate] || segment >= s->lastNSeg[learner])
-        return sfail(s, CPQ_ERR_NOT_READY, "the last score call did not run learner %d, candidate %d, segment %d", learner, candidate, segment);
-    CPQ_SHIP(s, hipSetDevice(s->device));
-    CPQ_SHIP(s, hipStreamSynchronize(s->stream));
+        return failTo(&s->lastError, CPQ_ERR_NOT_READY, "the last score call did not run learner %d, candidate %d, segment %d", learner, candidate, segment);
+    CPQ_OBJ_HIP(&s->lastError, hipSetDevice(s->device));
+    CPQ_OBJ_HIP(&s->lastError, hipStreamSynchronize(s->stream));
     const double* row = s->err.get() + (((size_t)learner * s->desc.max_candidates + candidate) * kScoreMaxSegments + segment) * 2 * kScoreLen;
-    if (left) CPQ_SHIP(s, hipMemcpy(left, row, kScoreLen * sizeof(double), hipMemcpyDeviceToHost));
-    if (right) CPQ_SHIP(s, hipMemcpy(right, row + kScoreLen, kScoreLen * sizeof(double), hipMemcpyDeviceToHost));
+    if (left) CPQ_OBJ_HIP(&s->lastError, hipMemcpy(left, row, kScoreLen * sizeof(double), hipMemcpyDeviceToHost));
+    if (right) CPQ_OBJ_HIP(&s->lastError, hipMemcpy(right, row + kScoreLen, kScoreLen * sizeof(double), hipMemcpyDeviceToHost));
     return CPQ_OK;
 }
 
 int32_t cpq_scorer_last_timing(cpq_scorer* s, double* latticeMs, double* spectrumMs)
 {
     if (!s) return CPQ_ERR_INVALID_ARG;
-    if (!s->scored) return sfail(s, CPQ_ERR_NOT_READY, "no score call yet");
+    if (!s->scored) return failTo(&s->lastError, CPQ_ERR_NOT_READY, "no score call yet");
     float a = 0.0f, b = 0.0f;
-    CPQ_SHIP(s, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-    CPQ_SHIP(s, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+    CPQ_OBJ_HIP(&s->lastError, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+    CPQ_OBJ_HIP(&s->lastError, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
     if (latticeMs) *latticeMs = a;
     if (spectrumMs) *spectrumMs = b;
     return CPQ_OK;

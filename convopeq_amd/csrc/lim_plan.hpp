@@ -195,10 +195,4 @@ CPQ_HD inline int limPairCount(int W) { return limStageLen(W, kLimTile) / 2 + 1;
 CPQ_HD inline bool limKeepMoves(const LimLaunch& a) { return a.keepLen > 0 && (a.keepShift > 0 || a.nVirt > a.hLen); }
 CPQ_HD inline int limKeepChunks(const LimLaunch& a) { return limKeepMoves(a) ? (a.keepLen + kLimKeepBlock - 1) / kLimKeepBlock : 0; }
 
-// rows [rows][n] at stride s from a and from b (addresses in doubles): the same rows, or apart
-inline bool limRowsOverlap(unsigned long long a, long long sa, unsigned long long b, long long sb, int rows, int n)
-{
-    return progApplyOverlap(a, sa, b, sb, rows, n);
-}
-
 }  // namespace cpq

@@ -4,14 +4,16 @@
 #pragma once
 
 #include "engine_internal.hpp"
+#include "object_support.hpp"
 
 #include <array>
+
+using cpqi::failTo;
 
 struct cpq_scorer {
     cpq_scorer_desc desc{};
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {};
     std::string lastError;
 
     cpq::ScoreTables tab;
@@ -36,6 +38,7 @@ struct cpq_scorer {
     std::vector<int> lastNSeg;
     int nChains = 0, nEvals = 0;                // of the tables on the device
     bool scored = false;
+    cpqi::TimingEvents<3> ev;                   // around lattice and spectrum; the last member: destroyed before the buffers are freed
 };
 
 namespace cpqi {

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from ._handle import Handle
 from .engine import CpqError
 
 STATE_ARRAYS = ("mean", "cov_upper", "rng", "best_raw", "best_scored")
@@ -95,29 +96,14 @@ def phase_params(mode, ph):
     return p, iv.value
 
 
-class ShaperLearner:
+class ShaperLearner(Handle):
     """CMA-ES over the scorer's learners.  The scorer is borrowed and kept alive by this object."""
+    _PREFIX = "cpq_learner"
 
     def __init__(self, scorer):
-        self._lib = K.load()
-        self._h = None
         self.scorer = scorer
-        h = C.c_void_p()
-        rc = self._lib.cpq_learner_create(scorer._h, C.byref(h))
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_learner_last_error(None).decode())
-        self._h, self.n_learners = h, scorer.n_learners
-
-    def _check(self, rc):
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_learner_last_error(self._h).decode())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cpq_learner_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        self._open(scorer._h)
+        self.n_learners = scorer.n_learners
 
     def init(self, parcor, seed, learner=K.CPQ_ALL_STREAMS):
         parcor = np.ascontiguousarray(parcor, dtype=np.float64)

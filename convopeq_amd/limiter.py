@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from ._handle import StreamHandle
 from .engine import CpqError
 
 
@@ -22,31 +23,16 @@ def limiter_default_window(sample_rate):
     return w
 
 
-class TruePeakLimiter:
+class TruePeakLimiter(StreamHandle):
+    _PREFIX = "cpq_limiter"
+
     def __init__(self, n_streams, sample_rate, ceiling_dbtp=-1.0, window=0, host=False, device=False):
-        self._h = None
         if host and device:
             raise ValueError("host and device exclude each other")
-        self._lib = K.load()
         flags = K.CPQ_LIM_HOST if host else K.CPQ_LIM_DEVICE if device else 0
-        h = C.c_void_p()
-        rc = self._lib.cpq_limiter_create(n_streams, float(sample_rate), float(ceiling_dbtp), int(window), flags, C.byref(h))
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_limiter_last_error(None).decode())
-        self._h, self.n_streams, self.sample_rate, self.host, self.device = h, n_streams, float(sample_rate), bool(host), bool(device)
+        self._open(n_streams, float(sample_rate), float(ceiling_dbtp), int(window), flags)
+        self.n_streams, self.sample_rate, self.host, self.device = n_streams, float(sample_rate), bool(host), bool(device)
         self.ceiling = 10.0 ** (float(ceiling_dbtp) / 20.0)
-        self._stream = None
-
-    def _check(self, rc):
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_limiter_last_error(self._h).decode())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cpq_limiter_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     @property
     def latency(self):
@@ -64,11 +50,6 @@ class TruePeakLimiter:
 
     def reset(self):
         self._check(self._lib.cpq_limiter_reset(self._h))
-
-    def set_stream(self, stream):
-        """the torch.cuda.Stream (None: the null stream) later calls enqueue on; the stream used so far is synchronised first"""
-        self._check(self._lib.cpq_limiter_set_stream(self._h, C.c_void_p(stream.cuda_stream if stream is not None else None)))
-        self._stream = stream           # kept alive as long as the object enqueues on it
 
     def set_gains(self, gains):
         """the pre-gain of every stream (ProgrammeLoudness.gain), only at the start of a programme: CpqError(CPQ_ERR_NOT_READY) later"""

@@ -9,6 +9,7 @@ import math
 import numpy as np
 
 from . import _capi as K
+from ._handle import StreamHandle
 from .engine import CpqError
 
 FIELDS = tuple(name for name, _ in K.LoudnessResult._fields_)
@@ -44,38 +45,18 @@ def loudness_peaks_host(rows, sample_rate):
     return tp, sp
 
 
-class ProgrammeLoudness:
+class ProgrammeLoudness(StreamHandle):
+    _PREFIX = "cpq_loudness"
+
     def __init__(self, n_streams, sample_rate, max_seconds, true_peak=False):
-        self._h = None
-        self._lib = K.load()
         desc = K.LoudnessDesc(n_streams, float(sample_rate), float(max_seconds), 0)
-        h = C.c_void_p()
-        rc = self._lib.cpq_loudness_create(C.byref(desc), C.byref(h))
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_loudness_last_error(None).decode())
-        self._h, self.n_streams, self.sample_rate = h, n_streams, float(sample_rate)
-        self._stream = None
+        self._open(C.byref(desc))
+        self.n_streams, self.sample_rate = n_streams, float(sample_rate)
         if true_peak:
             self.set_true_peak(True)
 
-    def _check(self, rc):
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_loudness_last_error(self._h).decode())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cpq_loudness_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def reset(self):
         self._check(self._lib.cpq_loudness_reset(self._h))
-
-    def set_stream(self, stream):
-        """the torch.cuda.Stream (None: the null stream) later calls enqueue on; the stream used so far is synchronised first"""
-        self._check(self._lib.cpq_loudness_set_stream(self._h, C.c_void_p(stream.cuda_stream if stream is not None else None)))
-        self._stream = stream           # kept alive as long as the object enqueues on it
 
     def process(self, rows):
         """rows [2 n_streams, n] float64 on the host: n more samples of every programme"""

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from ._handle import Handle
 from .engine import CpqError
 
 PARTS = ("noise_power", "spectral_flatness_penalty", "hf_penalty", "time_domain_rms", "composite_score")
@@ -44,29 +45,15 @@ def select_segments(left, right):
     return _segments(K.load().cpq_score_select_segments, _dp(left), _dp(right), left.size)
 
 
-class ShaperScorer:
+class ShaperScorer(Handle):
+    _PREFIX = "cpq_scorer"
+
     def __init__(self, n_learners=1, max_candidates=18, sample_rate_hz=48000.0, bit_depth=16, level_weights=(0.4, 0.3, 0.2, 0.1),
                  coeff_safety_margin=0.85, stability_check=True, rng_mode=K.CPQ_SCORE_RNG_FRESH):
-        self._lib = K.load()
-        self._h = None
         desc = K.ScorerDesc(n_learners, max_candidates, sample_rate_hz, bit_depth, (C.c_double * 4)(*level_weights), coeff_safety_margin,
                             int(bool(stability_check)), rng_mode)
-        h = C.c_void_p()
-        rc = self._lib.cpq_scorer_create(C.byref(desc), C.byref(h))
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_scorer_last_error(None).decode())
-        self._h, self.n_learners, self.max_candidates = h, n_learners, max_candidates
-
-    def _check(self, rc):
-        if rc != K.CPQ_OK:
-            raise CpqError(rc, self._lib.cpq_scorer_last_error(self._h).decode())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cpq_scorer_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+        self._open(C.byref(desc))
+        self.n_learners, self.max_candidates = n_learners, max_candidates
 
     def buildTrainingSegments(self, learner, left, right):
         """the learner's segments from the most recent samples of the two rows; returns how many it holds"""

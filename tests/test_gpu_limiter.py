@@ -210,6 +210,29 @@ def test_host_rows_through_the_device_object():
     assert dev.telemetry() == host.telemetry()
 
 
+def test_host_rows_that_grow_around_a_call_in_place():
+    """host rows of 7, TILE + 1 and 2 TILE + 5 samples: the object's row buffers are replaced before the second and the third
+    call.  Between those two a call in place on device rows of TILE + 3 samples, whose copy lies in the buffer the host rows go
+    through, and replaces it as well."""
+    W = 8
+    lengths = [7, TILE + 1, TILE + 3, 2 * TILE + 5]
+    starts = np.cumsum([0] + lengths)
+    x = noise(2, sum(lengths), 31)
+    plant(x, TILE)
+    plant(x, int(starts[2]) - 1)                # the last sample of the second call
+    dev, host = pair(2, W)
+    got = [dev.process(x[:, starts[0]:starts[1]]), dev.process(x[:, starts[1]:starts[2]])]
+    buf = torch.from_numpy(np.ascontiguousarray(x[:, starts[2]:starts[3]])).cuda()
+    assert dev.process_device(buf, buf) is buf
+    got += [buf.cpu().numpy(), dev.process(x[:, starts[3]:starts[4]]), dev.flush()]
+    want = host_pieces(host, x, lengths)
+    assert len(got) == len(want) == 5
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert same(g, w), f"piece {i}: {int((np.ascontiguousarray(g).view(np.uint64) != w.view(np.uint64)).sum())} doubles differ"
+    tel = dev.telemetry()
+    assert tel == host.telemetry() and all(t["limited_samples"] > 0 and t["min_gain"] < 1.0 for t in tel)
+
+
 def test_a_sample_that_is_not_finite():
     W = 72
     x = plant(noise(2, TILE + 300, 4), 700)

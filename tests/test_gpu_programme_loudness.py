@@ -268,6 +268,31 @@ def test_100_calls_back_to_back_then_finish(amd):
         assert len(hops[s]) == 35 and np.array_equal(bits(hops[s]), bits(want_h[s])) and res[s] == want_r[s]
 
 
+def test_host_rows_whose_calls_grow(amd):
+    """process() on host rows in calls of 1, 4801 (a hop and a sample) and 9600 samples (two hops): the object's row buffer is
+    replaced before the second and before the third call, its stride changing each time.  Bit for bit the hops of a second
+    object given the same rows call by call through process_device, where nothing is staged.  (The calls are the same on both:
+    another split of a programme is held to the bar above, not to equal bits.)"""
+    import torch
+    S, rate, calls = 2, 48000, [1, 4801, 9600]              # hops of 4800 samples
+    t = np.arange(sum(calls))
+    x = 0.1 * np.sin(2.0 * math.pi * 997.0 * t / rate + np.arange(2 * S)[:, None]) + 0.01 * np.random.default_rng(5).standard_normal((2 * S, len(t)))
+    staged, direct = amd.ProgrammeLoudness(S, rate, 4), amd.ProgrammeLoudness(S, rate, 4)
+    feed(staged, x, calls)
+    o, pieces = 0, []
+    for n in calls:
+        pieces.append(torch.from_numpy(np.ascontiguousarray(x[:, o:o + n])).cuda())        # its own tensor: 16-byte aligned
+        direct.process_device(pieces[-1])
+        o += n
+    for s in range(S):
+        got, want = staged.read_hops(s), direct.read_hops(s)
+        assert len(want) == 3 and np.all(want > 0.0)
+        assert got.shape == want.shape and np.array_equal(bits(got), bits(want)), s
+    assert staged.finish() == direct.finish()
+    staged.close()
+    direct.close()
+
+
 def test_finish_in_mid_programme_reset_and_max_hops(amd):
     ref = I.reference()["ebu_3342_1"]
     x = ref["x"]
