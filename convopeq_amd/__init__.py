@@ -18,10 +18,11 @@ from .learner import ShaperLearner
 from .resampler import StreamResampler
 from .loudness import ProgrammeLoudness, loudness_finish_host, loudness_peaks_host
 from .limiter import TruePeakLimiter, limiter_default_window
+from .quantizer import Quantizer
 
 _capi.load()   # no fallback: ImportError if the HIP library is absent
 
-__all__ = ["TruePeakLimiter", "limiter_default_window", "soft_clip_params", "soft_clip_host", "soft_clip_latency", "ShaperLearner", "ProgrammeLoudness", "loudness_finish_host", "loudness_peaks_host", "StreamResampler", "ir_minimum_phase", "ir_minimum_phase_batch", "ir_prepare_batch", "ir_resample", "ir_resample_batch", "resample_design", "ShaperScorer", "score_design", "select_segments", "CPQ_SCORE_RNG_FRESH", "CPQ_SCORE_RNG_CHAINED", "CPQ_SCORE_UNSTABLE", "BatchedEngine", "CpqError", "design_svf", "eq_params_default", "nuc_heff", "nuc_plan", "outfilter_design", "ir_load_wav", "ir_prepare", "ir_compute_scale_factor", "ir_convert_to_minimum_phase",
+__all__ = ["Quantizer", "TruePeakLimiter", "limiter_default_window", "soft_clip_params", "soft_clip_host", "soft_clip_latency", "ShaperLearner", "ProgrammeLoudness", "loudness_finish_host", "loudness_peaks_host", "StreamResampler", "ir_minimum_phase", "ir_minimum_phase_batch", "ir_prepare_batch", "ir_resample", "ir_resample_batch", "resample_design", "ShaperScorer", "score_design", "select_segments", "CPQ_SCORE_RNG_FRESH", "CPQ_SCORE_RNG_CHAINED", "CPQ_SCORE_UNSTABLE", "BatchedEngine", "CpqError", "design_svf", "eq_params_default", "nuc_heff", "nuc_plan", "outfilter_design", "ir_load_wav", "ir_prepare", "ir_compute_scale_factor", "ir_convert_to_minimum_phase",
            "ir_estimate_max_frequency_response_gain", "ir_estimate_peak_latency", "os_design_stage", "os_latency", "os_resolve_factor", "meter_kweighting", "meter_tp_design_stage",
            "CPQ_METER_LOUDNESS", "CPQ_METER_TRUE_PEAK", "out_design", "dither_design",
            "CPQ_DITHER_OFF", "CPQ_DITHER_FIXED4", "CPQ_DITHER_FIXED15", "CPQ_DITHER_ADAPTIVE9", "CPQ_DITHER_TILE",

@@ -47,6 +47,8 @@ CPQ_SRC_HOST = 1
 CPQ_SRC_DEVICE = 2
 CPQ_LIM_HOST = 1
 CPQ_LIM_DEVICE = 2
+CPQ_QUANT_HOST = 1
+CPQ_QUANT_DEVICE = 2
 CPQ_OS_IIR = 0
 CPQ_OS_LINEAR_PHASE = 1
 CPQ_METER_LOUDNESS = 1
@@ -388,6 +390,17 @@ SYMBOLS = {
     "cpq_limiter_flush": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
     "cpq_limiter_read_telemetry": (C.c_int32, [C.c_void_p, C.POINTER(LimiterTelemetry)]),
     "cpq_limiter_last_kernel_ms": (C.c_double, [C.c_void_p]),
+    "cpq_quantizer_create": (C.c_int32, [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "cpq_quantizer_destroy": (None, [C.c_void_p]),
+    "cpq_quantizer_last_error": (C.c_char_p, [C.c_void_p]),
+    "cpq_quantizer_set_stream": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "cpq_quantizer_reset": (C.c_int32, [C.c_void_p]),
+    "cpq_quantizer_set_gains": (C.c_int32, [C.c_void_p, c_double_p]),
+    "cpq_quantizer_set_adaptive_coeffs": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
+    "cpq_quantizer_get_adaptive_coeffs": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p]),
+    "cpq_quantizer_process_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "cpq_quantizer_process": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "cpq_quantizer_last_kernel_ms": (C.c_double, [C.c_void_p]),
     "cpq_ir_minimum_phase_batch": (C.c_int32, [C.POINTER(C.POINTER(IrBuffer)), C.c_int32, C.c_int64, C.POINTER(IrBuffer), C.POINTER(C.c_int32)]),
     "cpq_ir_minimum_phase": (C.c_int32, [C.POINTER(IrBuffer), C.POINTER(IrBuffer)]),
     "cpq_ir_minimum_phase_last_kernel_ms": (C.c_double, []),

@@ -22,28 +22,12 @@
 // nothing else fuses.  processStereoBlock's closing clampStateSIMD (+-1e12) cannot act on states advanceState already holds to
 // +-2 and is not built.
 #include "kernels.hpp"
-#include "lattice_device.hpp"
+#include "dither_device.hpp"
 
 namespace cpq {
 namespace {
 
-#ifndef CPQ_DITHER_CPL
-#define CPQ_DITHER_CPL 1
-#endif
-constexpr int kDitherCpl = CPQ_DITHER_CPL;          // channels per lane (measured: RESULTS.md, "dither stage")
-constexpr int kDitherRows = 64 * kDitherCpl;        // rows per wave
-constexpr int kDitherStep = kDitherTile / kDitherCpl;   // samples per tile: rows x (step + 1) doubles stay below 64 KiB of LDS
-constexpr int kDitherPitch = kDitherStep + 1;
-
-// the wave's rows x len samples from t0 on, into the tile and back: lane = sample
-__device__ __forceinline__ void dTileLoad(double* tile, const double* in, int64_t inStride, int row0, int rows, int t0, int len, int lane)
-{
-    if (lane < len) {
-#pragma unroll 8
-        for (int r = 0; r < rows; ++r) tile[r * kDitherPitch + lane] = in[(row0 + r) * inStride + t0 + lane];
-    }
-}
-
+// the tile of dither_device.hpp back to the rows it came from: lane = sample
 __device__ __forceinline__ void dTileStore(const double* tile, double* out, int64_t outStride, int row0, int rows, int t0, int len, int lane)
 {
     if (lane < len) {
@@ -53,46 +37,6 @@ __device__ __forceinline__ void dTileStore(const double* tile, double* out, int6
 }
 
 __device__ __forceinline__ double dScrub(double yq, int scrub) { return scrub ? (fabs(yq) < 1.0e300 ? yq : 0.0) : yq; }
-
-// processSample: x in, yq out; e and s are the channel's state
-template <int ORDER>
-__device__ __forceinline__ double dSample(double x, double (&e)[ORDER], unsigned long long (&s)[4], const DitherParams& p)
-{
-    double fb;
-    if constexpr (ORDER == 4) {
-        fb = p.c[0] * e[0] + p.c[1] * e[1] + p.c[2] * e[2] + p.c[3] * e[3];
-    } else {
-        fb = 0.0;
-#pragma unroll
-        for (int k = 0; k < ORDER; ++k) fb += p.c[k] * e[k];
-    }
-    const double y = x - fb;
-    double v = ORDER == 4 ? dFiniteOrZero(y) : y;
-    if (v < -1.0) v = -1.0;
-    else if (v > p.maxV) v = p.maxV;
-    const double u1 = dUniform(s);
-    const double u2 = dUniform(s);
-    v += (u1 + u2 - 1.0) * p.scale;
-    const double q = __builtin_rint(v * p.invScale);
-    const double lim = 2.0 * p.scale;
-    double yq, stored;
-    if constexpr (ORDER == 4) {
-        yq = dFiniteOrZero(q * p.scale);
-        const double error = yq - y;
-        stored = error < -lim ? -lim : (lim < error ? lim : error);         // std::clamp: a NaN stays
-    } else {
-        const double minQ = -p.invScale, maxQ = p.invScale - 1.0;
-        yq = (q < minQ ? minQ : (maxQ < q ? maxQ : q)) * p.scale;           // std::clamp: a NaN stays
-        const double error = yq - y;
-        stored = error > -lim ? error : -lim;                               // max_sd: a NaN gives the second operand
-        stored = stored < lim ? stored : lim;                               // min_sd
-    }
-    stored = dFiniteOrZero(stored);
-#pragma unroll
-    for (int k = ORDER - 1; k > 0; --k) e[k] = e[k - 1];
-    e[0] = stored;
-    return yq;
-}
 
 // grid: ceil(nCh / kDitherRows) workgroups of one wave.  err [kDitherMaxOrder][nCh], rng [4][nCh]
 template <int ORDER>

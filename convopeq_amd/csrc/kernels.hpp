@@ -317,6 +317,17 @@ constexpr int kPcmTile = 4096;     // samples of the packed side per workgroup: 
 bool launch_pcm_unpack(hipStream_t stream, const void* pcm, int format, int layout, double* rows, int n, int nStreams, int sanitizeCb);
 bool launch_pcm_pack(hipStream_t stream, const double* rows, void* pcm, int format, int layout, int n, int nStreams);
 
+// ---- quantizer (quant_kernels.hip): rows [nCh][n] at inStride, times gain[row / 2], through the shaper of `order` (as
+// launch_dither: err, rng and coef carried the same way; p.headroom and p.scrub are not read: 1.0, none), packed at the width of
+// format (CPQ_PCM_S16 / S24 / S32) into pcm: planar, channel r's row at r * pitch bytes; interleaved, stream s's at s * pitch.
+// pcm and pitch aligned to the element (S24: any byte); one launch.  false: no kernel for that order, format or layout.
+struct QuantLaunch {
+    int n, nCh, order, format, layout;
+    int64_t inStride, pitch;
+};
+bool launch_quantize(hipStream_t stream, const double* in, void* pcm, const QuantLaunch& a, const DitherParams& p, const double* gain,
+                     const double* coef, double* err, unsigned long long* rng);
+
 // ---- shaper scorer (score_kernels.hip): NoiseShaperLearner::evaluateCandidateMapped for many learners and candidates at once.
 // Rows are kScoreLen doubles.  Nothing here checks an index: every table below is built by engine_score.cpp from validated counts.
 // one lattice chain (a lane): segment row read, error row written, coefficient set [9], generator start [4]

@@ -1,4 +1,4 @@
-// object_support.hpp -- what the objects beside cpq_engine (cpq_loudness, cpq_limiter, cpq_scorer, cpq_learner; not yet cpq_src) and the
+// object_support.hpp -- what the objects beside cpq_engine (cpq_loudness, cpq_limiter, cpq_quantizer, cpq_scorer, cpq_learner; not yet cpq_src) and the
 // engine-less loader calls (cpq_ir_resample*, cpq_ir_minimum_phase*) share, written once:
 //
 //   failTo          the message into the object's lastError (the sink), or into cpq_last_error(NULL) before an object exists

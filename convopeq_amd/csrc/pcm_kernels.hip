@@ -14,6 +14,7 @@
 // CPQ_PCM_SANITIZE: the callback phase of sample i of a row of n is computed here from n and the callback length cb --
 // callback i / cb, of min(cb, n - start) samples, scalar tail = its last len % 4 samples.  No table.
 #include "kernels.hpp"
+#include "pcm_device.hpp"
 
 namespace cpq {
 namespace {
@@ -73,18 +74,6 @@ __device__ __forceinline__ double pcmDecode(const unsigned char* image, int off)
         const unsigned long long pair = ((unsigned long long)w[1] << 32) | w[0];
         return pcmFixedToDouble((int)((unsigned)(pair >> (8 * (off & 3))) << 8));
     }
-}
-
-// rint(x * 2^(bits-1)), ties to even, saturated, NaN -> 0
-template <int BITS>
-__device__ __forceinline__ int pcmQuantize(double x)
-{
-    constexpr double kScale = (double)(1ll << (BITS - 1));
-    double v = rint(x * kScale);
-    if (v != v) v = 0.0;
-    v = (-kScale < v) ? v : -kScale;
-    v = (v < kScale - 1.0) ? v : kScale - 1.0;
-    return (int)v;
 }
 
 template <int FMT>

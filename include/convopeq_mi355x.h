@@ -1080,6 +1080,76 @@ int32_t cpq_engine_process_block_pcm(cpq_engine* e, const void* in, int32_t in_f
 int32_t cpq_engine_process_block_pcm_device(cpq_engine* e, const void* d_in, int32_t in_format, void* d_out, int32_t out_format,
                                             int32_t layout, uint32_t flags, int32_t n_samples);
 
+/* ---------------------------------------------------------------- word-length reduction of delivered rows */
+/* cpq_quantizer: the last step of a delivery -- engine -> cpq_loudness -> cpq_limiter -> cpq_quantizer -- as an object of its own
+ * beside the engine: the stream's gain, a noise shaper and the PCM pack of fp64 rows in one pass, after every gain the chain
+ * applies.  n_streams stereo programmes at once, rows planar float64 at (2 s + channel) * stride + i, as cpq_limiter writes
+ * them.  Per call, channel and sample:
+ *     u  = x * gains[s]                  one rounding, nothing scrubbed (cpq_loudness_apply_device's rule); gains default to 1.0
+ *     yq = the shaper's processSample(u) exactly the text of "dither stage" above for CPQ_DITHER_FIXED4, CPQ_DITHER_FIXED15 or
+ *                                        CPQ_DITHER_ADAPTIVE9 at bit_depth, headroom 1.0, no scrub
+ *     b  = the "out, S24/S32" rule of "packed PCM in and out" at the width w of the container (16, 24 or 32):
+ *          rint(yq * 2^(w-1)), ties to even, saturated to [-2^(w-1), 2^(w-1) - 1], NaN -> 0
+ * and b is written as w / 8 little-endian bytes: CPQ_PCM_PLANAR, sample i of channel c at c * pcm_pitch_bytes + i * w / 8;
+ * CPQ_PCM_INTERLEAVED, sample i of channel ch of stream s at s * pcm_pitch_bytes + (2 i + ch) * w / 8.  pcm_pitch_bytes is the
+ * caller's, at least the width of a packed row (n_samples * w / 8, twice that interleaved); the bytes of a pitch gap are
+ * neither read nor written, and none outside a row's [base, base + width).  With bit_depth <= w the pack is exact for every
+ * value a shaper can emit with one exception: the 4-tap shaper does not clamp its code, so it can emit +1.0, which saturates to
+ * 2^(w-1) - 1 at every bit_depth (and, where both draws are 0, -1 - 2^-(bit_depth-1), which saturates to -2^(w-1) at
+ * bit_depth == w); the saturation is part of the definition.
+ * Design and seeds are cpq_dither_design's and the dither stage's at sample_rate and bit_depth, and every stream draws the same
+ * two sequences (L, R): at gain 1.0 the bytes equal what cpq_dither_process_device followed by cpq_pcm_pack_device give on an
+ * engine with the same shaper, bit depth and rate.  Error taps or lattice states and the generator words are carried over
+ * calls, so the bytes of a programme are the same for every split into calls, and equal from the object that computes on the
+ * host (CPQ_QUANT_HOST, no GPU needed) and the one that computes on the device (CPQ_QUANT_DEVICE, one gfx950 kernel per call;
+ * DESIGN.md 4.19).  Neither object ever stands in for the other.
+ *
+ * cpq_quantizer_create refuses, in this order: a null out, n_streams outside 1 ... 32767, unknown flags, both flags, a
+ * sample_rate that is not finite and > 0, a shaper that is none of the three, a container_format that is not CPQ_PCM_S16,
+ * CPQ_PCM_S24 or CPQ_PCM_S32, a bit_depth outside 1 ... 32 (all CPQ_ERR_INVALID_ARG); a bit_depth above the container's width,
+ * then flags == 0 (the caller says where the bytes are computed; both CPQ_ERR_UNSUPPORTED); CPQ_QUANT_DEVICE without a gfx950
+ * device (CPQ_ERR_NO_DEVICE).  The reason of a refused create is in cpq_last_error(NULL). */
+#define CPQ_HAS_QUANTIZER 1
+#define CPQ_QUANT_HOST   1u
+#define CPQ_QUANT_DEVICE 2u
+typedef struct cpq_quantizer cpq_quantizer;
+int32_t cpq_quantizer_create(int32_t n_streams, double sample_rate, int32_t shaper, int32_t bit_depth, int32_t container_format,
+                             uint32_t flags, cpq_quantizer** out);
+void cpq_quantizer_destroy(cpq_quantizer* p);
+const char* cpq_quantizer_last_error(const cpq_quantizer* p);
+/* Device object only (a host object: CPQ_ERR_INVALID_ARG).  Synchronises the stream used so far, then later calls enqueue on
+ * `stream` (a hipStream_t; NULL: the null stream). */
+int32_t cpq_quantizer_set_stream(cpq_quantizer* p, void* stream);
+/* The object is as new: errors (the lattice's states) cleared, generators reseeded, the sample count 0.  Gains and adaptive
+ * coefficients stay.  On a device object it synchronises the stream. */
+int32_t cpq_quantizer_reset(cpq_quantizer* p);
+/* gains[n_streams] (default 1.0; they stay over reset).  Refused in this order: a null object (no message) or null gains, a
+ * gain that is not finite or is negative (CPQ_ERR_INVALID_ARG), a programme that has started (CPQ_ERR_NOT_READY: reset first).
+ * On a device object it synchronises the stream. */
+int32_t cpq_quantizer_set_gains(cpq_quantizer* p, const double* gains);
+/* cpq_dither_set_adaptive_coeffs / cpq_dither_get_adaptive_coeffs on this object, with their rules: the set a cpq_learner
+ * publishes reaches a delivery.  One stream or CPQ_ALL_STREAMS takes clampCoeff(k[i]) for i < n and 0 from n on, and those
+ * streams' states are cleared; other streams and every generator are left alone; allowed in the middle of a programme, acts on
+ * the next call.  CPQ_ERR_NOT_READY unless the object runs CPQ_DITHER_ADAPTIVE9; CPQ_ERR_INVALID_ARG for a stream out of range,
+ * n outside 0 .. 9 or a null k with n > 0; every refusal happens before any state moves.  On a device object set synchronises
+ * the stream. */
+int32_t cpq_quantizer_set_adaptive_coeffs(cpq_quantizer* p, int32_t stream, const double* k, int32_t n);
+int32_t cpq_quantizer_get_adaptive_coeffs(const cpq_quantizer* p, int32_t stream, double k[9]);
+/* n_samples more of every programme, device rows in and device bytes out, asynchronous on the object's stream: d_in must stay
+ * as it is until that stream has reached the call.  layout is a cpq_pcm_layout.  Refused before any state moves, in this
+ * order, all CPQ_ERR_INVALID_ARG: a null object (no message), a host object, a null buffer, n_samples outside 1 ... 2^30, an
+ * unknown layout, in_stride below n_samples or pcm_pitch_bytes below the width of a packed row, d_in not 16-byte aligned, d_pcm
+ * or pcm_pitch_bytes not aligned to the element (2 or 4 bytes; S24: any byte), the byte range of the rows and that of the
+ * packed buffer overlapping.  CPQ_ERR_DEVICE: a launch failed. */
+int32_t cpq_quantizer_process_device(cpq_quantizer* p, const double* d_in, int64_t in_stride, void* d_pcm, int64_t pcm_pitch_bytes,
+                                     int32_t layout, int32_t n_samples);
+/* The same on host buffers, on either object (the device object copies through buffers it owns and synchronises); the same
+ * refusals in the same order without the host-object rule, and `in` on 8 bytes instead of 16. */
+int32_t cpq_quantizer_process(cpq_quantizer* p, const double* in, int64_t in_stride, void* pcm, int64_t pcm_pitch_bytes, int32_t layout,
+                              int32_t n_samples);
+/* Device time of the launch of the last call of a device object, waiting for it; -1 on a host object or before a call. */
+double cpq_quantizer_last_kernel_ms(cpq_quantizer* p);
+
 /* ---------------------------------------------------------------- profiling */
 /* Per-kernel HIP-event timing on the engine's stream (counterpart of the reference's CONV_TIME /
  * EQ_TIME diagnostics, src/convolver/ConvolverProcessor.Runtime.cpp:679-721). */
