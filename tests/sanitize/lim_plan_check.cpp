@@ -191,6 +191,8 @@ struct Pair {
     std::mt19937_64 rng;
     Values values = kNoise;
     const char* name;
+    int partCap = 0;                            // as engine_lim.cpp keeps it: the largest tile count seen
+    std::unique_ptr<LimPartial[]> part;         // [S][partCap]
 
     Pair(int W, int mask, double c, int streams, uint64_t seed, const char* nm) : m(W, mask, c, streams), rng(seed), name(nm)
     {
@@ -225,10 +227,14 @@ struct Pair {
               "plan: hLen %d hKeep %d base %lld", c.hLen, c.hKeep, c.base);
         const long long inStride = c.nIn + pad, outStride = c.nOut + pad;
         const int tiles = (c.nOut + kLimTile - 1) / kLimTile;
-        const LimLaunch a = limLaunch(W, m.mask, m.c, c, m.streams, inStride, outStride, tiles);
+        if (tiles > partCap) {
+            partCap = tiles;
+            part.reset(new LimPartial[(size_t)m.streams * (size_t)partCap]);
+        }
+        const LimLaunch a = limLaunch(W, m.mask, m.c, c, m.streams, inStride, outStride, partCap);
+        CHECK(a.tilesPerRow == tiles && a.partStride >= a.tilesPerRow, "%d tiles at a stride of %d", a.tilesPerRow, a.partStride);
         std::unique_ptr<double[]> in(new double[(size_t)rows * (size_t)inStride + 1]), out(new double[(size_t)rows * (size_t)outStride]),
             ref(new double[(size_t)rows * (size_t)outStride]);
-        std::unique_ptr<LimPartial[]> part(new LimPartial[(size_t)m.streams * (size_t)tiles]);
         for (int r = 0; r < rows; ++r)
             for (long long i = 0; i < inStride; ++i) in[(size_t)(r * inStride + i)] = i < c.nIn ? sample((int)i) : std::nan("");
         for (size_t i = 0; i < (size_t)rows * (size_t)outStride; ++i) out[i] = ref[i] = -7.0;
@@ -254,6 +260,27 @@ struct Pair {
         CHECK(hbad == 0, "%s W %d: %d history doubles differ after the keep step", name, W, hbad);
     }
 };
+
+// the calls of tests/test_gpu_limiter_windows.py's sweep: the history grows to one short of the halo in one call, reaches it with
+// the next sample and then moves by the call's length
+static void sweep(int W)
+{
+    Pair p(W, 0xF, std::pow(10.0, -1.0 / 20.0), 2, 300 + (uint64_t)W, "sweep");
+    const int lens[] = { 5, limHalo(W) - 6, 1, kLimTile + 1, 2, 2 * kLimTile + 3 };
+    const int pad = W % 2 ? 3 : 4;              // all lengths but one are odd: 3 is the 16-byte path, 4 the scalar one
+    for (int n : lens) p.call(n, false, pad);
+    p.call(0, true, pad);
+}
+
+// more than kLimKeepBlock tiles: a second trip of the fold, and partials whose stride is wider than the call's tile count
+static void fold()
+{
+    Pair p(8, 0xF, std::pow(10.0, -1.0 / 20.0), 2, 400, "fold");
+    const int lens[] = { 3, kLimKeepBlock * kLimTile, (kLimKeepBlock + 1) * kLimTile + 1, 1500 };
+    for (int n : lens) p.call(n, false, 2);
+    CHECK(p.partCap == kLimKeepBlock + 2, "partials for %d tiles", p.partCap);
+    p.call(0, true, 3);
+}
 
 static void window(int W, int mask, double c, const char* name)
 {
@@ -291,6 +318,9 @@ int main()
     window(9, 0x0, 0.75, "no phase");
     window(1024, 0xF, std::pow(10.0, -1.0 / 20.0), "four phases");
     window(1023, 0x5, 0.5, "two phases");
+    // M = 2^k - 1, 2^k, 2^k + 1; nR % 256 = 254, 0, 2; halo = 255, 257, ... 1025; D = 1023, 1024, 1025
+    for (int W : { 19, 20, 21, 117, 118, 122, 123, 124, 245, 246, 501, 502, 1013, 1014 }) sweep(W);
+    fold();
     std::printf("%lld calls, %lld outputs\n", g_calls, g_outputs);
     std::printf("\n%d failed checks\n", g_failed);
     return g_failed ? 1 : 0;

@@ -3,39 +3,19 @@
 The reference of every case is the host object (host=True) fed the same calls.  Device and host evaluate one definition in one
 order (csrc/lim_plan.hpp), so every comparison is for equal shape and equal bits (uint64 views): there is no tolerance.  Shapes
 follow the kernels: tiles of 1024 outputs, a halo of 2 W + 21 samples, r in rounds of 256, the kept history moved 256 samples at
-a time; no row is longer than 5 tiles."""
+a time; no row is longer than 5 tiles.  The windows at which one of those rules changes, and rows of more than 256 tiles, are
+tests/test_gpu_limiter_windows.py's; the numpy helpers both files use are tests/limiter_window_cases.py's."""
 import numpy as np
 import pytest
 import torch
 
 import convopeq_amd as amd
+from limiter_window_cases import CEIL_DB, RATE, TILE, gains, host_pieces, noise, plant, same
 
 pytestmark = pytest.mark.gpu
 
-TILE = 1024
-RATE = 48000
-CEIL_DB = -1.0
 SENTINEL = 1234.5
 WINDOWS = (8, 72, 1024)
-
-
-def same(got, want):
-    return got.shape == want.shape and np.array_equal(np.ascontiguousarray(got).view(np.uint64), np.ascontiguousarray(want).view(np.uint64))
-
-
-def noise(n_streams, n, seed, level=0.2):
-    return level * np.random.default_rng(seed).standard_normal((2 * n_streams, n))
-
-
-def plant(x, at, amp=2.5):
-    """a peak well above the ceiling at sample `at`, on alternating channels of every stream"""
-    for s in range(x.shape[0] // 2):
-        x[2 * s + (s + at) % 2, at] = amp * (-1.0) ** s
-    return x
-
-
-def gains(n_streams):
-    return 0.8 + 0.05 * (np.arange(n_streams) % 9)
 
 
 def pair(n_streams, W, rate=RATE):
@@ -44,16 +24,6 @@ def pair(n_streams, W, rate=RATE):
     for lim in (dev, host):
         lim.set_gains(gains(n_streams))
     return dev, host
-
-
-def host_pieces(host, x, lengths):
-    out, at = [], 0
-    for k in lengths:
-        out.append(host.process(x[:, at:at + k]))
-        at += k
-    assert at == x.shape[1]
-    out.append(host.flush())
-    return out
 
 
 def device_pieces(dev, x, lengths, stride_pad=0, in_place=False, sync_each=True):

@@ -1,6 +1,8 @@
 """lim_plan.hpp -- the definition of cpq_limiter, the plan of a call and the launch of its two kernels -- as a program of its own
 under the address and undefined-behaviour sanitizers: tests/sanitize/lim_plan_check.cpp restates k_lim_apply and k_lim_keep as host
-loops on exactly sized heap blocks and holds them to cpq::LimHost bit for bit, at windows 8, 9, 72, 1023 and 1024."""
+loops on exactly sized heap blocks and holds them to cpq::LimHost bit for bit, at windows 8, 9, 72, 1023 and 1024, on the calls of
+tests/test_gpu_limiter_windows.py's sweep at 14 of its windows, and on its rows of 256 and 257 tiles with the partials at the
+stride the object keeps."""
 import os
 import subprocess
 
